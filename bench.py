@@ -11,10 +11,19 @@ loss) + backward + RCCL gradient all-reduce + per-tensor clip + Adam.  Rank 0 pr
 --config 3 = configs[3] (K=30 at 256x256, bf16, batch 16 per GPU), --config 4 = configs[4] (K=50 at 128x128, f16 storage with
 the device-resident dynamic loss scale, batch 32 per GPU; --gpus 8 is the configuration as BASELINE.json states it).
 
-Timing protocol: the step is first spun for a fixed wall time (default 1 s, untimed) so that the clocks have
-settled, then W untimed warm-up steps, then `--windows` (default 3) windows of EXACTLY K steps, each bracketed by
-barrier + torch.cuda.synchronize() on both sides and reduced with MAX over ranks; `ms_per_step` / `value` are the
-MEDIAN window, all windows are listed under `step.windows_ms`.
+Timing protocol: the step is first spun untimed for about `--spin-seconds` (default 1 s) so that the clocks have
+settled — a fixed count of steps, the seconds over the workload's nominal step time, so that every run with the same
+arguments executes the same steps —, then W untimed warm-up steps, then `--windows` (default 1) windows of EXACTLY K
+steps, each bracketed by barrier + torch.cuda.synchronize() on both sides and reduced with MAX over ranks;
+`ms_per_step` / `value` are the MEDIAN window, all windows are listed under `step.windows_ms`.
+
+A plain run does only that.  `--full` adds what takes runs of its own: device-clock phases of the step, forward-only
+rates, per-kernel times and the roofline with live HBM traffic (rocprofv3), the CPU baseline and the parity against the
+oracle, and at N > 1 the check that every rank ends with the same parameters.
+
+`--dump-outputs DIR` writes what the last timed step computed on rank 0 as DIR/<name>.npy (float32 / float64, < 32 MB at
+the shipped workloads): loss, loss_terms, landmarks, future_im_pred and the updated params.  The inputs and the initial
+weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -35,12 +44,13 @@ if ROOT not in sys.path:
 
 PEAK_BF16_TFLOPS = 2500.0      # MI355X dense bf16 / f16 MFMA peak (MI355X_MICROARCH.md)
 # BASELINE.json configurations this file can run (configs[0] is the CPU-only plumbing case, configs[2] = --config 1 --gpus 8)
+# nominal_ms: step time of the round-6 build on one MI355X (README), only used to turn --spin-seconds into a fixed step count
 WORKLOADS = {
-    1: dict(batch=32, size=128, n_maps=10, dtype='bf16', name='BASELINE configs[1] (N>1: configs[2])',
+    1: dict(batch=32, size=128, n_maps=10, dtype='bf16', nominal_ms=3.0, name='BASELINE configs[1] (N>1: configs[2])',
             what='CelebA-shape 128x128 K=10 IMM training step'),
-    3: dict(batch=16, size=256, n_maps=30, dtype='bf16', name='BASELINE configs[3]',
+    3: dict(batch=16, size=256, n_maps=30, dtype='bf16', nominal_ms=5.3, name='BASELINE configs[3]',
             what='K=30 at 256x256 IMM training step (align-corners resize path, wider bottleneck)'),
-    4: dict(batch=32, size=128, n_maps=50, dtype='f16', name='BASELINE configs[4] (as stated at --gpus 8)',
+    4: dict(batch=32, size=128, n_maps=50, dtype='f16', nominal_ms=3.2, name='BASELINE configs[4] (as stated at --gpus 8)',
             what='AFLW-finetune shape 128x128 K=50 IMM training step, f16 storage + dynamic loss scale'),
 }
 WL = dict(WORKLOADS[1])        # the selected workload (set by --config before anything runs)
@@ -121,6 +131,19 @@ def forward_only_rates(dev, batches, steps=20):
         dt = (time.perf_counter() - t0) / steps
         out['b%d' % b] = {'ms': round(dt * 1e3, 4), 'images_per_s': round(b / dt, 1)}
     return out
+
+
+def dump_outputs(out_dir, eng):
+    """What a caller of TrainStep.step holds after the last step: its loss and loss terms, the landmarks and the predicted
+    image of its forward pass, and the parameters its update produced, as float32 / float64 .npy files in out_dir."""
+    import numpy as np
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {'loss': eng.loss.detach().double(), 'loss_terms': eng.loss_terms.detach().float(),
+              'landmarks': eng.mu.detach().float(), 'future_im_pred': eng.future_im_pred.detach().float(),
+              'params': eng.params.detach().float()}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), t.cpu().numpy())
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -215,13 +238,13 @@ def pmc_pass(steps):
 # ---------------------------------------------------------------------------------------------------------
 def cpu_baseline(budget_s=12.0):
     """CPU restatement of the TF1 graph (oracle/imm_oracle.py) timed on this node's host cores, bounded so
-    that the default bench run stays within minutes, at the thread count the oracle runs FASTEST with (torch's CPU
+    that a --full bench run stays within minutes, at the thread count the oracle runs FASTEST with (torch's CPU
     convolutions scale badly: "all cores" was the slowest point of the curve on the 128-core host of round 2):
       A  configs[0]: forward + perceptual loss, batch 4, swept over {1, 8, 16, 32, 64, all} threads
          (1 warm + 2 timed each, the faster one counts) -> best thread count
       B  configs[1]: training step (fwd + bwd + clip + Adam), batch 32, at that thread count: one untimed batch-4 step
          (autograd / allocator / thread-pool warm-up), then 3 timed steps, median            -> `value`
-    `python bench.py --cpu-baseline-full` runs the unbounded protocol of BASELINE.md §3 (>= 3 warm + >= 10 timed per leg)."""
+    `python bench.py --full --cpu-baseline-full` runs the unbounded protocol of BASELINE.md §3 (>= 3 warm + >= 10 timed per leg)."""
     from oracle import imm_oracle as O
     full = budget_s <= 0
     cfg = O.default_model_config(N_MAPS)
@@ -429,12 +452,19 @@ def main():
                          '(K=30 at 256x256), 4 = configs[4] (K=50, f16 + loss scale; --gpus 8 as stated)')
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=10)
-    ap.add_argument('--windows', type=int, default=3, help='timed windows of --steps steps each; the median is reported')
-    ap.add_argument('--spin-seconds', type=float, default=1.0, help='untimed wall time of steps before the counted warm-up (clock settling)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--cpu-baseline-full', action='store_true', help='BASELINE.md §3 protocol (>=3 warm, >=10 timed): minutes of CPU time')
+    ap.add_argument('--windows', type=int, default=1, help='timed windows of --steps steps each; the median is reported')
+    ap.add_argument('--spin-seconds', type=float, default=1.0,
+                    help='about this many seconds of untimed steps before the counted warm-up (clock settling); the step count is '
+                         'fixed by the workload\'s nominal step time, not measured')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what the headline does not need: phases, forward-only rates, per-kernel times and '
+                         'roofline, live HBM traffic, CPU baseline and parity vs the oracle, replicas at N > 1')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step (rank 0) to DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline and the parity leg')
+    ap.add_argument('--cpu-baseline-full', action='store_true', help='--full with the CPU baseline on the BASELINE.md §3 protocol (>=3 warm, >=10 timed): minutes of CPU time')
     ap.add_argument('--no-graph', action='store_true')
-    ap.add_argument('--no-pmc', action='store_true', help='do not collect live HBM traffic with rocprofv3 (falls back to profiles/)')
+    ap.add_argument('--no-pmc', action='store_true', help='--full without live HBM traffic from rocprofv3 (falls back to profiles/)')
     ap.add_argument('--force-dist', action='store_true', help='initialise the process group and run the split-graph + all-reduce path even at 1 GPU')
     ap.add_argument('--backend', default='nccl', help="torch.distributed backend: 'nccl' (= RCCL on ROCm) or 'gloo' (tests)")
     ap.add_argument('--share-gpu', action='store_true', help='tests: let several ranks share one device (needs --backend gloo)')
@@ -517,15 +547,11 @@ def main():
             ts.step(None)
         ts.synchronize()
 
-    # ---- clock settling: a fixed wall time of steps, the same count on every rank (the collectives must pair up) ----
-    run_steps(2)                                  # graph capture, code-object loading
-    barrier()
-    t0 = time.perf_counter(); run_steps(10); t10 = (time.perf_counter() - t0) / 10
+    # ---- clock settling: a fixed count of untimed steps, the same on every rank (the collectives must pair up) and in every run
+    # with these arguments (the state the timed steps end in, which --dump-outputs writes, depends on how many steps ran) ----
     ctrl = dev if args.backend == 'nccl' else 'cpu'      # small control collectives: device tensors for RCCL, host for gloo
-    n_spin = torch.tensor([max(0, int(args.spin_seconds / max(t10, 1e-5)))], dtype=torch.int64, device=ctrl)
-    if world > 1:
-        dist.broadcast(n_spin, 0)
-    run_steps(int(n_spin))
+    n_spin = max(0, int(round(args.spin_seconds * 1e3 / WL['nominal_ms'])))
+    run_steps(n_spin)
     run_steps(max(args.warmup, 1))
     windows = []
     for _ in range(max(args.windows, 1)):
@@ -540,6 +566,8 @@ def main():
             elapsed = float(t)
         windows.append(elapsed)
     elapsed = sorted(windows)[len(windows) // 2]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng)
     loss = float(eng.loss)
     assert loss == loss, 'NaN loss'
     if world > 1 or args.force_dist:
@@ -548,6 +576,55 @@ def main():
         dist.all_reduce(lt)
         loss = float(lt) / world
 
+    out = None
+    if rank == 0:
+        step_flops = eng.step_flops()
+        ms_per_step = elapsed / args.steps * 1e3
+        out = {
+            'metric': 'training images/sec at %dx%d K=%d' % (IMAGE_SIZE, IMAGE_SIZE, N_MAPS),
+            'value': round(world * BATCH_PER_GPU * args.steps / elapsed, 2),
+            'unit': 'images/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+            'ms_per_step': round(ms_per_step, 4), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+            'dtype': WL['dtype'], 'data': 'synthetic',
+            'config': {'workload': '%s: %s (fwd + VGG16 perceptual loss + bwd + clip + Adam), batch %d per GPU'
+                                   % (WL['name'], WL['what'], BATCH_PER_GPU),
+                       'baseline_config': WL.get('index', 1),
+                       'loss_scale': (None if eng.loss_scale_state is None else [float(v) for v in eng.loss_scale_state.tolist()]),
+                       'global_batch': world * BATCH_PER_GPU, 'image_size': IMAGE_SIZE, 'n_maps': N_MAPS,
+                       'parallelism': 'dp%d' % world, 'hip_graph': not args.no_graph,
+                       'collective': ({'backend': dist.get_backend(), 'world_size': dist.get_world_size(),
+                                       'mode': ts.collective, 'buckets': ts.buckets, 'graph_resident': bool(ts.graph_resident),
+                                       'native_rccl': ts.native_comm is not None, 'selfcheck': selfcheck,
+                                       'payload_mb': round(eng.tab.total * 4 / 1e6, 2),
+                                       # one ring over ONE xGMI link direction (~153 GB/s) moves 2 (N-1)/N of the payload per GPU:
+                                       # the per-link bound of a ring all-reduce; with all 7 links in rings it is 1/7 of that
+                                       'expected_ring_ms': round(2.0 * (world - 1) / max(world, 1) * eng.tab.total * 4 / 153e9 * 1e3, 4),
+                                       'expected_ring_ms_7_links': round(2.0 * (world - 1) / max(world, 1) * eng.tab.total * 4 / (7 * 153e9) * 1e3, 4)}
+                                      if dist.is_initialized() else None),
+                       'weights': 'seeded random init; synthetic VGG16 (vgg16.caffemodel.h5 unavailable offline)'},
+            'step': {'windows_ms': [round(w / args.steps * 1e3, 4) for w in windows],
+                     'min_ms': round(min(windows) / args.steps * 1e3, 4), 'max_ms': round(max(windows) / args.steps * 1e3, 4),
+                     'spin_steps': n_spin,
+                     'conv_gflop_per_image': round(step_flops / BATCH_PER_GPU / 1e9, 2),
+                     'step_tflops': round(step_flops / (ms_per_step * 1e-3) / 1e12, 1),
+                     'frac_of_peak': round(step_flops / (ms_per_step * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4),
+                     'loss': round(loss, 3), 'hbm_bytes_allocated': eng.memory_bytes()},
+        }
+    if args.full:
+        full_measurements(args, ts, dev, world, rank, ctrl, barrier, out)
+    if rank == 0:
+        sys.stdout.flush()
+        os.write(real_stdout, (json.dumps(out) + '\n').encode())
+    if dist.is_initialized():
+        dist.barrier()
+        dist.destroy_process_group()
+    return 0
+
+
+def full_measurements(args, ts, dev, world, rank, ctrl, barrier, out):
+    """--full: what the headline figure does not need, measured after the timed windows (the runs here move the engine's state
+    on).  Every rank takes part (the replicas check and the probed steps contain collectives); rank 0 adds the results to `out`."""
+    eng = ts.engine
     replicas_identical, replicas_diff = None, None
     if world > 1:
         # data-parallel invariant: after the same number of updates from all-reduced gradients every rank holds the SAME bits
@@ -614,67 +691,28 @@ def main():
         if traffic is None:
             traffic, f = pmc_traffic_from_profiles()
             traffic_src = ('profiles: ' + f) if f else None
-        roof = {'bound': 'mfma', 'kernel': 'conv_hdeep / conv_halo2 / conv_igemm64 / conv_igemm kernels (convolution fwd + data-gradient, %d launches/step)' % n_l,
-                'achieved': round(achieved, 2), 'peak': PEAK_BF16_TFLOPS, 'unit': 'TFLOP/s',
-                'frac': round(achieved / PEAK_BF16_TFLOPS, 4), 'traffic': traffic,
-                'traffic_unit': 'MB HBM per launch (rocprofv3 PMC FETCH_SIZE x2 [gfx950 correction] + WRITE_SIZE)',
-                'traffic_source': traffic_src,
-                'algorithmic_mb_per_launch': round(nb_l / n_l / 1e6, 2),
-                'avg_launch_us': round(ms_l * 1e3 / n_l, 2), 'gflop_per_launch': round(fl_l / n_l / 1e9, 3)}
-        breakdown = {t: {'launches': d[0], 'ms': round(d[1], 3), 'tflops': (round(d[2] / (d[1] * 1e-3) / 1e12, 1) if d[2] else None)}
-                     for t, d in sorted(by_tag.items(), key=lambda kv: -kv[1][1])}
-        total_ms = sum(d[1] for d in by_tag.values())
+        out['roofline'] = {
+            'bound': 'mfma', 'kernel': 'conv_hdeep / conv_halo2 / conv_igemm64 / conv_igemm kernels (convolution fwd + data-gradient, %d launches/step)' % n_l,
+            'achieved': round(achieved, 2), 'peak': PEAK_BF16_TFLOPS, 'unit': 'TFLOP/s',
+            'frac': round(achieved / PEAK_BF16_TFLOPS, 4), 'traffic': traffic,
+            'traffic_unit': 'MB HBM per launch (rocprofv3 PMC FETCH_SIZE x2 [gfx950 correction] + WRITE_SIZE)',
+            'traffic_source': traffic_src,
+            'algorithmic_mb_per_launch': round(nb_l / n_l / 1e6, 2),
+            'avg_launch_us': round(ms_l * 1e3 / n_l, 2), 'gflop_per_launch': round(fl_l / n_l / 1e9, 3)}
         tr = [by_tag[t] for t in ('conv_fwd', 'conv_dgrad', 'conv_wgrad') if t in by_tag]
-        step_flops = eng.step_flops()
-        ms_per_step = elapsed / args.steps * 1e3
-        out = {
-            'metric': 'training images/sec at %dx%d K=%d' % (IMAGE_SIZE, IMAGE_SIZE, N_MAPS),
-            'value': round(world * BATCH_PER_GPU * args.steps / elapsed, 2),
-            'unit': 'images/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-            'ms_per_step': round(ms_per_step, 4), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-            'dtype': WL['dtype'], 'data': 'synthetic',
-            'config': {'workload': '%s: %s (fwd + VGG16 perceptual loss + bwd + clip + Adam), batch %d per GPU'
-                                   % (WL['name'], WL['what'], BATCH_PER_GPU),
-                       'baseline_config': WL.get('index', 1),
-                       'loss_scale': (None if eng.loss_scale_state is None else [float(v) for v in eng.loss_scale_state.tolist()]),
-                       'global_batch': world * BATCH_PER_GPU, 'image_size': IMAGE_SIZE, 'n_maps': N_MAPS,
-                       'parallelism': 'dp%d' % world, 'hip_graph': not args.no_graph,
-                       'collective': ({'backend': dist.get_backend(), 'world_size': dist.get_world_size(),
-                                       'mode': ts.collective, 'buckets': ts.buckets, 'graph_resident': bool(ts.graph_resident),
-                                       'native_rccl': ts.native_comm is not None, 'selfcheck': selfcheck,
-                                       'payload_mb': round(eng.tab.total * 4 / 1e6, 2),
-                                       # one ring over ONE xGMI link direction (~153 GB/s) moves 2 (N-1)/N of the payload per GPU:
-                                       # the per-link bound of a ring all-reduce; with all 7 links in rings it is 1/7 of that
-                                       'expected_ring_ms': round(2.0 * (world - 1) / max(world, 1) * eng.tab.total * 4 / 153e9 * 1e3, 4),
-                                       'expected_ring_ms_7_links': round(2.0 * (world - 1) / max(world, 1) * eng.tab.total * 4 / (7 * 153e9) * 1e3, 4)}
-                                      if dist.is_initialized() else None),
-                       'weights': 'seeded random init; synthetic VGG16 (vgg16.caffemodel.h5 unavailable offline)'},
-            'roofline': roof,
-            'step': {'windows_ms': [round(w / args.steps * 1e3, 4) for w in windows],
-                     'min_ms': round(min(windows) / args.steps * 1e3, 4), 'max_ms': round(max(windows) / args.steps * 1e3, 4),
-                     'spin_steps': int(n_spin),
-                     'conv_gflop_per_image': round(step_flops / BATCH_PER_GPU / 1e9, 2),
-                     'step_tflops': round(step_flops / (ms_per_step * 1e-3) / 1e12, 1),
-                     'frac_of_peak': round(step_flops / (ms_per_step * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4),
-                     'trainable_conv_tflops': round(sum(d[2] for d in tr) / (sum(d[1] for d in tr) * 1e-3) / 1e12, 1) if tr else None,
-                     'sum_kernel_ms_eager': round(total_ms, 3), 'hbm_gb_per_step': hbm_gb_step, 'loss': round(loss, 3),
-                     'phases_ms': phases, 'fwd_only': fwd_only,
-                     'hbm_bytes_allocated': eng.memory_bytes(), 'replicas_identical': replicas_identical,
-                     'replicas_diff': (None if not replicas_diff else {k: v for k, v in list(replicas_diff.items())[:12]})},
-            'kernels': breakdown,
-        }
+        out['step'].update({
+            'trainable_conv_tflops': round(sum(d[2] for d in tr) / (sum(d[1] for d in tr) * 1e-3) / 1e12, 1) if tr else None,
+            'sum_kernel_ms_eager': round(sum(d[1] for d in by_tag.values()), 3), 'hbm_gb_per_step': hbm_gb_step,
+            'phases_ms': phases, 'fwd_only': fwd_only, 'replicas_identical': replicas_identical,
+            'replicas_diff': (None if not replicas_diff else {k: v for k, v in list(replicas_diff.items())[:12]})})
+        out['kernels'] = {t: {'launches': d[0], 'ms': round(d[1], 3), 'tflops': (round(d[2] / (d[1] * 1e-3) / 1e12, 1) if d[2] else None)}
+                          for t, d in sorted(by_tag.items(), key=lambda kv: -kv[1][1])}
         if (not args.no_cpu_baseline and world == 1) or args.cpu_baseline_full:
             out['cpu_baseline'] = cpu_baseline(0.0 if args.cpu_baseline_full else 12.0)
             try:        # the checker must never lose the measurement
                 out['parity'] = parity_vs_oracle(dev)
             except Exception as e:
                 out['parity'] = {'error': '%s: %s' % (type(e).__name__, e)}
-        sys.stdout.flush()
-        os.write(real_stdout, (json.dumps(out) + '\n').encode())
-    if dist.is_initialized():
-        dist.barrier()
-        dist.destroy_process_group()
-    return 0
 
 
 if __name__ == '__main__':

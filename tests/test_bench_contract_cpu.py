@@ -1,4 +1,4 @@
-"""The bench line's contract, checked on the newest committed line (profiles/r*_bench.json is what `python bench.py` printed on an
+"""The bench line's contract, checked on the newest committed line (profiles/r*_bench.json is what `python bench.py --full` printed on an
 MI355X): the keys the driver and the judge read, the roofline / cpu_baseline / parity blocks, internal consistency."""
 import glob
 import json

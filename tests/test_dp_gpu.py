@@ -223,7 +223,7 @@ def test_bench_self_spawns_two_ranks(tmp_path):
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--windows', '1',
-                          '--spin-seconds', '0', '--backend', 'gloo', '--share-gpu', '--no-cpu-baseline', '--no-pmc'],
+                          '--spin-seconds', '0', '--backend', 'gloo', '--share-gpu', '--full', '--no-cpu-baseline', '--no-pmc'],
                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=800)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     lines = [l for l in out.stdout.decode().splitlines() if l.strip().startswith('{')]
@@ -267,7 +267,7 @@ def _eight_rank_bench(env, extra):
     import json
     import subprocess
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '3', '--warmup', '1', '--windows', '1',
-                          '--spin-seconds', '0', '--backend', 'gloo', '--share-gpu', '--no-cpu-baseline', '--no-pmc', '--collective', 'pg']
+                          '--spin-seconds', '0', '--backend', 'gloo', '--share-gpu', '--full', '--no-cpu-baseline', '--no-pmc', '--collective', 'pg']
                          + list(extra), env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1400)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     lines = [l for l in out.stdout.decode().splitlines() if l.strip().startswith('{')]

@@ -480,7 +480,7 @@ def test_bench_rccl_path_single_rank():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT='29533', RANK='0', WORLD_SIZE='1', LOCAL_RANK='0')
     out = subprocess.run([sys.executable, os.path.join(repo, 'bench.py'), '--force-dist', '--steps', '3', '--warmup', '1',
-                          '--no-cpu-baseline'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+                          '--full', '--no-cpu-baseline'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert out.returncode == 0, out.stderr.decode()[-2000:]
     lines = [l for l in out.stdout.decode().splitlines() if l.strip()]
     assert len(lines) == 1, lines                                   # exactly one JSON line on stdout
@@ -499,6 +499,40 @@ def test_bench_rccl_path_single_rank():
     assert out.returncode == 0, out.stderr.decode()[-2000:]
     c = json.loads([l for l in out.stdout.decode().splitlines() if l.strip()][0])['config']['collective']
     assert c['mode'] == 'pg' and c['buckets'] == 1 and c['selfcheck'] is None
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain bench run times exactly --steps steps, measures nothing of --full, and --dump-outputs writes what the last step
+    computed: its loss (the line's), loss terms, landmarks, predicted image and updated parameters, float32 / float64, < 64 MB.
+    Two runs with the same arguments, clock-settling spin included, execute the same steps and write bit-identical outputs
+    (the spin is a fixed step count, not a measured one; the graph-replayed step is deterministic)."""
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(out_dir):
+        out = subprocess.run([sys.executable, os.path.join(repo, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                              '--spin-seconds', '0.05', '--dump-outputs', str(out_dir)], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                             timeout=600)
+        assert out.returncode == 0, out.stderr.decode()[-2000:]
+        lines = [l for l in out.stdout.decode().splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        return json.loads(lines[0]), {f[:-4]: np.load(str(out_dir / f)) for f in os.listdir(str(out_dir))}
+
+    d, arrays = run(tmp_path / 'a')
+    assert d['steps'] == 3 and len(d['step']['windows_ms']) == 1 and d['step']['spin_steps'] == 17     # 0.05 s / 3.0 ms nominal
+    assert abs(d['value'] - 32 / d['ms_per_step'] * 1e3) <= 1e-3 * d['value']
+    for k in ('roofline', 'kernels', 'cpu_baseline', 'parity'):
+        assert k not in d, k
+    shapes = {'loss': (), 'loss_terms': (6,), 'landmarks': (32, 10, 2), 'future_im_pred': (32, 128, 128, 3), 'params': (4138067,)}
+    assert {k: a.shape for k, a in arrays.items()} == shapes
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+    assert sum(os.path.getsize(str(tmp_path / 'a' / f)) for f in os.listdir(str(tmp_path / 'a'))) < 64 * 2 ** 20
+    assert abs(float(arrays['loss']) - d['step']['loss']) <= 1e-3 * abs(d['step']['loss']) + 1e-3
+    d2, arrays2 = run(tmp_path / 'b')
+    assert d2['step']['spin_steps'] == d['step']['spin_steps'] and sorted(arrays2) == sorted(arrays)
+    for k in arrays:
+        assert np.array_equal(arrays[k], arrays2[k]), k
 
 
 def _smooth_batch(B, S, seed=3):

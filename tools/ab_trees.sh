@@ -8,7 +8,8 @@ n=$1; shift
 for i in $(seq $n); do
   for t in new old; do
     if [ $t = new ]; then d=.; else d=build_ab/old; fi
-    (cd $d && timeout 240 python bench.py --no-cpu-baseline --no-pmc "$@" 2>/dev/null | tail -1) | python -c "
+    full=$(grep -q "'--full'" $d/bench.py && echo --full)      # trees older than --full print the kernel times by default
+    (cd $d && timeout 240 python bench.py $full --no-cpu-baseline --no-pmc "$@" 2>/dev/null | tail -1) | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernels']
 print('AB $t %.4f ms windows %s wgrad %.3f reduce %.3f adam %.3f' % (d['ms_per_step'], d['step']['windows_ms'], k.get('conv_wgrad',{}).get('ms',0), k.get('wgrad_reduce',{}).get('ms',0), k.get('clip_adam',{}).get('ms',0)))"

@@ -3,7 +3,7 @@ one GPU: configs[3] S=256 / K=30 bf16, the per-GPU shape of configs[4] S=128 / K
 
     python tools/bench_configs.py [--json profiles/r04_configs.json]
 
-Per configuration: HIP-graph replay time (median of three 40-step windows after 1 s of untimed steps, the protocol of bench.py),
+Per configuration: HIP-graph replay time (median of three 40-step windows after 1 s of untimed steps),
 and one eager pass with a HIP-event pair around every launch (engine.run_timed) -> time and TFLOP/s per launch class and the
 roofline fraction of the convolution forward + data-gradient family against the 2.5 PFLOP/s dense 16-bit MFMA peak."""
 import json

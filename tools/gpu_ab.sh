@@ -8,7 +8,7 @@ i=0
 while IFS= read -r line; do
   i=$((i+1))
   [ "$line" = "-" ] && line=""
-  env $line timeout 240 python bench.py --no-cpu-baseline --no-pmc "$@" > "$out/ab_$i.json" 2> "$out/ab_$i.err"
+  env $line timeout 240 python bench.py --full --no-cpu-baseline --no-pmc "$@" > "$out/ab_$i.json" 2> "$out/ab_$i.err"
   python - "$out/ab_$i.json" "$line" <<'PY'
 import json, sys
 try:
