@@ -9,8 +9,8 @@
 // requested one patch ahead), rounds it to 16 bits, gathers the [14 x 16 pixels][32 channels] operand tile from it and runs the
 // seven vertical taps as 7 k-steps of v_mfma_f32_16x16x32 against the filter image resident in LDS (the same packed image
 // Wt[n][ky*32 + kx*3 + c] the 7x1 form uses, so the arithmetic is unchanged: same 16-bit operands, f32 accumulation).  Epilogue =
-// conv_halo.hip's: bias, 16-bit NHWC store, batch-norm partial sums accumulated over the workgroup's patches (one row per
-// workgroup).  The packed copy is still produced for the layer's filter gradient, but off the forward chain.
+// conv_halo.hip's: bias, ReLU (the landmark detector's batch-norm-folded conv_1), 16-bit NHWC store, batch-norm partial sums
+// accumulated over the workgroup's patches (one row per workgroup).  The packed copy is still produced for the layer's filter gradient, but off the forward chain.
 #include "conv_common.h"
 
 #define CF_PH 8
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const ConvFirstArgs a) 
   const int t_q = tid & 3, t_pix0 = tid >> 2;
   const int t_src0 = (t_pix0 >> 4) * SROW + 3 * (t_pix0 & 15) + 8 * t_q;
 
-  const bool f_bias = a.flags & IMM_CONV_BIAS, f_stats = a.flags & IMM_CONV_STATS;
+  const bool f_bias = a.flags & IMM_CONV_BIAS, f_stats = a.flags & IMM_CONV_STATS, f_relu = a.flags & IMM_CONV_RELU;
   float s1[NT][4], s2[NT][4], bv[NT][4];
 #pragma unroll
   for (int j = 0; j < NT; ++j)
@@ -201,7 +201,10 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const ConvFirstArgs a) 
         const int n = j * 16 + 4 * fchunk;
         float v[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = acc[i][j][r] + bv[j][r];
+        for (int r = 0; r < 4; ++r) {
+          v[r] = acc[i][j][r] + bv[j][r];
+          if (f_relu) v[r] = fmaxf(v[r], 0.f);
+        }
         if (f_stats) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) { s1[j][r] += v[r]; s2[j][r] += v[r] * v[r]; }
@@ -294,7 +297,8 @@ extern "C" int imm_conv_first(const float* image, const void* wt, int kpad, cons
   if (!imm_conv_first_supported(batch, s, co, ldy))
     return imm_fail(IMM_E_UNSUPPORTED, "conv_first: batch %d side %d co %d ldy %d: needs side %% 16 == 0, co <= 32, co %% 4 == 0", batch, s, co, ldy);
   IMM_REQUIRE(kpad >= CF_K * 32 && kpad % 8 == 0, "conv_first: kpad=%d must hold 7 taps x 32 unrolled channels (imm_pack_weights, kh 7, kw 1, c_pad 32)", kpad);
-  IMM_REQUIRE(!(flags & ~(IMM_CONV_BIAS | IMM_CONV_STATS)), "conv_first: flags 0x%x (bias and batch-norm sums only)", flags);
+  IMM_REQUIRE(!(flags & ~(IMM_CONV_BIAS | IMM_CONV_RELU | IMM_CONV_STATS)), "conv_first: flags 0x%x (bias, ReLU and batch-norm sums only)",
+              flags);
   IMM_REQUIRE(!(flags & IMM_CONV_BIAS) || bias, "conv_first: bias flag without bias");
   IMM_REQUIRE(!(flags & IMM_CONV_STATS) || stats_partial, "conv_first: stats flag without buffer");
   IMM_REQUIRE(((uintptr_t)wt % 16 == 0) && ((uintptr_t)y % 8 == 0) && ((uintptr_t)image % 4 == 0), "conv_first: alignment");

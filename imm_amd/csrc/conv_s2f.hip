@@ -19,7 +19,8 @@
 // (the one row / column of bottom / right padding) is an out-of-range buffer offset: the DMA writes zeros.
 // Wave (wm, wn) of the NW = BN / 16 waves owns patch rows 4 wm .. 4 wm + 3 x 32 channels (8 MFMAs per k-step); a lane ends up with 8
 // consecutive channels of its pixel (conv_hdeep.hip's filter-row permutation): one 16-byte store per pixel.  Epilogue: bias and
-// the batch-norm partial sums (one row per patch) — the stride-2 layers are conv + BN + ReLU blocks (imm_model.py:182-217).
+// the batch-norm partial sums (one row per patch) — the stride-2 layers are conv + BN + ReLU blocks (imm_model.py:182-217) — and,
+// for the landmark detector whose batch norm is folded into W and b, the ReLU.
 #include "conv_common.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -254,7 +255,9 @@ __global__ __launch_bounds__(BN * 4) void conv_s2f_kernel(const S2fArgs ha) {
   __syncthreads();
 
   // ---- epilogue: lane = pixel (row 4 wm + i, col frow), 8 consecutive channels; bias is in the accumulators ----------------------
-  const bool f_stats = a.flags & IMM_CONV_STATS;
+  // ReLU on the f32 value before the 16-bit store (the batch-norm-folded detector's conv + bias + ReLU); the partial sums are of
+  // the stored value, as in conv_common.h
+  const bool f_stats = a.flags & IMM_CONV_STATS, f_relu = a.flags & IMM_CONV_RELU;
   const int nb = n0 + wn * 32 + q * 8;
   const int64_t m_first = ((int64_t)img * a.ho + y0 + wm * 4) * a.wo + x0 + frow;
   float s1[NT][4], s2[NT][4];
@@ -270,9 +273,10 @@ __global__ __launch_bounds__(BN * 4) void conv_s2f_kernel(const S2fArgs ha) {
     for (int j = 0; j < NT; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        v[4 * j + r] = acc[i][j][r];
-        s1[j][r] += acc[i][j][r];
-        s2[j][r] = fmaf(acc[i][j][r], acc[i][j][r], s2[j][r]);
+        const float t = f_relu ? fmaxf(acc[i][j][r], 0.f) : acc[i][j][r];
+        v[4 * j + r] = t;
+        s1[j][r] += t;
+        s2[j][r] = fmaf(t, t, s2[j][r]);
       }
     if (nb < a.co) *(uint4*)((uint16_t*)a.y + m * a.ldy + nb) = pack8<ET>(v);
   }
@@ -327,7 +331,7 @@ bool imm_s2f_applicable(const imm_conv_desc* d) {
   if ((d->hi & 1) || (d->wi & 1) || d->ho != d->hi / 2 || d->wo != d->wi / 2) return false;
   if (d->ci % 64 || d->co % 64 || d->kpad != 9 * d->ci) return false;     // pairs of 32-channel slices (32 -> 64, encoder conv_3: conv_halo.hip)
   if (d->ho % S2_PH || d->wo % S2_PW || d->ldy % 8) return false;
-  if (d->out_scale > 1 || (d->flags & ~(IMM_CONV_BIAS | IMM_CONV_STATS))) return false;
+  if (d->out_scale > 1 || (d->flags & ~(IMM_CONV_BIAS | IMM_CONV_RELU | IMM_CONV_STATS))) return false;
   const int64_t px = (int64_t)d->batch * d->hi * d->wi;
   if (px * d->ldx * 2 >= (1LL << 31) || (int64_t)d->co * d->kpad * 2 >= (1LL << 31)) return false;
   return true;

@@ -7,6 +7,9 @@
                                                        to the annotated ones, fitted on the training split
   interocular_error()   scripts/test.py:59-65          mean point distance / inter-ocular distance (first two GT points)
 
+detect_landmarks()     the same landmarks through a LandmarkDetector (imm_amd/inference.py: pose encoder only, batch norm
+                       folded); evaluate_regression(..., detector=...) uses it for both splits
+
 The network forward is the training step's own kernel path (IMMModel.build(..., training_pl=False, build_loss=False) ->
 IMMEngine.forward_model_only); the regression is host arithmetic like in the reference (scikit-learn's Ridge)."""
 import time
@@ -67,10 +70,26 @@ def interocular_error(landmarks_gt, landmarks_regressed):
     return float(np.mean(dist / ocular[:, None]))
 
 
-def evaluate_regression(net_instance, train_iter, test_iter, im_size, batch_size=100, bias=False):
-    """scripts/test.py:18-65 `evaluate`: unsupervised landmarks of both splits -> Ridge -> inter-ocular error."""
+def detect_landmarks(dataset_iter, detector):
+    """evaluate(..., eval_tensors=['gauss_yx', 'future_landmarks']) through a LandmarkDetector (imm_amd/inference.py): the pose
+    encoder alone with its batch norms folded, on the batches' `future_image` (the pose encoder's input)."""
+    results = {}
+    for inputs in dataset_iter:
+        mu = detector.detect(inputs['future_image'])
+        results.setdefault('gauss_yx', []).append(mu.cpu().numpy())
+        lm = inputs['future_landmarks']
+        results.setdefault('future_landmarks', []).append(lm.detach().float().cpu().numpy() if torch.is_tensor(lm) else np.asarray(lm))
+    return results
+
+
+def evaluate_regression(net_instance, train_iter, test_iter, im_size, batch_size=100, bias=False, detector=None):
+    """scripts/test.py:18-65 `evaluate`: unsupervised landmarks of both splits -> Ridge -> inter-ocular error.  detector: a
+    LandmarkDetector that computes the landmarks of both splits instead of net_instance.build."""
     def run(it):
-        res = evaluate(it, net_instance, batch_size=batch_size, random_seed=0, eval_tensors=['gauss_yx', 'future_landmarks'])
+        if detector is not None:
+            res = detect_landmarks(it, detector)
+        else:
+            res = evaluate(it, net_instance, batch_size=batch_size, random_seed=0, eval_tensors=['gauss_yx', 'future_landmarks'])
         return {k: np.concatenate(v) for k, v in res.items()}
     train_t, test_t = run(train_iter), run(test_iter)
     pred = regress_landmarks(train_t, test_t, im_size, bias)

@@ -1,0 +1,374 @@
+"""Landmark detection with a trained model: the pose encoder alone, batch norm folded into the convolutions.
+
+What the reference offers for detection is IMMModel.build(training_pl=False, build_loss=False): the whole model in eval mode
+(both encoders and the renderer) to read off `gauss_yx`, which depends on the pose encoder only.  On this build that path is a
+training engine per batch size (flat gradients, optimizer slots, VGG weights, every training activation) and every pose-encoder
+block is a 16-bit conv output followed by a batch-norm pass over it.
+
+In eval mode the batch norm of a block is a per-channel affine map with the moving statistics, so it folds into the convolution
+in front of it (host, f64, once per construction or refresh()):
+
+    s = gamma / sqrt(moving_variance + BN_EPS),   W' = W * s,   b' = (b - moving_mean) * s + beta
+    relu(BN_eval(conv(x, W) + b)) == relu(conv(x, W') + b')
+
+W' is packed to 16 bits once (imm_pack_weights: one rounding per weight, like the training engine's W), b' stays f32.  A batch
+of images is then 10 launches, captured into a HIP graph per power-of-two batch bucket:
+
+    [imm_resize_crop_u8]          u8 images of any size -> f32 S x S (TF1 bilinear, align_corners; list input only, issued
+                                  ahead of the graph because the packed pixel buffer changes from call to call)
+    conv_1 7x7, 3 -> f            imm_conv_first with BIAS | RELU (straight from the f32 image; tap-unrolled 7x1 form where
+                                  imm_conv_first_supported says no)
+    conv_2 .. conv_8              imm_conv2d with BIAS | RELU (the kernel family imm_conv2d_variant names)
+    pose head                     imm_pose_head_fwd: 1x1 conv 8f -> K, soft-argmax -> heat maps and mu
+
+No statistics, no batch-norm launches, nothing written back to the model: parameters, moving statistics, loss normalisers,
+step counters stay bit-identical.  Eval-mode batch norm is per sample, so the zero-padded tail of a bucket cannot change a result.
+"""
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import ops
+from .engine import BN_EPS, encoder_spec
+
+POSE_SCOPE = 'model/pose_encoder'
+MAX_LANDMARKS = 64            # the soft-argmax / pose-head kernels' limit
+
+
+def fold_batch_norm(w, b, gamma, beta, moving_mean, moving_variance, eps=BN_EPS):
+    """(W', b') in f64 with conv(x, W') + b' == BN_eval(conv(x, W) + b); w is HWIO [kh, kw, ci, co], the rest [co]."""
+    w = np.asarray(w, dtype=np.float64)
+    b, gamma, beta, mm, mv = (np.asarray(v, dtype=np.float64) for v in (b, gamma, beta, moving_mean, moving_variance))
+    s = gamma / np.sqrt(mv + eps)
+    return w * s, (b - mm) * s + beta
+
+
+def bucket_sizes(max_batch):
+    """The batch sizes a detector captures programs for: powers of two below max_batch, and max_batch itself."""
+    if max_batch < 1:
+        raise ValueError('max_batch must be >= 1, got %r' % (max_batch,))
+    return [1 << i for i in range(max_batch.bit_length()) if (1 << i) < max_batch] + [int(max_batch)]
+
+
+def plan_buckets(n, max_batch):
+    """[(start, count, bucket)]: images [start, start + count) run as one program of batch `bucket` (count <= bucket <=
+    max_batch; the bucket's last bucket - count rows are zero padding).  Every image is covered exactly once."""
+    sizes = bucket_sizes(int(max_batch))
+    out, start = [], 0
+    while start < n:
+        count = min(int(max_batch), n - start)
+        out.append((start, count, next(s for s in sizes if s >= count)))
+        start += count
+    return out
+
+
+def pose_encoder_names(n_filters):
+    """Variables the detector reads: (parameter names, batch-norm state names), engine / checkpoint naming."""
+    params, state = [], []
+    for i in range(len(encoder_spec(n_filters))):
+        scope = '%s/encoder/conv_%d' % (POSE_SCOPE, i + 1)
+        params += [scope + '/w', scope + '/b', scope + '/gamma', scope + '/beta']
+        state += [scope + '/moving_mean', scope + '/moving_variance']
+    params += [POSE_SCOPE + '/conv_1/w', POSE_SCOPE + '/conv_1/b']
+    return params, state
+
+
+def read_checkpoint(path, n_filters):
+    """Pose-encoder variables of a checkpoint as host f32 tensors: a `.pt` file written by scripts/train.py ({'params', 'state'})
+    or the prefix of a TensorFlow bundle (`<prefix>.index` next to it; the reference's released checkpoints)."""
+    import os
+    pnames, snames = pose_encoder_names(n_filters)
+    if os.path.isfile(path + '.index'):
+        from .utils.tf_checkpoint import read_bundle, tf_variable_name
+        want = {tf_variable_name(n): n for n in pnames + snames}
+        data = read_bundle(path, names=set(want))
+        missing = [t for t in want if t not in data]
+        if missing:
+            raise KeyError('%s lacks %d pose-encoder variables (e.g. %s)' % (path, len(missing), missing[0]))
+        get = {n: torch.from_numpy(np.asarray(data[t], dtype=np.float32)) for t, n in want.items()}
+    elif os.path.isfile(path):
+        ck = torch.load(path, map_location='cpu')
+        src = dict(ck['params'])
+        src.update(ck.get('state') or {})
+        missing = [n for n in pnames + snames if n not in src]
+        if missing:
+            raise KeyError('%s lacks %d pose-encoder variables (e.g. %s)' % (path, len(missing), missing[0]))
+        get = {n: torch.as_tensor(src[n], dtype=torch.float32) for n in pnames + snames}
+    else:
+        raise FileNotFoundError('checkpoint %s not found (neither a file nor a TensorFlow bundle prefix)' % path)
+    return {n: get[n] for n in pnames}, {n: get[n] for n in snames}
+
+
+class _Launch(object):
+    __slots__ = ('tag', 'name', 'family', 'fn')
+
+    def __init__(self, tag, name, family, fn):
+        self.tag, self.name, self.family, self.fn = tag, name, family, fn
+
+
+class LandmarkDetector(object):
+    """Unsupervised landmarks of a trained model: detect(images) -> mu f32 [N, K, 2], (y, x) in [-1, 1] (= the eval path's
+    `gauss_yx`).  `model` is an IMMModel whose variables exist (trained, restored, or built once); the detector reads them,
+    never writes them, and refresh() re-reads them after further training."""
+
+    def __init__(self, model, image_size=128, max_batch=256, use_graph=True):
+        eng = getattr(model, '_master', None) or getattr(model, 'engine', None)
+        if eng is None:
+            raise RuntimeError('the model has no variables yet: build, train or restore it first '
+                               '(or use LandmarkDetector.from_checkpoint)')
+        self._model = model
+        self._static = None
+        self._setup(model._config, model.dtype, eng.dev, image_size, max_batch, use_graph)
+        self.refresh()
+
+    @classmethod
+    def from_checkpoint(cls, config, path, image_size=128, max_batch=256, dtype=torch.bfloat16, device=None, use_graph=True):
+        """A detector straight from a checkpoint (`.pt` file or TensorFlow bundle prefix), without a training engine.
+        config: the `model:` block of the experiment config (config.model)."""
+        det = cls.__new__(cls)
+        det._model = None
+        det._static = read_checkpoint(path, int(config.n_filters))
+        if device is None:
+            device = 'cuda:%d' % torch.cuda.current_device()
+        det._setup(config, dtype, torch.device(device), image_size, max_batch, use_graph)
+        det.refresh()
+        return det
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    def _setup(self, cfg, dtype, device, image_size, max_batch, use_graph):
+        if dtype == torch.float32:
+            raise NotImplementedError('the landmark detector runs the 16-bit kernels (bf16 / f16); the f32 witness engine is a '
+                                      'test instrument without one')
+        ops.dtype_enum(dtype)
+        S = int(image_size)
+        if S % 16 or S < 64:
+            raise ValueError('image side must be a multiple of 16 and >= 64')
+        K, nf = int(cfg.n_maps), int(cfg.n_filters)
+        if not 1 <= K <= MAX_LANDMARKS:
+            raise NotImplementedError('the detector serves 1..%d landmarks (the soft-argmax limit), got %d' % (MAX_LANDMARKS, K))
+        ops.gauss_mode_enum(cfg.gauss_mode)
+        L.load()
+        self.cfg, self.dt, self.dev, self.S, self.K, self.nf = cfg, dtype, torch.device(device), S, K, nf
+        self.max_batch = int(max_batch)
+        bucket_sizes(self.max_batch)
+        self.use_graph = bool(use_graph)
+        self.He = S // 8
+        self.inv_std = 1.0 / float(cfg.gauss_std)
+        self.spec = encoder_spec(nf)
+        if self.spec[0][0] != 7 or self.spec[0][1] != 3:
+            raise NotImplementedError('first encoder layer must be 7x7 over RGB')
+        self.ldh = ops.round_up(K, 4)
+        C, He = 8 * nf, self.He
+        # the one-launch pose head (imm_pose_head_fwd), under the engine's conditions; else the 1x1 convolution + soft-argmax pair
+        self.fused_head = (C % 32 == 0 and (He * He) % 16 == 0 and 4 * (He * He * K + 2 * He * K + 2 * K) <= 158 * 1024 and
+                           4 * ((2 + 2 * He) * K + 516) + He * He * ops.round_up(K, 32) * 2 <= 158 * 1024)
+        self.stream = torch.cuda.Stream(device=self.dev)
+        self._stager = ops.PinnedStager()
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            # packed filters and folded biases (shared by every bucket)
+            self.wt, self.bias, self.kpad = [], [], []
+            for i, (k, ci, co, _st) in enumerate(self.spec):
+                kpad = ops.round_up(7 * 32, 32) if i == 0 else ops.round_up(k * k * ci, 32)
+                self.kpad.append(kpad)
+                self.wt.append(torch.zeros(ops.round_up(co, 128), kpad, dtype=dtype, device=self.dev))
+                self.bias.append(torch.zeros(co, dtype=torch.float32, device=self.dev))
+            self.wt_head = torch.zeros(ops.round_up(K, 128), ops.round_up(C, 32), dtype=dtype, device=self.dev)
+            self.bias_head = torch.zeros(K, dtype=torch.float32, device=self.dev)
+        self._cap = 0
+        self._graphs = {}
+
+    def refresh(self):
+        """(Re-)read the variables (the model's current ones, or the checkpoint's), fold the batch norms and re-pack the filters
+        in place: captured programs stay valid."""
+        if self._static is not None:
+            params, state = self._static
+        else:
+            eng = getattr(self._model, '_master', None) or self._model.engine
+            pnames, snames = pose_encoder_names(self.nf)
+            params = {n: ops.download(eng.pview[n]) for n in pnames}
+            state = {n: ops.download(eng.state[n]) for n in snames}
+        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            for i, (k, ci, co, _st) in enumerate(self.spec):
+                scope = '%s/encoder/conv_%d' % (POSE_SCOPE, i + 1)
+                g = lambda n: params[scope + '/' + n].double().numpy()
+                wf, bf = fold_batch_norm(g('w'), g('b'), g('gamma'), g('beta'), state[scope + '/moving_mean'].double().numpy(),
+                                         state[scope + '/moving_variance'].double().numpy())
+                if wf.shape != (k, k, ci, co):
+                    raise ValueError('%s/w: shape %s != %s' % (scope, wf.shape, (k, k, ci, co)))
+                w_dev = torch.empty(wf.shape, dtype=torch.float32, device=self.dev)
+                ops.upload(w_dev, torch.from_numpy(wf.astype(np.float32)), scope + '/w (folded)')
+                rows, kpad = self.wt[i].shape
+                if i == 0:      # HWIO [7, 7, 3, co] is [7, 1, 21, co]: the tap-unrolled 7x1 filter image both conv_1 forms read
+                    ops.pack_weights(w_dev, self.wt[i], 0, k, 1, 3 * k, co, 32, rows, kpad)
+                else:
+                    ops.pack_weights(w_dev, self.wt[i], 0, k, k, ci, co, ci, rows, kpad)
+                ops.upload(self.bias[i], torch.from_numpy(bf.astype(np.float32)), scope + '/b (folded)')
+            C = 8 * self.nf
+            w_dev = torch.empty(1, 1, C, self.K, dtype=torch.float32, device=self.dev)
+            ops.upload(w_dev, params[POSE_SCOPE + '/conv_1/w'], POSE_SCOPE + '/conv_1/w')
+            rows, kpad = self.wt_head.shape
+            ops.pack_weights(w_dev, self.wt_head, 0, 1, 1, C, self.K, C, rows, kpad)
+            ops.upload(self.bias_head, params[POSE_SCOPE + '/conv_1/b'], POSE_SCOPE + '/conv_1/b')
+            self.stream.synchronize()
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    def _ensure_capacity(self, batch):
+        """Activations of one bucket, sized for the largest bucket run so far (smaller buckets use leading views)."""
+        if batch <= self._cap:
+            return
+        self.stream.synchronize()
+        self._graphs = {}                              # they address the old buffers
+        S, K, He, nf = self.S, self.K, self.He, self.nf
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            self._img = torch.zeros(batch, S, S, 3, device=self.dev)
+            self._xin = None
+            n_act = max(batch * (S // down) ** 2 * co for down, co in self._act_shapes())
+            self._act = [torch.zeros(n_act, dtype=self.dt, device=self.dev) for _ in range(2)]
+            self._heat = torch.zeros(batch, He, He, self.ldh, device=self.dev)
+            self._mu = torch.zeros(batch, K, 2, device=self.dev)
+            self._py = torch.zeros(batch, He, K, device=self.dev)
+            self._px = torch.zeros(batch, He, K, device=self.dev)
+        self._cap = batch
+
+    def _act_shapes(self):
+        """(down-scaling of the side, channels) of every layer's output."""
+        out, f = [], 1
+        for (_k, _ci, co, st) in self.spec:
+            f *= st
+            out.append((f, co))
+        return out
+
+    def _xin_for(self, batch):
+        if self._xin is None or self._xin.shape[0] < batch:
+            with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+                self._xin = torch.zeros(self._cap, self.S, self.S, 32, dtype=self.dt, device=self.dev)
+        return self._xin[:batch]
+
+    def program(self, batch, u8=False):
+        """The launches of one bucket: [_Launch(tag, name, family, fn)].  tag: 'resize' | 'pack_image' | 'conv' | 'pose_head'
+        (| 'softargmax' for heads the one-launch kernel does not serve); family: the conv kernel family (imm_conv2d_variant's,
+        'first' for imm_conv_first)."""
+        self._ensure_capacity(batch)
+        B, S, dt = int(batch), self.S, self.dt
+        prog = []
+        if u8:
+            prog.append(_Launch('resize', 'resize_crop_u8', 'resize', None))     # issued by detect() with the call's pixels
+        img = self._img[:B]
+        x, H, ci, ld = None, S, 3, 3
+        for i, (k, ci_, co, st) in enumerate(self.spec):
+            name = '%s/encoder/conv_%d' % (POSE_SCOPE, i + 1)
+            y = self._act[i % 2][:B * (-(-H // st)) ** 2 * co].view(B, -(-H // st), -(-H // st), co)
+            if i == 0:
+                if ops.conv_first_supported(B, S, co, co):
+                    prog.append(_Launch('conv', name, 'first', (lambda y=y, i=i, co=co: ops.conv_first(
+                        img, self.wt[i], self.bias[i], y, co, None, B, S, co, L.CONV_BIAS | L.CONV_RELU))))
+                else:
+                    xin = self._xin_for(B)
+                    prog.append(_Launch('pack_image', name + '/pack', 'pack_image',
+                                        lambda xin=xin: ops.pack_image_taps(img, xin, B, S, S, 7, 3, 32)))
+                    d = ops.fwd_desc(B, S, S, 32, 32, co, co, 7, 1, L.CONV_BIAS | L.CONV_RELU, kw=1)
+                    prog.append(_Launch('conv', name, ops.conv2d_variant(d, dt)[0],
+                                        (lambda d=d, xin=xin, y=y, i=i: ops.conv2d(d, xin, self.wt[i], self.bias[i], y))))
+            else:
+                d = ops.fwd_desc(B, H, H, ci, ld, co, co, k, st, L.CONV_BIAS | L.CONV_RELU)
+                prog.append(_Launch('conv', name, ops.conv2d_variant(d, dt)[0],
+                                    (lambda d=d, x=x, y=y, i=i: ops.conv2d(d, x, self.wt[i], self.bias[i], y))))
+            x, H, ci, ld = y, y.shape[1], co, co
+        He, K, C = self.He, self.K, 8 * self.nf
+        assert H == He
+        heat, mu, py, px = self._heat[:B], self._mu[:B], self._py[:B], self._px[:B]
+        mode = self.cfg.gauss_mode
+        if self.fused_head:
+            prog.append(_Launch('pose_head', POSE_SCOPE + '/conv_1', 'pose_head', lambda: ops.pose_head_fwd(
+                x, C, C, self.wt_head, self.bias_head, B, He, He, K, self.inv_std, 16, heat, self.ldh, mu, py, px, None, K, dt, mode)))
+        else:
+            d = ops.fwd_desc(B, He, He, C, C, K, self.ldh, 1, 1, L.CONV_BIAS | L.CONV_OUT_F32)
+            prog.append(_Launch('conv', POSE_SCOPE + '/conv_1', ops.conv2d_variant(d, dt)[0],
+                                lambda: ops.conv2d(d, x, self.wt_head, self.bias_head, heat)))
+            prog.append(_Launch('softargmax', POSE_SCOPE + '/softargmax', 'softargmax', lambda: ops.softargmax_gauss_fwd(
+                heat, self.ldh, B, He, He, K, self.inv_std, 16, mu, py, px, None, K, dt, mode)))
+        return prog
+
+    def _run(self, batch):
+        """Issue the (graph of the) program of bucket `batch` on the detector's stream."""
+        if not self.use_graph:
+            for l in self.program(batch):
+                if l.fn is not None:
+                    l.fn()
+            return
+        g = self._graphs.get(batch)
+        if g is None:
+            prog = [l for l in self.program(batch) if l.fn is not None]
+            for l in prog:                 # warm-up outside capture (code-object loading, LDS attribute calls)
+                l.fn()
+            self.stream.synchronize()
+            g = ops.Graph()
+            g.capture_begin()
+            for l in prog:
+                l.fn()
+            g.capture_end()
+            self._graphs[batch] = g
+        g.launch()
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    def _stage_u8(self, images, count):
+        """Pack u8 HWC images back to back (16-byte aligned starts, like the data loader) and resize them on the GPU into
+        the first `count` rows of the input buffer."""
+        decoded = []
+        for a in images:
+            a = np.asarray(a)
+            if a.dtype != np.uint8:
+                raise TypeError('image arrays must be uint8 HWC, got %s' % a.dtype)
+            if a.ndim == 2:
+                a = a[:, :, None]
+            if a.ndim != 3 or a.shape[2] not in (1, 3):
+                raise ValueError('image arrays must be HxW, HxWx1 or HxWx3, got shape %s' % (a.shape,))
+            if a.shape[2] == 1:
+                a = np.repeat(a, 3, axis=2)
+            decoded.append(np.ascontiguousarray(a))
+        offs = np.zeros(count, dtype=np.int64)
+        total = 0
+        for i, a in enumerate(decoded):
+            offs[i] = total
+            total += (a.size + 15) & ~15
+        packed = np.zeros(max(total, 16), dtype=np.uint8)
+        for a, o in zip(decoded, offs):
+            packed[o:o + a.size] = a.reshape(-1)
+        hw = np.array([a.shape[:2] for a in decoded], dtype=np.int32)
+        src = ops.to_device_pinned(packed, self.dev)
+        offs_d = ops.to_device_pinned(offs, self.dev)
+        hw_d = ops.to_device_pinned(hw, self.dev)
+        ops.resize_crop_u8(src, offs_d, hw_d, 3, (self.S, self.S), (0, 0), (self.S, self.S), self._img[:count])
+
+    def detect(self, images, heatmaps=False):
+        """images: NHWC float [N, S, S, 3] with values in [0, 255] (host or device), or a list of u8 HWC arrays of any sizes
+        (resized to S x S on the GPU).  Returns mu f32 [N, K, 2] on the detector's device, and with heatmaps=True also the pose
+        head's heat maps f32 [N, S/8, S/8, K]."""
+        u8 = isinstance(images, (list, tuple))
+        if not u8:
+            images = torch.as_tensor(images)
+            if images.dim() != 4 or tuple(images.shape[1:]) != (self.S, self.S, 3):
+                raise ValueError('images must be [N, %d, %d, 3], got %s' % (self.S, self.S, tuple(images.shape)))
+            if images.is_cuda and images.dtype != torch.float32:
+                images = images.float()
+        N, K, He = len(images), self.K, self.He
+        cur = torch.cuda.current_stream(self.dev)
+        mu_out = torch.empty(N, K, 2, device=self.dev)
+        heat_out = torch.empty(N, He, He, K, device=self.dev) if heatmaps else None
+        self.stream.wait_stream(cur)
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            for start, count, bucket in plan_buckets(N, self.max_batch):
+                self._ensure_capacity(bucket)
+                if u8:
+                    self._stage_u8(images[start:start + count], count)
+                else:
+                    self._stager.copy(self._img[:count], images[start:start + count], ('images', count))
+                if count < bucket:
+                    self._img[count:bucket].zero_()
+                self._run(bucket)
+                mu_out[start:start + count].copy_(self._mu[:count])
+                if heatmaps:
+                    heat_out[start:start + count].copy_(self._heat[:count, ..., :K])
+        cur.wait_stream(self.stream)
+        return (mu_out, heat_out) if heatmaps else mu_out

@@ -111,6 +111,12 @@ class IMMModel(BaseModel):
         self.engine = self._engines[key]
         return self.engine
 
+    def landmark_detector(self, image_size, max_batch=256):
+        """A LandmarkDetector (imm_amd/inference.py) over this model's current variables: the pose encoder alone, batch norm
+        folded into the convolutions, one captured program per power-of-two batch bucket up to max_batch."""
+        from ..inference import LandmarkDetector
+        return LandmarkDetector(self, image_size=image_size, max_batch=max_batch)
+
     # -- reference surface -----------------------------------------------------------------------------
     def build(self, inputs, training_pl, costs_collection='costs', scope=None, var_device='/cpu:0',
               output_tensors=False, build_loss=True):

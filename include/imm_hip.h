@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define IMM_ABI_VERSION 21   /* 21: imm_masked_sse_all.  20: imm_vgg_head_fwd / imm_vgg_head_supported / imm_vgg_head_scratch_bytes (conv1_1 + conv1_2 in one launch).  19: imm_set_cu_limit / imm_get_cu_limit, imm_masked_sse_pool with pool_a == NULL.  18: imm_copy_f32.  17: imm_cost_ema, imm_rms16 (summaries).  16: imm_conv2d_variant.  15: imm_conv2d_dgrad_s2, imm_conv2d_nol, imm_conv_first, imm_wgrad_job.x_scale/x_shift/x_relu; entry points removed
+#define IMM_ABI_VERSION 22   /* 22: s2f / conv_first accept IMM_CONV_RELU.  21: imm_masked_sse_all.  20: imm_vgg_head_fwd / imm_vgg_head_supported / imm_vgg_head_scratch_bytes (conv1_1 + conv1_2 in one launch).  19: imm_set_cu_limit / imm_get_cu_limit, imm_masked_sse_pool with pool_a == NULL.  18: imm_copy_f32.  17: imm_cost_ema, imm_rms16 (summaries).  16: imm_conv2d_variant.  15: imm_conv2d_dgrad_s2, imm_conv2d_nol, imm_conv_first, imm_wgrad_job.x_scale/x_shift/x_relu; entry points removed
                                   since 14 (imm_bn_bwd_reduce_finalize, imm_conv2d_stats_workspace_bytes) finally counted */
 
 /* IMM_F32 (round 6): f32 activation storage — the exact-arithmetic WITNESS of the wiring, a test instrument (the reference computes
@@ -308,7 +308,7 @@ int imm_pack_image_taps(const float* src, void* dst, int dtype, int batch, int h
  * straight from the f32 image [batch,s,s,3]: the tap-unrolled operand tile of the 7x1 form above is built in LDS per 8x16-pixel
  * patch instead of being written to HBM by imm_pack_image_taps and read back.  wt = the SAME packed filter image the 7x1 form uses
  * (imm_pack_weights mode 0, kh 7, kw 1, ci_real 21, c_pad 32: row length kpad >= 224), so the arithmetic (16-bit operands, f32
- * accumulation) is unchanged.  y 16-bit [batch,s,s] with pixel stride ldy; flags: IMM_CONV_BIAS, IMM_CONV_STATS (partial rows
+ * accumulation) is unchanged.  y 16-bit [batch,s,s] with pixel stride ldy; flags: IMM_CONV_BIAS, IMM_CONV_RELU, IMM_CONV_STATS (partial rows
  * [imm_conv_first_stats_blocks(batch, s)][2][co]).  s % 16 == 0, co % 4 == 0.  imm_conv_first_supported: 1 / 0. */
 int imm_conv_first_supported(int batch, int s, int co, int ldy);
 int imm_conv_first_stats_blocks(int batch, int s);

@@ -73,8 +73,9 @@ def main(args):
     else:
         ck = torch.load(ckpt, map_location='cpu')
         eng.load_parameters(ck['params'], ck.get('state'))
+    detector = net.landmark_detector(args.im_size, max_batch=args.batch_size) if args.detector else None
     err = eval_imm.evaluate_regression(net, train_it, test_it, [args.im_size, args.im_size], batch_size=args.batch_size,
-                                       bias=args.bias)
+                                       bias=args.bias, detector=detector)
     model_dataset = config.training.train_dset_params.dataset if hasattr(config.training, 'train_dset_params') and \
         'dataset' in config.training.train_dset_params else getattr(config.training, 'dset', '?')
     print('')
@@ -102,4 +103,6 @@ if __name__ == '__main__':
     parser.add_argument('--checkpoint', type=str, default=None, help='explicit checkpoint file (default: <logdir>/model.ckpt[-N].pt)')
     parser.add_argument('--train-npz', type=str, default=None)
     parser.add_argument('--test-npz', type=str, default=None)
+    parser.add_argument('--detector', action='store_true',
+                        help='landmarks through the LandmarkDetector (pose encoder only, batch norm folded) instead of the full eval model')
     main(parser.parse_args())
