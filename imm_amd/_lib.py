@@ -20,7 +20,7 @@ CONV_BIAS, CONV_RELU, CONV_STATS, CONV_MASK, CONV_OUT_F32 = 1, 2, 4, 8, 16
 SSE_BLOCKS = 512
 OPTIMIZERS = {'adam': 0, 'adadelta': 1, 'adagrad': 2}      # IMM_OPT_* (scripts/train.py:97-104)
 GAUSS_MODES = {'rot': 0, 'flat': 1, 'ankush': 2}     # IMM_GAUSS_* (config key gauss_mode, imm_model.py:48-72)
-ABI_VERSION = 22     # 22: s2f / conv_first accept IMM_CONV_RELU
+ABI_VERSION = 23     # 23: render-only mode of imm_softargmax_gauss_fwd (heat NULL).  22: s2f / conv_first accept IMM_CONV_RELU
 
 
 class ImmHipError(RuntimeError):

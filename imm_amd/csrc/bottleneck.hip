@@ -323,6 +323,24 @@ __global__ __launch_bounds__(HEAD ? PH_BWD_THREADS : BT_THREADS) void softargmax
   }
 }
 
+// Render-only mode of imm_softargmax_gauss_fwd (heat == NULL): the Gaussian maps of landmarks given as an INPUT (the image generator's
+// render from detected, edited or averaged mu).  No heat map, no LDS; one thread per (pixel, landmark) and grid.y = the sample,
+// grid.x = enough 256-thread workgroups to cover that sample's s*s*K values, so a small batch still spreads over the chip.  The
+// value is bt_softargmax_tail's render, expression for expression (lin_pm1, gauss_value, ET::from_f32): bit-identical to what the
+// soft-argmax and pose-head kernels write for the same mu.  Channels k < K only; the caller owns the rest of the pixel's row.
+template <typename ET>
+__global__ __launch_bounds__(BT_THREADS) void gauss_render_fwd_kernel(const float* __restrict__ mu, int K, float inv_std, int s,
+                                                                      typename ET::T* __restrict__ gauss, int ldg, int mode) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x * BT_THREADS + threadIdx.x;
+  if (i >= s * s * K) return;
+  const int p = i / K, k = i - p * K;
+  const int yy = p / s, xx = p - yy * s;
+  const float* mb = mu + ((int64_t)b * K + k) * 2;
+  const float dy = lin_pm1(yy, s) - mb[0], dx = lin_pm1(xx, s) - mb[1];
+  gauss[((int64_t)b * s * s + p) * ldg + k] = ET::from_f32(gauss_value(mode, dy, dx, inv_std));
+}
+
 __global__ void gauss_render_f32_kernel(const float* __restrict__ mu, int K, float inv_std, int s, float* __restrict__ out,
                                         int64_t total, int mode) {
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
@@ -351,8 +369,19 @@ static int set_dyn_lds(K_ kernel, size_t bytes) {
 extern "C" int imm_softargmax_gauss_fwd(const float* heat, int ldh, int batch, int h, int w, int k, float inv_std, int s,
                                         float* mu, float* py, float* px, void* gauss_out, int ldg, int dtype,
                                         int gauss_mode, void* stream) {
-  IMM_REQUIRE(heat && mu && py && px, "softargmax_fwd: null");
   IMM_REQUIRE(gauss_mode >= IMM_GAUSS_ROT && gauss_mode <= IMM_GAUSS_ANKUSH, "softargmax_fwd: gauss_mode %d", gauss_mode);
+  if (heat == nullptr) {            // render-only mode: mu is the input, py / px are not touched
+    IMM_REQUIRE(mu && gauss_out, "softargmax_fwd: null");
+    IMM_REQUIRE(batch > 0 && k > 0 && s > 0 && ldg >= k && batch <= 65535, "softargmax_fwd: dims");
+    const int64_t per = (int64_t)s * s * k;
+    IMM_REQUIRE(per < (1LL << 31), "softargmax_fwd: %dx%dx%d render", s, s, k);
+    const dim3 grid((unsigned)((per + BT_THREADS - 1) / BT_THREADS), (unsigned)batch);
+    IMM_DISPATCH_DTYPE_F32(dtype, hipLaunchKernelGGL((gauss_render_fwd_kernel<ET>), grid, dim3(BT_THREADS), 0, (hipStream_t)stream, mu, k,
+                                                     inv_std, s, (typename ET::T*)gauss_out, ldg, gauss_mode));
+    IMM_CHECK_LAUNCH("imm_softargmax_gauss_fwd(render)");
+    return 0;
+  }
+  IMM_REQUIRE(mu && py && px, "softargmax_fwd: null");
   IMM_REQUIRE(batch > 0 && h > 0 && w > 0 && k > 0 && ldh >= k && s > 0, "softargmax_fwd: dims");
   IMM_REQUIRE(gauss_out == nullptr || ldg >= k, "softargmax_fwd: ldg");
   const size_t lds = sizeof(float) * ((size_t)h * w * k + (size_t)(h + w) * k + 2 * (size_t)k);

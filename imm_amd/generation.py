@@ -1,0 +1,336 @@
+"""Image generation with a trained model: render image y from the appearance of image x and the landmarks of y, batch norm folded.
+
+What the reference offers is IMMModel.build(inputs, training_pl=False, build_loss=False)['future_im_pred']: a training engine per
+batch size, a batch-norm pass after every encoder and renderer convolution, and image[i] paired with future_image[i] only.
+ImageGenerator runs the eval-mode model as three captured stages per power-of-two bucket, each batch norm folded into the
+convolution in front of it on the host in f64 (inference.fold_batch_norm), filters packed once to 16 bits, biases f32:
+
+    appearance   image encoder, 8 x conv + bias + ReLU (inference.folded_encoder_program); conv_8 writes its 8f channels straight
+                 into channels [0, 8f) of the joint buffer at He = 16, or through imm_resize_ac_fwd (align corners) at He != 16
+    pose         the LandmarkDetector's own program (gen.detector): its landmarks are detect()'s, bit for bit
+    render       Gaussian maps of the INPUT landmarks at 16 x 16 into channels [8f, 8f + K) of the joint buffer (render-only
+                 imm_softargmax_gauss_fwd), then renderer_spec: conv + bias + ReLU blocks, imm_upsample2x_fwd after the
+                 up-sampled ones, and the final conv + bias in f32 (no batch norm, no activation)
+
+The joint buffer [n, 16, 16, Cj] is allocated zeroed; its channels [8f + K, Cj) (Cj = round_up(8f + K, 64), the padding the
+deep-K kernels need) are never written.  Eval-mode batch norm is per sample, so a zero-padded bucket tail changes no result.
+Nothing is written to the model: parameters, moving statistics, loss normalisers and step counters stay bit-identical.
+"""
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import ops
+from .engine import encoder_spec, n_renderer_out, render_sizes, renderer_spec, trainable_spec
+from .inference import (LandmarkDetector, _Launch, alloc_encoder_weights, as_image_batch, bucket_sizes, check_limits,
+                        encoder_act_elems, fold_batch_norm, folded_encoder_program, pack_folded_encoder, plan_buckets,
+                        read_variables, stage_u8)
+
+IMAGE_SCOPE = 'model/image_encoder'
+RENDER_SCOPE = 'model/renderer'
+
+
+def generator_names(cfg, image_size):
+    """Variables the generator reads: (every trainable name of trainable_spec, every batch-norm block's moving statistics)."""
+    params = [n for n, _shape, _wd in trainable_spec(cfg, image_size)]
+    state = []
+    for n in params:
+        if n.endswith('/gamma'):
+            sc = n[:-len('/gamma')]
+            state += [sc + '/moving_mean', sc + '/moving_variance']
+    return params, state
+
+
+def plan_pairs(n_a, n_p, max_batch):
+    """[(start, count, bucket, a_idx, p_idx)]: pairs [start, start + count) of the a-major A x P grid (pair i = (i // P, i % P))
+    rendered as one program of batch `bucket`; every (a, p) is covered exactly once."""
+    out = []
+    for start, count, bucket in plan_buckets(n_a * n_p, max_batch):
+        idx = np.arange(start, start + count)
+        out.append((start, count, bucket, idx // n_p, idx % n_p))
+    return out
+
+
+def _split(names, get):
+    return {n: get[n] for n in names}
+
+
+class ImageGenerator(object):
+    """reconstruct(x, y) / render(x, landmarks) / transfer(appearance, poses) of a trained model (see the module docstring).
+    `model` is an IMMModel whose variables exist; the generator reads them, never writes them, and refresh() re-reads them."""
+
+    def __init__(self, model, image_size=128, max_batch=128, use_graph=True):
+        eng = getattr(model, '_master', None) or getattr(model, 'engine', None)
+        if eng is None:
+            raise RuntimeError('the model has no variables yet: build, train or restore it first '
+                               '(or use ImageGenerator.from_checkpoint)')
+        self._model = model
+        self._static = None
+        self._check(model._config, model.dtype, image_size)
+        self.detector = LandmarkDetector(model, image_size=image_size, max_batch=max_batch, use_graph=use_graph)
+        self._setup(model._config, model.dtype, eng.dev, image_size, max_batch, use_graph)
+        self.refresh(detector=False)
+
+    @classmethod
+    def from_checkpoint(cls, config, path, image_size=128, max_batch=128, dtype=torch.bfloat16, device=None, use_graph=True):
+        """A generator straight from a checkpoint (`.pt` file written by scripts/train.py or TensorFlow bundle prefix), without a
+        training engine.  config: the `model:` block of the experiment config (config.model)."""
+        cls._check(config, dtype, image_size)
+        pnames, snames = generator_names(config, int(image_size))
+        get = read_variables(path, pnames + snames, 'generator')
+        gen = cls.__new__(cls)
+        gen._model = None
+        gen._static = (_split(pnames, get), _split(snames, get))
+        if device is None:
+            device = 'cuda:%d' % torch.cuda.current_device()
+        gen.detector = LandmarkDetector._from_variables(config, gen._static, image_size, max_batch, dtype, device, use_graph)
+        gen._setup(config, dtype, torch.device(device), image_size, max_batch, use_graph)
+        gen.refresh(detector=False)
+        return gen
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _check(cfg, dtype, image_size):
+        check_limits(cfg, dtype, image_size, 'generator')
+        s16 = render_sizes(cfg, int(image_size))[-1]
+        if s16 != 16:
+            raise NotImplementedError('renderer starts at 16x16 (min_res 16, renderer_stride 2): got %d' % s16)
+
+    def _setup(self, cfg, dtype, device, image_size, max_batch, use_graph):
+        S, K, nf = check_limits(cfg, dtype, image_size, 'generator')
+        L.load()
+        self.cfg, self.dt, self.dev, self.S, self.K, self.nf = cfg, dtype, torch.device(device), S, K, nf
+        self.max_batch = int(max_batch)
+        bucket_sizes(self.max_batch)
+        self.use_graph = bool(use_graph)
+        self.He = S // 8
+        self.C8 = 8 * nf
+        self.Cj = ops.round_up(self.C8 + K, 64)      # the engine's joint width: whole 64-channel K slices, zero padded
+        self.inv_std = 1.0 / float(cfg.gauss_std)
+        self.spec = encoder_spec(nf)
+        self.n_out = n_renderer_out(cfg)
+        self.rspec = renderer_spec(cfg, S, self.n_out)
+        self.ldp = ops.round_up(self.n_out, 4)
+        self.stream = torch.cuda.Stream(device=self.dev)
+        self._stager = ops.PinnedStager()
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            self.wt_im, self.bias_im = alloc_encoder_weights(self.spec, dtype, self.dev)
+            self.wt_r, self.bias_r = [], []
+            ci_pad = self.Cj
+            for (k, _ci, co, _bn, _up) in self.rspec:
+                self.wt_r.append(torch.zeros(ops.round_up(co, 128), ops.round_up(k * k * ci_pad, 32), dtype=dtype, device=self.dev))
+                self.bias_r.append(torch.zeros(co, dtype=torch.float32, device=self.dev))
+                ci_pad = co
+        self._cap = 0
+        self._graphs = {}
+
+    def refresh(self, detector=True):
+        """(Re-)read the variables (the model's current ones, or the checkpoint's), fold the batch norms and re-pack the filters
+        in place: captured programs stay valid.  detector=True refreshes gen.detector too."""
+        if self._static is not None:
+            params, state = self._static
+        else:
+            eng = getattr(self._model, '_master', None) or self._model.engine
+            pnames, snames = generator_names(self.cfg, self.S)
+            params = {n: ops.download(eng.pview[n]) for n in pnames}
+            state = {n: ops.download(eng.state[n]) for n in snames}
+        if detector:
+            self.detector.refresh()
+        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            pack_folded_encoder(params, state, IMAGE_SCOPE, self.spec, self.wt_im, self.bias_im, self.dev)
+            ci_real, ci_pad = self.C8 + self.K, self.Cj
+            for i, (k, ci, co, bn, _up) in enumerate(self.rspec):
+                sc = '%s/conv_%d' % (RENDER_SCOPE, i + 1)
+                w, b = params[sc + '/w'].double().numpy(), params[sc + '/b'].double().numpy()
+                if bn:
+                    w, b = fold_batch_norm(w, b, params[sc + '/gamma'], params[sc + '/beta'], state[sc + '/moving_mean'],
+                                           state[sc + '/moving_variance'])
+                if w.shape != (k, k, ci, co) or ci != ci_real:
+                    raise ValueError('%s/w: shape %s != %s' % (sc, w.shape, (k, k, ci_real, co)))
+                w_dev = torch.empty(w.shape, dtype=torch.float32, device=self.dev)
+                ops.upload(w_dev, torch.from_numpy(w.astype(np.float32)), sc + '/w (folded)' if bn else sc + '/w')
+                rows, kpad = self.wt_r[i].shape
+                ops.pack_weights(w_dev, self.wt_r[i], 0, k, k, ci_real, co, ci_pad, rows, kpad)
+                ops.upload(self.bias_r[i], torch.from_numpy(b.astype(np.float32)), sc + '/b (folded)' if bn else sc + '/b')
+                ci_real, ci_pad = co, co
+            self.stream.synchronize()
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    def _render_act_elems(self, batch):
+        H, n = 16, 0
+        for (_k, _ci, co, bn, up) in self.rspec:
+            if bn:
+                n = max(n, batch * H * H * co)
+            if up:
+                H *= 2
+                n = max(n, batch * H * H * co)
+        return n
+
+    def _ensure_capacity(self, batch):
+        """Buffers of one bucket, sized for the largest bucket run so far (smaller buckets use leading views)."""
+        if batch <= self._cap:
+            return
+        self.stream.synchronize()
+        self._graphs = {}                              # they address the old buffers
+        S, K = self.S, self.K
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            self._img = torch.zeros(batch, S, S, 3, device=self.dev)
+            self._xin = None
+            n_act = encoder_act_elems(self.spec, S, batch)
+            self._act = [torch.zeros(n_act, dtype=self.dt, device=self.dev) for _ in range(2)]
+            self._joint = torch.zeros(batch, 16, 16, self.Cj, dtype=self.dt, device=self.dev)    # padding channels stay zero
+            self._mu = torch.zeros(batch, K, 2, device=self.dev)
+            n_r = self._render_act_elems(batch)
+            self._ract = [torch.zeros(n_r, dtype=self.dt, device=self.dev) for _ in range(2)]
+            self._pred = torch.zeros(batch, S, S, self.ldp, device=self.dev)
+        self._cap = batch
+
+    def _xin_for(self, batch):
+        if self._xin is None or self._xin.shape[0] < batch:
+            with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+                self._xin = torch.zeros(self._cap, self.S, self.S, 32, dtype=self.dt, device=self.dev)
+        return self._xin[:batch]
+
+    def program(self, stage, batch):
+        """The launches of one bucket of a stage: [_Launch(tag, name, family, fn)].  stage 'appearance': image rows
+        -> joint channels [0, 8f); 'render': landmark rows -> Gaussian maps in the joint buffer -> renderer -> f32 prediction.
+        tag: 'conv' | 'pack_image' | 'resize_ac' | 'gauss' | 'upsample'; family: the conv kernel family (imm_conv2d_variant's)."""
+        self._ensure_capacity(batch)
+        B, dt, C8, Cj = int(batch), self.dt, self.C8, self.Cj
+        joint = self._joint[:B]
+        if stage == 'appearance':
+            direct = self.He == 16
+            prog, x, H, ld = folded_encoder_program(IMAGE_SCOPE, self.spec, B, self.S, self._img[:B], self._act, self.wt_im,
+                                                    self.bias_im, self._xin_for, dt, out=joint if direct else None,
+                                                    ldo=Cj if direct else None)
+            if not direct:       # imm_model.py:324-335: align_corners resize of the 8f-channel embedding down to 16x16
+                prog.append(_Launch('resize_ac', IMAGE_SCOPE + '/resize', 'resize_ac', lambda x=x, H=H, ld=ld: ops.resize_ac_fwd(
+                    x, joint, B, H, H, 16, 16, C8, ld, Cj)))
+            return prog
+        if stage != 'render':
+            raise ValueError('stage must be appearance or render, got %r' % (stage,))
+        mu, mode = self._mu[:B], self.cfg.gauss_mode
+        prog = [_Launch('gauss', 'gaussian_maps', 'gauss_render', lambda: ops.gauss_render_fwd(
+            mu, B, self.K, self.inv_std, 16, joint[..., C8:], Cj, dt, mode))]
+        x, H, ldx, ci_pad = joint, 16, Cj, Cj
+        act_i = 0
+        for i, (k, _ci, co, bn, up) in enumerate(self.rspec):
+            name = '%s/conv_%d' % (RENDER_SCOPE, i + 1)
+            if bn:
+                y = self._ract[act_i][:B * H * H * co].view(B, H, H, co)
+                act_i ^= 1
+                d = ops.fwd_desc(B, H, H, ci_pad, ldx, co, co, k, 1, L.CONV_BIAS | L.CONV_RELU)
+            else:
+                y = self._pred[:B]
+                d = ops.fwd_desc(B, H, H, ci_pad, ldx, co, self.ldp, k, 1, L.CONV_BIAS | L.CONV_OUT_F32)
+            prog.append(_Launch('conv', name, ops.conv2d_variant(d, dt)[0],
+                                (lambda d=d, x=x, y=y, i=i: ops.conv2d(d, x, self.wt_r[i], self.bias_r[i], y))))
+            x, ldx, ci_pad = y, co, co
+            if up:
+                u = self._ract[act_i][:B * 4 * H * H * co].view(B, 2 * H, 2 * H, co)
+                act_i ^= 1
+                prog.append(_Launch('upsample', name + '/upsample', 'upsample', (lambda x=x, u=u, H=H, co=co: ops.upsample2x_fwd(
+                    x, u, B, H, H, co, co, co))))
+                x, H = u, 2 * H
+        assert H == self.S
+        return prog
+
+    def _run(self, stage, batch):
+        """Issue the (graph of the) program of one stage and bucket on the generator's stream."""
+        if not self.use_graph:
+            for l in self.program(stage, batch):
+                l.fn()
+            return
+        g = self._graphs.get((stage, batch))
+        if g is None:
+            prog = self.program(stage, batch)
+            for l in prog:                 # warm-up outside capture (code-object loading, LDS attribute calls)
+                l.fn()
+            self.stream.synchronize()
+            g = ops.Graph()
+            g.capture_begin()
+            for l in prog:
+                l.fn()
+            g.capture_end()
+            self._graphs[(stage, batch)] = g
+        g.launch()
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    def _encode(self, images, u8, start, count, bucket):
+        """Appearance stage of images [start, start + count) into joint rows [0, count) (bucket `bucket`, tail zero images)."""
+        self._ensure_capacity(bucket)
+        if u8:
+            stage_u8(images[start:start + count], self._img[:count], self.S, self.dev)
+        else:
+            self._stager.copy(self._img[:count], images[start:start + count], ('images', count))
+        if count < bucket:
+            self._img[count:bucket].zero_()
+        self._run('appearance', bucket)
+
+    def _landmarks(self, landmarks, n):
+        lm = torch.as_tensor(landmarks)
+        if tuple(lm.shape) != (n, self.K, 2):
+            raise ValueError('landmarks must be [%d, %d, 2], got %s' % (n, self.K, tuple(lm.shape)))
+        return lm.to(device=self.dev, dtype=torch.float32)
+
+    def render(self, images, landmarks):
+        """images (detect()'s forms, N of them) rendered at landmarks f32 [N, K, 2] ((y, x) in [-1, 1]): f32 [N, S, S, 3],
+        unclipped, in the 0..255 scale of future_im_pred."""
+        images, u8 = as_image_batch(images, self.S)
+        N = len(images)
+        cur = torch.cuda.current_stream(self.dev)
+        lm = self._landmarks(landmarks, N)
+        out = torch.empty(N, self.S, self.S, 3, device=self.dev)
+        self.stream.wait_stream(cur)
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            for start, count, bucket in plan_buckets(N, self.max_batch):
+                self._encode(images, u8, start, count, bucket)
+                self._mu[:count].copy_(lm[start:start + count])
+                if count < bucket:
+                    self._mu[count:bucket].zero_()
+                self._run('render', bucket)
+                out[start:start + count].copy_(self._pred[:count, ..., :3])
+        cur.wait_stream(self.stream)
+        return out
+
+    def reconstruct(self, images, future_images):
+        """future_images rendered from the appearance of images (pair i = (images[i], future_images[i])): f32 [N, S, S, 3], the
+        eval path's future_im_pred."""
+        images, _ = as_image_batch(images, self.S)
+        future_images, _ = as_image_batch(future_images, self.S)
+        if len(images) != len(future_images):
+            raise ValueError('images and future_images differ in number: %d != %d' % (len(images), len(future_images)))
+        return self.render(images, self.detector.detect(future_images))
+
+    def transfer(self, appearance, poses, return_landmarks=False):
+        """Every appearance image rendered at every pose image's landmarks: f32 [A, P, S, S, 3], [a, p] = reconstruct(appearance[a],
+        poses[p]).  Each image is encoded once (the appearance stage per A bucket, the detector per P bucket); the A x P pairs are
+        rendered in buckets, their joint rows gathered from the stored features.  return_landmarks=True: (images, the poses'
+        landmarks f32 [P, K, 2] it rendered at)."""
+        appearance, u8 = as_image_batch(appearance, self.S)
+        n_a = len(appearance)
+        mu_p = self.detector.detect(poses)
+        n_p = mu_p.shape[0]
+        cur = torch.cuda.current_stream(self.dev)
+        out = torch.empty(n_a * n_p, self.S, self.S, 3, device=self.dev)
+        self.stream.wait_stream(cur)
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            feats = torch.empty(n_a, 16, 16, self.C8, dtype=self.dt, device=self.dev)
+            for start, count, bucket in plan_buckets(n_a, self.max_batch):
+                self._encode(appearance, u8, start, count, bucket)
+                feats[start:start + count].copy_(self._joint[:count, ..., :self.C8])
+            for start, count, bucket, a_idx, p_idx in plan_pairs(n_a, n_p, self.max_batch):
+                self._ensure_capacity(bucket)
+                a_idx = torch.from_numpy(a_idx).to(self.dev)
+                p_idx = torch.from_numpy(p_idx).to(self.dev)
+                self._joint[:count, ..., :self.C8].copy_(feats.index_select(0, a_idx))
+                self._mu[:count].copy_(mu_p.index_select(0, p_idx))
+                if count < bucket:
+                    self._joint[count:bucket, ..., :self.C8].zero_()
+                    self._mu[count:bucket].zero_()
+                self._run('render', bucket)
+                out[start:start + count].copy_(self._pred[:count, ..., :3])
+        cur.wait_stream(self.stream)
+        out = out.view(n_a, n_p, self.S, self.S, 3)
+        return (out, mu_p) if return_landmarks else out

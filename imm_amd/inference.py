@@ -62,41 +62,184 @@ def plan_buckets(n, max_batch):
     return out
 
 
-def pose_encoder_names(n_filters):
-    """Variables the detector reads: (parameter names, batch-norm state names), engine / checkpoint naming."""
+def encoder_names(scope, n_filters):
+    """(parameter names, batch-norm state names) of one encoder's eight conv + BN blocks, engine / checkpoint naming."""
     params, state = [], []
     for i in range(len(encoder_spec(n_filters))):
-        scope = '%s/encoder/conv_%d' % (POSE_SCOPE, i + 1)
-        params += [scope + '/w', scope + '/b', scope + '/gamma', scope + '/beta']
-        state += [scope + '/moving_mean', scope + '/moving_variance']
+        sc = '%s/encoder/conv_%d' % (scope, i + 1)
+        params += [sc + '/w', sc + '/b', sc + '/gamma', sc + '/beta']
+        state += [sc + '/moving_mean', sc + '/moving_variance']
+    return params, state
+
+
+def pose_encoder_names(n_filters):
+    """Variables the detector reads: (parameter names, batch-norm state names), engine / checkpoint naming."""
+    params, state = encoder_names(POSE_SCOPE, n_filters)
     params += [POSE_SCOPE + '/conv_1/w', POSE_SCOPE + '/conv_1/b']
     return params, state
 
 
-def read_checkpoint(path, n_filters):
-    """Pose-encoder variables of a checkpoint as host f32 tensors: a `.pt` file written by scripts/train.py ({'params', 'state'})
-    or the prefix of a TensorFlow bundle (`<prefix>.index` next to it; the reference's released checkpoints)."""
+def read_variables(path, names, what='model'):
+    """The named variables of a checkpoint as host f32 tensors {name: tensor}: a `.pt` file written by scripts/train.py
+    ({'params', 'state'}) or the prefix of a TensorFlow bundle (`<prefix>.index` next to it; the reference's released checkpoints)."""
     import os
-    pnames, snames = pose_encoder_names(n_filters)
+    names = list(names)
     if os.path.isfile(path + '.index'):
         from .utils.tf_checkpoint import read_bundle, tf_variable_name
-        want = {tf_variable_name(n): n for n in pnames + snames}
+        want = {tf_variable_name(n): n for n in names}
         data = read_bundle(path, names=set(want))
         missing = [t for t in want if t not in data]
         if missing:
-            raise KeyError('%s lacks %d pose-encoder variables (e.g. %s)' % (path, len(missing), missing[0]))
+            raise KeyError('%s lacks %d %s variables (e.g. %s)' % (path, len(missing), what, missing[0]))
         get = {n: torch.from_numpy(np.asarray(data[t], dtype=np.float32)) for t, n in want.items()}
     elif os.path.isfile(path):
         ck = torch.load(path, map_location='cpu')
         src = dict(ck['params'])
         src.update(ck.get('state') or {})
-        missing = [n for n in pnames + snames if n not in src]
+        missing = [n for n in names if n not in src]
         if missing:
-            raise KeyError('%s lacks %d pose-encoder variables (e.g. %s)' % (path, len(missing), missing[0]))
-        get = {n: torch.as_tensor(src[n], dtype=torch.float32) for n in pnames + snames}
+            raise KeyError('%s lacks %d %s variables (e.g. %s)' % (path, len(missing), what, missing[0]))
+        get = {n: torch.as_tensor(src[n], dtype=torch.float32) for n in names}
     else:
         raise FileNotFoundError('checkpoint %s not found (neither a file nor a TensorFlow bundle prefix)' % path)
+    return {n: get[n] for n in names}
+
+
+def read_checkpoint(path, n_filters):
+    """Pose-encoder variables of a checkpoint as host f32 tensors (params, state): see read_variables."""
+    pnames, snames = pose_encoder_names(n_filters)
+    get = read_variables(path, pnames + snames, 'pose-encoder')
     return {n: get[n] for n in pnames}, {n: get[n] for n in snames}
+
+
+def alloc_encoder_weights(spec, dtype, device):
+    """Packed-filter images and folded-bias vectors of a folded encoder (zeros; filled by pack_folded_encoder)."""
+    wt, bias = [], []
+    for i, (k, ci, co, _st) in enumerate(spec):
+        kpad = ops.round_up(7 * 32, 32) if i == 0 else ops.round_up(k * k * ci, 32)
+        wt.append(torch.zeros(ops.round_up(co, 128), kpad, dtype=dtype, device=device))
+        bias.append(torch.zeros(co, dtype=torch.float32, device=device))
+    return wt, bias
+
+
+def pack_folded_encoder(params, state, scope, spec, wt, bias, device):
+    """Fold every block's eval-mode batch norm into its convolution (host, f64) and pack the filters in place (current stream)."""
+    for i, (k, ci, co, _st) in enumerate(spec):
+        sc = '%s/encoder/conv_%d' % (scope, i + 1)
+        g = lambda n: params[sc + '/' + n].double().numpy()
+        wf, bf = fold_batch_norm(g('w'), g('b'), g('gamma'), g('beta'), state[sc + '/moving_mean'].double().numpy(),
+                                 state[sc + '/moving_variance'].double().numpy())
+        if wf.shape != (k, k, ci, co):
+            raise ValueError('%s/w: shape %s != %s' % (sc, wf.shape, (k, k, ci, co)))
+        w_dev = torch.empty(wf.shape, dtype=torch.float32, device=device)
+        ops.upload(w_dev, torch.from_numpy(wf.astype(np.float32)), sc + '/w (folded)')
+        rows, kpad = wt[i].shape
+        if i == 0:      # HWIO [7, 7, 3, co] is [7, 1, 21, co]: the tap-unrolled 7x1 filter image both conv_1 forms read
+            ops.pack_weights(w_dev, wt[i], 0, k, 1, 3 * k, co, 32, rows, kpad)
+        else:
+            ops.pack_weights(w_dev, wt[i], 0, k, k, ci, co, ci, rows, kpad)
+        ops.upload(bias[i], torch.from_numpy(bf.astype(np.float32)), sc + '/b (folded)')
+
+
+def encoder_act_elems(spec, S, batch):
+    """Elements of the larger ping-pong activation buffer a folded encoder of this batch needs."""
+    out, f = 0, 1
+    for (_k, _ci, co, st) in spec:
+        f *= st
+        out = max(out, batch * (S // f) ** 2 * co)
+    return out
+
+
+def folded_encoder_program(scope, spec, B, S, img, act, wt, bias, xin_for, dt, out=None, ldo=None):
+    """The launches of a folded encoder over B images f32 [B, S, S, 3] (`img`): conv_1 straight from the f32 image (imm_conv_first;
+    the tap-unrolled 7x1 form where it says no), conv_2 .. conv_8 by imm_conv2d, every one with BIAS | RELU; outputs ping-pong
+    between the two flat buffers `act`.  out / ldo: where conv_8 writes (pixel stride ldo), e.g. the renderer's joint buffer.
+    Returns (launches, last output, its side, its pixel stride)."""
+    prog = []
+    x, H, ld = None, S, 3
+    for i, (k, ci_, co, st) in enumerate(spec):
+        name = '%s/encoder/conv_%d' % (scope, i + 1)
+        Ho = -(-H // st)
+        if out is not None and i == len(spec) - 1:
+            y, ldy = out, ldo
+        else:
+            y, ldy = act[i % 2][:B * Ho * Ho * co].view(B, Ho, Ho, co), co
+        if i == 0:
+            if ops.conv_first_supported(B, S, co, ldy):
+                prog.append(_Launch('conv', name, 'first', (lambda y=y, i=i, co=co, ldy=ldy: ops.conv_first(
+                    img, wt[i], bias[i], y, ldy, None, B, S, co, L.CONV_BIAS | L.CONV_RELU))))
+            else:
+                xin = xin_for(B)
+                prog.append(_Launch('pack_image', name + '/pack', 'pack_image',
+                                    lambda xin=xin: ops.pack_image_taps(img, xin, B, S, S, 7, 3, 32)))
+                d = ops.fwd_desc(B, S, S, 32, 32, co, ldy, 7, 1, L.CONV_BIAS | L.CONV_RELU, kw=1)
+                prog.append(_Launch('conv', name, ops.conv2d_variant(d, dt)[0],
+                                    (lambda d=d, xin=xin, y=y, i=i: ops.conv2d(d, xin, wt[i], bias[i], y))))
+        else:
+            d = ops.fwd_desc(B, H, H, ci_, ld, co, ldy, k, st, L.CONV_BIAS | L.CONV_RELU)
+            prog.append(_Launch('conv', name, ops.conv2d_variant(d, dt)[0],
+                                (lambda d=d, x=x, y=y, i=i: ops.conv2d(d, x, wt[i], bias[i], y))))
+        x, H, ld = y, Ho, ldy
+    return prog, x, H, ld
+
+
+def check_limits(cfg, dtype, image_size, what='detector'):
+    """The folded inference paths' limits (16-bit storage, S a multiple of 16 and >= 64, 1..64 landmarks): (S, K, n_filters)."""
+    if dtype == torch.float32:
+        raise NotImplementedError('the landmark %s runs the 16-bit kernels (bf16 / f16); the f32 witness engine is a '
+                                  'test instrument without one' % what)
+    ops.dtype_enum(dtype)
+    S = int(image_size)
+    if S % 16 or S < 64:
+        raise ValueError('image side must be a multiple of 16 and >= 64')
+    K, nf = int(cfg.n_maps), int(cfg.n_filters)
+    if not 1 <= K <= MAX_LANDMARKS:
+        raise NotImplementedError('the %s serves 1..%d landmarks (the soft-argmax limit), got %d' % (what, MAX_LANDMARKS, K))
+    ops.gauss_mode_enum(cfg.gauss_mode)
+    return S, K, nf
+
+
+def as_image_batch(images, S):
+    """detect()'s input forms: (NHWC float tensor [N, S, S, 3] in [0, 255] (host or device), False) or (list of u8 arrays, True)."""
+    u8 = isinstance(images, (list, tuple))
+    if not u8:
+        images = torch.as_tensor(images)
+        if images.dim() != 4 or tuple(images.shape[1:]) != (S, S, 3):
+            raise ValueError('images must be [N, %d, %d, 3], got %s' % (S, S, tuple(images.shape)))
+        if images.is_cuda and images.dtype != torch.float32:
+            images = images.float()
+    return images, u8
+
+
+def stage_u8(images, dst, S, device):
+    """Pack u8 HWC images back to back (16-byte aligned starts, like the data loader) and resize them on the GPU (TF1 bilinear,
+    align_corners) into dst f32 [len(images), S, S, 3] (current stream)."""
+    decoded = []
+    for a in images:
+        a = np.asarray(a)
+        if a.dtype != np.uint8:
+            raise TypeError('image arrays must be uint8 HWC, got %s' % a.dtype)
+        if a.ndim == 2:
+            a = a[:, :, None]
+        if a.ndim != 3 or a.shape[2] not in (1, 3):
+            raise ValueError('image arrays must be HxW, HxWx1 or HxWx3, got shape %s' % (a.shape,))
+        if a.shape[2] == 1:
+            a = np.repeat(a, 3, axis=2)
+        decoded.append(np.ascontiguousarray(a))
+    count = len(decoded)
+    offs = np.zeros(count, dtype=np.int64)
+    total = 0
+    for i, a in enumerate(decoded):
+        offs[i] = total
+        total += (a.size + 15) & ~15
+    packed = np.zeros(max(total, 16), dtype=np.uint8)
+    for a, o in zip(decoded, offs):
+        packed[o:o + a.size] = a.reshape(-1)
+    hw = np.array([a.shape[:2] for a in decoded], dtype=np.int32)
+    src = ops.to_device_pinned(packed, device)
+    offs_d = ops.to_device_pinned(offs, device)
+    hw_d = ops.to_device_pinned(hw, device)
+    ops.resize_crop_u8(src, offs_d, hw_d, 3, (S, S), (0, 0), (S, S), dst)
 
 
 class _Launch(object):
@@ -125,9 +268,15 @@ class LandmarkDetector(object):
     def from_checkpoint(cls, config, path, image_size=128, max_batch=256, dtype=torch.bfloat16, device=None, use_graph=True):
         """A detector straight from a checkpoint (`.pt` file or TensorFlow bundle prefix), without a training engine.
         config: the `model:` block of the experiment config (config.model)."""
+        return cls._from_variables(config, read_checkpoint(path, int(config.n_filters)), image_size, max_batch, dtype, device,
+                                   use_graph)
+
+    @classmethod
+    def _from_variables(cls, config, static, image_size, max_batch, dtype, device, use_graph):
+        """A detector over host variables (params, state) that it keeps for refresh()."""
         det = cls.__new__(cls)
         det._model = None
-        det._static = read_checkpoint(path, int(config.n_filters))
+        det._static = static
         if device is None:
             device = 'cuda:%d' % torch.cuda.current_device()
         det._setup(config, dtype, torch.device(device), image_size, max_batch, use_graph)
@@ -136,17 +285,7 @@ class LandmarkDetector(object):
 
     # ------------------------------------------------------------------------------------------------------------------------
     def _setup(self, cfg, dtype, device, image_size, max_batch, use_graph):
-        if dtype == torch.float32:
-            raise NotImplementedError('the landmark detector runs the 16-bit kernels (bf16 / f16); the f32 witness engine is a '
-                                      'test instrument without one')
-        ops.dtype_enum(dtype)
-        S = int(image_size)
-        if S % 16 or S < 64:
-            raise ValueError('image side must be a multiple of 16 and >= 64')
-        K, nf = int(cfg.n_maps), int(cfg.n_filters)
-        if not 1 <= K <= MAX_LANDMARKS:
-            raise NotImplementedError('the detector serves 1..%d landmarks (the soft-argmax limit), got %d' % (MAX_LANDMARKS, K))
-        ops.gauss_mode_enum(cfg.gauss_mode)
+        S, K, nf = check_limits(cfg, dtype, image_size)
         L.load()
         self.cfg, self.dt, self.dev, self.S, self.K, self.nf = cfg, dtype, torch.device(device), S, K, nf
         self.max_batch = int(max_batch)
@@ -166,12 +305,8 @@ class LandmarkDetector(object):
         self._stager = ops.PinnedStager()
         with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
             # packed filters and folded biases (shared by every bucket)
-            self.wt, self.bias, self.kpad = [], [], []
-            for i, (k, ci, co, _st) in enumerate(self.spec):
-                kpad = ops.round_up(7 * 32, 32) if i == 0 else ops.round_up(k * k * ci, 32)
-                self.kpad.append(kpad)
-                self.wt.append(torch.zeros(ops.round_up(co, 128), kpad, dtype=dtype, device=self.dev))
-                self.bias.append(torch.zeros(co, dtype=torch.float32, device=self.dev))
+            self.wt, self.bias = alloc_encoder_weights(self.spec, dtype, self.dev)
+            self.kpad = [w.shape[1] for w in self.wt]
             self.wt_head = torch.zeros(ops.round_up(K, 128), ops.round_up(C, 32), dtype=dtype, device=self.dev)
             self.bias_head = torch.zeros(K, dtype=torch.float32, device=self.dev)
         self._cap = 0
@@ -189,21 +324,7 @@ class LandmarkDetector(object):
             state = {n: ops.download(eng.state[n]) for n in snames}
         self.stream.wait_stream(torch.cuda.current_stream(self.dev))
         with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
-            for i, (k, ci, co, _st) in enumerate(self.spec):
-                scope = '%s/encoder/conv_%d' % (POSE_SCOPE, i + 1)
-                g = lambda n: params[scope + '/' + n].double().numpy()
-                wf, bf = fold_batch_norm(g('w'), g('b'), g('gamma'), g('beta'), state[scope + '/moving_mean'].double().numpy(),
-                                         state[scope + '/moving_variance'].double().numpy())
-                if wf.shape != (k, k, ci, co):
-                    raise ValueError('%s/w: shape %s != %s' % (scope, wf.shape, (k, k, ci, co)))
-                w_dev = torch.empty(wf.shape, dtype=torch.float32, device=self.dev)
-                ops.upload(w_dev, torch.from_numpy(wf.astype(np.float32)), scope + '/w (folded)')
-                rows, kpad = self.wt[i].shape
-                if i == 0:      # HWIO [7, 7, 3, co] is [7, 1, 21, co]: the tap-unrolled 7x1 filter image both conv_1 forms read
-                    ops.pack_weights(w_dev, self.wt[i], 0, k, 1, 3 * k, co, 32, rows, kpad)
-                else:
-                    ops.pack_weights(w_dev, self.wt[i], 0, k, k, ci, co, ci, rows, kpad)
-                ops.upload(self.bias[i], torch.from_numpy(bf.astype(np.float32)), scope + '/b (folded)')
+            pack_folded_encoder(params, state, POSE_SCOPE, self.spec, self.wt, self.bias, self.dev)
             C = 8 * self.nf
             w_dev = torch.empty(1, 1, C, self.K, dtype=torch.float32, device=self.dev)
             ops.upload(w_dev, params[POSE_SCOPE + '/conv_1/w'], POSE_SCOPE + '/conv_1/w')
@@ -223,21 +344,13 @@ class LandmarkDetector(object):
         with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
             self._img = torch.zeros(batch, S, S, 3, device=self.dev)
             self._xin = None
-            n_act = max(batch * (S // down) ** 2 * co for down, co in self._act_shapes())
+            n_act = encoder_act_elems(self.spec, S, batch)
             self._act = [torch.zeros(n_act, dtype=self.dt, device=self.dev) for _ in range(2)]
             self._heat = torch.zeros(batch, He, He, self.ldh, device=self.dev)
             self._mu = torch.zeros(batch, K, 2, device=self.dev)
             self._py = torch.zeros(batch, He, K, device=self.dev)
             self._px = torch.zeros(batch, He, K, device=self.dev)
         self._cap = batch
-
-    def _act_shapes(self):
-        """(down-scaling of the side, channels) of every layer's output."""
-        out, f = [], 1
-        for (_k, _ci, co, st) in self.spec:
-            f *= st
-            out.append((f, co))
-        return out
 
     def _xin_for(self, batch):
         if self._xin is None or self._xin.shape[0] < batch:
@@ -254,27 +367,9 @@ class LandmarkDetector(object):
         prog = []
         if u8:
             prog.append(_Launch('resize', 'resize_crop_u8', 'resize', None))     # issued by detect() with the call's pixels
-        img = self._img[:B]
-        x, H, ci, ld = None, S, 3, 3
-        for i, (k, ci_, co, st) in enumerate(self.spec):
-            name = '%s/encoder/conv_%d' % (POSE_SCOPE, i + 1)
-            y = self._act[i % 2][:B * (-(-H // st)) ** 2 * co].view(B, -(-H // st), -(-H // st), co)
-            if i == 0:
-                if ops.conv_first_supported(B, S, co, co):
-                    prog.append(_Launch('conv', name, 'first', (lambda y=y, i=i, co=co: ops.conv_first(
-                        img, self.wt[i], self.bias[i], y, co, None, B, S, co, L.CONV_BIAS | L.CONV_RELU))))
-                else:
-                    xin = self._xin_for(B)
-                    prog.append(_Launch('pack_image', name + '/pack', 'pack_image',
-                                        lambda xin=xin: ops.pack_image_taps(img, xin, B, S, S, 7, 3, 32)))
-                    d = ops.fwd_desc(B, S, S, 32, 32, co, co, 7, 1, L.CONV_BIAS | L.CONV_RELU, kw=1)
-                    prog.append(_Launch('conv', name, ops.conv2d_variant(d, dt)[0],
-                                        (lambda d=d, xin=xin, y=y, i=i: ops.conv2d(d, xin, self.wt[i], self.bias[i], y))))
-            else:
-                d = ops.fwd_desc(B, H, H, ci, ld, co, co, k, st, L.CONV_BIAS | L.CONV_RELU)
-                prog.append(_Launch('conv', name, ops.conv2d_variant(d, dt)[0],
-                                    (lambda d=d, x=x, y=y, i=i: ops.conv2d(d, x, self.wt[i], self.bias[i], y))))
-            x, H, ci, ld = y, y.shape[1], co, co
+        enc, x, H, _ld = folded_encoder_program(POSE_SCOPE, self.spec, B, S, self._img[:B], self._act, self.wt, self.bias,
+                                                self._xin_for, dt)
+        prog += enc
         He, K, C = self.He, self.K, 8 * self.nf
         assert H == He
         heat, mu, py, px = self._heat[:B], self._mu[:B], self._py[:B], self._px[:B]
@@ -313,45 +408,14 @@ class LandmarkDetector(object):
 
     # ------------------------------------------------------------------------------------------------------------------------
     def _stage_u8(self, images, count):
-        """Pack u8 HWC images back to back (16-byte aligned starts, like the data loader) and resize them on the GPU into
-        the first `count` rows of the input buffer."""
-        decoded = []
-        for a in images:
-            a = np.asarray(a)
-            if a.dtype != np.uint8:
-                raise TypeError('image arrays must be uint8 HWC, got %s' % a.dtype)
-            if a.ndim == 2:
-                a = a[:, :, None]
-            if a.ndim != 3 or a.shape[2] not in (1, 3):
-                raise ValueError('image arrays must be HxW, HxWx1 or HxWx3, got shape %s' % (a.shape,))
-            if a.shape[2] == 1:
-                a = np.repeat(a, 3, axis=2)
-            decoded.append(np.ascontiguousarray(a))
-        offs = np.zeros(count, dtype=np.int64)
-        total = 0
-        for i, a in enumerate(decoded):
-            offs[i] = total
-            total += (a.size + 15) & ~15
-        packed = np.zeros(max(total, 16), dtype=np.uint8)
-        for a, o in zip(decoded, offs):
-            packed[o:o + a.size] = a.reshape(-1)
-        hw = np.array([a.shape[:2] for a in decoded], dtype=np.int32)
-        src = ops.to_device_pinned(packed, self.dev)
-        offs_d = ops.to_device_pinned(offs, self.dev)
-        hw_d = ops.to_device_pinned(hw, self.dev)
-        ops.resize_crop_u8(src, offs_d, hw_d, 3, (self.S, self.S), (0, 0), (self.S, self.S), self._img[:count])
+        """Resize u8 images of any sizes on the GPU into the first `count` rows of the input buffer."""
+        stage_u8(images[:count], self._img[:count], self.S, self.dev)
 
     def detect(self, images, heatmaps=False):
         """images: NHWC float [N, S, S, 3] with values in [0, 255] (host or device), or a list of u8 HWC arrays of any sizes
         (resized to S x S on the GPU).  Returns mu f32 [N, K, 2] on the detector's device, and with heatmaps=True also the pose
         head's heat maps f32 [N, S/8, S/8, K]."""
-        u8 = isinstance(images, (list, tuple))
-        if not u8:
-            images = torch.as_tensor(images)
-            if images.dim() != 4 or tuple(images.shape[1:]) != (self.S, self.S, 3):
-                raise ValueError('images must be [N, %d, %d, 3], got %s' % (self.S, self.S, tuple(images.shape)))
-            if images.is_cuda and images.dtype != torch.float32:
-                images = images.float()
+        images, u8 = as_image_batch(images, self.S)
         N, K, He = len(images), self.K, self.He
         cur = torch.cuda.current_stream(self.dev)
         mu_out = torch.empty(N, K, 2, device=self.dev)

@@ -117,6 +117,12 @@ class IMMModel(BaseModel):
         from ..inference import LandmarkDetector
         return LandmarkDetector(self, image_size=image_size, max_batch=max_batch)
 
+    def image_generator(self, image_size, max_batch=128):
+        """An ImageGenerator (imm_amd/generation.py) over this model's current variables: both encoders and the renderer with
+        batch norm folded into the convolutions, reconstruct / render / transfer, captured programs per batch bucket."""
+        from ..generation import ImageGenerator
+        return ImageGenerator(self, image_size=image_size, max_batch=max_batch)
+
     # -- reference surface -----------------------------------------------------------------------------
     def build(self, inputs, training_pl, costs_collection='costs', scope=None, var_device='/cpu:0',
               output_tensors=False, build_loss=True):

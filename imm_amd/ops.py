@@ -375,6 +375,13 @@ def softargmax_gauss_fwd(heat, ldh, batch, h, w, k, inv_std, s, mu, py, px, gaus
          _p(gauss_out), ldg, dtype_enum(dtype), gauss_mode_enum(mode), _s())
 
 
+def gauss_render_fwd(mu, batch, k, inv_std, s, gauss_out, ldg, dtype, mode='rot'):
+    """Render-only mode of imm_softargmax_gauss_fwd (heat NULL): the 16-bit Gaussian maps of the INPUT landmarks mu f32 [B, K, 2]
+    at gauss_out[((b*s + y)*s + x)*ldg + k], k < K only (bit-identical to the soft-argmax / pose-head writers' maps)."""
+    call('imm_softargmax_gauss_fwd', None, 0, batch, 0, 0, k, float(inv_std), s, _p(mu), None, None, _p(gauss_out), ldg,
+         dtype_enum(dtype), gauss_mode_enum(mode), _s())
+
+
 def softargmax_gauss_bwd(dgauss, ldg, batch, h, w, k, inv_std, s, mu, py, px, dheat, lddh, mode='rot'):
     call('imm_softargmax_gauss_bwd', _p(dgauss), ldg, dtype_enum(dheat.dtype), batch, h, w, k, float(inv_std), s, _p(mu),
          _p(py), _p(px), _p(dheat), lddh, gauss_mode_enum(mode), _s())

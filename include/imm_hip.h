@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define IMM_ABI_VERSION 22   /* 22: s2f / conv_first accept IMM_CONV_RELU.  21: imm_masked_sse_all.  20: imm_vgg_head_fwd / imm_vgg_head_supported / imm_vgg_head_scratch_bytes (conv1_1 + conv1_2 in one launch).  19: imm_set_cu_limit / imm_get_cu_limit, imm_masked_sse_pool with pool_a == NULL.  18: imm_copy_f32.  17: imm_cost_ema, imm_rms16 (summaries).  16: imm_conv2d_variant.  15: imm_conv2d_dgrad_s2, imm_conv2d_nol, imm_conv_first, imm_wgrad_job.x_scale/x_shift/x_relu; entry points removed
+#define IMM_ABI_VERSION 23   /* 23: render-only mode of the soft-argmax forward (heat == NULL: mu is the input).  22: s2f / conv_first accept IMM_CONV_RELU.  21: imm_masked_sse_all.  20: imm_vgg_head_fwd / imm_vgg_head_supported / imm_vgg_head_scratch_bytes (conv1_1 + conv1_2 in one launch).  19: imm_set_cu_limit / imm_get_cu_limit, imm_masked_sse_pool with pool_a == NULL.  18: imm_copy_f32.  17: imm_cost_ema, imm_rms16 (summaries).  16: imm_conv2d_variant.  15: imm_conv2d_dgrad_s2, imm_conv2d_nol, imm_conv_first, imm_wgrad_job.x_scale/x_shift/x_relu; entry points removed
                                   since 14 (imm_bn_bwd_reduce_finalize, imm_conv2d_stats_workspace_bytes) finally counted */
 
 /* IMM_F32 (round 6): f32 activation storage — the exact-arithmetic WITNESS of the wiring, a test instrument (the reference computes
@@ -322,7 +322,11 @@ int imm_conv_first(const float* image, const void* wt, int kpad, const float* bi
 #define IMM_GAUSS_FLAT 1
 #define IMM_GAUSS_ANKUSH 2
 /* heat f32 [B,h,w,ldh] (k<K) -> mu [B,K,2] (y,x), py [B,h,K], px [B,w,K];
- * gauss: 16-bit written at gauss_out[((b*s+y)*s+x)*ldg + k] for k<K. */
+ * gauss: 16-bit written at gauss_out[((b*s+y)*s+x)*ldg + k] for k<K.
+ * Render-only mode (heat == NULL; ABI 23): mu f32 [B,K,2] (y,x) in [-1,1] is the INPUT, h / w / ldh are ignored, py / px may be NULL
+ * and are not touched; the maps of those mu are written to gauss_out (required) as above, channels k<K only (the caller owns the
+ * others), bit-identical to what this function and the pose-head forward write for the same mu in every gauss_mode.  Several
+ * workgroups per sample (s*s*K / 256), no LDS.  mu == NULL or gauss_out == NULL in this mode fails with "softargmax_fwd: null". */
 int imm_softargmax_gauss_fwd(const float* heat, int ldh, int batch, int h, int w, int k, float inv_std, int s,
                              float* mu, float* py, float* px, void* gauss_out, int ldg, int dtype, int gauss_mode,
                              void* stream);
