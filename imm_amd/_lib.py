@@ -20,7 +20,7 @@ CONV_BIAS, CONV_RELU, CONV_STATS, CONV_MASK, CONV_OUT_F32 = 1, 2, 4, 8, 16
 SSE_BLOCKS = 512
 OPTIMIZERS = {'adam': 0, 'adadelta': 1, 'adagrad': 2}      # IMM_OPT_* (scripts/train.py:97-104)
 GAUSS_MODES = {'rot': 0, 'flat': 1, 'ankush': 2}     # IMM_GAUSS_* (config key gauss_mode, imm_model.py:48-72)
-ABI_VERSION = 23     # 23: render-only mode of imm_softargmax_gauss_fwd (heat NULL).  22: s2f / conv_first accept IMM_CONV_RELU
+ABI_VERSION = 24     # 24: box-crop mode of imm_resize_crop_u8, keypoint epilogue of imm_pose_head_fwd.  23: render-only mode of imm_softargmax_gauss_fwd (heat NULL).  22: s2f / conv_first accept IMM_CONV_RELU
 
 
 class ImmHipError(RuntimeError):
@@ -44,6 +44,11 @@ class OptHParams(C.Structure):
                 ('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float), ('clip', C.c_float),
                 ('grad_scale', C.c_float), ('optim', C.c_int32),
                 ('scale_growth_interval', C.c_int32), ('scale_max', C.c_float)]
+
+
+class KeypointDesc(C.Structure):
+    _fields_ = [('w', C.c_void_p), ('b', C.c_void_p), ('geom', C.c_void_p), ('keypoints', C.c_void_p), ('m', C.c_int32),
+                ('image_size', C.c_int32)]
 
 
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
@@ -94,7 +99,8 @@ _SIGS = {
     'imm_softargmax_gauss_fwd': [_P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _I, _I, _I, _P],
     'imm_softargmax_gauss_bwd': [_P, _I, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _I, _I, _P],
     'imm_gauss_render_f32': [_P, _I, _I, _F, _I, _P, _I, _P],
-    'imm_pose_head_fwd': [_P, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P],
+    'imm_pose_head_fwd': [_P, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _P, _I, _P, _P, _P, _P, _I, _I,
+                          C.POINTER(KeypointDesc), _P],
     'imm_pose_head_bwd': [_P, _I, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _I, _I, _P, _I, _I, _P, _I, _P, _P],
     'imm_vgg_conv1_1_fwd': [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P],
     'imm_vgg_head_supported': [_I, _I, _I],
@@ -122,7 +128,7 @@ _SIGS = {
     'imm_rccl_init': [_I, _I, _P, C.POINTER(C.c_void_p)],
     'imm_rccl_allreduce': [_P, _P, _L, _P],
     'imm_rccl_destroy': [_P],
-    'imm_resize_crop_u8': [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P],
+    'imm_resize_crop_u8': [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P],
     'imm_unpool_tap_grad': [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P],
     'imm_masked_sse_pool': [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P],
     'imm_masked_sse_multi': [_I, _P, _P, _P, _P, _P, _I, _I, _P, _I, _I, _P],

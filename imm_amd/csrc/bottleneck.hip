@@ -128,11 +128,10 @@ __global__ __launch_bounds__(BT_THREADS) void softargmax_gauss_fwd_kernel(
 // wave v takes the tiles v, v+16, ...
 #define PH_THREADS 1024           // forward: 16 waves
 #define PH_BWD_THREADS 512        // backward: 8 waves (the filter rows of the data gradient take 64-128 registers per lane)
-template <typename ET, int GM = -1>
-__global__ __launch_bounds__(PH_THREADS) void pose_head_fwd_kernel(
-    const uint16_t* __restrict__ feat, int ldf, int C, const uint16_t* __restrict__ wt, int kpad, const float* __restrict__ bias,
-    float* __restrict__ heat, int ldh, int h, int w, int K, float inv_std, int s, float* __restrict__ mu,
-    float* __restrict__ py, float* __restrict__ px, uint16_t* __restrict__ gauss, int ldg, int mode) {
+template <typename ET, int GM>
+__device__ __forceinline__ void pose_head_fwd_body(
+    const uint16_t* feat, int ldf, int C, const uint16_t* wt, int kpad, const float* bias, float* heat, int ldh, int h, int w, int K,
+    float inv_std, int s, float* mu, float* py, float* px, uint16_t* gauss, int ldg, int mode) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int hw = h * w, NT = (K + 15) >> 4, KK = C >> 5;
@@ -176,6 +175,39 @@ __global__ __launch_bounds__(PH_THREADS) void pose_head_fwd_kernel(
   }
   __syncthreads();
   bt_softargmax_tail<ET, PH_THREADS, GM>(sm, b, tid, h, w, K, inv_std, s, mu, py, px, gauss, ldg, mode);
+}
+
+template <typename ET, int GM = -1>
+__global__ __launch_bounds__(PH_THREADS) void pose_head_fwd_kernel(
+    const uint16_t* __restrict__ feat, int ldf, int C, const uint16_t* __restrict__ wt, int kpad, const float* __restrict__ bias,
+    float* __restrict__ heat, int ldh, int h, int w, int K, float inv_std, int s, float* __restrict__ mu,
+    float* __restrict__ py, float* __restrict__ px, uint16_t* __restrict__ gauss, int ldg, int mode) {
+  pose_head_fwd_body<ET, GM>(feat, ldf, C, wt, kpad, bias, heat, ldh, h, w, K, inv_std, s, mu, py, px, gauss, ldg, mode);
+}
+
+// Keypoint epilogue (the detector's keypoints(); a kernel of its own so that the training step's instantiation above keeps its
+// code): the annotated points of a fitted linear regressor from this sample's mu, still in LDS after the soft-argmax, mapped to
+// source pixels.  Thread j < 2M owns output coordinate j:
+//   x_i = (mu_i + 1) / 2 * S  (i < 2K, mu flattened (y0, x0, y1, x1, ...): convert_landmarks),  kp_j = b_j + sum_i x_i W[i][j],
+//   out_j = geom[axis] + kp_j * geom[2 + axis]  (axis = j & 1; geom = (y0, x0, sy, sx) inverts ImagePairDataset._resize_points).
+// 2K x 2M <= 128 x 32 multiply-adds per sample, f32 in ascending i.
+template <typename ET, int GM = -1>
+__global__ __launch_bounds__(PH_THREADS) void pose_head_kp_fwd_kernel(
+    const uint16_t* __restrict__ feat, int ldf, int C, const uint16_t* __restrict__ wt, int kpad, const float* __restrict__ bias,
+    float* __restrict__ heat, int ldh, int h, int w, int K, float inv_std, int s, float* __restrict__ mu,
+    float* __restrict__ py, float* __restrict__ px, uint16_t* __restrict__ gauss, int ldg, int mode, imm_keypoint_desc kp) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  pose_head_fwd_body<ET, GM>(feat, ldf, C, wt, kpad, bias, heat, ldh, h, w, K, inv_std, s, mu, py, px, gauss, ldg, mode);
+  // smu (bt_softargmax_tail's [K][2]) was completed before the tail's last barrier and only read since
+  const float* smu = sm + h * w * K + (h + w) * K;
+  const int b = blockIdx.x, j = threadIdx.x, M2 = 2 * kp.m;
+  if (j < M2) {
+    const float S = (float)kp.image_size;
+    float acc = kp.b[j];
+    for (int i = 0; i < 2 * K; ++i) acc += ((smu[i] + 1.f) * 0.5f * S) * kp.w[i * M2 + j];
+    const float* g = kp.geom + (int64_t)b * 4;
+    kp.keypoints[(int64_t)b * M2 + j] = g[j & 1] + acc * g[2 + (j & 1)];
+  }
 }
 
 // backward: dG -> dmu (through the Gaussian) -> d row/col means (through softmax-expectation) -> dheat
@@ -413,7 +445,7 @@ extern "C" int imm_softargmax_gauss_bwd(const void* dgauss, int ldg, int dtype, 
 // ---- the pose head as one launch each way ---------------------------------------------------------------------------------
 extern "C" int imm_pose_head_fwd(const void* feat, int ldf, int c, const void* wt, int kpad, const float* bias, int dtype,
                                  int batch, int h, int w, int k, float inv_std, int s, float* heat, int ldh, float* mu, float* py,
-                                 float* px, void* gauss_out, int ldg, int gauss_mode, void* stream) {
+                                 float* px, void* gauss_out, int ldg, int gauss_mode, const imm_keypoint_desc* kp, void* stream) {
   IMM_REQUIRE(feat && wt && bias && heat && mu && py && px, "pose_head_fwd: null");
   IMM_REQUIRE(gauss_mode >= IMM_GAUSS_ROT && gauss_mode <= IMM_GAUSS_ANKUSH, "pose_head_fwd: gauss_mode %d", gauss_mode);
   IMM_REQUIRE(batch > 0 && h > 0 && w > 0 && k > 0 && ldh >= k && s > 0, "pose_head_fwd: dims");
@@ -421,10 +453,26 @@ extern "C" int imm_pose_head_fwd(const void* feat, int ldf, int c, const void* w
   IMM_REQUIRE(((uintptr_t)feat % 16 == 0) && ((uintptr_t)wt % 16 == 0) && ldf % 8 == 0 && kpad % 8 == 0, "pose_head_fwd: alignment");
   if (c <= 0 || c % 32 || ldf < c || kpad < c || k > 64 || (h * w) % 16)
     return imm_fail(IMM_E_UNSUPPORTED, "pose_head_fwd: needs c %% 32 == 0, k <= 64, h*w %% 16 == 0 (c=%d k=%d h*w=%d)", c, k, h * w);
+  if (kp != nullptr) {
+    IMM_REQUIRE(kp->w && kp->b && kp->geom && kp->keypoints, "pose_head_fwd: keypoint descriptor: null");
+    IMM_REQUIRE(kp->m >= 1 && kp->m <= 16, "pose_head_fwd: keypoints: 1..16 annotated points, got %d", kp->m);
+    IMM_REQUIRE(kp->image_size > 0, "pose_head_fwd: keypoints: image size %d", kp->image_size);
+  }
   const size_t lds = sizeof(float) * ((size_t)h * w * k + (size_t)(h + w) * k + 2 * (size_t)k);
   if (lds > kMaxDynLds) return imm_fail(IMM_E_UNSUPPORTED, "pose_head_fwd: heat-map %dx%dx%d needs %zu B LDS", h, w, k, lds);
   IMM_DISPATCH_DTYPE(dtype, {
-    if (gauss_mode == IMM_GAUSS_ROT) {
+    // the keypoint kernels take the same Gaussian-mode specialisation as the plain ones: mu and the maps are the same bits
+    if (kp != nullptr && gauss_mode == IMM_GAUSS_ROT) {
+      if (set_dyn_lds(pose_head_kp_fwd_kernel<ET, IMM_GAUSS_ROT>, lds)) return IMM_E_HIP;
+      hipLaunchKernelGGL((pose_head_kp_fwd_kernel<ET, IMM_GAUSS_ROT>), dim3(batch), dim3(PH_THREADS), lds, (hipStream_t)stream,
+                         (const uint16_t*)feat, ldf, c, (const uint16_t*)wt, kpad, bias, heat, ldh, h, w, k, inv_std, s, mu, py, px,
+                         (uint16_t*)gauss_out, ldg, gauss_mode, *kp);
+    } else if (kp != nullptr) {
+      if (set_dyn_lds(pose_head_kp_fwd_kernel<ET>, lds)) return IMM_E_HIP;
+      hipLaunchKernelGGL((pose_head_kp_fwd_kernel<ET>), dim3(batch), dim3(PH_THREADS), lds, (hipStream_t)stream,
+                         (const uint16_t*)feat, ldf, c, (const uint16_t*)wt, kpad, bias, heat, ldh, h, w, k, inv_std, s, mu, py, px,
+                         (uint16_t*)gauss_out, ldg, gauss_mode, *kp);
+    } else if (gauss_mode == IMM_GAUSS_ROT) {
       if (set_dyn_lds(pose_head_fwd_kernel<ET, IMM_GAUSS_ROT>, lds)) return IMM_E_HIP;
       hipLaunchKernelGGL((pose_head_fwd_kernel<ET, IMM_GAUSS_ROT>), dim3(batch), dim3(PH_THREADS), lds, (hipStream_t)stream,
                          (const uint16_t*)feat, ldf, c, (const uint16_t*)wt, kpad, bias, heat, ldh, h, w, k, inv_std, s, mu, py, px,

@@ -9,6 +9,7 @@
 
 detect_landmarks()     the same landmarks through a LandmarkDetector (imm_amd/inference.py: pose encoder only, batch norm
                        folded); evaluate_regression(..., detector=...) uses it for both splits
+fit_regression()       evaluate_regression that also returns the fitted regressor (imm_amd/keypoints.py: LandmarkRegressor)
 
 The network forward is the training step's own kernel path (IMMModel.build(..., training_pl=False, build_loss=False) ->
 IMMEngine.forward_model_only); the regression is host arithmetic like in the reference (scikit-learn's Ridge)."""
@@ -94,3 +95,21 @@ def evaluate_regression(net_instance, train_iter, test_iter, im_size, batch_size
     train_t, test_t = run(train_iter), run(test_iter)
     pred = regress_landmarks(train_t, test_t, im_size, bias)
     return interocular_error(test_t['future_landmarks'], pred)
+
+
+def fit_regression(net_instance, train_iter, test_iter, im_size, batch_size=100, bias=False, detector=None, dataset='', checkpoint=''):
+    """evaluate_regression's error, computed through a LandmarkRegressor (imm_amd/keypoints.py: the same Ridge fit and prediction,
+    kept) -> (error, regressor)."""
+    from ..keypoints import LandmarkRegressor
+
+    def run(it):
+        if detector is not None:
+            res = detect_landmarks(it, detector)
+        else:
+            res = evaluate(it, net_instance, batch_size=batch_size, random_seed=0, eval_tensors=['gauss_yx', 'future_landmarks'])
+        return {k: np.concatenate(v) for k, v in res.items()}
+    train_t, test_t = run(train_iter), run(test_iter)
+    reg = LandmarkRegressor.fit(train_t, im_size, bias, dataset=dataset, checkpoint=checkpoint)
+    gt = np.asarray(test_t['future_landmarks']).astype(np.float32)
+    pred = reg.predict(test_t['gauss_yx']).reshape(gt.shape)
+    return interocular_error(test_t['future_landmarks'], pred), reg

@@ -211,9 +211,8 @@ def as_image_batch(images, S):
     return images, u8
 
 
-def stage_u8(images, dst, S, device):
-    """Pack u8 HWC images back to back (16-byte aligned starts, like the data loader) and resize them on the GPU (TF1 bilinear,
-    align_corners) into dst f32 [len(images), S, S, 3] (current stream)."""
+def decode_u8(images):
+    """detect()'s u8 input arrays as contiguous HxWx3 u8 arrays (grey images repeated to three channels)."""
     decoded = []
     for a in images:
         a = np.asarray(a)
@@ -226,6 +225,14 @@ def stage_u8(images, dst, S, device):
         if a.shape[2] == 1:
             a = np.repeat(a, 3, axis=2)
         decoded.append(np.ascontiguousarray(a))
+    return decoded
+
+
+def stage_u8(images, dst, S, device, boxes=None):
+    """Pack u8 HWC images back to back (16-byte aligned starts, like the data loader) and resize them on the GPU (TF1 bilinear,
+    align_corners) into dst f32 [len(images), S, S, 3] (current stream).  boxes: int32 [n, 5] rows (image, y0, x0, y1, x1) checked
+    by keypoints.check_boxes: dst row b is then box b cut from images[boxes[b][0]] (zero-padded) and resized, dst [n, S, S, 3]."""
+    decoded = decode_u8(images)
     count = len(decoded)
     offs = np.zeros(count, dtype=np.int64)
     total = 0
@@ -239,7 +246,8 @@ def stage_u8(images, dst, S, device):
     src = ops.to_device_pinned(packed, device)
     offs_d = ops.to_device_pinned(offs, device)
     hw_d = ops.to_device_pinned(hw, device)
-    ops.resize_crop_u8(src, offs_d, hw_d, 3, (S, S), (0, 0), (S, S), dst)
+    boxes_d = None if boxes is None else ops.to_device_pinned(np.ascontiguousarray(boxes, dtype=np.int32), device)
+    ops.resize_crop_u8(src, offs_d, hw_d, 3, (S, S), (0, 0), (S, S), dst, boxes=boxes_d)
 
 
 class _Launch(object):
@@ -309,6 +317,9 @@ class LandmarkDetector(object):
             self.kpad = [w.shape[1] for w in self.wt]
             self.wt_head = torch.zeros(ops.round_up(K, 128), ops.round_up(C, 32), dtype=dtype, device=self.dev)
             self.bias_head = torch.zeros(K, dtype=torch.float32, device=self.dev)
+            # keypoints(): the regressor's W [2K, 2M] and b [2M] at fixed addresses (rewritten before each call's replays)
+            self._kp_w = torch.zeros(2 * K * 2 * ops.MAX_KEYPOINTS, device=self.dev)
+            self._kp_b = torch.zeros(2 * ops.MAX_KEYPOINTS, device=self.dev)
         self._cap = 0
         self._graphs = {}
 
@@ -350,6 +361,8 @@ class LandmarkDetector(object):
             self._mu = torch.zeros(batch, K, 2, device=self.dev)
             self._py = torch.zeros(batch, He, K, device=self.dev)
             self._px = torch.zeros(batch, He, K, device=self.dev)
+            self._geom = torch.zeros(batch, 4, device=self.dev)                        # keypoints(): (y0, x0, sy, sx) per row
+            self._kp = torch.zeros(batch * ops.MAX_KEYPOINTS * 2, device=self.dev)     # keypoints(): [batch, M, 2]
         self._cap = batch
 
     def _xin_for(self, batch):
@@ -358,10 +371,11 @@ class LandmarkDetector(object):
                 self._xin = torch.zeros(self._cap, self.S, self.S, 32, dtype=self.dt, device=self.dev)
         return self._xin[:batch]
 
-    def program(self, batch, u8=False):
+    def program(self, batch, u8=False, kp_m=None):
         """The launches of one bucket: [_Launch(tag, name, family, fn)].  tag: 'resize' | 'pack_image' | 'conv' | 'pose_head'
         (| 'softargmax' for heads the one-launch kernel does not serve); family: the conv kernel family (imm_conv2d_variant's,
-        'first' for imm_conv_first)."""
+        'first' for imm_conv_first).  kp_m: the program of keypoints() with M annotated points: the pose head with its keypoint
+        epilogue (tag 'pose_head_kp')."""
         self._ensure_capacity(batch)
         B, S, dt = int(batch), self.S, self.dt
         prog = []
@@ -374,7 +388,17 @@ class LandmarkDetector(object):
         assert H == He
         heat, mu, py, px = self._heat[:B], self._mu[:B], self._py[:B], self._px[:B]
         mode = self.cfg.gauss_mode
-        if self.fused_head:
+        if kp_m is not None:
+            if not self.fused_head:
+                raise NotImplementedError('keypoints() needs the one-launch pose head (imm_pose_head_fwd), which does not serve '
+                                          'this model (8 * n_filters = %d, heat map %dx%d, K = %d)' % (C, He, He, K))
+            M = int(kp_m)
+            kw, kb = self._kp_w[:2 * K * 2 * M].view(2 * K, 2 * M), self._kp_b[:2 * M]
+            geom, kp = self._geom[:B], self._kp[:B * M * 2].view(B, M, 2)
+            prog.append(_Launch('pose_head_kp', POSE_SCOPE + '/conv_1', 'pose_head', lambda: ops.pose_head_fwd(
+                x, C, C, self.wt_head, self.bias_head, B, He, He, K, self.inv_std, 16, heat, self.ldh, mu, py, px, None, K, dt, mode,
+                keypoints=ops.keypoint_desc(kw, kb, geom, kp, self.S))))
+        elif self.fused_head:
             prog.append(_Launch('pose_head', POSE_SCOPE + '/conv_1', 'pose_head', lambda: ops.pose_head_fwd(
                 x, C, C, self.wt_head, self.bias_head, B, He, He, K, self.inv_std, 16, heat, self.ldh, mu, py, px, None, K, dt, mode)))
         else:
@@ -385,16 +409,17 @@ class LandmarkDetector(object):
                 heat, self.ldh, B, He, He, K, self.inv_std, 16, mu, py, px, None, K, dt, mode)))
         return prog
 
-    def _run(self, batch):
-        """Issue the (graph of the) program of bucket `batch` on the detector's stream."""
+    def _run(self, batch, kp_m=None):
+        """Issue the (graph of the) program of bucket `batch` (with the keypoint epilogue of M = kp_m points) on the detector's stream."""
         if not self.use_graph:
-            for l in self.program(batch):
+            for l in self.program(batch, kp_m=kp_m):
                 if l.fn is not None:
                     l.fn()
             return
-        g = self._graphs.get(batch)
+        key = batch if kp_m is None else (batch, int(kp_m))
+        g = self._graphs.get(key)
         if g is None:
-            prog = [l for l in self.program(batch) if l.fn is not None]
+            prog = [l for l in self.program(batch, kp_m=kp_m) if l.fn is not None]
             for l in prog:                 # warm-up outside capture (code-object loading, LDS attribute calls)
                 l.fn()
             self.stream.synchronize()
@@ -403,7 +428,7 @@ class LandmarkDetector(object):
             for l in prog:
                 l.fn()
             g.capture_end()
-            self._graphs[batch] = g
+            self._graphs[key] = g
         g.launch()
 
     # ------------------------------------------------------------------------------------------------------------------------
@@ -436,3 +461,52 @@ class LandmarkDetector(object):
                     heat_out[start:start + count].copy_(self._heat[:count, ..., :K])
         cur.wait_stream(self.stream)
         return (mu_out, heat_out) if heatmaps else mu_out
+
+    def keypoints(self, images, regressor, boxes=None, return_mu=False):
+        """The regressor's M annotated points in source pixels: f32 [n, M, 2] (y, x) on the detector's device, one row per box
+        (per image without boxes), and with return_mu=True also the landmarks mu f32 [n, K, 2] of the same rows.
+        images: as detect() takes them.  regressor: a keypoints.LandmarkRegressor fitted for this detector's K and S.
+        boxes: only with a list of u8 arrays: rows (image, y0, x0, y1, x1) or one (y0, x0, y1, x1) per image, half-open, in source
+        pixels (keypoints.check_boxes); each box is cut from its image with zero padding where it leaves it and resized to S x S on
+        the GPU.  Without boxes, u8 images are resized whole (the points scale back by h / S, w / S) and a tensor batch is already
+        the S x S frame."""
+        from . import keypoints as KP
+        regressor.check(self.K, self.S)
+        w, b = regressor.epilogue_weights()
+        M = regressor.M
+        images, u8 = as_image_batch(images, self.S)
+        if u8:
+            images = decode_u8(images)
+            rows = KP.check_boxes([(0, 0, a.shape[0], a.shape[1]) for a in images] if boxes is None else boxes, len(images))
+            geom = KP.box_geometry(rows, self.S)
+        else:
+            if boxes is not None:
+                raise ValueError('boxes need the images as a list of u8 arrays (a tensor batch is already S x S)')
+            geom = np.tile(np.array([0, 0, 1, 1], np.float32), (len(images), 1))
+        N, K = len(geom), self.K
+        cur = torch.cuda.current_stream(self.dev)
+        kp_out = torch.empty(N, M, 2, device=self.dev)
+        mu_out = torch.empty(N, K, 2, device=self.dev) if return_mu else None
+        self.stream.wait_stream(cur)
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            self._stager.copy(self._kp_w[:w.size], torch.from_numpy(w.reshape(-1)), ('kp_w', M))
+            self._stager.copy(self._kp_b[:b.size], torch.from_numpy(b), ('kp_b', M))
+            for start, count, bucket in plan_buckets(N, self.max_batch):
+                self._ensure_capacity(bucket)
+                if u8:
+                    # the images this bucket's boxes cut from, packed once each; box rows renumbered into that list
+                    part = rows[start:start + count]
+                    used, idx = np.unique(part[:, 0], return_inverse=True)
+                    local = np.concatenate([idx.reshape(-1, 1).astype(np.int32), part[:, 1:]], axis=1)
+                    stage_u8([images[i] for i in used], self._img[:count], self.S, self.dev, boxes=local)
+                else:
+                    self._stager.copy(self._img[:count], images[start:start + count], ('images', count))
+                if count < bucket:
+                    self._img[count:bucket].zero_()
+                self._stager.copy(self._geom[:count], torch.from_numpy(geom[start:start + count]), ('geom', count))
+                self._run(bucket, M)
+                kp_out[start:start + count].copy_(self._kp[:count * M * 2].view(count, M, 2))
+                if return_mu:
+                    mu_out[start:start + count].copy_(self._mu[:count])
+        cur.wait_stream(self.stream)
+        return (kp_out, mu_out) if return_mu else kp_out

@@ -387,9 +387,33 @@ def softargmax_gauss_bwd(dgauss, ldg, batch, h, w, k, inv_std, s, mu, py, px, dh
          _p(py), _p(px), _p(dheat), lddh, gauss_mode_enum(mode), _s())
 
 
-def pose_head_fwd(feat, ldf, c, wt, bias, batch, h, w, k, inv_std, s, heat, ldh, mu, py, px, gauss_out, ldg, dtype, mode='rot'):
+MAX_KEYPOINTS = 16            # annotated points of the pose head's keypoint epilogue
+
+
+def keypoint_desc(w, b, geom, keypoints, image_size):
+    """The keypoint epilogue's descriptor (include/imm_hip.h: imm_keypoint_desc): w f32 [2K, 2M], b f32 [2M], geom f32 [>= batch, 4]
+    (y0, x0, sy, sx), keypoints f32 [>= batch, M, 2]; all contiguous device tensors.  M is keypoints.shape[1]."""
+    m = int(keypoints.shape[1])
+    if not 1 <= m <= MAX_KEYPOINTS:
+        raise ValueError('the keypoint epilogue serves 1..%d annotated points, got %d' % (MAX_KEYPOINTS, m))
+    if tuple(w.shape[1:]) != (2 * m,) or tuple(b.shape) != (2 * m,) or geom.shape[1:] != (4,) or keypoints.shape[2:] != (2,):
+        raise ValueError('keypoint descriptor shapes: w %s, b %s, geom %s, keypoints %s' % (
+            tuple(w.shape), tuple(b.shape), tuple(geom.shape), tuple(keypoints.shape)))
+    for t in (w, b, geom, keypoints):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError('keypoint descriptor tensors must be contiguous float32')
+    return L.KeypointDesc(w.data_ptr(), b.data_ptr(), geom.data_ptr(), keypoints.data_ptr(), m, int(image_size))
+
+
+def pose_head_fwd(feat, ldf, c, wt, bias, batch, h, w, k, inv_std, s, heat, ldh, mu, py, px, gauss_out, ldg, dtype, mode='rot',
+                  keypoints=None):
+    """keypoints: None, or the epilogue's descriptor (keypoint_desc(...)): the regressed annotated points in source pixels."""
+    if keypoints is not None:
+        if int(keypoints.m) > MAX_KEYPOINTS or k > 64:
+            raise ValueError('the keypoint epilogue serves M <= %d, K <= 64 (M=%d, K=%d)' % (MAX_KEYPOINTS, int(keypoints.m), k))
+        keypoints = C.byref(keypoints)
     call('imm_pose_head_fwd', _p(feat), ldf, c, _p(wt), wt.shape[1], _p(bias), dtype_enum(dtype), batch, h, w, k, float(inv_std), s,
-         _p(heat), ldh, _p(mu), _p(py), _p(px), _p(gauss_out), ldg, gauss_mode_enum(mode), _s())
+         _p(heat), ldh, _p(mu), _p(py), _p(px), _p(gauss_out), ldg, gauss_mode_enum(mode), keypoints, _s())
 
 
 def pose_head_bwd(dgauss, ldg, batch, h, w, k, inv_std, s, mu, py, px, dheat, lddh, wt_dgrad, c, dfeat, lddf, bias_partial, mode='rot'):
@@ -652,11 +676,16 @@ def tps_warp_pad(src, basis_t, w_tps, pad_yx, grid_hw, crop_yx, dst):
          dst.shape[1], dst.shape[2], _p(basis_t), basis_t.shape[0], _p(w_tps), _p(dst), dst.stride(2), _s())
 
 
-def resize_crop_u8(src_u8, offsets, hw, c, resize_hw, crop_yx, out_hw, dst, ld_dst=None):
+def resize_crop_u8(src_u8, offsets, hw, c, resize_hw, crop_yx, out_hw, dst, ld_dst=None, boxes=None):
     """src_u8: flat u8 device buffer of packed HWC images; offsets i64 [B]; hw i32 [B,2]; dst f32 view whose element
-    (b,y,x,0) is dst.data_ptr() + ((b*oh+y)*ow+x)*ld_dst floats (include/imm_hip.h: imm_resize_crop_u8)."""
-    call('imm_resize_crop_u8', _p(src_u8), _p(offsets), _p(hw), hw.shape[0], c, resize_hw[0], resize_hw[1], crop_yx[0], crop_yx[1],
-         out_hw[0], out_hw[1], _p(dst), dst.stride(2) if ld_dst is None else ld_dst, _s())
+    (b,y,x,0) is dst.data_ptr() + ((b*oh+y)*ow+x)*ld_dst floats (include/imm_hip.h: imm_resize_crop_u8).
+    boxes: None, or int32 [n, 5] device rows (image, y0, x0, y1, x1) checked on the host beforehand
+    (imm_amd.keypoints.check_boxes): output row b is box b cut from its image, zero-padded, then resized and cropped."""
+    if boxes is not None and (boxes.dtype != torch.int32 or boxes.dim() != 2 or boxes.shape[1] != 5 or not boxes.is_contiguous()):
+        raise ValueError('boxes must be contiguous int32 [n, 5], got %s %s' % (boxes.dtype, tuple(boxes.shape)))
+    batch = hw.shape[0] if boxes is None else boxes.shape[0]
+    call('imm_resize_crop_u8', _p(src_u8), _p(offsets), _p(hw), _p(boxes), batch, c, resize_hw[0], resize_hw[1], crop_yx[0],
+         crop_yx[1], out_hw[0], out_hw[1], _p(dst), dst.stride(2) if ld_dst is None else ld_dst, _s())
 
 
 def masked_sse_pool(a, b, batch, s, c, mask, S, partial, pool_a, pool_b):

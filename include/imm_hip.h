@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define IMM_ABI_VERSION 23   /* 23: render-only mode of the soft-argmax forward (heat == NULL: mu is the input).  22: s2f / conv_first accept IMM_CONV_RELU.  21: imm_masked_sse_all.  20: imm_vgg_head_fwd / imm_vgg_head_supported / imm_vgg_head_scratch_bytes (conv1_1 + conv1_2 in one launch).  19: imm_set_cu_limit / imm_get_cu_limit, imm_masked_sse_pool with pool_a == NULL.  18: imm_copy_f32.  17: imm_cost_ema, imm_rms16 (summaries).  16: imm_conv2d_variant.  15: imm_conv2d_dgrad_s2, imm_conv2d_nol, imm_conv_first, imm_wgrad_job.x_scale/x_shift/x_relu; entry points removed
+#define IMM_ABI_VERSION 24   /* 24: box-crop mode of imm_resize_crop_u8 (boxes), keypoint epilogue of imm_pose_head_fwd (imm_keypoint_desc).  23: render-only mode of the soft-argmax forward (heat == NULL: mu is the input).  22: s2f / conv_first accept IMM_CONV_RELU.  21: imm_masked_sse_all.  20: imm_vgg_head_fwd / imm_vgg_head_supported / imm_vgg_head_scratch_bytes (conv1_1 + conv1_2 in one launch).  19: imm_set_cu_limit / imm_get_cu_limit, imm_masked_sse_pool with pool_a == NULL.  18: imm_copy_f32.  17: imm_cost_ema, imm_rms16 (summaries).  16: imm_conv2d_variant.  15: imm_conv2d_dgrad_s2, imm_conv2d_nol, imm_conv_first, imm_wgrad_job.x_scale/x_shift/x_relu; entry points removed
                                   since 14 (imm_bn_bwd_reduce_finalize, imm_conv2d_stats_workspace_bytes) finally counted */
 
 /* IMM_F32 (round 6): f32 activation storage — the exact-arithmetic WITNESS of the wiring, a test instrument (the reference computes
@@ -344,9 +344,24 @@ int imm_softargmax_gauss_bwd(const void* dgauss, int ldg, int dtype, int batch, 
  *      image, row length kpad_d >= lddh) and bias_partial f32 [B][K] = per-sample column sums of the stored dheat, to be summed
  *      over B by imm_wgrad_reduce_multi (job {bias_partial, db, B, 1, 1, 1, K, 1}).  Replaces imm_softargmax_gauss_bwd +
  *      imm_colsum + imm_conv2d(data gradient) of the head. */
+/* Keypoint epilogue of imm_pose_head_fwd (ABI 24; kp == NULL: none, the kernel and its results of before).  A host struct read at
+ * the call (a captured graph keeps its values); the pointers are device pointers.  Per sample b, after mu:
+ *   x[i] = (mu[i] + 1) / 2 * image_size   (i < 2K, mu flattened (y0, x0, y1, x1, ...): scripts/test.py convert_landmarks)
+ *   kp[j] = b[j] + sum_i x[i] * w[i * 2M + j]                     (j < 2M: a fitted linear regressor, f32)
+ *   keypoints[b][m] = (geom[b][0] + kp[2m] * geom[b][2], geom[b][1] + kp[2m+1] * geom[b][3])   (source pixels)
+ * geom (y0, x0, sy, sx) inverts imm/datasets/impair_dataset.py:116-123 _resize_points: sy = box height / image_size.  A kernel of
+ * its own (the one without kp is unchanged); mu, heat, py, px and the maps are bit-identical with and without kp.  1 <= m <= 16. */
+typedef struct imm_keypoint_desc {
+  const float* w;           /* f32 [2K, 2M]                                          */
+  const float* b;           /* f32 [2M] (zeros without an intercept)                 */
+  const float* geom;        /* f32 [batch, 4]: (y0, x0, sy, sx)                       */
+  float* keypoints;         /* f32 [batch, M, 2] (y, x), written                     */
+  int32_t m;                /* M annotated points                                    */
+  int32_t image_size;       /* S of the landmark frame                               */
+} imm_keypoint_desc;
 int imm_pose_head_fwd(const void* feat, int ldf, int c, const void* wt, int kpad, const float* bias, int dtype, int batch, int h,
                       int w, int k, float inv_std, int s, float* heat, int ldh, float* mu, float* py, float* px, void* gauss_out,
-                      int ldg, int gauss_mode, void* stream);
+                      int ldg, int gauss_mode, const imm_keypoint_desc* kp, void* stream);
 int imm_pose_head_bwd(const void* dgauss, int ldg, int dtype, int batch, int h, int w, int k, float inv_std, int s, const float* mu,
                       const float* py, const float* px, void* dheat, int lddh, int gauss_mode, const void* wt_dgrad, int kpad_d,
                       int c, void* dfeat, int lddf, float* bias_partial, void* stream);
@@ -529,9 +544,15 @@ int imm_tps_warp_pad(const float* src, int ld_src, int batch, int h, int w, int 
  * hw[2b] rows x hw[2b+1] columns x c channels (1 <= c <= 4).  Each is resized (TF1 resize_bilinear, align_corners=True) to
  * resize_h x resize_w and the window [crop_y0, crop_y0+out_h) x [crop_x0, crop_x0+out_w) of that is written as float32
  * (values stay in [0, 255]) to dst[b][y][x][0..c-1], pixel stride ld_dst floats (>= c: dst may point at channel 1 of
- * the mask||image stack imm_tps_warp reads).  Float32 arithmetic in TF's order, unfused: bit-exact vs the host oracle. */
-int imm_resize_crop_u8(const uint8_t* src, const int64_t* offsets, const int32_t* hw, int batch, int c, int resize_h,
-                       int resize_w, int crop_y0, int crop_x0, int out_h, int out_w, float* dst, int ld_dst, void* stream);
+ * the mask||image stack imm_tps_warp reads).  Float32 arithmetic in TF's order, unfused: bit-exact vs the host oracle.
+ * Box-crop mode (boxes != NULL; ABI 24): boxes int32 [batch, 5] = (image, y0, x0, y1, x1), half-open, in source pixels, may reach
+ * outside the image; output row b is that box cut from image boxes[b][0] with zeros where it leaves the image
+ * (impair_dataset.py:96-113 _crop_to_box with padding), then resized and cropped as above.  Rows may share an image; offsets / hw
+ * are indexed by image.  The caller guarantees 0 <= image < the number of packed images, y1 > y0 and x1 > x0.  boxes == NULL:
+ * the kernel and results of before. */
+int imm_resize_crop_u8(const uint8_t* src, const int64_t* offsets, const int32_t* hw, const int32_t* boxes, int batch, int c,
+                       int resize_h, int resize_w, int crop_y0, int crop_x0, int out_h, int out_w, float* dst, int ld_dst,
+                       void* stream);
 
 /* ---- host utility: CRC-32C of TensorFlow checkpoint bundles (cnn_train_multi.py:404-439 tf.train.Saver files) ---- */
 /* *crc_inout = crc32c(*crc_inout continued over data[0..n)); start with 0.  Host memory, no GPU work. */

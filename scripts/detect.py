@@ -5,7 +5,11 @@ to --im-size on the GPU (TF1 bilinear, align_corners), like the data loaders do.
         --checkpoint logs/celeba-10pts/model.ckpt-2000 --images-dir faces/ --out landmarks.npz [--plot landmarks.png]
 The checkpoint is a `.pt` file written by scripts/train.py or a TensorFlow bundle prefix (the authors' release).
 landmarks.npz holds `files` [N], `mu` [N, K, 2] ((y, x) in [-1, 1]), `landmarks` [N, K, 2] ((y, x) pixels of the im-size x im-size
-image, the convert_landmarks convention of scripts/test.py) and `sizes` [N, 2] (the decoded images' heights and widths)."""
+image, the convert_landmarks convention of scripts/test.py) and `sizes` [N, 2] (the decoded images' heights and widths).
+With --regressor (a file written by scripts/test.py --save-regressor) it also holds the regressed annotated points of every face:
+`keypoints` [F, M, 2] ((y, x) pixels of the source image), `boxes` [F, 4] ((y0, x0, y1, x1) source pixels, half-open) and `owner`
+[F] (the index into `files` of each face's image).  The faces are the rows of --boxes, a CSV (`file, y0, x0, y1, x1` per line) or
+JSON ([[file, y0, x0, y1, x1], ...]) file, in its order; without --boxes, one face per image, the whole image."""
 from __future__ import print_function
 
 import argparse
@@ -19,9 +23,35 @@ import torch
 sys.path.insert(0, osp.dirname(osp.dirname(osp.abspath(__file__))))
 from imm_amd.datasets.impair_dataset import decode_image   # noqa: E402
 from imm_amd.inference import LandmarkDetector              # noqa: E402
+from imm_amd.keypoints import LandmarkRegressor              # noqa: E402
 from imm_amd.utils.config import load_configs               # noqa: E402
 
 EXTENSIONS = ('.jpg', '.jpeg', '.png', '.bmp')
+
+
+def read_boxes(path, files):
+    """Rows `file, y0, x0, y1, x1` of a CSV or JSON file -> (owner int [F], boxes int [F, 4]); owner indexes `files`."""
+    import csv
+    import json
+    with open(path) as f:
+        text = f.read()
+    if path.lower().endswith('.json'):
+        rows = json.loads(text)
+    else:
+        rows = [r for r in csv.reader(text.splitlines()) if r and not r[0].lstrip().startswith('#')]
+        if rows and rows[0][0].strip() == 'file':
+            rows = rows[1:]
+    index = {f: i for i, f in enumerate(files)}
+    owner, boxes = [], []
+    for r in rows:
+        if len(r) != 5:
+            raise ValueError('%s: a row is `file, y0, x0, y1, x1`, got %r' % (path, r))
+        name = str(r[0]).strip()
+        if name not in index:
+            raise ValueError('%s: %s is not an image of the folder' % (path, name))
+        owner.append(index[name])
+        boxes.append([int(float(v)) for v in r[1:]])
+    return np.array(owner, dtype=np.int64), np.array(boxes, dtype=np.int64).reshape(-1, 4)
 
 
 def main(args):
@@ -33,17 +63,48 @@ def main(args):
     dtype = {'bf16': torch.bfloat16, 'f16': torch.float16}[args.dtype]
     det = LandmarkDetector.from_checkpoint(config.model, args.checkpoint, image_size=args.im_size, max_batch=args.batch_size,
                                            dtype=dtype, device='cuda:0')
+    reg = LandmarkRegressor.load(args.regressor, detector=det) if args.regressor else None
+    if args.boxes and reg is None:
+        raise ValueError('--boxes needs --regressor')
+    owner, boxes = read_boxes(args.boxes, files) if args.boxes else (None, None)
     mus, sizes = [], []
+    kps = np.zeros((0 if reg is None else (len(files) if boxes is None else len(boxes)), 0 if reg is None else reg.M, 2), np.float32)
     chunk = 4 * args.batch_size                  # images decoded and held on the host at a time
     for i in range(0, len(files), chunk):
         ims = [decode_image(osp.join(args.images_dir, f)) for f in files[i:i + chunk]]
         sizes += [im.shape[:2] for im in ims]
         mus.append(det.detect(ims).cpu().numpy())
+        if reg is not None and boxes is None:
+            kps[i:i + len(ims)] = det.keypoints(ims, reg).cpu().numpy()
+        elif reg is not None:
+            rows = np.nonzero((owner >= i) & (owner < i + len(ims)))[0]
+            if rows.size:
+                local = np.concatenate([owner[rows, None] - i, boxes[rows]], axis=1)
+                kps[rows] = det.keypoints(ims, reg, boxes=local.tolist()).cpu().numpy()
     mu = np.concatenate(mus)
     landmarks = ((mu + 1) / 2.0) * args.im_size
-    np.savez(args.out, files=np.array(files), mu=mu, landmarks=landmarks, sizes=np.array(sizes, dtype=np.int32))
+    out = dict(files=np.array(files), mu=mu, landmarks=landmarks, sizes=np.array(sizes, dtype=np.int32))
+    if reg is not None:
+        if boxes is None:
+            owner = np.arange(len(files), dtype=np.int64)
+            boxes = np.concatenate([np.zeros((len(files), 2), np.int64), np.array(sizes, dtype=np.int64).reshape(-1, 2)], axis=1)
+        out.update(keypoints=kps, boxes=boxes.astype(np.int32), owner=owner.astype(np.int32))
+    np.savez(args.out, **out)
     print('%d images, %d landmarks each -> %s' % (mu.shape[0], mu.shape[1], args.out))
-    if args.plot:
+    if reg is not None:
+        print('%d faces, %d keypoints each (%s)' % (kps.shape[0], reg.M, ', '.join(reg.labels)))
+    if args.plot and reg is not None:
+        from PIL import Image
+        from imm_amd.utils.plot_landmarks import plot_landmarks
+        tiles = []
+        for j, f in list(enumerate(files))[:args.plot_max]:
+            pts = kps[owner == j].reshape(-1, 2)                   # every face of the image, in its source pixels
+            h, w = sizes[j]
+            with Image.open(osp.join(args.images_dir, f)) as im:
+                small = np.asarray(im.convert('RGB').resize((args.im_size, args.im_size), Image.BILINEAR))
+            tiles.append(np.asarray(plot_landmarks(small, pts * np.array([args.im_size / h, args.im_size / w]), scale=2)))
+        save_sheet(tiles, args.plot)
+    elif args.plot:
         from PIL import Image
         from imm_amd.utils.plot_landmarks import plot_landmarks
         tiles = []
@@ -51,14 +112,19 @@ def main(args):
             with Image.open(osp.join(args.images_dir, f)) as im:
                 small = np.asarray(im.convert('RGB').resize((args.im_size, args.im_size), Image.BILINEAR))
             tiles.append(np.asarray(plot_landmarks(small, lm, scale=2)))
-        cols = min(len(tiles), 8)
-        rows = -(-len(tiles) // cols)
-        h, w = tiles[0].shape[:2]
-        sheet = np.full((rows * h, cols * w, 3), 255, dtype=np.uint8)
-        for j, t in enumerate(tiles):
-            sheet[(j // cols) * h:(j // cols + 1) * h, (j % cols) * w:(j % cols + 1) * w] = t
-        Image.fromarray(sheet).save(args.plot)
-        print('plot -> %s' % args.plot)
+        save_sheet(tiles, args.plot)
+
+
+def save_sheet(tiles, path):
+    from PIL import Image
+    cols = min(len(tiles), 8)
+    rows = -(-len(tiles) // cols)
+    h, w = tiles[0].shape[:2]
+    sheet = np.full((rows * h, cols * w, 3), 255, dtype=np.uint8)
+    for j, t in enumerate(tiles):
+        sheet[(j // cols) * h:(j // cols + 1) * h, (j % cols) * w:(j % cols + 1) * w] = t
+    Image.fromarray(sheet).save(path)
+    print('plot -> %s' % path)
 
 
 if __name__ == '__main__':
@@ -72,4 +138,8 @@ if __name__ == '__main__':
     parser.add_argument('--im-size', type=int, default=128)
     parser.add_argument('--batch-size', type=int, default=256, help='largest batch bucket of the detector')
     parser.add_argument('--dtype', choices=('bf16', 'f16'), default='bf16')
+    parser.add_argument('--regressor', type=str, default=None,
+                        help='regressor .npz of scripts/test.py --save-regressor: also write the annotated points of every face')
+    parser.add_argument('--boxes', type=str, default=None,
+                        help='CSV or JSON face boxes, one row `file, y0, x0, y1, x1` per face (default: each whole image)')
     main(parser.parse_args())

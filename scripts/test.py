@@ -3,7 +3,9 @@ test split come from the MAFL / AFLW loaders (imm_amd/datasets, tps=False, order
     python scripts/test.py --experiment-name celeba-10pts --train-dataset mafl --test-dataset mafl [--iteration N]
 or, without dataset files, from .npz files with `image`, `future_image` (NHWC float32, [0,255]) and `future_landmarks`
 ([N,L,2] (y, x) pixels, first two points = the eyes):
-    python scripts/test.py --configs a.yaml b.yaml --train-npz mafl_train.npz --test-npz mafl_test.npz --checkpoint x.pt"""
+    python scripts/test.py --configs a.yaml b.yaml --train-npz mafl_train.npz --test-npz mafl_test.npz --checkpoint x.pt
+--save-regressor PATH also writes the regressor behind the printed error (coef, intercept, K, S, ...; imm_amd/keypoints.py), which
+scripts/detect.py --regressor applies to photos."""
 from __future__ import print_function
 
 import argparse
@@ -74,8 +76,14 @@ def main(args):
         ck = torch.load(ckpt, map_location='cpu')
         eng.load_parameters(ck['params'], ck.get('state'))
     detector = net.landmark_detector(args.im_size, max_batch=args.batch_size) if args.detector else None
-    err = eval_imm.evaluate_regression(net, train_it, test_it, [args.im_size, args.im_size], batch_size=args.batch_size,
-                                       bias=args.bias, detector=detector)
+    if args.save_regressor:
+        err, reg = eval_imm.fit_regression(net, train_it, test_it, [args.im_size, args.im_size], batch_size=args.batch_size,
+                                           bias=args.bias, detector=detector,
+                                           dataset=args.train_dataset if args.train_npz is None else args.train_npz, checkpoint=ckpt)
+        reg.save(args.save_regressor)
+    else:
+        err = eval_imm.evaluate_regression(net, train_it, test_it, [args.im_size, args.im_size], batch_size=args.batch_size,
+                                           bias=args.bias, detector=detector)
     model_dataset = config.training.train_dset_params.dataset if hasattr(config.training, 'train_dset_params') and \
         'dataset' in config.training.train_dset_params else getattr(config.training, 'dset', '?')
     print('')
@@ -105,4 +113,7 @@ if __name__ == '__main__':
     parser.add_argument('--test-npz', type=str, default=None)
     parser.add_argument('--detector', action='store_true',
                         help='landmarks through the LandmarkDetector (pose encoder only, batch norm folded) instead of the full eval model')
+    parser.add_argument('--save-regressor', type=str, default=None,
+                        help='also write the fitted regressor behind the printed error to this .npz (imm_amd/keypoints.py; for '
+                             'scripts/detect.py --regressor)')
     main(parser.parse_args())
