@@ -20,7 +20,7 @@ CONV_BIAS, CONV_RELU, CONV_STATS, CONV_MASK, CONV_OUT_F32 = 1, 2, 4, 8, 16
 SSE_BLOCKS = 512
 OPTIMIZERS = {'adam': 0, 'adadelta': 1, 'adagrad': 2}      # IMM_OPT_* (scripts/train.py:97-104)
 GAUSS_MODES = {'rot': 0, 'flat': 1, 'ankush': 2}     # IMM_GAUSS_* (config key gauss_mode, imm_model.py:48-72)
-ABI_VERSION = 24     # 24: box-crop mode of imm_resize_crop_u8, keypoint epilogue of imm_pose_head_fwd.  23: render-only mode of imm_softargmax_gauss_fwd (heat NULL).  22: s2f / conv_first accept IMM_CONV_RELU
+ABI_VERSION = 25     # 25: imm_align_coeffs / imm_align_warp_u8 (include/imm_align.h).  24: box-crop mode of imm_resize_crop_u8, keypoint epilogue of imm_pose_head_fwd.  23: render-only mode of imm_softargmax_gauss_fwd (heat NULL).  22: s2f / conv_first accept IMM_CONV_RELU
 
 
 class ImmHipError(RuntimeError):
@@ -143,6 +143,12 @@ _SIGS = {
     'imm_clip_adam_step': [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(OptHParams), _P, _P],
 }
 
+# the alignment entry points (include/imm_align.h, ABI 25)
+_SIGS_ALIGN = {
+    'imm_align_coeffs': [_P, _P, _I, _I, _I, _P, _P],
+    'imm_align_warp_u8': [_P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P],
+}
+
 # byte-size twins of the row-count queries (int64 result; < 0 = unsupported)
 _SIGS64 = {
     'imm_conv2d_workspace_bytes': [C.POINTER(ConvDesc)],
@@ -160,7 +166,13 @@ _lib = None
 
 
 def declared_symbols():
+    """The entry points include/imm_hip.h itself declares."""
     return sorted(list(_SIGS) + list(_SIGS64) + ['imm_last_error', 'imm_source_digest'])
+
+
+def alignment_symbols():
+    """The entry points include/imm_align.h declares."""
+    return sorted(_SIGS_ALIGN)
 
 
 def load():
@@ -185,7 +197,7 @@ def load():
     for name in ('imm_last_error', 'imm_source_digest'):
         getattr(lib, name).restype = C.c_char_p
         getattr(lib, name).argtypes = []
-    for name, args in _SIGS.items():
+    for name, args in list(_SIGS.items()) + list(_SIGS_ALIGN.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int

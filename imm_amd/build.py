@@ -33,7 +33,7 @@ def source_digest():
     the production library."""
     h = hashlib.sha256()
     h.update(('arch=%s flags=%s\0' % (ARCH, ' '.join(_extra_flags()))).encode())
-    for p in _sources() + sorted(glob.glob(os.path.join(CSRC, '*.h'))) + [os.path.join(ROOT, 'include', 'imm_hip.h')]:
+    for p in _sources() + sorted(glob.glob(os.path.join(CSRC, '*.h'))) + sorted(glob.glob(os.path.join(ROOT, 'include', '*.h'))):
         with open(p, 'rb') as f:
             h.update(os.path.relpath(p, ROOT).replace(os.sep, '/').encode() + b'\0' + f.read() + b'\0')
     return h.hexdigest()

@@ -83,9 +83,10 @@ def detect_landmarks(dataset_iter, detector):
     return results
 
 
-def evaluate_regression(net_instance, train_iter, test_iter, im_size, batch_size=100, bias=False, detector=None):
+def evaluate_regression(net_instance, train_iter, test_iter, im_size, batch_size=100, bias=False, detector=None, landmarks_out=None):
     """scripts/test.py:18-65 `evaluate`: unsupervised landmarks of both splits -> Ridge -> inter-ocular error.  detector: a
-    LandmarkDetector that computes the landmarks of both splits instead of net_instance.build."""
+    LandmarkDetector that computes the landmarks of both splits instead of net_instance.build.  landmarks_out: a dict that receives
+    the training split's landmarks as 'gauss_yx' [N, K, 2] (what a LandmarkTemplate is the mean shape of)."""
     def run(it):
         if detector is not None:
             res = detect_landmarks(it, detector)
@@ -93,13 +94,16 @@ def evaluate_regression(net_instance, train_iter, test_iter, im_size, batch_size
             res = evaluate(it, net_instance, batch_size=batch_size, random_seed=0, eval_tensors=['gauss_yx', 'future_landmarks'])
         return {k: np.concatenate(v) for k, v in res.items()}
     train_t, test_t = run(train_iter), run(test_iter)
+    if landmarks_out is not None:
+        landmarks_out['gauss_yx'] = train_t['gauss_yx']
     pred = regress_landmarks(train_t, test_t, im_size, bias)
     return interocular_error(test_t['future_landmarks'], pred)
 
 
-def fit_regression(net_instance, train_iter, test_iter, im_size, batch_size=100, bias=False, detector=None, dataset='', checkpoint=''):
+def fit_regression(net_instance, train_iter, test_iter, im_size, batch_size=100, bias=False, detector=None, dataset='', checkpoint='',
+                   landmarks_out=None):
     """evaluate_regression's error, computed through a LandmarkRegressor (imm_amd/keypoints.py: the same Ridge fit and prediction,
-    kept) -> (error, regressor)."""
+    kept) -> (error, regressor).  landmarks_out: as evaluate_regression takes it."""
     from ..keypoints import LandmarkRegressor
 
     def run(it):
@@ -109,6 +113,8 @@ def fit_regression(net_instance, train_iter, test_iter, im_size, batch_size=100,
             res = evaluate(it, net_instance, batch_size=batch_size, random_seed=0, eval_tensors=['gauss_yx', 'future_landmarks'])
         return {k: np.concatenate(v) for k, v in res.items()}
     train_t, test_t = run(train_iter), run(test_iter)
+    if landmarks_out is not None:
+        landmarks_out['gauss_yx'] = train_t['gauss_yx']
     reg = LandmarkRegressor.fit(train_t, im_size, bias, dataset=dataset, checkpoint=checkpoint)
     gt = np.asarray(test_t['future_landmarks']).astype(np.float32)
     pred = reg.predict(test_t['gauss_yx']).reshape(gt.shape)

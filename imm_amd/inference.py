@@ -228,10 +228,9 @@ def decode_u8(images):
     return decoded
 
 
-def stage_u8(images, dst, S, device, boxes=None):
-    """Pack u8 HWC images back to back (16-byte aligned starts, like the data loader) and resize them on the GPU (TF1 bilinear,
-    align_corners) into dst f32 [len(images), S, S, 3] (current stream).  boxes: int32 [n, 5] rows (image, y0, x0, y1, x1) checked
-    by keypoints.check_boxes: dst row b is then box b cut from images[boxes[b][0]] (zero-padded) and resized, dst [n, S, S, 3]."""
+def pack_u8(images, device, boxes=None):
+    """Pack u8 HWC images back to back (16-byte aligned starts, like the data loader) into one device buffer: (src u8, offsets i64
+    [count], hw i32 [count, 2], boxes i32 [n, 5] or None), what imm_resize_crop_u8 and imm_align_warp_u8 read."""
     decoded = decode_u8(images)
     count = len(decoded)
     offs = np.zeros(count, dtype=np.int64)
@@ -247,7 +246,16 @@ def stage_u8(images, dst, S, device, boxes=None):
     offs_d = ops.to_device_pinned(offs, device)
     hw_d = ops.to_device_pinned(hw, device)
     boxes_d = None if boxes is None else ops.to_device_pinned(np.ascontiguousarray(boxes, dtype=np.int32), device)
+    return src, offs_d, hw_d, boxes_d
+
+
+def stage_u8(images, dst, S, device, boxes=None):
+    """Pack u8 HWC images (pack_u8) and resize them on the GPU (TF1 bilinear, align_corners) into dst f32 [len(images), S, S, 3]
+    (current stream).  boxes: int32 [n, 5] rows (image, y0, x0, y1, x1) checked by keypoints.check_boxes: dst row b is then box b cut
+    from images[boxes[b][0]] (zero-padded) and resized, dst [n, S, S, 3].  Returns the packed device tensors."""
+    src, offs_d, hw_d, boxes_d = pack_u8(images, device, boxes)
     ops.resize_crop_u8(src, offs_d, hw_d, 3, (S, S), (0, 0), (S, S), dst, boxes=boxes_d)
+    return src, offs_d, hw_d, boxes_d
 
 
 class _Launch(object):
@@ -320,6 +328,10 @@ class LandmarkDetector(object):
             # keypoints(): the regressor's W [2K, 2M] and b [2M] at fixed addresses (rewritten before each call's replays)
             self._kp_w = torch.zeros(2 * K * 2 * ops.MAX_KEYPOINTS, device=self.dev)
             self._kp_b = torch.zeros(2 * ops.MAX_KEYPOINTS, device=self.dev)
+            # align(): F transposed [2K, 2 m3] at a fixed address (rewritten before each call's replays); the tps bases
+            # [m3, So * So] are made on first use, per (template, So)
+            self._al_ft = torch.zeros(2 * K * 2 * ops.MAX_ALIGN_M3, device=self.dev)
+        self._al_basis = {}
         self._cap = 0
         self._graphs = {}
 
@@ -363,6 +375,7 @@ class LandmarkDetector(object):
             self._px = torch.zeros(batch, He, K, device=self.dev)
             self._geom = torch.zeros(batch, 4, device=self.dev)                        # keypoints(): (y0, x0, sy, sx) per row
             self._kp = torch.zeros(batch * ops.MAX_KEYPOINTS * 2, device=self.dev)     # keypoints(): [batch, M, 2]
+            self._al_coef = torch.zeros(batch * ops.MAX_ALIGN_M3 * 2, device=self.dev)  # align(): [batch, m3, 2]
         self._cap = batch
 
     def _xin_for(self, batch):
@@ -371,11 +384,14 @@ class LandmarkDetector(object):
                 self._xin = torch.zeros(self._cap, self.S, self.S, 32, dtype=self.dt, device=self.dev)
         return self._xin[:batch]
 
-    def program(self, batch, u8=False, kp_m=None):
+    def program(self, batch, u8=False, kp_m=None, align=None):
         """The launches of one bucket: [_Launch(tag, name, family, fn)].  tag: 'resize' | 'pack_image' | 'conv' | 'pose_head'
         (| 'softargmax' for heads the one-launch kernel does not serve); family: the conv kernel family (imm_conv2d_variant's,
         'first' for imm_conv_first).  kp_m: the program of keypoints() with M annotated points: the pose head with its keypoint
-        epilogue (tag 'pose_head_kp')."""
+        epilogue (tag 'pose_head_kp').  align = (model, m3): the program of align(): detect()'s, then 'align_coeffs' (captured with
+        it) and 'align_warp' (issued by align() with the call's pixels, like 'resize')."""
+        if align is not None and kp_m is not None:
+            raise ValueError('a program serves keypoints() or align(), not both')
         self._ensure_capacity(batch)
         B, S, dt = int(batch), self.S, self.dt
         prog = []
@@ -407,19 +423,29 @@ class LandmarkDetector(object):
                                 lambda: ops.conv2d(d, x, self.wt_head, self.bias_head, heat)))
             prog.append(_Launch('softargmax', POSE_SCOPE + '/softargmax', 'softargmax', lambda: ops.softargmax_gauss_fwd(
                 heat, self.ldh, B, He, He, K, self.inv_std, 16, mu, py, px, None, K, dt, mode)))
+        if align is not None:
+            m3 = int(align[1])
+            if m3 != (K + 3 if align[0] == 'tps' else 3):
+                raise ValueError('align = (model, m3): %r has m3 = %d at K = %d' % (align[0], K + 3 if align[0] == 'tps' else 3, K))
+            ft, coef = self._al_ft[:2 * K * 2 * m3].view(2 * K, 2 * m3), self._al_coef[:B * m3 * 2].view(B, m3, 2)
+            prog.append(_Launch('align_coeffs', 'align/coeffs', 'align', lambda: ops.align_coeffs(mu, ft, K, m3, coef)))
+            prog.append(_Launch('align_warp', 'align/warp', 'align', None))     # issued by align() with the call's pixels
         return prog
 
-    def _run(self, batch, kp_m=None):
-        """Issue the (graph of the) program of bucket `batch` (with the keypoint epilogue of M = kp_m points) on the detector's stream."""
+    def _run(self, batch, kp_m=None, align=None):
+        """Issue the (graph of the) program of bucket `batch` (with the keypoint epilogue of M = kp_m points, or with align()'s
+        coefficient launch) on the detector's stream."""
         if not self.use_graph:
-            for l in self.program(batch, kp_m=kp_m):
+            for l in self.program(batch, kp_m=kp_m, align=align):
                 if l.fn is not None:
                     l.fn()
             return
         key = batch if kp_m is None else (batch, int(kp_m))
+        if align is not None:
+            key = (batch, 'align', int(align[1]))
         g = self._graphs.get(key)
         if g is None:
-            prog = [l for l in self.program(batch, kp_m=kp_m) if l.fn is not None]
+            prog = [l for l in self.program(batch, kp_m=kp_m, align=align) if l.fn is not None]
             for l in prog:                 # warm-up outside capture (code-object loading, LDS attribute calls)
                 l.fn()
             self.stream.synchronize()
@@ -510,3 +536,104 @@ class LandmarkDetector(object):
                     mu_out[start:start + count].copy_(self._mu[:count])
         cur.wait_stream(self.stream)
         return (kp_out, mu_out) if return_mu else kp_out
+
+    def _align_basis(self, template, model, So):
+        """The tps basis f32 [m3, So * So] of a template on the device (made once per template and output size); None for the
+        similarity and affine models, which read none."""
+        if model != 'tps':
+            return None
+        key = (template.points.tobytes(), int(So))
+        if key not in self._al_basis:
+            if len(self._al_basis) >= 8:                                   # a caller cycling through templates: drop the oldest
+                self._al_basis.pop(next(iter(self._al_basis)))
+            self._al_basis[key] = ops.to_device_pinned(np.ascontiguousarray(template.basis('tps', So), dtype=np.float32), self.dev)
+        return self._al_basis[key]
+
+    def landmarks(self, images, boxes=None):
+        """detect() per face box: mu f32 [n, K, 2] of the rows keypoints() and align() would work on (one per box, cut with zero
+        padding and resized to S x S on the GPU; one per image without boxes)."""
+        from . import keypoints as KP
+        images, u8 = as_image_batch(images, self.S)
+        if not u8:
+            if boxes is not None:
+                raise ValueError('boxes need the images as a list of u8 arrays (a tensor batch is already S x S)')
+            return self.detect(images)
+        images = decode_u8(images)
+        rows = KP.check_boxes([(0, 0, a.shape[0], a.shape[1]) for a in images] if boxes is None else boxes, len(images))
+        N = len(rows)
+        cur = torch.cuda.current_stream(self.dev)
+        mu_out = torch.empty(N, self.K, 2, device=self.dev)
+        self.stream.wait_stream(cur)
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            for start, count, bucket in plan_buckets(N, self.max_batch):
+                self._ensure_capacity(bucket)
+                part = rows[start:start + count]
+                used, idx = np.unique(part[:, 0], return_inverse=True)
+                local = np.concatenate([idx.reshape(-1, 1).astype(np.int32), part[:, 1:]], axis=1)
+                stage_u8([images[i] for i in used], self._img[:count], self.S, self.dev, boxes=local)
+                if count < bucket:
+                    self._img[count:bucket].zero_()
+                self._run(bucket)
+                mu_out[start:start + count].copy_(self._mu[:count])
+        cur.wait_stream(self.stream)
+        return mu_out
+
+    def align(self, images, template, boxes=None, model='similarity', lam=0.0, out_size=None, return_transform=False):
+        """Every face warped so that its landmarks land on the template: f32 [n, So, So, 3] in [0, 255] on the detector's device, one
+        row per box (per image without boxes); with return_transform=True also an alignment.Alignment (coef, geom, mu, to_source,
+        to_aligned).  images, boxes: as keypoints() takes them.  template: an alignment.LandmarkTemplate of this detector's K and S.
+        model: 'similarity' | 'affine' | 'tps' (lam >= 0: its smoothing).  out_size So defaults to S.
+        The landmarks come from detect()'s program on the S x S crop of each box; the backward map's coefficients are one more launch
+        in that program (imm_align_coeffs) and the photo is then sampled ONCE, straight from the packed u8 pixels, through the map and
+        the box geometry (imm_align_warp_u8) - the S x S crop is not resampled.  A tensor batch [N, S, S, 3] is its own source: the
+        staged f32 copy the detector reads is sampled in place of u8 photos, geometry (0, 0, 1, 1)."""
+        from . import alignment as AL
+        from . import keypoints as KP
+        lam = AL.check_model(model, lam)
+        template.check(self.K, self.S)
+        So = self.S if out_size is None else int(out_size)
+        if So < 1 or So > 8192:
+            raise ValueError('out_size must be in [1, 8192], got %d' % So)
+        K, m3 = self.K, AL.n_basis(model, self.K)
+        ft = np.ascontiguousarray(template.fit_matrix(model, lam).T, dtype=np.float32)             # [2K, 2 m3]
+        images, u8 = as_image_batch(images, self.S)
+        if u8:
+            images = decode_u8(images)
+            rows = KP.check_boxes([(0, 0, a.shape[0], a.shape[1]) for a in images] if boxes is None else boxes, len(images))
+            geom = KP.box_geometry(rows, self.S)
+        else:
+            if boxes is not None:
+                raise ValueError('boxes need the images as a list of u8 arrays (a tensor batch is already S x S)')
+            geom = np.tile(np.array([0, 0, 1, 1], np.float32), (len(images), 1))
+        N = len(geom)
+        cur = torch.cuda.current_stream(self.dev)
+        out = torch.empty(N, So, So, 3, device=self.dev)
+        coef_out = torch.empty(N, m3, 2, device=self.dev) if return_transform else None
+        mu_out = torch.empty(N, K, 2, device=self.dev) if return_transform else None
+        self.stream.wait_stream(cur)
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            basis = self._align_basis(template, model, So)
+            self._stager.copy(self._al_ft[:ft.size], torch.from_numpy(ft.reshape(-1)), ('al_ft', m3))
+            for start, count, bucket in plan_buckets(N, self.max_batch):
+                self._ensure_capacity(bucket)
+                if u8:
+                    part = rows[start:start + count]
+                    used, idx = np.unique(part[:, 0], return_inverse=True)
+                    local = np.concatenate([idx.reshape(-1, 1).astype(np.int32), part[:, 1:]], axis=1)
+                    src, offs_d, hw_d, boxes_d = stage_u8([images[i] for i in used], self._img[:count], self.S, self.dev, boxes=local)
+                else:
+                    self._stager.copy(self._img[:count], images[start:start + count], ('images', count))
+                    src, offs_d, hw_d, boxes_d = self._img[:count], None, None, None
+                if count < bucket:
+                    self._img[count:bucket].zero_()
+                self._stager.copy(self._geom[:count], torch.from_numpy(geom[start:start + count]), ('geom', count))
+                self._run(bucket, align=(model, m3))
+                coef = self._al_coef[:bucket * m3 * 2].view(bucket, m3, 2)[:count]
+                ops.align_warp_u8(src, offs_d, hw_d, boxes_d, self._geom[:count], coef, basis, self.S, out[start:start + count])
+                if return_transform:
+                    coef_out[start:start + count].copy_(coef)
+                    mu_out[start:start + count].copy_(self._mu[:count])
+        cur.wait_stream(self.stream)
+        if return_transform:
+            return out, AL.Alignment(coef_out, ops.to_device_pinned(geom, self.dev), mu_out, model, lam, template, So)
+        return out

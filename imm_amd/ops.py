@@ -688,6 +688,45 @@ def resize_crop_u8(src_u8, offsets, hw, c, resize_hw, crop_yx, out_hw, dst, ld_d
          crop_yx[1], out_hw[0], out_hw[1], _p(dst), dst.stride(2) if ld_dst is None else ld_dst, _s())
 
 
+MAX_ALIGN_M3 = 67             # basis functions of an alignment map: K <= 64 radial ones + 1, q_y, q_x
+
+
+def align_coeffs(mu, ft, k, m3, coef):
+    """coef f32 [n, m3, 2] = F . vec(mu) per row; mu f32 [n, K, 2]; ft f32 [2K, 2 m3] = F transposed (include/imm_align.h:
+    imm_align_coeffs)."""
+    if ft.dtype != torch.float32 or ft.numel() != 4 * k * m3 or not ft.is_contiguous():
+        raise ValueError('ft must be contiguous f32 [2K, 2 m3] = [%d, %d], got %s %s' % (2 * k, 2 * m3, ft.dtype, tuple(ft.shape)))
+    n = mu.shape[0]
+    assert mu.is_contiguous() and coef.is_contiguous() and mu.numel() == n * 2 * k and coef.numel() == n * 2 * m3
+    call('imm_align_coeffs', _p(mu), _p(ft), n, int(k), int(m3), _p(coef), _s())
+
+
+def align_warp_u8(src, offsets, hw, boxes, geom, coef, basis_t, image_size, dst, ld_dst=None):
+    """dst f32 [n, So, So, >= 3]: every row's photo sampled once through its map and geometry (include/imm_align.h: imm_align_warp_u8).
+    src: the packed u8 buffer with offsets i64 [images], hw i32 [images, 2] and boxes i32 [n, 5] (as resize_crop_u8 takes them), or an
+    f32 tensor [n, S, S, 3] with offsets = hw = boxes = None.  geom f32 [n, 4]; coef f32 [n, m3, 2]; basis_t f32 [m3, So * So] or None
+    (m3 == 3)."""
+    n, So = dst.shape[0], dst.shape[1]
+    m3 = coef.shape[1]
+    f32 = src.dtype == torch.float32
+    if f32:
+        if tuple(src.shape) != (n, image_size, image_size, 3) or not src.is_contiguous():
+            raise ValueError('an f32 source must be contiguous [n, S, S, 3], got %s' % (tuple(src.shape),))
+        n_images = n
+    else:
+        if src.dtype != torch.uint8 or offsets is None or hw is None or boxes is None:
+            raise ValueError('a u8 source needs offsets, hw and boxes')
+        if boxes.dtype != torch.int32 or tuple(boxes.shape) != (n, 5) or not boxes.is_contiguous():
+            raise ValueError('boxes must be contiguous int32 [n, 5], got %s %s' % (boxes.dtype, tuple(boxes.shape)))
+        n_images = hw.shape[0]
+    if dst.shape[2] != So or tuple(geom.shape) != (n, 4) or tuple(coef.shape) != (n, m3, 2) or not (geom.is_contiguous() and coef.is_contiguous()):
+        raise ValueError('dst [n, So, So, c], geom [n, 4], coef [n, m3, 2] (contiguous)')
+    if (m3 > 3) != (basis_t is not None) or (basis_t is not None and (tuple(basis_t.shape) != (m3, So * So) or not basis_t.is_contiguous())):
+        raise ValueError('basis_t must be contiguous f32 [m3, So * So] for m3 > 3 and None for m3 == 3')
+    call('imm_align_warp_u8', _p(src), int(f32), _p(offsets), _p(hw), int(n_images), _p(boxes), _p(geom), _p(coef), _p(basis_t), int(m3),
+         n, int(image_size), So, _p(dst), dst.stride(2) if ld_dst is None else ld_dst, _s())
+
+
 def masked_sse_pool(a, b, batch, s, c, mask, S, partial, pool_a, pool_b):
     call('imm_masked_sse_pool', _p(a), _p(b), dtype_enum(a.dtype), batch, s, c, _p(mask), S, _p(partial), _p(pool_a), _p(pool_b), _s())
 

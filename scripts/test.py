@@ -5,7 +5,8 @@ or, without dataset files, from .npz files with `image`, `future_image` (NHWC fl
 ([N,L,2] (y, x) pixels, first two points = the eyes):
     python scripts/test.py --configs a.yaml b.yaml --train-npz mafl_train.npz --test-npz mafl_test.npz --checkpoint x.pt
 --save-regressor PATH also writes the regressor behind the printed error (coef, intercept, K, S, ...; imm_amd/keypoints.py), which
-scripts/detect.py --regressor applies to photos."""
+scripts/detect.py --regressor applies to photos.  --save-template PATH writes the mean landmark shape of the regressor's training
+split (imm_amd/alignment.py: LandmarkTemplate, Procrustes-refined), which scripts/align.py --template aligns photos to."""
 from __future__ import print_function
 
 import argparse
@@ -76,14 +77,19 @@ def main(args):
         ck = torch.load(ckpt, map_location='cpu')
         eng.load_parameters(ck['params'], ck.get('state'))
     detector = net.landmark_detector(args.im_size, max_batch=args.batch_size) if args.detector else None
+    train_name = args.train_dataset if args.train_npz is None else args.train_npz
+    landmarks = {} if args.save_template else None
     if args.save_regressor:
         err, reg = eval_imm.fit_regression(net, train_it, test_it, [args.im_size, args.im_size], batch_size=args.batch_size,
-                                           bias=args.bias, detector=detector,
-                                           dataset=args.train_dataset if args.train_npz is None else args.train_npz, checkpoint=ckpt)
+                                           bias=args.bias, detector=detector, dataset=train_name, checkpoint=ckpt,
+                                           landmarks_out=landmarks)
         reg.save(args.save_regressor)
     else:
         err = eval_imm.evaluate_regression(net, train_it, test_it, [args.im_size, args.im_size], batch_size=args.batch_size,
-                                           bias=args.bias, detector=detector)
+                                           bias=args.bias, detector=detector, landmarks_out=landmarks)
+    if args.save_template:
+        from imm_amd.alignment import LandmarkTemplate
+        LandmarkTemplate.from_landmarks(landmarks['gauss_yx'], args.im_size, dataset=train_name, checkpoint=ckpt).save(args.save_template)
     model_dataset = config.training.train_dset_params.dataset if hasattr(config.training, 'train_dset_params') and \
         'dataset' in config.training.train_dset_params else getattr(config.training, 'dset', '?')
     print('')
@@ -116,4 +122,7 @@ if __name__ == '__main__':
     parser.add_argument('--save-regressor', type=str, default=None,
                         help='also write the fitted regressor behind the printed error to this .npz (imm_amd/keypoints.py; for '
                              'scripts/detect.py --regressor)')
+    parser.add_argument('--save-template', type=str, default=None,
+                        help="also write the mean landmark shape of the regressor's training split to this .npz "
+                             '(imm_amd/alignment.py; for scripts/align.py --template)')
     main(parser.parse_args())
