@@ -161,7 +161,12 @@ int imm_conv2d_dgrad_s2(const void* dy, int lddy, const void* wt, int kpad, void
  * geometry of y), store, partial sums.  IMM_CONV_STATS alone: rows of (sum v, sum v^2) — the batch statistics of a forward
  * convolution.  IMM_CONV_STATS | IMM_CONV_MASK: rows of (sum v, sum v * mask_ref) — the batch-norm BACKWARD sums (sum dz,
  * sum dz * out) of the conv+BN+ReLU block whose output gradient this data gradient produces (mask_ref = that block's stored
- * activation `out`), which replaces a separate reduction pass over dz (tf.gradients of nn_utils.py:201-209). */
+ * activation `out`), which replaces a separate reduction pass over dz (tf.gradients of nn_utils.py:201-209).
+ * Ownership of y: channels [0, co) of every output pixel of the launch are written, exactly once; the padding channels [co, ldy) belong to the
+ * caller and are never written, in any kernel family and for 16-bit and f32 outputs alike (a caller that feeds y to another
+ * convolution zeroes them once, see the conventions above).  Nothing before y[0] or past the last pixel's channel co - 1 is
+ * written.  The same holds for imm_conv2d_nol and imm_conv_first; tests/test_kernels_gpu.py asserts
+ * it on buffers whose padding and surroundings are pre-filled (tests/guarded.py). */
 int imm_conv2d(const imm_conv_desc* desc_host, int dtype, const void* x, const void* wt, const float* bias,
                void* y, float* stats_partial, const void* mask_ref, void* stream);
 int imm_conv_stats_blocks(const imm_conv_desc* desc_host);

@@ -13,6 +13,8 @@ from oracle import imm_oracle as O
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from dataset_fixtures import make_celeba_tree     # noqa: E402
+import guarded                                    # noqa: E402
+from guarded import close                         # noqa: E402  (|got - ref| <= atol_frac * max|ref| + rtol * |ref|, NaN / inf fail)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -34,13 +36,17 @@ def rnd(shape, seed, scale=1.0, dt=torch.bfloat16):
     return (torch.randn(shape, generator=g) * scale).to(dt)
 
 
-def close(got, ref, rtol, atol_frac, what):
-    """tests/test_kernels_gpu.py's comparison: |got - ref| <= atol_frac * max|ref| + rtol * |ref|."""
-    got, ref = got.detach().float().cpu(), ref.detach().float().cpu()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    err = (got - ref).abs()
-    bad = err > atol_frac * (float(ref.abs().max()) + 1e-30) + rtol * ref.abs()
-    assert not bool(bad.any()), '%s: %d/%d off, max err %.4g' % (what, int(bad.sum()), bad.numel(), float(err.max()))
+def dev(x):
+    """A host (or device) tensor as a guarded operand on the device."""
+    return guarded.inp(x, DEV, depth=2)
+
+
+@pytest.fixture(autouse=True)
+def _guards_intact():
+    """After every test: no kernel wrote outside a tensor it was handed (tests/guarded.py)."""
+    guarded.reset()
+    yield
+    guarded.check_guards()
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
@@ -54,7 +60,7 @@ def test_s2f_relu_epilogue_bit_exact(ops, H, ci, co, B, dt):
     is max(the same kernel's BIAS output, 0) bit for bit (ReLU on the f32 accumulator before the 16-bit store); with STATS the sums
     are those of the stored values; against the oracle within test_kernels_gpu.py's conv-forward tolerances."""
     from imm_amd import _lib as L
-    x = rnd((B, H, H, ci), 301, 1.0, dt).to(DEV)
+    x = dev(rnd((B, H, H, ci), 301, 1.0, dt))
     w = rnd((3, 3, ci, co), 302, 0.05, dt)
     b = rnd((co,), 303, 0.5, torch.float32).to(DEV)
     d_b = ops.fwd_desc(B, H, H, ci, ci, co, co, 3, 2, L.CONV_BIAS)
@@ -63,10 +69,10 @@ def test_s2f_relu_epilogue_bit_exact(ops, H, ci, co, B, dt):
     assert ops.conv2d_variant(d_r, dt)[0] == 's2f' and ops.conv2d_variant(d_r, dt) == ops.conv2d_variant(d_b, dt)
     assert ops.conv2d_variant(d_rs, dt) == ops.conv2d_variant(d_b, dt)
     rows = ops.round_up(co, 128)
-    wt = torch.zeros(rows, d_b.kpad, dtype=dt, device=DEV)
+    wt = guarded.out((rows, d_b.kpad), dt, DEV, fill=0)
     ops.pack_weights(w.float().to(DEV).contiguous(), wt, 0, 3, 3, ci, co, ci, rows, d_b.kpad)
-    ys = [torch.full((B, H // 2, H // 2, co), float('nan'), dtype=dt, device=DEV) for _ in range(3)]
-    stats = torch.full((ops.conv_stats_blocks(d_rs), 2, co), float('nan'), device=DEV)
+    ys = [guarded.out((B, H // 2, H // 2, co), dt, DEV) for _ in range(3)]
+    stats = guarded.out((ops.conv_stats_blocks(d_rs), 2, co), torch.float32, DEV)
     ops.conv2d(d_b, x, wt, b, ys[0])
     ops.conv2d(d_r, x, wt, b, ys[1])
     ops.conv2d(d_rs, x, wt, b, ys[2], stats)
@@ -93,12 +99,12 @@ def test_conv_first_relu_epilogue_bit_exact(ops, B, S, dt):
     src = torch.rand(B, S, S, 3, generator=g) * 255
     w = rnd((7, 7, 3, co), 311, 0.01, torch.float32)
     bias = rnd((co,), 312, 0.5, torch.float32).to(DEV)
-    srcd = src.to(DEV).contiguous()
+    srcd = dev(src)
     assert ops.conv_first_supported(B, S, co, co)
-    wt = torch.zeros(128, 224, dtype=dt, device=DEV)
+    wt = guarded.out((128, 224), dt, DEV, fill=0)
     ops.pack_weights(w.to(DEV).contiguous(), wt, 0, 7, 1, 21, co, 32, 128, 224)
-    ys = [torch.full((B, S, S, co), float('nan'), dtype=dt, device=DEV) for _ in range(3)]
-    stats = torch.full((ops.conv_first_stats_blocks(B, S), 2, co), float('nan'), device=DEV)
+    ys = [guarded.out((B, S, S, co), dt, DEV) for _ in range(3)]
+    stats = guarded.out((ops.conv_first_stats_blocks(B, S), 2, co), torch.float32, DEV)
     ops.conv_first(srcd, wt, bias, ys[0], co, None, B, S, co, L.CONV_BIAS)
     ops.conv_first(srcd, wt, bias, ys[1], co, None, B, S, co, L.CONV_BIAS | L.CONV_RELU)
     ops.conv_first(srcd, wt, bias, ys[2], co, stats, B, S, co, L.CONV_BIAS | L.CONV_RELU | L.CONV_STATS)
@@ -117,9 +123,9 @@ def test_unchanged_refusals(ops):
     """imm_conv2d_nol still refuses RELU (the new flag reaches s2f and conv_first only); conv_first still refuses MASK."""
     from imm_amd import _lib as L
     assert not ops.conv2d_nol_supported(ops.fwd_desc(2, 128, 128, 32, 32, 32, 32, 3, 1, L.CONV_BIAS | L.CONV_RELU))
-    img = torch.zeros(2, 64, 64, 3, device=DEV)
-    wt = torch.zeros(128, 224, dtype=torch.bfloat16, device=DEV)
-    y = torch.zeros(2, 64, 64, 32, dtype=torch.bfloat16, device=DEV)
+    img = guarded.out((2, 64, 64, 3), torch.float32, DEV, fill=0)
+    wt = guarded.out((128, 224), torch.bfloat16, DEV, fill=0)
+    y = guarded.out((2, 64, 64, 32), torch.bfloat16, DEV, fill=0)
     with pytest.raises(L.ImmHipError):
         ops.conv_first(img, wt, None, y, 32, None, 2, 64, 32, L.CONV_MASK)
 
@@ -308,7 +314,7 @@ def test_u8_images_of_any_size(ops):
     buf = np.zeros(total, np.uint8)
     for im, o in zip(ims, offs):
         buf[o:o + im.size] = im.reshape(-1)
-    f32 = torch.empty(len(ims), 128, 128, 3, device=DEV)
+    f32 = guarded.out((len(ims), 128, 128, 3), torch.float32, DEV)
     ops.resize_crop_u8(ops.to_device_pinned(buf, DEV), ops.to_device_pinned(np.array(offs, np.int64), DEV),
                        ops.to_device_pinned(np.array(sizes, np.int32), DEV), 3, (128, 128), (0, 0), (128, 128), f32)
     assert torch.equal(mu, det.detect(f32))

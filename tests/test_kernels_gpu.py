@@ -5,12 +5,18 @@ only differences are accumulation order and the final rounding of the stored res
 written next to each comparison.
 """
 import math
+import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import imm_oracle as O
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import guarded                                                              # noqa: E402
+from guarded import close, untouched                                        # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -32,24 +38,24 @@ def rnd(shape, seed, scale=1.0, dt=torch.bfloat16):
     return (torch.randn(shape, generator=g) * scale).to(dt)
 
 
-def close(got, ref, rtol, atol_frac, what):
-    got = got.detach().float().cpu()
-    ref = ref.detach().float().cpu()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    scale = float(ref.abs().max()) + 1e-30
-    err = (got - ref).abs()
-    tol = atol_frac * scale + rtol * ref.abs()
-    bad = err > tol
-    assert not bool(bad.any()), '%s: %d/%d elements off, max err %.4g (ref max %.4g), first bad idx %s got %.6g ref %.6g' % (
-        what, int(bad.sum()), bad.numel(), float(err.max()), scale,
-        tuple(int(i) for i in bad.nonzero()[0]), float(got[bad][0]), float(ref[bad][0]))
-
-
 def padded(x, ld):
-    """[..., c] -> [..., ld] zero padded, contiguous, on device."""
+    """[..., c] -> [..., ld] zero padded, contiguous, on device, between guard bands (a read past either end meets NaN)."""
     out = torch.zeros(x.shape[:-1] + (ld,), dtype=x.dtype)
     out[..., :x.shape[-1]] = x
-    return out.to(DEV).contiguous()
+    return guarded.inp(out, DEV, depth=2)
+
+
+def dev(x):
+    """A host (or device) tensor as a guarded operand on the device."""
+    return guarded.inp(x, DEV, depth=2)
+
+
+@pytest.fixture(autouse=True)
+def _guards_intact():
+    """After every test: no kernel wrote outside a tensor it was handed (tests/guarded.py)."""
+    guarded.reset()
+    yield
+    guarded.check_guards()
 
 
 # ----------------------------------------------------------------------------------------------
@@ -131,13 +137,13 @@ def run_conv(ops, x16, w, bias, k, stride, co, ci_pad, out_f32, extra_flags=0, m
     ldy = ldy or ops.round_up(co, 8 if not out_f32 else 4)
     desc = ops.fwd_desc(B, H, W, ci_pad, ci_pad, co, ldy, k, stride, flags, ldmask=(mask.shape[-1] if mask is not None else 0))
     rows = ops.round_up(co, 128)
-    wt = torch.zeros(rows, desc.kpad, dtype=dt, device=DEV)
+    wt = guarded.out((rows, desc.kpad), dt, DEV, fill=0)
     wd = w.float().to(DEV).contiguous()
     ops.pack_weights(wd, wt, 0, k, k, ci_real, co, ci_pad, rows, desc.kpad)
-    y = torch.full((B, desc.ho, desc.wo, ldy), float('nan'), dtype=torch.float32 if out_f32 else dt, device=DEV)
+    y = guarded.out((B, desc.ho, desc.wo, ldy), torch.float32 if out_f32 else dt, DEV)
     stats = None
     if extra_flags & L.CONV_STATS:
-        stats = torch.full((ops.conv_stats_blocks(desc), 2, co), float('nan'), dtype=torch.float32, device=DEV)
+        stats = guarded.out((ops.conv_stats_blocks(desc), 2, co), torch.float32, DEV)
     bd = bias.float().to(DEV) if bias is not None else None
     ops.conv2d(desc, xd, wt, bd, y, stats, mask)
     torch.cuda.synchronize()
@@ -157,8 +163,7 @@ def test_conv_forward(ops, case, dt):
     # f32 out: accumulation-order error only; 16-bit out: one rounding (2^-8 bf16, 2^-11 f16)
     rt = 2e-3 if out_f32 else (1e-2 if dt == torch.bfloat16 else 2e-3)
     close(y[..., :co], ref, rt, 2e-3 if not out_f32 else 2e-4, 'conv_fwd/' + tag)
-    if y.shape[-1] > co and not out_f32:
-        pass  # padding channels are not written by the kernel (caller owns them)
+    assert untouched(y[..., co:]), 'padding channels [co, ldy) belong to the caller: imm_conv2d must not write them'
 
 
 @pytest.mark.parametrize('B,H,ci,co,dt', [(2, 32, 32, 64, torch.bfloat16), (2, 64, 64, 64, torch.bfloat16),
@@ -194,7 +199,7 @@ def test_conv_relu_stats_mask(ops, B, H, ci, co, dt):
     close(s[1], (ref ** 2).sum(dim=(0, 1, 2)), 1e-3, 1e-3, 'conv+stats/sumsq')
     y2, _, _ = run_conv(ops, x, w, b, 3, 1, co, ci, False, extra_flags=L.CONV_RELU)
     close(y2, torch.relu(ref), 1e-2, 2e-3, 'conv+relu')
-    mref = rnd((B, H, H, co), 7, 1.0, dt).to(DEV).contiguous()
+    mref = dev(rnd((B, H, H, co), 7, 1.0, dt))
     y3, _, _ = run_conv(ops, x, w, b, 3, 1, co, ci, False, extra_flags=L.CONV_MASK, mask=mref)
     close(y3, ref * (mref.float().cpu() > 0), 1e-2, 2e-3, 'conv+mask')
 
@@ -277,12 +282,13 @@ def test_conv_dgrad(ops, case, dt):
     desc = ops.dgrad_desc(B, H, H, ci_real, ci_pad, co_pad, co_pad, k, stride, 0)
     check_family(ops, desc, dt, tag)
     rows = ops.round_up(ci_real, 128)
-    wt = torch.zeros(rows, desc.kpad, dtype=dt, device=DEV)
+    wt = guarded.out((rows, desc.kpad), dt, DEV, fill=0)
     ops.pack_weights(w.float().to(DEV).contiguous(), wt, 1, k, k, ci_real, co, co_pad, rows, desc.kpad)
-    dx = torch.zeros(B, H, H, ci_pad, dtype=dt, device=DEV)
+    dx = guarded.out((B, H, H, ci_pad), dt, DEV)
     ops.conv2d(desc, padded(dy, co_pad), wt, None, dx)
     torch.cuda.synchronize()
     close(dx[..., :ci_real], gx, 1e-2 if dt == torch.bfloat16 else 2e-3, 2e-3, 'dgrad/' + tag)
+    assert untouched(dx[..., ci_real:]), 'padding channels [co, ldy) of imm_conv2d belong to the caller'
 
 
 @pytest.mark.parametrize('H,ci,co', [(16, 32, 64), (32, 64, 128), (64, 128, 256), (64, 32, 64)])
@@ -297,11 +303,11 @@ def test_conv_dgrad_stride2_parity_classes(ops, H, ci, co, dt):
     (gx,) = torch.autograd.grad(yref, xr, dy.float())
     descs = ops.dgrad_s2_class_descs(B, H, H, ci, ci, co, co, k)
     assert descs is not None and len(descs) == 4 and sorted(d.kh * d.kw for d, _ in descs) == [1, 2, 2, 4]
-    dx = torch.full((B, H, H, ci), float('nan'), dtype=dt, device=DEV)
-    dyd = dy.to(DEV).contiguous()
+    dx = guarded.out((B, H, H, ci), dt, DEV)
+    dyd = dev(dy)
     rows = ops.round_up(ci, 128)
     for d, mode in descs:
-        wt = torch.zeros(rows, d.kpad, dtype=dt, device=DEV)
+        wt = guarded.out((rows, d.kpad), dt, DEV, fill=0)
         ops.pack_weights(w.float().to(DEV).contiguous(), wt, mode, k, k, ci, co, co, rows, d.kpad)
         ops.conv2d(d, dyd, wt, None, dx)
     torch.cuda.synchronize()
@@ -324,11 +330,11 @@ def _nol_inputs(B, H, ci, dt, seed):
     """raw conv output y (16-bit), per-channel scale (both signs) / shift, and the normalised tensor the stand-alone apply pass
     stores: relu(scale * y + shift) rounded to 16 bits."""
     from imm_amd import ops as _ops
-    y = rnd((B, H, H, ci), seed, 1.0, dt).to(DEV).contiguous()
+    y = dev(rnd((B, H, H, ci), seed, 1.0, dt))
     g = torch.Generator().manual_seed(seed + 1)
     scale = (torch.randn(ci, generator=g) * 0.8 + 0.3).to(DEV)
     shift = (torch.randn(ci, generator=g) * 0.7 + 0.4).to(DEV)      # mostly positive: relu(shift) != 0, so a normalised padding pixel shows
-    out = torch.empty_like(y)
+    out = guarded.out(y.shape, y.dtype, DEV)
     _ops.bn_apply_relu(y, B * H * H, ci, ci, scale, shift, True, out, ci)
     torch.cuda.synchronize()
     return y, scale, shift, out
@@ -351,15 +357,15 @@ def test_conv_norm_on_load(ops, case, dt):
     desc = ops.fwd_desc(B, H, H, ci, ci, co, ldy, 3, stride, flags)
     assert ops.conv2d_nol_supported(desc)
     rows = ops.round_up(co, 128)
-    wt = torch.zeros(rows, desc.kpad, dtype=dt, device=DEV)
+    wt = guarded.out((rows, desc.kpad), dt, DEV, fill=0)
     ops.pack_weights(w.float().to(DEV).contiguous(), wt, 0, 3, 3, ci, co, ci, rows, desc.kpad)
     bd = bias.to(DEV)
     odt = torch.float32 if out_f32 else dt
-    z_nol = torch.full((B, desc.ho, desc.wo, ldy), float('nan'), dtype=odt, device=DEV)
-    st_nol = torch.full((ops.conv2d_nol_stats_blocks(desc), 2, co), float('nan'), dtype=torch.float32, device=DEV)
+    z_nol = guarded.out((B, desc.ho, desc.wo, ldy), odt, DEV)
+    st_nol = guarded.out((ops.conv2d_nol_stats_blocks(desc), 2, co), torch.float32, DEV)
     ops.conv2d_nol(desc, y, scale, shift, True, wt, bd, z_nol, st_nol)
-    z_ref = torch.full((B, desc.ho, desc.wo, ldy), float('nan'), dtype=odt, device=DEV)
-    st_ref = torch.full((ops.conv_stats_blocks(desc), 2, co), float('nan'), dtype=torch.float32, device=DEV)
+    z_ref = guarded.out((B, desc.ho, desc.wo, ldy), odt, DEV)
+    st_ref = guarded.out((ops.conv_stats_blocks(desc), 2, co), torch.float32, DEV)
     ops.conv2d(desc, out, wt, bd, z_ref, st_ref)
     torch.cuda.synchronize()
     zo = O.conv2d_same(out.float().cpu(), w.float(), bias, stride)
@@ -367,9 +373,10 @@ def test_conv_norm_on_load(ops, case, dt):
     close(z_nol[..., :co], z_ref[..., :co], (2.0 ** -7 if dt == torch.bfloat16 else 2.0 ** -10) if not out_f32 else 1e-4, 1e-4,
           'conv_nol vs apply + conv')
     close(st_nol.sum(0), st_ref.sum(0), 2e-4, 2e-4, 'conv_nol batch-norm partial sums')
+    assert untouched(z_nol[..., co:]) and untouched(z_ref[..., co:]), 'padding channels [co, ldy) belong to the caller'
     # without the ReLU (a block built with relu = False)
     ops.conv2d_nol(desc, y, scale, shift, False, wt, bd, z_nol, st_nol)
-    out2 = torch.empty_like(y)
+    out2 = guarded.out(y.shape, y.dtype, DEV)
     ops.bn_apply_relu(y, B * H * H, ci, ci, scale, shift, False, out2, ci)
     ops.conv2d(desc, out2, wt, bd, z_ref, st_ref)
     torch.cuda.synchronize()
@@ -383,15 +390,15 @@ def test_conv_norm_on_load_rejects_unserved_shapes(ops):
     assert not ops.conv2d_nol_supported(ops.fwd_desc(2, 64, 64, 64, 64, 128, 128, 3, 2, L.CONV_BIAS))       # stride 2 from 64 channels
     assert not ops.conv2d_nol_supported(ops.fwd_desc(2, 128, 128, 32, 32, 32, 32, 3, 1, L.CONV_BIAS | L.CONV_RELU))
     d = ops.fwd_desc(2, 32, 32, 128, 128, 128, 128, 3, 1, L.CONV_BIAS)
-    x = torch.zeros(2, 32, 32, 128, dtype=torch.bfloat16, device=DEV)
-    v = torch.zeros(128, device=DEV)
+    x = guarded.out((2, 32, 32, 128), torch.bfloat16, DEV, fill=0)
+    v = guarded.out((128,), torch.float32, DEV, fill=0)
     with pytest.raises(L.ImmHipError):
-        ops.conv2d_nol(d, x, v, v, True, torch.zeros(128, d.kpad, dtype=torch.bfloat16, device=DEV), v, torch.empty_like(x))
+        ops.conv2d_nol(d, x, v, v, True, guarded.out((128, d.kpad), torch.bfloat16, DEV, fill=0), v, guarded.out(x.shape, x.dtype, DEV))
     # a filter-gradient job with normalise-on-load must be an LDS-halo variant
     d8 = ops.fwd_desc(2, 8, 8, 128, 128, 128, 128, 3, 1, 0)            # 8x8 maps: the transpose-read kernel's job
     assert ops.conv2d_wgrad_variant(d8, 128, torch.bfloat16)[0] // 100000 != 2
-    x8 = torch.zeros(2, 8, 8, 128, dtype=torch.bfloat16, device=DEV)
-    slab = torch.zeros(2, d8.kpad, 128, device=DEV)
+    x8 = guarded.out((2, 8, 8, 128), torch.bfloat16, DEV, fill=0)
+    slab = guarded.out((2, d8.kpad, 128), torch.float32, DEV, fill=0)
     with pytest.raises(L.ImmHipError):
         ops.WgradMulti([(d8, x8, x8, 128, slab, 2, (v, v, True))], torch.bfloat16)
 
@@ -423,10 +430,10 @@ def test_conv_wgrad_norm_on_load(ops, case, dt):
     dzd = padded(dz, lddy)
     res = []
     for nol in (True, False):
-        slab = torch.full((nsplit, desc.kpad, co), float('nan'), dtype=torch.float32, device=DEV)
+        slab = guarded.out((nsplit, desc.kpad, co), torch.float32, DEV)
         job = (desc, y, dzd, lddy, slab, nsplit, (scale, shift, True)) if nol else (desc, out, dzd, lddy, slab, nsplit)
         ops.conv2d_wgrad_multi(ops.WgradMulti([job], dt))
-        dw = torch.full((3, 3, ci, co), float('nan'), dtype=torch.float32, device=DEV)
+        dw = guarded.out((3, 3, ci, co), torch.float32, DEV)
         ops.conv2d_wgrad_reduce(slab, nsplit, 3, 3, ci, ci, co, desc.kpad, dw)
         torch.cuda.synchronize()
         res.append(dw)
@@ -469,17 +476,17 @@ def test_conv_dgrad_stride2_one_launch(ops, case, dt):
     assert ops.conv2d_dgrad_s2_supported(B, h, h, co, ci, ci)
     rows = ops.round_up(ci, 128)
     wd = w.float().to(DEV).contiguous()
-    wt = torch.zeros(rows, 9 * co, dtype=dt, device=DEV)
+    wt = guarded.out((rows, 9 * co), dt, DEV, fill=0)
     ops.pack_weights(wd, wt, 1, k, k, ci, co, co, rows, 9 * co)
-    dx = torch.full((B, H, H, ci), float('nan'), dtype=dt, device=DEV)
-    dyd = dy.to(DEV).contiguous()
+    dx = guarded.out((B, H, H, ci), dt, DEV)
+    dyd = dev(dy)
     ops.conv2d_dgrad_s2(dyd, co, wt, dx, ci, ci, B, h, h)
     torch.cuda.synchronize()
     close(dx, gx, 1e-2, 2e-3, 'dgrad_s2_one_launch')           # every pixel written exactly once (no NaN left)
     # the four class launches
-    dx4 = torch.full((B, H, H, ci), float('nan'), dtype=dt, device=DEV)
+    dx4 = guarded.out((B, H, H, ci), dt, DEV)
     for d, mode in ops.dgrad_s2_class_descs(B, H, H, ci, ci, co, co, k):
-        wt_c = torch.zeros(rows, d.kpad, dtype=dt, device=DEV)
+        wt_c = guarded.out((rows, d.kpad), dt, DEV, fill=0)
         ops.pack_weights(wd, wt_c, mode, k, k, ci, co, co, rows, d.kpad)
         ops.conv2d(d, dyd, wt_c, None, dx4)
     torch.cuda.synchronize()
@@ -487,7 +494,7 @@ def test_conv_dgrad_stride2_one_launch(ops, case, dt):
     # padded output stride: channels beyond c_dx are left alone
     if ci % 32:
         ld = ops.round_up(ci, 32)
-        dxp = torch.full((B, H, H, ld), 7.0, dtype=dt, device=DEV)
+        dxp = guarded.out((B, H, H, ld), dt, DEV, fill=7.0)
         ops.conv2d_dgrad_s2(dyd, co, wt, dxp, ld, ci, B, h, h)
         torch.cuda.synchronize()
         assert torch.equal(dxp[..., :ci], dx) and bool((dxp[..., ci:] == 7.0).all())
@@ -499,9 +506,9 @@ def test_conv_dgrad_stride2_one_launch_rejects_unserved_shapes(ops):
     assert not ops.conv2d_dgrad_s2_supported(2, 16, 16, 32, 32, 32)      # dy channels % 64
     assert not ops.conv2d_dgrad_s2_supported(2, 16, 16, 64, 12, 16)      # dx channels % 8
     assert ops.conv2d_dgrad_s2_supported(2, 16, 16, 64, 32, 32)
-    dy = torch.zeros(2, 8, 8, 64, dtype=torch.bfloat16, device=DEV)
-    wt = torch.zeros(128, 576, dtype=torch.bfloat16, device=DEV)
-    dx = torch.zeros(2, 16, 16, 32, dtype=torch.bfloat16, device=DEV)
+    dy = guarded.out((2, 8, 8, 64), torch.bfloat16, DEV, fill=0)
+    wt = guarded.out((128, 576), torch.bfloat16, DEV, fill=0)
+    dx = guarded.out((2, 16, 16, 32), torch.bfloat16, DEV, fill=0)
     from imm_amd import _lib as L
     with pytest.raises(L.ImmHipError):
         ops.conv2d_dgrad_s2(dy, 64, wt, dx, 32, 32, 2, 8, 8)
@@ -516,19 +523,19 @@ def test_conv_dgrad_with_tap_epilogue(ops, B, H, cin, cout, l1, dt):
     conv3_2 / conv4_2 (imm_model.py:142-147) in the epilogue of the data gradient that enters the tapped layer."""
     S = 128
     w = rnd((3, 3, cin, cout), 171, 0.02, dt)
-    dz = rnd((B, H, H, cout), 172, 1e-3, dt).to(DEV).contiguous()
-    act = rnd((2 * B, H, H, cin), 173, 1.0, dt).to(DEV).contiguous()          # [gt ; pred] halves of the tapped activation
-    mask = torch.rand(B, S, S, device=DEV)
+    dz = dev(rnd((B, H, H, cout), 172, 1e-3, dt))
+    act = dev(rnd((2 * B, H, H, cin), 173, 1.0, dt))          # [gt ; pred] halves of the tapped activation
+    mask = dev(torch.rand(B, S, S, device=DEV))
     coef = torch.tensor([0.0, 3.7e-4, 0.0], device=DEV)
     desc = ops.dgrad_desc(B, H, H, cin, cin, cout, cout, 3, 1, 0)
     assert ops.conv2d_tap_supported(desc)
-    wt = torch.zeros(ops.round_up(cin, 128), desc.kpad, dtype=dt, device=DEV)
+    wt = guarded.out((ops.round_up(cin, 128), desc.kpad), dt, DEV, fill=0)
     ops.pack_weights(w.float().to(DEV).contiguous(), wt, 1, 3, 3, cin, cout, cout, wt.shape[0], desc.kpad)
     for mk in (mask, None):
-        ref = torch.full((B, H, H, cin), float('nan'), dtype=dt, device=DEV)
+        ref = guarded.out((B, H, H, cin), dt, DEV)
         ops.conv2d(desc, dz, wt, None, ref)
         ops.tap_grad(ref, True, act[B:], act[:B], B, H, cin, mk, S, coef, 1, True, l1)
-        got = torch.full_like(ref, float('nan'))
+        got = guarded.out(ref.shape, ref.dtype, DEV)
         ops.conv2d_tap(desc, dz, wt, got, act[B:], act[:B], cin, mk, S, coef, 1, l1)
         torch.cuda.synchronize()
         assert torch.equal(got, ref), float((got.float() - ref.float()).abs().max())
@@ -556,9 +563,9 @@ def test_conv_wgrad(ops, case, dt):
     dy = rnd(tuple(yref.shape), 22, 1.0, dt)
     (gw,) = torch.autograd.grad(yref, wr, dy.float())
     desc = ops.fwd_desc(B, H, H, ci_pad, ci_pad, co, lddy, k, stride, 0)
-    slab = torch.full((nsplit, desc.kpad, co), float('nan'), dtype=torch.float32, device=DEV)
+    slab = guarded.out((nsplit, desc.kpad, co), torch.float32, DEV)
     ops.conv2d_wgrad(desc, padded(x, ci_pad), padded(dy, lddy), lddy, slab, nsplit)
-    dw = torch.full((k, k, ci_real, co), float('nan'), dtype=torch.float32, device=DEV)
+    dw = guarded.out((k, k, ci_real, co), torch.float32, DEV)
     ops.conv2d_wgrad_reduce(slab, nsplit, k, k, ci_pad, ci_real, co, desc.kpad, dw)
     torch.cuda.synchronize()
     close(dw, gw, 2e-3, 5e-4, 'wgrad/' + tag)     # f32 accumulate of exact bf16 products
@@ -583,16 +590,16 @@ def test_conv_wgrad_halo(ops, case, dt):
     desc = ops.fwd_desc(B, H, H, ci, ci, co, lddy, 3, 1, 0)
     nsplit = ops.conv2d_wgrad_splits(desc, lddy)
     assert nsplit > 0, 'case should select the halo kernel'
-    slab = torch.full((nsplit, desc.kpad, co), float('nan'), dtype=torch.float32, device=DEV)
-    ops.conv2d_wgrad(desc, x.to(DEV), padded(dy, lddy), lddy, slab, nsplit)
-    dw = torch.full((3, 3, ci, co), float('nan'), dtype=torch.float32, device=DEV)
+    slab = guarded.out((nsplit, desc.kpad, co), torch.float32, DEV)
+    ops.conv2d_wgrad(desc, dev(x), padded(dy, lddy), lddy, slab, nsplit)
+    dw = guarded.out((3, 3, ci, co), torch.float32, DEV)
     ops.conv2d_wgrad_reduce(slab, nsplit, 3, 3, ci, ci, co, desc.kpad, dw)
     torch.cuda.synchronize()
     close(dw, gw, 2e-3, 5e-4, 'wgrad_halo/' + tag)
     # the general kernel (any other split count) must agree
-    slab2 = torch.empty(3, desc.kpad, co, dtype=torch.float32, device=DEV)
-    ops.conv2d_wgrad(desc, x.to(DEV), padded(dy, lddy), lddy, slab2, 3)
-    dw2 = torch.empty(3, 3, ci, co, dtype=torch.float32, device=DEV)
+    slab2 = guarded.out((3, desc.kpad, co), torch.float32, DEV)
+    ops.conv2d_wgrad(desc, dev(x), padded(dy, lddy), lddy, slab2, 3)
+    dw2 = guarded.out((3, 3, ci, co), torch.float32, DEV)
     ops.conv2d_wgrad_reduce(slab2, 3, 3, 3, ci, ci, co, desc.kpad, dw2)
     torch.cuda.synchronize()
     close(dw, dw2, 1e-3, 2e-4, 'wgrad_halo_vs_general/' + tag)
@@ -616,8 +623,8 @@ def test_conv_wgrad_multi_equals_single_launches(ops, dt):
         dy = rnd(tuple(yref.shape), 600 + i, 1.0, dt)
         (gw,) = torch.autograd.grad(yref, wr, dy.float())
         desc = ops.fwd_desc(B, H, H, ci, ci, co, lddy, k, stride, 0)
-        xd, dyd = x.to(DEV).contiguous(), padded(dy, lddy)
-        slab_m = torch.full((nsplit, desc.kpad, co), float('nan'), dtype=torch.float32, device=DEV)
+        xd, dyd = dev(x), padded(dy, lddy)
+        slab_m = guarded.out((nsplit, desc.kpad, co), torch.float32, DEV)
         made.append((desc, xd, dyd, lddy, nsplit, k, ci, co, gw, slab_m))
         multi_jobs.append((desc, xd, dyd, lddy, slab_m, nsplit))
         keys.append(ops.conv2d_wgrad_variant(desc, lddy, dt)[0])
@@ -626,13 +633,13 @@ def test_conv_wgrad_multi_equals_single_launches(ops, dt):
     ops.conv2d_wgrad_multi(multi)
     torch.cuda.synchronize()
     for i, (desc, xd, dyd, lddy, nsplit, k, ci, co, gw, slab_m) in enumerate(made):
-        dw = torch.full((k, k, ci, co), float('nan'), dtype=torch.float32, device=DEV)
+        dw = guarded.out((k, k, ci, co), torch.float32, DEV)
         ops.conv2d_wgrad_reduce(slab_m, nsplit, k, k, ci, ci, co, desc.kpad, dw)
         torch.cuda.synchronize()
         close(dw, gw, 2e-3, 5e-4, 'wgrad_multi/job%d' % i)
         if keys[i] // 100000 == 2 and nsplit != ops.conv2d_wgrad_splits(desc, lddy):
             continue     # the single entry point only takes the halo kernel at its own split count: nothing to compare bitwise
-        slab_s = torch.full_like(slab_m, float('nan'))
+        slab_s = guarded.out(slab_m.shape, slab_m.dtype, DEV)
         ops.conv2d_wgrad(desc, xd, dyd, lddy, slab_s, nsplit)
         torch.cuda.synchronize()
         assert torch.equal(slab_s, slab_m), 'job %d (variant %d)' % (i, keys[i])
@@ -654,17 +661,17 @@ def test_conv_wgrad_halo_7x1_first_layer(ops, B, S, dt):
     desc = ops.fwd_desc(B, S, S, ci, ci, co, co, 7, 1, 0, kw=1)
     key, wps, units, pcu = ops.conv2d_wgrad_variant(desc, co, dt)
     assert key // 100000 == 2 and wps == 1 and pcu == 2, key                 # LDS-halo family, whole filter = one slice
-    xd, dyd = x.to(DEV).contiguous(), dy.to(DEV).contiguous()
+    xd, dyd = dev(x), dev(dy)
     nsplit = ops.conv2d_wgrad_splits(desc, co)
     assert nsplit > 0
     res = []
     for ns, multi in ((nsplit, False), (7, True), (3, False)):       # (3, False): any other split count = transpose-read kernel
-        slab = torch.full((ns, desc.kpad, co), float('nan'), dtype=torch.float32, device=DEV)
+        slab = guarded.out((ns, desc.kpad, co), torch.float32, DEV)
         if multi:
             ops.conv2d_wgrad_multi(ops.WgradMulti([(desc, xd, dyd, co, slab, ns)], dt))
         else:
             ops.conv2d_wgrad(desc, xd, dyd, co, slab, ns)
-        dw = torch.full((7, 1, ci, co), float('nan'), dtype=torch.float32, device=DEV)
+        dw = guarded.out((7, 1, ci, co), torch.float32, DEV)
         ops.conv2d_wgrad_reduce(slab, ns, 7, 1, ci, ci, co, desc.kpad, dw)
         torch.cuda.synchronize()
         close(dw, gw, 2e-3, 5e-4, 'wgrad_halo_7x1/%d%s' % (ns, 'm' if multi else ''))
@@ -688,17 +695,17 @@ def test_conv_wgrad_halo_stride2(ops, B, S, co, dt):
     desc = ops.fwd_desc(B, S, S, ci, ci, co, 64, 3, 2, 0)
     key, wps, units, pcu = ops.conv2d_wgrad_variant(desc, 64, dt)
     assert key == 200000 + 20000 + 3264 and wps == 1 and pcu == 1, key
-    xd, dyd = x.to(DEV).contiguous(), dy.to(DEV).contiguous()
+    xd, dyd = dev(x), dev(dy)
     nsplit = ops.conv2d_wgrad_splits(desc, 64)
     assert nsplit > 0
     res = []
     for ns, multi in ((nsplit, False), (5, True), (3, False)):       # (3, False): any other split count = transpose-read kernel
-        slab = torch.full((ns, desc.kpad, co), float('nan'), dtype=torch.float32, device=DEV)
+        slab = guarded.out((ns, desc.kpad, co), torch.float32, DEV)
         if multi:
             ops.conv2d_wgrad_multi(ops.WgradMulti([(desc, xd, dyd, 64, slab, ns)], dt))
         else:
             ops.conv2d_wgrad(desc, xd, dyd, 64, slab, ns)
-        dw = torch.full((3, 3, ci, co), float('nan'), dtype=torch.float32, device=DEV)
+        dw = guarded.out((3, 3, ci, co), torch.float32, DEV)
         ops.conv2d_wgrad_reduce(slab, ns, 3, 3, ci, ci, co, desc.kpad, dw)
         torch.cuda.synchronize()
         close(dw, gw, 2e-3, 5e-4, 'wgrad_halo_s2/%d%s' % (ns, 'm' if multi else ''))
@@ -713,27 +720,33 @@ def test_table_driven_pack_and_reduce(ops):
               (1, 256, 256, 10, 0), (3, 64, 128, 128, 4), (3, 64, 128, 128, 7)]
     jobs, items, refs = [], [], []
     for k, ci_real, c_pad, co, mode in layers:
-        w = rnd((k, k, ci_real, co), 100 + ci_real, 0.1, torch.float32).to(DEV).contiguous()
+        w = dev(rnd((k, k, ci_real, co), 100 + ci_real, 0.1, torch.float32))
         if mode == 0:
             rows, kpad = ops.round_up(co, 128), ops.round_up(k * k * c_pad, 32)
         else:
             rows, kpad = ops.round_up(ci_real, 128), ops.round_up(k * k * c_pad, 32)
-        wt_ref = torch.zeros(rows, kpad, dtype=dt, device=DEV)
-        wt = torch.full((rows, kpad), float('nan'), dtype=dt, device=DEV)
+        wt_ref = guarded.out((rows, kpad), dt, DEV)
+        wt = guarded.out((rows, kpad), dt, DEV)
         ops.pack_weights(w, wt_ref, mode, k, k, ci_real, co, c_pad, rows, kpad)
         jobs.append((w.data_ptr(), wt.data_ptr(), mode, k, k, ci_real, co, c_pad, rows, kpad)); items.append(rows * kpad)
         refs.append((w, wt, wt_ref))
     tab = ops.pack_table(jobs, DEV)
     ops.pack_weights_multi(tab, dt)
     torch.cuda.synchronize()
-    for _w, wt, wt_ref in refs:
+    for (k, ci_real, c_pad, co, mode), (_w, wt, wt_ref) in zip(layers, refs):
         assert torch.equal(wt.view(torch.int16), wt_ref.view(torch.int16))
+        # imm_pack_weights owns the whole [rows][kpad] image: rows >= the real count and the padded k are written as zeros
+        assert not bool(torch.isnan(wt_ref.float()).any()), (k, ci_real, c_pad, co, mode)
+        real = co if mode == 0 else ci_real
+        assert real == wt_ref.shape[0] or float(wt_ref[real:].float().abs().max()) == 0.0
+        if mode in (0, 1) and k * k * c_pad < wt_ref.shape[1]:
+            assert float(wt_ref[:, k * k * c_pad:].float().abs().max()) == 0.0
     jobs, items, refs = [], [], []
     for k, ci_real, ci_pad, co, nsplit in [(3, 32, 32, 32, 5), (7, 3, 8, 32, 3), (3, 266, 288, 256, 2), (1, 256, 256, 10, 1),
                                            (3, 64, 64, 64, 1), (3, 32, 32, 9, 54), (3, 128, 128, 128, 16), (1, 1, 1, 10, 32)]:
         kpad = ops.round_up(k * k * ci_pad, 32)
-        slab = rnd((nsplit, kpad, co), 200 + co, 1.0, torch.float32).to(DEV).contiguous()
-        dw_ref = torch.empty(k, k, ci_real, co, device=DEV); dw = torch.full((k, k, ci_real, co), float('nan'), device=DEV)
+        slab = dev(rnd((nsplit, kpad, co), 200 + co, 1.0, torch.float32))
+        dw_ref = guarded.out((k, k, ci_real, co), torch.float32, DEV); dw = guarded.out((k, k, ci_real, co), torch.float32, DEV)
         ops.conv2d_wgrad_reduce(slab, nsplit, k, k, ci_pad, ci_real, co, kpad, dw_ref)
         jobs.append((slab.data_ptr(), dw.data_ptr(), nsplit, k * k, ci_pad, ci_real, co, kpad)); items.append(k * k * ci_real * co)
         refs.append((slab, dw, dw_ref))
@@ -750,8 +763,8 @@ def test_table_driven_pack_and_reduce(ops):
 def test_colsum(ops):
     dy = rnd((3000, 10), 31)
     dd = padded(dy, 16)
-    part = torch.empty(ops.colsum_blocks(3000, 16), 16, dtype=torch.float32, device=DEV)
-    out = torch.full((16,), -7.0, dtype=torch.float32, device=DEV)
+    part = guarded.out((ops.colsum_blocks(3000, 16), 16), torch.float32, DEV)
+    out = guarded.out((16,), torch.float32, DEV, fill=-7.0)
     ops.colsum(dd, 3000, 16, 10, 16, part, out)
     torch.cuda.synchronize()
     close(out[:10], dy.float().sum(0), 1e-4, 1e-5, 'colsum')
@@ -769,11 +782,11 @@ def test_batch_norm_fwd_bwd(ops, c, npix):
     beta = rnd((c,), 43, 0.5, torch.float32)
     yf = y.float()
     partial = torch.stack([yf.sum(0), (yf * yf).sum(0)]).reshape(1, 2, c).to(DEV).contiguous()
-    mm, mv = torch.zeros(c, device=DEV), torch.ones(c, device=DEV)
-    scale, shift, mean, rstd = (torch.empty(c, device=DEV) for _ in range(4))
+    mm, mv = guarded.out((c,), torch.float32, DEV, fill=0), guarded.out((c,), torch.float32, DEV, fill=1)
+    scale, shift, mean, rstd = (guarded.out((c,), torch.float32, DEV) for _ in range(4))
     ops.bn_finalize(partial, 1, c, npix, gamma.to(DEV), beta.to(DEV), 1e-3, 0.99, True, mm, mv, scale, shift, mean, rstd)
     yd = y.to(DEV)
-    xo = torch.empty(npix, c, dtype=dt, device=DEV)
+    xo = guarded.out((npix, c), dt, DEV)
     ops.bn_apply_relu(yd, npix, c, c, scale, shift, True, xo, c)
     torch.cuda.synchronize()
     yr = yf.reshape(1, 1, npix, c).clone().requires_grad_(True)
@@ -784,21 +797,21 @@ def test_batch_norm_fwd_bwd(ops, c, npix):
     close(mm, rmm, 1e-4, 1e-5, 'bn_moving_mean')
     close(mv, rmv, 1e-4, 1e-5, 'bn_moving_var')
     # eval mode: uses the moving statistics, leaves them untouched
-    mm2, mv2 = mm.clone(), mv.clone()
-    ops.bn_finalize(None, 0, c, npix, gamma.to(DEV), beta.to(DEV), 1e-3, 0.99, False, mm2, mv2, scale.clone(), shift.clone(),
-                    mean.clone(), rstd.clone())
+    mm2, mv2 = dev(mm), dev(mv)
+    ops.bn_finalize(None, 0, c, npix, gamma.to(DEV), beta.to(DEV), 1e-3, 0.99, False, mm2, mv2, dev(scale), dev(shift),
+                    dev(mean), dev(rstd))
     torch.cuda.synchronize()
     assert torch.equal(mm2, mm) and torch.equal(mv2, mv)
     # backward
     dout = rnd((npix, c), 44)
     gy, gg, gb = torch.autograd.grad(ref, [yr, g_, b_], dout.float().reshape(1, 1, npix, c))
     nblk = ops.bn_bwd_blocks(npix, c)
-    part = torch.empty(nblk, 2, c, dtype=torch.float32, device=DEV)
+    part = guarded.out((nblk, 2, c), torch.float32, DEV)
     dod = dout.to(DEV)
     ops.bn_bwd_reduce(dod, c, yd, c, npix, c, scale, shift, mean, rstd, True, part)
-    dg, db, coef = torch.empty(c, device=DEV), torch.empty(c, device=DEV), torch.empty(3, c, device=DEV)
+    dg, db, coef = guarded.out((c,), torch.float32, DEV), guarded.out((c,), torch.float32, DEV), guarded.out((3, c), torch.float32, DEV)
     ops.bn_bwd_finalize(part, nblk, c, npix, gamma.to(DEV), beta.to(DEV), rstd, dg, db, coef)
-    dyo = torch.empty(npix, c, dtype=dt, device=DEV)
+    dyo = guarded.out((npix, c), dt, DEV)
     ops.bn_bwd_apply(dod, c, yd, c, npix, c, scale, shift, mean, rstd, True, coef, dyo, c)
     torch.cuda.synchronize()
     close(dg, gg, 2e-3, 1e-3, 'bn_dgamma')
@@ -815,8 +828,8 @@ def test_masked_sse_multi_equals_single_launches(ops):
     feats, single = [], []
     for s_, c in ((32, 256), (16, 512), (8, 64)):
         y = torch.randn(2 * B, s_, s_, c, generator=g).to(torch.bfloat16).to(DEV)
-        part = torch.full((L.SSE_BLOCKS,), float('nan'), device=DEV)
-        ref = torch.empty(L.SSE_BLOCKS, device=DEV)
+        part = guarded.out((L.SSE_BLOCKS,), torch.float32, DEV)
+        ref = guarded.out((L.SSE_BLOCKS,), torch.float32, DEV)
         ops.masked_sse(y[:B], y[B:], B, s_, c, mask, S, ref)
         feats.append((y[:B], y[B:], s_, c, part)); single.append(ref)
     for l1 in (False, True):
@@ -832,9 +845,9 @@ def test_masked_sse_multi_equals_single_launches(ops):
         gt = (torch.rand(B, S, S, 3, generator=g) * 255).to(DEV)
         pred = torch.zeros(B, S, S, ldp); pred[..., :3] = torch.rand(B, S, S, 3, generator=g) * 255
         pred = pred.to(DEV)
-        img_ref = torch.empty(L.SSE_BLOCKS, device=DEV)
+        img_ref = guarded.out((L.SSE_BLOCKS,), torch.float32, DEV)
         ops.masked_sse_f32(gt, 3, pred, ldp, B, S, 3, mask, img_ref, l1=l1)
-        img_part = torch.full((L.SSE_BLOCKS,), float('nan'), device=DEV)
+        img_part = guarded.out((L.SSE_BLOCKS,), torch.float32, DEV)
         for (_a, _b, _s, _c, part) in feats:
             part.fill_(float('nan'))
         ops.masked_sse_all(ops.SseMulti(feats), B, mask, S, gt, 3, pred, ldp, 3, img_part, l1=l1)
@@ -855,11 +868,11 @@ def test_bn_bwd_reduce_with_upsampling_adjoint(ops, B, h, c, dt):
     mean = rnd((c,), 195, 0.5, torch.float32).to(DEV); rstd = (rnd((c,), 196, 0.1, torch.float32).abs() + 0.5).to(DEV)
     npix = B * h * h
     nblk = ops.bn_bwd_blocks(npix, c)
-    d_ref = torch.full((B, h, h, c), float('nan'), dtype=dt, device=DEV)
-    p_ref = torch.full((nblk, 2, c), float('nan'), device=DEV)
+    d_ref = guarded.out((B, h, h, c), dt, DEV)
+    p_ref = guarded.out((nblk, 2, c), torch.float32, DEV)
     ops.upsample2x_bwd(dy_up, d_ref, B, h, h, c, c, c)
     ops.bn_bwd_reduce(d_ref, c, y, c, npix, c, scale, shift, mean, rstd, True, p_ref)
-    d_got = torch.full_like(d_ref, float('nan')); p_got = torch.full_like(p_ref, float('nan'))
+    d_got = guarded.out(d_ref.shape, d_ref.dtype, DEV); p_got = guarded.out(p_ref.shape, p_ref.dtype, DEV)
     ops.bn_bwd_reduce_up(dy_up, c, d_got, c, y, c, B, h, h, c, scale, shift, mean, rstd, True, p_got)
     torch.cuda.synchronize()
     assert torch.equal(d_got, d_ref)
@@ -874,7 +887,7 @@ def test_rows_reduce(ops, rows, width, group):
     n = -(-rows // group)
     outs = []
     for _ in range(2):
-        dst = torch.full((n, width), float('nan'), device=DEV)
+        dst = guarded.out((n, width), torch.float32, DEV)
         ops.rows_reduce(src, rows, width, group, dst)
         torch.cuda.synchronize()
         outs.append(dst)
@@ -899,9 +912,9 @@ def test_batch_norm_finalize_fused_into_apply(ops, c, npix, nrows):
     part = torch.stack([torch.stack([yf[idx[r]:idx[r + 1]].sum(0), (yf[idx[r]:idx[r + 1]] ** 2).sum(0)]) for r in range(nrows)]).contiguous()
     res = {}
     for fused in (False, True):
-        mm, mv = torch.full((c,), 0.3, device=DEV), torch.full((c,), 1.7, device=DEV)
-        scale, shift, mean, rstd = (torch.full((c,), float('nan'), device=DEV) for _ in range(4))
-        xo = torch.full((npix, c), float('nan'), dtype=dt, device=DEV)
+        mm, mv = guarded.out((c,), torch.float32, DEV, fill=0.3), guarded.out((c,), torch.float32, DEV, fill=1.7)
+        scale, shift, mean, rstd = (guarded.out((c,), torch.float32, DEV) for _ in range(4))
+        xo = guarded.out((npix, c), dt, DEV)
         if fused:
             ops.bn_apply_fused(part, nrows, c, npix, gamma, beta, 1e-3, 0.99, True, mm, mv, scale, shift, mean, rstd, y, c, True, xo, c)
         else:
@@ -914,9 +927,9 @@ def test_batch_norm_finalize_fused_into_apply(ops, c, npix, nrows):
     assert float((res[True][0].float() != res[False][0].float()).float().mean()) < 1e-3       # 16-bit outputs: (almost) all identical
     # eval mode: moving statistics, untouched
     scale, shift, mean, rstd = res[False][3:]
-    mm, mv = res[False][1].clone(), res[False][2].clone()
-    xo_e = torch.empty(npix, c, dtype=dt, device=DEV); xo_r = torch.empty_like(xo_e)
-    s2, h2, m2, r2 = (torch.empty(c, device=DEV) for _ in range(4))
+    mm, mv = dev(res[False][1]), dev(res[False][2])
+    xo_e = guarded.out((npix, c), dt, DEV); xo_r = guarded.out(xo_e.shape, xo_e.dtype, DEV)
+    s2, h2, m2, r2 = (guarded.out((c,), torch.float32, DEV) for _ in range(4))
     ops.bn_apply_fused(None, 0, c, npix, gamma, beta, 1e-3, 0.99, False, mm, mv, s2, h2, m2, r2, y, c, True, xo_e, c)
     ops.bn_finalize(None, 0, c, npix, gamma, beta, 1e-3, 0.99, False, mm, mv, scale, shift, mean, rstd)
     ops.bn_apply_relu(y, npix, c, c, scale, shift, True, xo_r, c)
@@ -925,10 +938,10 @@ def test_batch_norm_finalize_fused_into_apply(ops, c, npix, nrows):
     # with the renderer's x2 up-sampling written in the same pass: bitwise the separate kernel applied to the 16-bit output
     if npix % 64 == 0:
         Bq, hq = (npix // 64, 8) if npix <= 8192 else (npix // 1024, 32)
-        up_f = torch.full((Bq, 2 * hq, 2 * hq, c), float('nan'), dtype=dt, device=DEV)
-        xo_u = torch.empty(npix, c, dtype=dt, device=DEV)
+        up_f = guarded.out((Bq, 2 * hq, 2 * hq, c), dt, DEV)
+        xo_u = guarded.out((npix, c), dt, DEV)
         ops.bn_apply_fused(None, 0, c, npix, gamma, beta, 1e-3, 0.99, False, mm, mv, s2, h2, m2, r2, y, c, True, xo_u, c, up_f, c, hq, hq)
-        up_r = torch.empty_like(up_f)
+        up_r = guarded.out(up_f.shape, up_f.dtype, DEV)
         ops.upsample2x_fwd(xo_r.reshape(Bq, hq, hq, c), up_r, Bq, hq, hq, c, c, c)
         torch.cuda.synchronize()
         assert torch.equal(xo_u, xo_r) and torch.equal(up_f, up_r)
@@ -936,14 +949,14 @@ def test_batch_norm_finalize_fused_into_apply(ops, c, npix, nrows):
     dout = rnd((npix, c), 244).to(DEV)
     nblk = ops.bn_bwd_blocks(npix, c)
     assert nblk <= 256
-    bpart = torch.empty(nblk, 2, c, dtype=torch.float32, device=DEV)
+    bpart = guarded.out((nblk, 2, c), torch.float32, DEV)
     ops.bn_bwd_reduce(dout, c, y, c, npix, c, scale, shift, mean, rstd, True, bpart)
-    dg, db, coef = torch.empty(c, device=DEV), torch.empty(c, device=DEV), torch.empty(3, c, device=DEV)
+    dg, db, coef = guarded.out((c,), torch.float32, DEV), guarded.out((c,), torch.float32, DEV), guarded.out((3, c), torch.float32, DEV)
     ops.bn_bwd_finalize(bpart, nblk, c, npix, gamma, beta, rstd, dg, db, coef)
-    dy_ref = torch.empty(npix, c, dtype=dt, device=DEV)
+    dy_ref = guarded.out((npix, c), dt, DEV)
     ops.bn_bwd_apply(dout, c, y, c, npix, c, scale, shift, mean, rstd, True, coef, dy_ref, c)
-    dg2, db2 = torch.empty(c, device=DEV), torch.empty(c, device=DEV)
-    dy_f = torch.full((npix, c), float('nan'), dtype=dt, device=DEV)
+    dg2, db2 = guarded.out((c,), torch.float32, DEV), guarded.out((c,), torch.float32, DEV)
+    dy_f = guarded.out((npix, c), dt, DEV)
     ops.bn_bwd_apply_fused(bpart, nblk, c, npix, gamma, dout, c, y, c, scale, shift, mean, rstd, True, dg2, db2, dy_f, c)
     torch.cuda.synchronize()
     close(dg2, dg, 1e-6, 1e-6, 'bn_bwd_fused/dgamma'); close(db2, db, 1e-6, 1e-6, 'bn_bwd_fused/dbeta')
@@ -963,11 +976,11 @@ def test_batch_norm_bwd_from_producer_sums(ops, c, ldp, npix):
     beta = rnd((c,), 143, 0.5, torch.float32)
     yf = y.float()
     partial = torch.stack([yf.sum(0), (yf * yf).sum(0)]).reshape(1, 2, c).to(DEV).contiguous()
-    mm, mv = torch.zeros(c, device=DEV), torch.ones(c, device=DEV)
-    scale, shift, mean, rstd = (torch.empty(c, device=DEV) for _ in range(4))
+    mm, mv = guarded.out((c,), torch.float32, DEV, fill=0), guarded.out((c,), torch.float32, DEV, fill=1)
+    scale, shift, mean, rstd = (guarded.out((c,), torch.float32, DEV) for _ in range(4))
     ops.bn_finalize(partial, 1, c, npix, gamma.to(DEV), beta.to(DEV), 1e-3, 0.99, True, mm, mv, scale, shift, mean, rstd)
     yd = y.to(DEV)
-    out = torch.empty(npix, c, dtype=dt, device=DEV)
+    out = guarded.out((npix, c), dt, DEV)
     ops.bn_apply_relu(yd, npix, c, c, scale, shift, True, out, c)
     torch.cuda.synchronize()
     yr = yf.reshape(1, 1, npix, c).clone().requires_grad_(True)
@@ -984,9 +997,9 @@ def test_batch_norm_bwd_from_producer_sums(ops, c, ldp, npix):
         sl = slice(r * npix // 3, (r + 1) * npix // 3)
         rows[r, 0, :c] = dz[sl].sum(0); rows[r, 1, :c] = (dz[sl] * of[sl]).sum(0)
     rows[:, :, c:] = 123.0                     # columns of the producer's other channels: must be ignored
-    dg, db, coef = torch.empty(c, device=DEV), torch.empty(c, device=DEV), torch.empty(3, c, device=DEV)
+    dg, db, coef = guarded.out((c,), torch.float32, DEV), guarded.out((c,), torch.float32, DEV), guarded.out((3, c), torch.float32, DEV)
     ops.bn_bwd_finalize(rows.to(DEV), 3, c, npix, gamma.to(DEV), beta.to(DEV), rstd, dg, db, coef, from_out=True, ldp=ldp)
-    dyo = torch.empty(npix, c, dtype=dt, device=DEV)
+    dyo = guarded.out((npix, c), dt, DEV)
     ops.bn_bwd_apply(dz.to(dt).to(DEV), c, yd, c, npix, c, scale, shift, mean, rstd, False, coef, dyo, c)
     torch.cuda.synchronize()
     # xhat recovered from the 16-bit `out` = one more rounding than from y: |err| ~ sqrt(N) |dz| |out| 2^-9 (measured 4e-3 of
@@ -1008,7 +1021,7 @@ def test_conv_mask_with_bn_backward_sums(ops, B, H, ci, co, dt):
     from imm_amd import _lib as L
     x = rnd((B, H, H, ci), 4, 1.0, dt)
     w = rnd((3, 3, ci, co), 5, 0.1, dt)
-    mref = rnd((B, H, H, co), 7, 1.0, dt).to(DEV).contiguous()
+    mref = dev(rnd((B, H, H, co), 7, 1.0, dt))
     ref = O.conv2d_same(x.float(), w.float(), None, 1)
     y3, _, _ = run_conv(ops, x, w, None, 3, 1, co, ci, False, extra_flags=L.CONV_MASK, mask=mref)
     y4, stats, _ = run_conv(ops, x, w, None, 3, 1, co, ci, False, extra_flags=L.CONV_MASK | L.CONV_STATS, mask=mref)
@@ -1028,23 +1041,23 @@ def test_conv_group_mask_with_bn_backward_sums(ops, H, ci, co):
     from imm_amd import _lib as L
     B, k, dt = 8, 3, torch.bfloat16
     w = rnd((k, k, ci, co), 401, 0.05)
-    dy = rnd((B, H // 2, H // 2, co), 402).to(DEV).contiguous()
-    mref = rnd((B, H, H, ci), 403).to(DEV).contiguous()
+    dy = dev(rnd((B, H // 2, H // 2, co), 402))
+    mref = dev(rnd((B, H, H, ci), 403))
     plain = ops.dgrad_s2_class_descs(B, H, H, ci, ci, co, co, k)
     classes = ops.dgrad_s2_class_descs(B, H, H, ci, ci, co, co, k, flags=L.CONV_MASK | L.CONV_STATS, ldmask=ci)
     rows = ops.round_up(ci, 128)
     wts = []
     for d, mode in classes:
-        wt = torch.zeros(rows, d.kpad, dtype=dt, device=DEV)
+        wt = guarded.out((rows, d.kpad), dt, DEV, fill=0)
         ops.pack_weights(w.float().to(DEV).contiguous(), wt, mode, k, k, ci, co, co, rows, d.kpad)
         wts.append(wt)
-    ref = torch.full((B, H, H, ci), float('nan'), dtype=dt, device=DEV)
+    ref = guarded.out((B, H, H, ci), dt, DEV)
     for (d, _m), wt in zip(plain, wts):
         ops.conv2d(d, dy, wt, None, ref)
     grp = ops.ConvGroup([d for d, _m in classes], wts)
     nrows = ops.conv2d_group_stats_blocks(grp)
-    stats = torch.full((nrows, 2, ci), float('nan'), dtype=torch.float32, device=DEV)
-    got = torch.full((B, H, H, ci), float('nan'), dtype=dt, device=DEV)
+    stats = guarded.out((nrows, 2, ci), torch.float32, DEV)
+    got = guarded.out((B, H, H, ci), dt, DEV)
     ops.conv2d_group(grp, dy, got, stats, mref)
     torch.cuda.synchronize()
     mf = mref.float()
@@ -1060,11 +1073,11 @@ def test_upsample2x_bwd_with_bn_backward_sums(ops, B, h, c):
     dt = torch.bfloat16
     dy = rnd((B, 2 * h, 2 * h, c), 52).to(DEV)
     out = rnd((B, h, h, c), 55).to(DEV)
-    plain = torch.empty(B, h, h, c, dtype=dt, device=DEV)
+    plain = guarded.out((B, h, h, c), dt, DEV)
     ops.upsample2x_bwd(dy, plain, B, h, h, c, c, c)
     nblk = ops.upsample2x_bwd_bn_blocks(B, h, h, c)
-    part = torch.full((nblk, 2, c), float('nan'), dtype=torch.float32, device=DEV)
-    dx = torch.empty(B, h, h, c, dtype=dt, device=DEV)
+    part = guarded.out((nblk, 2, c), torch.float32, DEV)
+    dx = guarded.out((B, h, h, c), dt, DEV)
     ops.upsample2x_bwd_bn(dy, dx, B, h, h, c, c, c, out, c, part)
     torch.cuda.synchronize()
     want = plain.float() * (out.float() > 0)
@@ -1082,11 +1095,11 @@ def test_upsample2x(ops):
     x = rnd((B, h, h, c), 51)
     xr = x.float().requires_grad_(True)
     ref = O.resize_bilinear(xr, 2 * h, 2 * h)
-    y = torch.empty(B, 2 * h, 2 * h, c, dtype=x.dtype, device=DEV)
+    y = guarded.out((B, 2 * h, 2 * h, c), x.dtype, DEV)
     ops.upsample2x_fwd(x.to(DEV), y, B, h, h, c, c, c)
     dy = rnd((B, 2 * h, 2 * h, c), 52)
     (gx,) = torch.autograd.grad(ref, xr, dy.float())
-    dx = torch.empty(B, h, h, c, dtype=x.dtype, device=DEV)
+    dx = guarded.out((B, h, h, c), x.dtype, DEV)
     ops.upsample2x_bwd(dy.to(DEV), dx, B, h, h, c, c, c)
     torch.cuda.synchronize()
     close(y, ref, 8e-3, 1e-3, 'upsample_fwd')
@@ -1098,11 +1111,11 @@ def test_resize_align_corners(ops):
     x = rnd((B, hi, hi, c), 53)
     xr = x.float().requires_grad_(True)
     ref = O.resize_bilinear(xr, ho, ho, align_corners=True)
-    y = torch.empty(B, ho, ho, c, dtype=x.dtype, device=DEV)
+    y = guarded.out((B, ho, ho, c), x.dtype, DEV)
     ops.resize_ac_fwd(x.to(DEV), y, B, hi, hi, ho, ho, c, c, c)
     dy = rnd((B, ho, ho, c), 54)
     (gx,) = torch.autograd.grad(ref, xr, dy.float())
-    dx = torch.empty(B, hi, hi, c, dtype=x.dtype, device=DEV)
+    dx = guarded.out((B, hi, hi, c), x.dtype, DEV)
     ops.resize_ac_bwd(dy.to(DEV), dx, B, hi, hi, ho, ho, c, c, c)
     torch.cuda.synchronize()
     close(y, ref, 8e-3, 2e-3, 'resize_ac_fwd')
@@ -1114,14 +1127,14 @@ def test_maxpool(ops):
     x = torch.relu(rnd((B, h, h, c), 55))     # post-ReLU activations: many exact zeros / ties at 0
     xr = x.float().requires_grad_(True)
     ref = O.max_pool2(xr)
-    y = torch.empty(B, h // 2, h // 2, c, dtype=x.dtype, device=DEV)
+    y = guarded.out((B, h // 2, h // 2, c), x.dtype, DEV)
     ops.maxpool2_fwd(x.to(DEV), y, B, h, h, c)
     torch.cuda.synchronize()
     assert torch.equal(y.float().cpu(), ref.detach())      # exact
     dy = rnd((B, h // 2, h // 2, c), 56)
     (gx,) = torch.autograd.grad(ref, xr, dy.float())
     for relu_mask in (0, 1):
-        dx = torch.empty(B, h, h, c, dtype=x.dtype, device=DEV)
+        dx = guarded.out((B, h, h, c), x.dtype, DEV)
         ops.maxpool2_bwd(x.to(DEV), dy.to(DEV), dx, B, h, h, c, relu_mask)
         torch.cuda.synchronize()
         if relu_mask:
@@ -1142,8 +1155,8 @@ def test_first_conv_as_tap_unrolled_7x1(ops, B, S):
     co, dt = 32, torch.bfloat16
     src = torch.rand(B, S, S, 3) * 255
     w = rnd((7, 7, 3, co), 57, 0.01, torch.float32)
-    xin = torch.full((B, S, S, 32), float('nan'), dtype=dt, device=DEV)
-    ops.pack_image_taps(src.to(DEV), xin, B, S, S, 7, 3, 32)
+    xin = guarded.out((B, S, S, 32), dt, DEV)
+    ops.pack_image_taps(dev(src), xin, B, S, S, 7, 3, 32)
     torch.cuda.synchronize()
     xp = torch.nn.functional.pad(src.to(dt), (0, 0, 3, 3))
     for kx in range(7):
@@ -1151,23 +1164,23 @@ def test_first_conv_as_tap_unrolled_7x1(ops, B, S):
     assert float(xin[..., 21:].float().abs().max()) == 0.0
     desc = ops.fwd_desc(B, S, S, 32, 32, co, co, 7, 1, 0, kw=1)
     assert (desc.kh, desc.kw, desc.pad_t, desc.pad_l, desc.kpad) == (7, 1, 3, 0, 224)
-    wt = torch.zeros(128, desc.kpad, dtype=dt, device=DEV)
+    wt = guarded.out((128, desc.kpad), dt, DEV, fill=0)
     ops.pack_weights(w.to(DEV).contiguous(), wt, 0, 7, 1, 21, co, 32, 128, desc.kpad)
-    y = torch.empty(B, S, S, co, dtype=dt, device=DEV)
+    y = guarded.out((B, S, S, co), dt, DEV)
     ops.conv2d(desc, xin, wt, None, y)
     ref = O.conv2d_same(src.to(dt).float(), w.to(dt).float(), None, 1)
     dy = rnd((B, S, S, co), 58)
-    slab = torch.empty(3, desc.kpad, co, device=DEV)
-    ops.conv2d_wgrad(desc, xin, dy.to(DEV), co, slab, 3)
-    dw = torch.empty(7, 7, 3, co, device=DEV)
+    slab = guarded.out((3, desc.kpad, co), torch.float32, DEV)
+    ops.conv2d_wgrad(desc, xin, dev(dy), co, slab, 3)
+    dw = guarded.out((7, 7, 3, co), torch.float32, DEV)
     ops.conv2d_wgrad_reduce(slab, 3, 7, 1, 32, 21, co, desc.kpad, dw)
     torch.cuda.synchronize()
     close(y, ref, 1e-2, 2e-3, 'conv7x1')
     # epilogue variant used by the encoders: bias + BN partial sums
     bias = rnd((co,), 59, 0.5, torch.float32)
     d2 = ops.fwd_desc(B, S, S, 32, 32, co, co, 7, 1, L.CONV_BIAS | L.CONV_STATS, kw=1)
-    stats = torch.full((ops.conv_stats_blocks(d2), 2, co), float('nan'), dtype=torch.float32, device=DEV)
-    y2 = torch.empty(B, S, S, co, dtype=dt, device=DEV)
+    stats = guarded.out((ops.conv_stats_blocks(d2), 2, co), torch.float32, DEV)
+    y2 = guarded.out((B, S, S, co), dt, DEV)
     ops.conv2d(d2, xin, wt, bias.to(DEV), y2, stats)
     torch.cuda.synchronize()
     close(y2, ref + bias, 1e-2, 2e-3, 'conv7x1+bias')
@@ -1191,20 +1204,20 @@ def test_first_conv_from_the_f32_image(ops, B, S, co, dt):
     src = torch.rand(B, S, S, 3, generator=g) * 255
     w = rnd((7, 7, 3, co), 57, 0.01, torch.float32)
     bias = rnd((co,), 59, 0.5, torch.float32)
-    srcd = src.to(DEV).contiguous()
+    srcd = dev(src)
     ldy = ops.round_up(co, 8)
     assert ops.conv_first_supported(B, S, co, ldy)
-    wt = torch.zeros(128, 224, dtype=dt, device=DEV)
+    wt = guarded.out((128, 224), dt, DEV, fill=0)
     ops.pack_weights(w.to(DEV).contiguous(), wt, 0, 7, 1, 21, co, 32, 128, 224)
-    y = torch.full((B, S, S, ldy), float('nan'), dtype=dt, device=DEV)
-    stats = torch.full((ops.conv_first_stats_blocks(B, S), 2, co), float('nan'), dtype=torch.float32, device=DEV)
+    y = guarded.out((B, S, S, ldy), dt, DEV)
+    stats = guarded.out((ops.conv_first_stats_blocks(B, S), 2, co), torch.float32, DEV)
     ops.conv_first(srcd, wt, bias.to(DEV), y, ldy, stats, B, S, co, L.CONV_BIAS | L.CONV_STATS)
     # the form it replaces
-    xin = torch.empty(B, S, S, 32, dtype=dt, device=DEV)
+    xin = guarded.out((B, S, S, 32), dt, DEV)
     ops.pack_image_taps(srcd, xin, B, S, S, 7, 3, 32)
     d2 = ops.fwd_desc(B, S, S, 32, 32, co, ldy, 7, 1, L.CONV_BIAS | L.CONV_STATS, kw=1)
-    stats2 = torch.full((ops.conv_stats_blocks(d2), 2, co), float('nan'), dtype=torch.float32, device=DEV)
-    y2 = torch.full((B, S, S, ldy), float('nan'), dtype=dt, device=DEV)
+    stats2 = guarded.out((ops.conv_stats_blocks(d2), 2, co), torch.float32, DEV)
+    y2 = guarded.out((B, S, S, ldy), dt, DEV)
     ops.conv2d(d2, xin, wt, bias.to(DEV), y2, stats2)
     torch.cuda.synchronize()
     ref = O.conv2d_same(src.to(dt).float(), w.to(dt).float(), bias, 1)
@@ -1212,9 +1225,9 @@ def test_first_conv_from_the_f32_image(ops, B, S, co, dt):
     close(y[..., :co], y2[..., :co], 2.0 ** -7 if dt == torch.bfloat16 else 2.0 ** -10, 1e-4, 'conv_first vs pack + 7x1 conv')
     close(stats.sum(0), stats2.sum(0), 2e-4, 2e-4, 'conv_first batch-norm partial sums')
     if ldy > co:
-        assert bool(torch.isnan(y[..., co:].float()).all())          # padding channels are left alone
+        assert untouched(y[..., co:])                                # padding channels are left alone
     # no bias, no sums (the inference form)
-    y3 = torch.full((B, S, S, ldy), float('nan'), dtype=dt, device=DEV)
+    y3 = guarded.out((B, S, S, ldy), dt, DEV)
     ops.conv_first(srcd, wt, None, y3, ldy, None, B, S, co, 0)
     torch.cuda.synchronize()
     close(y3[..., :co], ref - bias, 1e-2, 2e-3, 'conv_first without bias')
@@ -1225,16 +1238,16 @@ def test_first_conv_from_the_f32_image_rejects_unserved_shapes(ops):
     assert not ops.conv_first_supported(2, 72, 32, 32)       # side % 16
     assert not ops.conv_first_supported(2, 64, 64, 64)       # more than 32 filters
     assert not ops.conv_first_supported(2, 64, 30, 32)       # co % 4
-    img = torch.zeros(2, 72, 72, 3, device=DEV)
-    wt = torch.zeros(128, 224, dtype=torch.bfloat16, device=DEV)
-    y = torch.zeros(2, 72, 72, 32, dtype=torch.bfloat16, device=DEV)
+    img = guarded.out((2, 72, 72, 3), torch.float32, DEV, fill=0)
+    wt = guarded.out((128, 224), torch.bfloat16, DEV, fill=0)
+    y = guarded.out((2, 72, 72, 32), torch.bfloat16, DEV, fill=0)
     with pytest.raises(L.ImmHipError):
         ops.conv_first(img, wt, None, y, 32, None, 2, 72, 32, 0)
 
 
 def test_pack_image(ops):
     src = torch.rand(5, 7, 7, 3) * 255
-    dst = torch.empty(5, 7, 7, 8, dtype=torch.bfloat16, device=DEV)
+    dst = guarded.out((5, 7, 7, 8), torch.bfloat16, DEV)
     ops.pack_image(src.to(DEV), dst, 5 * 49)
     torch.cuda.synchronize()
     assert torch.equal(dst[..., :3].cpu(), src.to(torch.bfloat16)) and float(dst[..., 3:].float().abs().max()) == 0.0
@@ -1254,8 +1267,8 @@ def test_softargmax_gauss(ops, h, K, s, mode):
     hr = heat.clone().requires_grad_(True)
     mu_r, py_r, px_r = O.soft_argmax(hr)
     g_r = O.gaussian_maps(mu_r, [s, s], 10.0, mode)
-    mu = torch.empty(B, K, 2, device=DEV); py = torch.empty(B, h, K, device=DEV); px = torch.empty(B, h, K, device=DEV)
-    joint = torch.zeros(B, s, s, ldg, dtype=torch.bfloat16, device=DEV)
+    mu = guarded.out((B, K, 2), torch.float32, DEV); py = guarded.out((B, h, K), torch.float32, DEV); px = guarded.out((B, h, K), torch.float32, DEV)
+    joint = guarded.out((B, s, s, ldg), torch.bfloat16, DEV, fill=0)
     ops.softargmax_gauss_fwd(padded(heat, ldh), ldh, B, h, h, K, 10.0, s, mu, py, px, joint[..., 256:], ldg, torch.bfloat16, mode)
     torch.cuda.synchronize()
     close(mu, mu_r, 1e-4, 1e-5, 'mu')                     # f32 math: landmarks to ~1e-6
@@ -1265,14 +1278,14 @@ def test_softargmax_gauss(ops, h, K, s, mode):
     assert float(joint[..., :256].float().abs().max()) == 0.0 and float(joint[..., 256 + K:].float().abs().max()) == 0.0
     dg = rnd((B, s, s, K), 62)
     (gh,) = torch.autograd.grad(g_r, hr, dg.float())
-    dj = torch.zeros(B, s, s, ldg, dtype=torch.bfloat16, device=DEV)
+    dj = guarded.out((B, s, s, ldg), torch.bfloat16, DEV, fill=0)
     dj[..., 256:256 + K] = dg.to(DEV)
-    dheat = torch.full((B, h, h, 64), float('nan'), dtype=torch.bfloat16, device=DEV)
+    dheat = guarded.out((B, h, h, 64), torch.bfloat16, DEV)
     ops.softargmax_gauss_bwd(dj[..., 256:], ldg, B, h, h, K, 10.0, s, mu, py, px, dheat, 64, mode)
     torch.cuda.synchronize()
     close(dheat[..., :K], gh, 1e-2, 2e-3, 'dheat')
     assert float(dheat[..., K:].float().abs().max()) == 0.0
-    out = torch.empty(B, 128, 128, K, device=DEV)
+    out = guarded.out((B, 128, 128, K), torch.float32, DEV)
     ops.gauss_render_f32(mu, B, K, 10.0, 128, out, mode)
     torch.cuda.synchronize()
     close(out, O.gaussian_maps(mu_r.detach(), [128, 128], 10.0, mode), 1e-4, 1e-5, 'render128')
@@ -1297,12 +1310,12 @@ def test_pose_head_fused(ops, h, K, mode, dt):
     g_r = O.gaussian_maps(mu_r, [s, s], 10.0, mode)
     # ---- forward
     fd = ops.fwd_desc(B, h, h, C, C, K, ldh, 1, 1, 0)
-    wt = torch.zeros(128, fd.kpad, dtype=dt, device=DEV)
+    wt = guarded.out((128, fd.kpad), dt, DEV, fill=0)
     ops.pack_weights(w.float().to(DEV).contiguous(), wt, 0, 1, 1, C, K, C, 128, fd.kpad)
     featd = feat.to(DEV).contiguous()
-    heat = torch.zeros(B, h, h, ldh, device=DEV)
-    mu = torch.empty(B, K, 2, device=DEV); py = torch.empty(B, h, K, device=DEV); px = torch.empty(B, h, K, device=DEV)
-    joint = torch.zeros(B, s, s, ldg, dtype=dt, device=DEV)
+    heat = guarded.out((B, h, h, ldh), torch.float32, DEV, fill=0)
+    mu = guarded.out((B, K, 2), torch.float32, DEV); py = guarded.out((B, h, K), torch.float32, DEV); px = guarded.out((B, h, K), torch.float32, DEV)
+    joint = guarded.out((B, s, s, ldg), dt, DEV, fill=0)
     ops.pose_head_fwd(featd, C, C, wt, bias.to(DEV), B, h, h, K, 10.0, s, heat, ldh, mu, py, px, joint[..., C:], ldg, dt, mode)
     torch.cuda.synchronize()
     close(heat[..., :K], heat_r, 2e-3, 2e-4, 'heat')                 # f32 accumulation of exact 16-bit products
@@ -1312,9 +1325,9 @@ def test_pose_head_fused(ops, h, K, mode, dt):
     assert float(joint[..., :C].float().abs().max()) == 0.0 and float(joint[..., C + K:].float().abs().max()) == 0.0
     # the two-launch path it replaces: same heat-map to accumulation order, same landmarks
     fd2 = ops.fwd_desc(B, h, h, C, C, K, ldh, 1, 1, L_CONV_BIAS_F32)
-    heat2 = torch.zeros(B, h, h, ldh, device=DEV)
+    heat2 = guarded.out((B, h, h, ldh), torch.float32, DEV, fill=0)
     ops.conv2d(fd2, featd, wt, bias.to(DEV), heat2)
-    mu2 = torch.empty_like(mu); py2 = torch.empty_like(py); px2 = torch.empty_like(px)
+    mu2 = guarded.out(mu.shape, mu.dtype, DEV); py2 = guarded.out(py.shape, py.dtype, DEV); px2 = guarded.out(px.shape, px.dtype, DEV)
     ops.softargmax_gauss_fwd(heat2, ldh, B, h, h, K, 10.0, s, mu2, py2, px2, None, ldg, dt, mode)
     torch.cuda.synchronize()
     close(heat[..., :K], heat2[..., :K], 1e-4, 1e-5, 'heat vs conv2d')
@@ -1322,16 +1335,16 @@ def test_pose_head_fused(ops, h, K, mode, dt):
     # ---- backward
     dg = rnd((B, s, s, K), 164, 1.0, dt)
     gf, gw, gb = torch.autograd.grad(g_r, (fr, wr, br), dg.float())
-    dj = torch.zeros(B, s, s, ldg, dtype=dt, device=DEV)
+    dj = guarded.out((B, s, s, ldg), dt, DEV, fill=0)
     dj[..., C:C + K] = dg.to(DEV)
-    wtd = torch.zeros(ops.round_up(C, 128), lddh, dtype=dt, device=DEV)
+    wtd = guarded.out((ops.round_up(C, 128), lddh), dt, DEV, fill=0)
     ops.pack_weights(w.float().to(DEV).contiguous(), wtd, 1, 1, 1, C, K, lddh, wtd.shape[0], lddh)
-    dheat = torch.full((B, h, h, lddh), float('nan'), dtype=dt, device=DEV)
-    dfeat = torch.full((B, h, h, C), float('nan'), dtype=dt, device=DEV)
-    bpart = torch.full((B, K), float('nan'), device=DEV)
+    dheat = guarded.out((B, h, h, lddh), dt, DEV)
+    dfeat = guarded.out((B, h, h, C), dt, DEV)
+    bpart = guarded.out((B, K), torch.float32, DEV)
     ops.pose_head_bwd(dj[..., C:], ldg, B, h, h, K, 10.0, s, mu, py, px, dheat, lddh, wtd, C, dfeat, C, bpart, mode)
     torch.cuda.synchronize()
-    dheat2 = torch.full_like(dheat, float('nan'))
+    dheat2 = guarded.out(dheat.shape, dheat.dtype, DEV)
     ops.softargmax_gauss_bwd(dj[..., C:], ldg, B, h, h, K, 10.0, s, mu, py, px, dheat2, lddh, mode)
     torch.cuda.synchronize()
     assert torch.equal(dheat, dheat2)                                 # the shared part of the pass: bit for bit
@@ -1357,12 +1370,12 @@ def test_vgg_conv1_1(ops):
     ims = torch.cat([gt, pr], 0)
     gray = ims.mean(dim=3, keepdim=True) / 255.0 - O.VGG_GRAY_MEAN / 255.0
     ref = torch.relu(O.conv2d_same(gray, w, b))
-    out = torch.empty(2 * B, S, S, 64, dtype=torch.bfloat16, device=DEV)
+    out = guarded.out((2 * B, S, S, 64), torch.bfloat16, DEV)
     ops.vgg_conv1_1_fwd(gt.to(DEV), pred.to(DEV), ldp, B, S, w.reshape(9, 64).to(DEV).contiguous(), b.to(DEV), out)
     torch.cuda.synchronize()
     close(out, ref, 8e-3, 1e-3, 'vgg1_1_fwd')
     # halves: 1 = gt images only, 2 = pred images only; together bitwise equal to the single launch
-    out2 = torch.zeros_like(out)
+    out2 = guarded.out(out.shape, out.dtype, DEV, fill=0)
     ops.vgg_conv1_1_fwd(gt.to(DEV), pred.to(DEV), ldp, B, S, w.reshape(9, 64).to(DEV).contiguous(), b.to(DEV), out2, 1)
     torch.cuda.synchronize()
     assert torch.equal(out2[:B], out[:B]) and float(out2[B:].float().abs().max()) == 0.0
@@ -1374,7 +1387,7 @@ def test_vgg_conv1_1(ops):
     coef = torch.tensor([0.37, 0, 0, 0, 0, 0])
     loss = (ref[B:] * dz.float()).sum() + 0.5 * 0.37 * (mask.unsqueeze(-1) * (pr - gt) ** 2).sum()
     (gp,) = torch.autograd.grad(loss, pr)
-    dpred = torch.full((B, S, S, ldp), float('nan'), dtype=torch.bfloat16, device=DEV)
+    dpred = guarded.out((B, S, S, ldp), torch.bfloat16, DEV)
     ops.vgg_conv1_1_bwd(dz.to(DEV), B, S, w.reshape(9, 64).to(DEV).contiguous(), gt.to(DEV), pred.to(DEV), ldp, mask.to(DEV),
                         coef.to(DEV), dpred, ldp)
     torch.cuda.synchronize()
@@ -1409,20 +1422,20 @@ def test_vgg_head_fused(ops, B, S, dt, store_from, tag):
     w12 = rnd((3, 3, 64, 64), 83, 0.05, torch.float32); b12 = rnd((64,), 84, 0.1, torch.float32)
     sf = B if store_from is None else store_from
     fd = ops.fwd_desc(2 * B, S, S, 64, 64, 64, 64, 3, 1, L.CONV_BIAS | L.CONV_RELU)
-    wt = torch.zeros(128, fd.kpad, dtype=dt, device=DEV)
+    wt = guarded.out((128, fd.kpad), dt, DEV, fill=0)
     ops.pack_weights(w12.to(DEV), wt, 0, 3, 3, 64, 64, 64, 128, fd.kpad)
     gtd, pd = gt.to(DEV), pred.to(DEV)
     w11d, b11d, b12d = w11.reshape(9, 64).to(DEV).contiguous(), b11.to(DEV), b12.to(DEV)
     # (b) the two-launch sequence
-    a_ref = torch.empty(2 * B, S, S, 64, dtype=dt, device=DEV)
-    y_ref = torch.empty(2 * B, S, S, 64, dtype=dt, device=DEV)
+    a_ref = guarded.out((2 * B, S, S, 64), dt, DEV)
+    y_ref = guarded.out((2 * B, S, S, 64), dt, DEV)
     ops.vgg_conv1_1_fwd(gtd, pd, ldp, B, S, w11d, b11d, a_ref)
     ops.conv2d(fd, a_ref, wt, b12d, y_ref)
     # the fused launch
     sentinel = 7.0
-    a11 = torch.full((2 * B, S, S, 64), sentinel, dtype=dt, device=DEV)
-    y12 = torch.full((2 * B, S, S, 64), float('nan'), dtype=dt, device=DEV)
-    scratch = torch.empty(ops.vgg_head_scratch_bytes(B, S), dtype=torch.uint8, device=DEV)
+    a11 = guarded.out((2 * B, S, S, 64), dt, DEV, fill=sentinel)
+    y12 = guarded.out((2 * B, S, S, 64), dt, DEV)
+    scratch = guarded.out((ops.vgg_head_scratch_bytes(B, S),), torch.uint8, DEV)
     ops.vgg_head_fwd(gtd, pd, ldp, B, S, w11d, b11d, wt, b12d, a11, sf, y12, scratch)
     torch.cuda.synchronize()
     assert not bool(torch.isnan(y12.float()).any()), 'every output pixel is written'
@@ -1450,9 +1463,9 @@ def test_perceptual_loss_pieces(ops):
     mask = O.smooth_mask(S, S, margin=2, step=6).reshape(1, S, S).repeat(B, 1, 1).contiguous()
     feats = [(32, 3), (32, 64), (16, 128), (8, 256)]
     nf = len(feats)
-    partial = torch.zeros(nf, L.SSE_BLOCKS, device=DEV)
+    partial = guarded.out((nf, L.SSE_BLOCKS), torch.float32, DEV, fill=0)
     agg0 = torch.tensor([100.0, 1.6, 2.3, 1.8])
-    agg = agg0.clone().to(DEV)
+    agg = dev(agg0)
     tens, ref_terms, ref_m, ref_grads = [], [], [], []
     for i, (s, c) in enumerate(feats):
         if i == 0:
@@ -1471,7 +1484,7 @@ def test_perceptual_loss_pieces(ops):
         tens.append((a, b)); ref_terms.append(float(term)); ref_m.append(float(m)); ref_grads.append(g)
     nel = torch.tensor([float(B * s * s * c) for s, c in feats], device=DEV)
     wd = torch.tensor([0.125], device=DEV)
-    out = torch.zeros(3 * nf + 3, device=DEV)
+    out = guarded.out((3 * nf + 3,), torch.float32, DEV, fill=0)
     ops.perceptual_finalize(partial, nf, nel, agg, True, wd, out)
     torch.cuda.synchronize()
     o = out.cpu()
@@ -1484,12 +1497,12 @@ def test_perceptual_loss_pieces(ops):
     s, c = feats[2]
     a, b = tens[2]
     din = rnd((B, s, s, c), 99)
-    da = din.clone().to(DEV)
+    da = dev(din)
     ops.tap_grad(da, True, b.to(DEV), a.to(DEV), B, s, c, mask.to(DEV), S, out[2 * nf:], 2, True)
     torch.cuda.synchronize()
     ref = (din.float() + ref_grads[2]) * (b.float() > 0)
     close(da, ref, 1e-2, 2e-3, 'tap_grad')
-    da2 = torch.full((B, s, s, c), float('nan'), dtype=torch.bfloat16, device=DEV)
+    da2 = guarded.out((B, s, s, c), torch.bfloat16, DEV)
     ops.tap_grad(da2, False, b.to(DEV), a.to(DEV), B, s, c, mask.to(DEV), S, out[2 * nf:], 2, False)
     torch.cuda.synchronize()
     close(da2, ref_grads[2], 1e-2, 2e-3, 'tap_grad_noin')
@@ -1503,12 +1516,12 @@ def test_clip_adam_and_weight_decay(ops):
     P = {('t%d/w' % i if wds[i] else 't%d/b' % i): torch.randn(n, generator=g) * 0.3 for i, n in enumerate(sizes)}
     G = {k: torch.randn(v.shape, generator=g) * (3.0 if i % 2 == 0 else 1e-3) for i, (k, v) in enumerate(P.items())}
     flat = lambda d: torch.cat([v.reshape(-1) for v in d.values()]).to(DEV)
-    params, grads = flat(P), flat(G) * 2.0          # grads hold the SUM over 2 towers
-    m, v = torch.zeros_like(params), torch.zeros_like(params)
-    part = torch.empty(tab.nblk, device=DEV); norm2 = torch.empty(tab.nseg, device=DEV)
-    step = torch.zeros(1, dtype=torch.int32, device=DEV); lrs = torch.zeros(2, device=DEV)
-    adam_t = torch.zeros(1, dtype=torch.int32, device=DEV)
-    wdl = torch.zeros(1, device=DEV)
+    params, grads = dev(flat(P)), flat(G) * 2.0          # grads hold the SUM over 2 towers
+    m, v = guarded.out(params.shape, params.dtype, DEV, fill=0), guarded.out(params.shape, params.dtype, DEV, fill=0)
+    part = guarded.out((tab.nblk,), torch.float32, DEV); norm2 = guarded.out((tab.nseg,), torch.float32, DEV)
+    step = guarded.out((1,), torch.int32, DEV, fill=0); lrs = guarded.out((2,), torch.float32, DEV, fill=0)
+    adam_t = guarded.out((1,), torch.int32, DEV, fill=0)
+    wdl = guarded.out((1,), torch.float32, DEV, fill=0)
     ops.weight_decay_loss(params, tab, part, wdl)
     torch.cuda.synchronize()
     np.testing.assert_allclose(float(wdl), float(O.weight_decay_loss(P)), rtol=1e-5)
@@ -1557,17 +1570,18 @@ def test_clip_adam_loss_scaling(ops):
     hp = ops.OptHParams(**kw)
 
     def fresh():
-        return dict(params=params0.clone(), m=torch.zeros_like(params0), v=torch.zeros_like(params0),
-                    part=torch.empty(tab.nblk, device=DEV), norm2=torch.empty(tab.nseg, device=DEV),
-                    step=torch.zeros(1, dtype=torch.int32, device=DEV), adam_t=torch.zeros(1, dtype=torch.int32, device=DEV),
-                    lrs=torch.zeros(2, device=DEV))
+        return dict(params=dev(params0), m=guarded.out(params0.shape, params0.dtype, DEV, fill=0),
+                    v=guarded.out(params0.shape, params0.dtype, DEV, fill=0),
+                    part=guarded.out((tab.nblk,), torch.float32, DEV), norm2=guarded.out((tab.nseg,), torch.float32, DEV),
+                    step=guarded.out((1,), torch.int32, DEV, fill=0), adam_t=guarded.out((1,), torch.int32, DEV, fill=0),
+                    lrs=guarded.out((2,), torch.float32, DEV, fill=0))
 
     def run(st, grads, ls):
         ops.clip_adam_step(st['params'], grads, st['m'], st['v'], tab, st['part'], st['norm2'], st['step'], st['adam_t'], st['lrs'],
                            hp, ls)
         torch.cuda.synchronize()
     a, b = fresh(), fresh()
-    ls = torch.tensor([1024.0, 0.0, 0.0, 0.0], device=DEV)
+    ls = dev(torch.tensor([1024.0, 0.0, 0.0, 0.0]))
     scales = []
     for it in range(3):
         S = float(ls[0]); scales.append(S)
@@ -1590,10 +1604,10 @@ def test_clip_adam_loss_scaling(ops):
     run(a, G.clone(), None); run(b, G * float(ls[0]), ls)
     assert torch.equal(a['params'], b['params']) and ls.tolist() == [512.0, 1.0, 2.0, 0.0] and int(b['step']) == 4
     # S never grows past scale_max, never drops below 1
-    ls = torch.tensor([4096.0, 1.0, 0.0, 0.0], device=DEV)
+    ls = dev(torch.tensor([4096.0, 1.0, 0.0, 0.0]))
     run(b, G * 4096.0, ls)
     assert float(ls[0]) == 4096.0
-    ls = torch.tensor([1.0, 0.0, 0.0, 0.0], device=DEV)
+    ls = dev(torch.tensor([1.0, 0.0, 0.0, 0.0]))
     bad = G.clone(); bad[0] = float('inf')
     run(b, bad, ls)
     assert float(ls[0]) == 1.0 and float(ls[3]) == 1.0
@@ -1621,11 +1635,11 @@ def test_clip_adam_many_workgroups(ops):
                         grad_scale=1.0, scale_growth_interval=0, scale_max=0.0)
     res = []
     for tab in tabs:
-        params, m, v = p0.clone(), torch.zeros_like(p0), torch.zeros_like(p0)
-        part = torch.empty(tab.nblk, device=DEV); norm2 = torch.empty(tab.nseg, device=DEV)
-        step = torch.zeros(1, dtype=torch.int32, device=DEV); adam_t = torch.zeros(1, dtype=torch.int32, device=DEV)
-        lrs = torch.zeros(2, device=DEV)
-        ls = torch.tensor([8.0, 0.0, 0.0, 0.0], device=DEV)
+        params, m, v = dev(p0), guarded.out(p0.shape, p0.dtype, DEV, fill=0), guarded.out(p0.shape, p0.dtype, DEV, fill=0)
+        part = guarded.out((tab.nblk,), torch.float32, DEV); norm2 = guarded.out((tab.nseg,), torch.float32, DEV)
+        step = guarded.out((1,), torch.int32, DEV, fill=0); adam_t = guarded.out((1,), torch.int32, DEV, fill=0)
+        lrs = guarded.out((2,), torch.float32, DEV, fill=0)
+        ls = dev(torch.tensor([8.0, 0.0, 0.0, 0.0]))
         for it in range(4):
             ops.clip_adam_step(params, G * 8.0 * (1.0 + it), m, v, tab, part, norm2, step, adam_t, lrs, hp, ls)
             torch.cuda.synchronize()
@@ -1652,9 +1666,9 @@ def test_perceptual_finalize_loss_scale(ops):
     nel = torch.tensor([1000.0, 5000.0, 64.0], device=DEV)
     wd = torch.tensor([0.25], device=DEV)
     outs = []
-    for ls in (None, torch.tensor([256.0, 0, 0, 0], device=DEV)):
-        agg = torch.tensor([100.0, 1.6, 2.3], device=DEV)
-        out = torch.zeros(3 * nfeat + 3, device=DEV)
+    for ls in (None, dev(torch.tensor([256.0, 0, 0, 0]))):
+        agg = dev(torch.tensor([100.0, 1.6, 2.3]))
+        out = guarded.out((3 * nfeat + 3,), torch.float32, DEV, fill=0)
         ops.perceptual_finalize(part, nfeat, nel, agg, True, wd, out, False, ops.LOSS_PERCEPTUAL, ls)
         torch.cuda.synchronize()
         outs.append(out.cpu())
@@ -1674,12 +1688,12 @@ def test_clip_adadelta_adagrad(ops, optim):
     P = {('t%d/w' % i if wds[i] else 't%d/b' % i): torch.randn(n, generator=g) * 0.3 for i, n in enumerate(sizes)}
     G = {k: torch.randn(v.shape, generator=g) * (3.0 if i % 2 == 0 else 1e-3) for i, (k, v) in enumerate(P.items())}
     flat = lambda d: torch.cat([v.reshape(-1) for v in d.values()]).to(DEV)
-    params = flat(P)
-    m = torch.zeros_like(params)
-    v = torch.full_like(params, 0.1) if optim == 'adagrad' else torch.zeros_like(params)
-    part = torch.empty(tab.nblk, device=DEV); norm2 = torch.empty(tab.nseg, device=DEV)
-    step = torch.zeros(1, dtype=torch.int32, device=DEV); adam_t = torch.zeros(1, dtype=torch.int32, device=DEV)
-    lrs = torch.zeros(2, device=DEV)
+    params = dev(flat(P))
+    m = guarded.out(params.shape, params.dtype, DEV, fill=0)
+    v = guarded.out(params.shape, params.dtype, DEV, fill=0.1) if optim == 'adagrad' else guarded.out(params.shape, params.dtype, DEV, fill=0)
+    part = guarded.out((tab.nblk,), torch.float32, DEV); norm2 = guarded.out((tab.nseg,), torch.float32, DEV)
+    step = guarded.out((1,), torch.int32, DEV, fill=0); adam_t = guarded.out((1,), torch.int32, DEV, fill=0)
+    lrs = guarded.out((2,), torch.float32, DEV, fill=0)
     hp = ops.OptHParams(lr_start=1e-2, lr_decay=0.95, lr_step=100000, lr_multiple=1.0, beta1=0.95 if optim == 'adadelta' else 0.9,
                         beta2=0.999, eps=1e-6 if optim == 'adadelta' else 1e-8, clip=1.0, grad_scale=0.5, optim=L.OPTIMIZERS[optim])
     opt = {'m': {k: torch.zeros_like(x) for k, x in P.items()}, 'v': {k: torch.zeros_like(x) for k, x in P.items()}} \
@@ -1698,7 +1712,7 @@ def test_clip_adadelta_adagrad(ops, optim):
 
 def test_graph_capture_replay(ops):
     x = torch.rand(4, 4, 4, 3, device=DEV) * 255
-    dst = torch.zeros(4, 4, 4, 8, dtype=torch.bfloat16, device=DEV)
+    dst = guarded.out((4, 4, 4, 8), torch.bfloat16, DEV, fill=0)
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
         g = ops.Graph()
@@ -1724,11 +1738,11 @@ def test_masked_sse_fused_with_maxpool(ops, dt):
     b = rnd((B, s, s, c), 302, 1.0, dt).to(DEV).contiguous()
     mask = torch.rand(B, S, S, device=DEV)
     for mk in (mask, None):
-        p1 = torch.zeros(L.SSE_BLOCKS, device=DEV); p2 = torch.zeros(L.SSE_BLOCKS, device=DEV)
-        pa = torch.empty(B, s // 2, s // 2, c, dtype=dt, device=DEV); pb = torch.empty_like(pa)
+        p1 = guarded.out((L.SSE_BLOCKS,), torch.float32, DEV, fill=0); p2 = guarded.out((L.SSE_BLOCKS,), torch.float32, DEV, fill=0)
+        pa = guarded.out((B, s // 2, s // 2, c), dt, DEV); pb = guarded.out(pa.shape, pa.dtype, DEV)
         ops.masked_sse_pool(a, b, B, s, c, mk, S, p1, pa, pb)
         ops.masked_sse(a, b, B, s, c, mk, S, p2)
-        ra = torch.empty_like(pa); rb = torch.empty_like(pb)
+        ra = guarded.out(pa.shape, pa.dtype, DEV); rb = guarded.out(pb.shape, pb.dtype, DEV)
         ops.maxpool2_fwd(a, ra, B, s, s, c); ops.maxpool2_fwd(b, rb, B, s, s, c)
         torch.cuda.synchronize()
         assert torch.equal(pa, ra) and torch.equal(pb, rb)
@@ -1749,10 +1763,10 @@ def test_unpool_fused_with_tap_grad(ops):
     mask = torch.rand(B, S, S, device=DEV)
     coef = torch.tensor([0.0, 0.37, 0.0, 0.0, 0.0, 0.0], device=DEV)
     for mk in (mask, None):
-        ref = torch.full((B, s, s, c), float('nan'), dtype=dt, device=DEV)
+        ref = guarded.out((B, s, s, c), dt, DEV)
         ops.maxpool2_bwd(ap, dpool, ref, B, s, s, c, 0)
         ops.tap_grad(ref, True, ap, ag, B, s, c, mk, S, coef, 1, True)
-        got = torch.full((B, s, s, c), float('nan'), dtype=dt, device=DEV)
+        got = guarded.out((B, s, s, c), dt, DEV)
         ops.unpool_tap_grad(got, dpool, ap, ag, B, s, c, mk, S, coef, 1)
         torch.cuda.synchronize()
         assert torch.equal(got, ref)
@@ -1763,18 +1777,18 @@ def test_conv_group_equals_sequential(ops, H, ci, co):
     """imm_conv2d_group (stride-2 dgrad parity classes in one launch) == the four launches, bit for bit."""
     B, k, dt = 8, 3, torch.bfloat16
     w = rnd((k, k, ci, co), 401, 0.05)
-    dy = rnd((B, H // 2, H // 2, co), 402).to(DEV).contiguous()
+    dy = dev(rnd((B, H // 2, H // 2, co), 402))
     classes = ops.dgrad_s2_class_descs(B, H, H, ci, ci, co, co, k)
     rows = ops.round_up(ci, 128)
     wts = []
     for d, mode in classes:
-        wt = torch.zeros(rows, d.kpad, dtype=dt, device=DEV)
+        wt = guarded.out((rows, d.kpad), dt, DEV, fill=0)
         ops.pack_weights(w.float().to(DEV).contiguous(), wt, mode, k, k, ci, co, co, rows, d.kpad)
         wts.append(wt)
-    ref = torch.full((B, H, H, ci), float('nan'), dtype=dt, device=DEV)
+    ref = guarded.out((B, H, H, ci), dt, DEV)
     for (d, _m), wt in zip(classes, wts):
         ops.conv2d(d, dy, wt, None, ref)
-    got = torch.full((B, H, H, ci), float('nan'), dtype=dt, device=DEV)
+    got = guarded.out((B, H, H, ci), dt, DEV)
     grp = ops.ConvGroup([d for d, _m in classes], wts)
     ops.conv2d_group(grp, dy, got)
     torch.cuda.synchronize()
@@ -1785,7 +1799,7 @@ def test_conv_group_equals_sequential(ops, H, ci, co):
 def test_cost_ema_and_activation_rms(ops):
     """Round 5: the reference's device-side summaries.  imm_cost_ema against oracle.cost_ema_update (base_model.py:52-60, the biased TF-1.10
     moving averages of three costs over several steps); imm_rms16 against sqrt(mean(z^2)) (selfsup/vgg16.py:232-234), bf16 and f16."""
-    st = torch.zeros(4, device=DEV)
+    st = guarded.out((4,), torch.float32, DEV, fill=0)
     ref = [0.0, 0.0, 0.0, 0.0]
     g = torch.Generator().manual_seed(3)
     for it in range(6):
@@ -1797,7 +1811,7 @@ def test_cost_ema_and_activation_rms(ops):
     assert float(got[3]) == 6.0
     np.testing.assert_allclose(got[:3].numpy(), ref[:3], rtol=1e-5)
     np.testing.assert_allclose(got[:3].numpy(), avg, rtol=1e-5)
-    part, out = torch.zeros(1024, device=DEV), torch.zeros(1, device=DEV)
+    part, out = guarded.out((1024,), torch.float32, DEV, fill=0), guarded.out((1,), torch.float32, DEV, fill=0)
     for dt in (torch.bfloat16, torch.float16):
         for shape in ((2, 16, 16, 64), (64, 128, 128, 64), (3, 5, 7, 8)):
             x = rnd(shape, 11, 2.0, dt).to(DEV)
@@ -1812,7 +1826,7 @@ def test_upload_and_download_through_pinned_memory(ops):
     stream-synchronised, and an upload is read back (ops.upload / ops.download; DESIGN.md §7: a pageable 2.4 / 2.9 MB source freed
     right after `copy_` was what made one of eight co-resident ranks start from other weights about once in 100 constructions)."""
     x = np.random.default_rng(0).standard_normal((3, 3, 320, 256)).astype(np.float32)      # 2.9 MB: the size class that was torn
-    d = torch.full(x.shape, float('nan'), device=DEV)
+    d = guarded.out(x.shape, torch.float32, DEV)
     ops.upload(d, x, 'x')
     del x
     ref = np.random.default_rng(0).standard_normal((3, 3, 320, 256)).astype(np.float32)
@@ -1820,11 +1834,11 @@ def test_upload_and_download_through_pinned_memory(ops):
     assert not back.is_cuda and not back.is_pinned() and torch.equal(back, torch.from_numpy(ref))
     # layout and dtype conversion happen on the host side of the staging buffer
     src = torch.arange(35.).reshape(7, 5).t()                                               # non-contiguous
-    d16 = torch.empty(5, 7, dtype=torch.bfloat16, device=DEV)
+    d16 = guarded.out((5, 7), torch.bfloat16, DEV)
     ops.upload(d16, src)
     assert torch.equal(d16.float().cpu(), src.contiguous())
     # a flat destination takes any source of the same size; a device source is a plain stream-ordered copy
-    flat = torch.empty(35, device=DEV)
+    flat = guarded.out((35,), torch.float32, DEV)
     ops.upload(flat, src)
     assert torch.equal(flat.cpu(), src.reshape(-1))
     ops.upload(flat, (flat * 2).reshape(5, 7))
@@ -1843,7 +1857,7 @@ def test_pinned_stager_and_to_device_pinned(ops):
     ops.to_device_pinned.  A source overwritten right after the call (what a training loop's generator does) must not reach the
     device; many consecutive steps keep the right bytes; buffers are reused, not re-allocated."""
     st = ops.PinnedStager()
-    dst = torch.empty(32, 128, 128, 3, device=DEV)                                          # 6.3 MB: a real input batch
+    dst = guarded.out((32, 128, 128, 3), torch.float32, DEV)                                          # 6.3 MB: a real input batch
     g = torch.Generator().manual_seed(5)
     for it in range(6):
         src = torch.rand(32, 128, 128, 3, generator=g)
@@ -1856,7 +1870,7 @@ def test_pinned_stager_and_to_device_pinned(ops):
             assert [b.data_ptr() for b in st._slots['image']['bufs']] == bufs
         assert torch.equal(dst.cpu(), want), it
     # dtype / layout conversion on the host side, device sources as plain stream-ordered copies
-    d16 = torch.empty(5, 7, dtype=torch.bfloat16, device=DEV)
+    d16 = guarded.out((5, 7), torch.bfloat16, DEV)
     srcT = torch.arange(35.).reshape(7, 5).t()
     st.copy(d16, srcT, 'x')
     assert torch.equal(d16.float().cpu(), srcT.contiguous())
