@@ -15,6 +15,11 @@ convolution in front of it on the host in f64 (inference.fold_batch_norm), filte
 The joint buffer [n, 16, 16, Cj] is allocated zeroed; its channels [8f + K, Cj) (Cj = round_up(8f + K, 64), the padding the
 deep-K kernels need) are never written.  Eval-mode batch norm is per sample, so a zero-padded bucket tail changes no result.
 Nothing is written to the model: parameters, moving statistics, loss normalisers and step counters stay bit-identical.
+
+repose() puts the generated face back where it came from: photos and face boxes in, the same photos out as u8 with every box's face
+re-posed.  Per bucket the boxes are cut from the packed u8 photos (imm_resize_crop_u8 box mode), run through the appearance and render
+programs, and one imm_compose_u8 launch resamples the f32 predictions to the boxes' sizes and blends them over a device copy of the
+photos with a linear edge ramp (include/imm_compose.h): the f32 tiles never leave the prediction buffer.
 """
 import numpy as np
 import torch
@@ -22,9 +27,10 @@ import torch
 from . import _lib as L
 from . import ops
 from .engine import encoder_spec, n_renderer_out, render_sizes, renderer_spec, trainable_spec
-from .inference import (LandmarkDetector, _Launch, alloc_encoder_weights, as_image_batch, bucket_sizes, check_limits,
-                        encoder_act_elems, fold_batch_norm, folded_encoder_program, pack_folded_encoder, plan_buckets,
+from .inference import (LandmarkDetector, _Launch, alloc_encoder_weights, as_image_batch, bucket_sizes, check_limits, decode_u8,
+                        encoder_act_elems, fold_batch_norm, folded_encoder_program, pack_folded_encoder, pack_u8, plan_buckets,
                         read_variables, stage_u8)
+from .keypoints import check_boxes
 
 IMAGE_SCOPE = 'model/image_encoder'
 RENDER_SCOPE = 'model/renderer'
@@ -49,6 +55,64 @@ def plan_pairs(n_a, n_p, max_batch):
         idx = np.arange(start, start + count)
         out.append((start, count, bucket, idx // n_p, idx % n_p))
     return out
+
+
+NEEDS_U8 = 'boxes need the images as a list of u8 arrays (a tensor batch is already S x S)'
+
+
+def compose_links(rows):
+    """Box rows int [n, 5] (image, y0, x0, y1, x1) of ONE imm_compose_u8 launch -> int32 [n, 2]: per row (the previous row of the
+    same photo, the next one), -1 for none.  The kernel's threads find a pixel's first covering row along the first column and apply
+    the later rows along the second."""
+    rows = np.asarray(rows).reshape(-1, 5)
+    links = np.full((len(rows), 2), -1, dtype=np.int32)
+    last = {}
+    for b, img in enumerate(rows[:, 0].tolist()):
+        if img in last:
+            links[b, 0] = last[img]
+            links[last[img], 1] = b
+        last[img] = b
+    return links
+
+
+def check_feather(feather):
+    f = float(feather)
+    if not 0.0 <= f <= 0.5:                          # NaN fails both comparisons
+        raise ValueError('feather must lie in [0, 0.5] (the share of the box side the ramp takes), got %r' % (feather,))
+    return f
+
+
+def compose_inv_ramp(rows, feather):
+    """f32 [n, 2]: per row the reciprocals of the edge ramp's widths feather * ih and feather * iw in pixels, and 2 where that width
+    is <= 0.5 pixels (every weight is then 1: a hard paste; feather == 0 always is)."""
+    f = check_feather(feather)
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, 5)
+    ramp = f * (rows[:, 3:5] - rows[:, 1:3]).astype(np.float64)
+    return np.where(ramp <= 0.5, 2.0, 1.0 / np.maximum(ramp, 0.5)).astype(np.float32)
+
+
+def plan_repose(photos, poses, boxes, pose_boxes, feather, K):
+    """repose()'s arguments checked on the host, before anything reaches the device: (photos as decoded u8 arrays, box rows int32
+    [n, 5], poses, feather).  poses comes back as ('landmarks', f32 tensor [n or 1, K, 2]) or ('photos', decoded u8 arrays, pose_boxes)."""
+    feather = check_feather(feather)
+    if not isinstance(photos, (list, tuple)):
+        raise ValueError(NEEDS_U8)
+    photos = decode_u8(photos)
+    rows = check_boxes([(0, 0, a.shape[0], a.shape[1]) for a in photos] if boxes is None else boxes, len(photos))
+    n = len(rows)
+    if isinstance(poses, (list, tuple)) and len(poses) and not np.isscalar(poses[0]) and np.asarray(poses[0]).dtype == np.uint8:
+        pose_photos = decode_u8(poses)
+        n_p = len(pose_photos) if pose_boxes is None else len(check_boxes(pose_boxes, len(pose_photos)))
+        if n_p not in (n, 1):
+            raise ValueError('%d poses for %d faces: give one per face, or one for all' % (n_p, n))
+        return photos, rows, ('photos', pose_photos, pose_boxes), feather
+    if pose_boxes is not None:
+        raise ValueError('pose_boxes need the poses as a list of u8 photos')
+    lm = torch.as_tensor(poses)
+    if lm.dim() != 3 or tuple(lm.shape[1:]) != (K, 2) or lm.shape[0] not in (n, 1):
+        raise ValueError('poses must be landmarks [%d, %d, 2] or [1, %d, 2] (or a list of u8 pose photos), got %s' % (
+            n, K, K, tuple(lm.shape)))
+    return photos, rows, ('landmarks', lm.float()), feather
 
 
 def _split(names, get):
@@ -195,7 +259,11 @@ class ImageGenerator(object):
     def program(self, stage, batch):
         """The launches of one bucket of a stage: [_Launch(tag, name, family, fn)].  stage 'appearance': image rows
         -> joint channels [0, 8f); 'render': landmark rows -> Gaussian maps in the joint buffer -> renderer -> f32 prediction.
-        tag: 'conv' | 'pack_image' | 'resize_ac' | 'gauss' | 'upsample'; family: the conv kernel family (imm_conv2d_variant's)."""
+        tag: 'conv' | 'pack_image' | 'resize_ac' | 'gauss' | 'upsample'; family: the conv kernel family (imm_conv2d_variant's).
+        stage 'compose': one bucket of repose(): the appearance launches, the render launches, then 'compose' (imm_compose_u8 over the
+        bucket's predictions; issued by repose() with the call's photos and boxes, like the detector's 'resize')."""
+        if stage == 'compose':
+            return self.program('appearance', batch) + self.program('render', batch) + [_Launch('compose', 'compose_u8', 'compose', None)]
         self._ensure_capacity(batch)
         B, dt, C8, Cj = int(batch), self.dt, self.C8, self.Cj
         joint = self._joint[:B]
@@ -209,7 +277,7 @@ class ImageGenerator(object):
                     x, joint, B, H, H, 16, 16, C8, ld, Cj)))
             return prog
         if stage != 'render':
-            raise ValueError('stage must be appearance or render, got %r' % (stage,))
+            raise ValueError('stage must be appearance, render or compose, got %r' % (stage,))
         mu, mode = self._mu[:B], self.cfg.gauss_mode
         prog = [_Launch('gauss', 'gaussian_maps', 'gauss_render', lambda: ops.gauss_render_fwd(
             mu, B, self.K, self.inv_std, 16, joint[..., C8:], Cj, dt, mode))]
@@ -257,10 +325,28 @@ class ImageGenerator(object):
         g.launch()
 
     # ------------------------------------------------------------------------------------------------------------------------
-    def _encode(self, images, u8, start, count, bucket):
-        """Appearance stage of images [start, start + count) into joint rows [0, count) (bucket `bucket`, tail zero images)."""
+    def _rows(self, images, boxes):
+        """(images, u8, rows): detect()'s input forms, and with boxes (u8 photos only; keypoints.check_boxes) the photos decoded and
+        the box rows int32 [n, 5] that take the images' place; rows is None without boxes."""
+        images, u8 = as_image_batch(images, self.S)
+        if boxes is None:
+            return images, u8, None
+        if not u8:
+            raise ValueError(NEEDS_U8)
+        images = decode_u8(images)
+        return images, u8, check_boxes(boxes, len(images))
+
+    def _encode(self, images, u8, start, count, bucket, rows=None):
+        """Appearance stage of images [start, start + count) into joint rows [0, count) (bucket `bucket`, tail zero images).  With
+        rows (int32 [n, 5] boxes over u8 photos) the rows [start, start + count) take the images' place, cut and resized on the GPU."""
         self._ensure_capacity(bucket)
-        if u8:
+        if rows is not None:
+            # the photos this bucket's boxes cut from, packed once each; box rows renumbered into that list (as keypoints() does)
+            part = rows[start:start + count]
+            used, idx = np.unique(part[:, 0], return_inverse=True)
+            local = np.concatenate([idx.reshape(-1, 1).astype(np.int32), part[:, 1:]], axis=1)
+            stage_u8([images[i] for i in used], self._img[:count], self.S, self.dev, boxes=local)
+        elif u8:
             stage_u8(images[start:start + count], self._img[:count], self.S, self.dev)
         else:
             self._stager.copy(self._img[:count], images[start:start + count], ('images', count))
@@ -274,18 +360,19 @@ class ImageGenerator(object):
             raise ValueError('landmarks must be [%d, %d, 2], got %s' % (n, self.K, tuple(lm.shape)))
         return lm.to(device=self.dev, dtype=torch.float32)
 
-    def render(self, images, landmarks):
+    def render(self, images, landmarks, boxes=None):
         """images (detect()'s forms, N of them) rendered at landmarks f32 [N, K, 2] ((y, x) in [-1, 1]): f32 [N, S, S, 3],
-        unclipped, in the 0..255 scale of future_im_pred."""
-        images, u8 = as_image_batch(images, self.S)
-        N = len(images)
+        unclipped, in the 0..255 scale of future_im_pred.  boxes (as keypoints() takes them, u8 photos only): the N rows are the
+        boxes, cut from their photos with zero padding and resized to S x S on the GPU."""
+        images, u8, rows = self._rows(images, boxes)
+        N = len(images) if rows is None else len(rows)
         cur = torch.cuda.current_stream(self.dev)
         lm = self._landmarks(landmarks, N)
         out = torch.empty(N, self.S, self.S, 3, device=self.dev)
         self.stream.wait_stream(cur)
         with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
             for start, count, bucket in plan_buckets(N, self.max_batch):
-                self._encode(images, u8, start, count, bucket)
+                self._encode(images, u8, start, count, bucket, rows)
                 self._mu[:count].copy_(lm[start:start + count])
                 if count < bucket:
                     self._mu[count:bucket].zero_()
@@ -294,23 +381,32 @@ class ImageGenerator(object):
         cur.wait_stream(self.stream)
         return out
 
-    def reconstruct(self, images, future_images):
+    def reconstruct(self, images, future_images, boxes=None, pose_boxes=None):
         """future_images rendered from the appearance of images (pair i = (images[i], future_images[i])): f32 [N, S, S, 3], the
-        eval path's future_im_pred."""
-        images, _ = as_image_batch(images, self.S)
-        future_images, _ = as_image_batch(future_images, self.S)
-        if len(images) != len(future_images):
-            raise ValueError('images and future_images differ in number: %d != %d' % (len(images), len(future_images)))
-        return self.render(images, self.detector.detect(future_images))
+        eval path's future_im_pred.  boxes / pose_boxes (u8 photos only): the rows of either side are its boxes (row i of one pairs
+        with row i of the other)."""
+        images, _, rows = self._rows(images, boxes)
+        future_images, _, prows = self._rows(future_images, pose_boxes)
+        n, n_f = (len(images) if rows is None else len(rows)), (len(future_images) if prows is None else len(prows))
+        if n != n_f:
+            raise ValueError('images and future_images differ in number: %d != %d' % (n, n_f))
+        mu = self.detector.detect(future_images) if prows is None else self.detector.landmarks(future_images, pose_boxes)
+        return self.render(images, mu, boxes=boxes)
 
-    def transfer(self, appearance, poses, return_landmarks=False):
+    def transfer(self, appearance, poses, return_landmarks=False, boxes=None, pose_boxes=None):
         """Every appearance image rendered at every pose image's landmarks: f32 [A, P, S, S, 3], [a, p] = reconstruct(appearance[a],
         poses[p]).  Each image is encoded once (the appearance stage per A bucket, the detector per P bucket); the A x P pairs are
         rendered in buckets, their joint rows gathered from the stored features.  return_landmarks=True: (images, the poses'
-        landmarks f32 [P, K, 2] it rendered at)."""
-        appearance, u8 = as_image_batch(appearance, self.S)
-        n_a = len(appearance)
-        mu_p = self.detector.detect(poses)
+        landmarks f32 [P, K, 2] it rendered at).  boxes / pose_boxes (u8 photos only): the A appearance rows / the P pose rows are
+        the boxes of those photos."""
+        appearance, u8, rows = self._rows(appearance, boxes)
+        n_a = len(appearance) if rows is None else len(rows)
+        if pose_boxes is None:
+            mu_p = self.detector.detect(poses)
+        else:
+            if not isinstance(poses, (list, tuple)):
+                raise ValueError(NEEDS_U8)
+            mu_p = self.detector.landmarks(poses, pose_boxes)
         n_p = mu_p.shape[0]
         cur = torch.cuda.current_stream(self.dev)
         out = torch.empty(n_a * n_p, self.S, self.S, 3, device=self.dev)
@@ -318,7 +414,7 @@ class ImageGenerator(object):
         with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
             feats = torch.empty(n_a, 16, 16, self.C8, dtype=self.dt, device=self.dev)
             for start, count, bucket in plan_buckets(n_a, self.max_batch):
-                self._encode(appearance, u8, start, count, bucket)
+                self._encode(appearance, u8, start, count, bucket, rows)
                 feats[start:start + count].copy_(self._joint[:count, ..., :self.C8])
             for start, count, bucket, a_idx, p_idx in plan_pairs(n_a, n_p, self.max_batch):
                 self._ensure_capacity(bucket)
@@ -334,3 +430,56 @@ class ImageGenerator(object):
         cur.wait_stream(self.stream)
         out = out.view(n_a, n_p, self.S, self.S, 3)
         return (out, mu_p) if return_landmarks else out
+
+    def repose(self, photos, poses, boxes=None, pose_boxes=None, feather=0.125, return_faces=False):
+        """The photos with every box's face re-posed: a list of u8 device tensors [h_i, w_i, 3], one per photo, views of one packed
+        buffer.  photos: a list of u8 arrays of any sizes (decode_u8's forms).  boxes: as keypoints() takes them, n rows; by default
+        one whole-photo box per photo.  poses: landmarks f32 [n, K, 2] (or [1, K, 2] for all rows), or a list of u8 pose photos whose
+        landmarks are detector.landmarks(poses, pose_boxes), n rows or 1.  feather in [0, 0.5]: the share of each box side over which
+        the paste fades into the photo (0: a hard paste).  return_faces=True: (photos, faces f32 [n, S, S, 3], landmarks f32 [n, K, 2]).
+        Every row's crop is cut from the ORIGINAL pixels and the faces are composited into a device copy, in row order (a later box
+        blends over an earlier paste, imm_compose_u8's rule): an overlapping later box never sees an earlier paste in its crop.  A
+        face is resampled bilinearly, without a pre-filter: a box much smaller than S x S point-samples its face."""
+        S = self.S
+        photos, rows, pose, feather = plan_repose(photos, poses, boxes, pose_boxes, feather, self.K)
+        n = len(rows)
+        if pose[0] == 'photos':
+            lm = self.detector.landmarks(pose[1], pose[2])
+        else:
+            lm = pose[1].to(device=self.dev, dtype=torch.float32)
+        if lm.shape[0] != n:
+            lm = lm.expand(n, self.K, 2)
+        buckets = plan_buckets(n, self.max_batch)
+        links = np.concatenate([compose_links(rows[start:start + count]) for start, count, _b in buckets])
+        area = (rows[:, 3] - rows[:, 1]).astype(np.int64) * (rows[:, 4] - rows[:, 2]).astype(np.int64)
+        cur = torch.cuda.current_stream(self.dev)
+        with torch.cuda.device(self.dev):
+            src, offs_d, hw_d, boxes_d = pack_u8(photos, self.dev, rows)            # all photos, once per call
+            canvas = src.clone()
+            links_d = ops.to_device_pinned(links, self.dev)
+            ramp_d = ops.to_device_pinned(compose_inv_ramp(rows, feather), self.dev)
+            faces = torch.empty(n, S, S, 3, device=self.dev) if return_faces else None
+        self.stream.wait_stream(cur)
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            for start, count, bucket in buckets:
+                self._ensure_capacity(bucket)
+                part = slice(start, start + count)
+                ops.resize_crop_u8(src, offs_d, hw_d, 3, (S, S), (0, 0), (S, S), self._img[:count], boxes=boxes_d[part])
+                self._mu[:count].copy_(lm[part])
+                if count < bucket:
+                    self._img[count:bucket].zero_()
+                    self._mu[count:bucket].zero_()
+                self._run('appearance', bucket)
+                self._run('render', bucket)
+                ops.compose_u8(canvas, offs_d, hw_d, boxes_d[part], links_d[part], ramp_d[part], self._pred[:count],
+                               int(min(area[part].max(), 2 ** 31 - 1)))
+                if return_faces:
+                    faces[part].copy_(self._pred[:count, ..., :3])
+        cur.wait_stream(self.stream)
+        for t in (src, offs_d, hw_d, boxes_d, links_d, ramp_d):
+            t.record_stream(self.stream)
+        offs = [0]
+        for a in photos[:-1]:
+            offs.append(offs[-1] + ((a.size + 15) & ~15))
+        out = [canvas[o:o + a.size].view(a.shape) for o, a in zip(offs, photos)]
+        return (out, faces, lm.contiguous()) if return_faces else out

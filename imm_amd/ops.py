@@ -727,6 +727,29 @@ def align_warp_u8(src, offsets, hw, boxes, geom, coef, basis_t, image_size, dst,
          n, int(image_size), So, _p(dst), dst.stride(2) if ld_dst is None else ld_dst, _s())
 
 
+def compose_u8(photos, offsets, hw, boxes, links, inv_ramp, faces, max_box_pixels):
+    """The packed u8 photos (as resize_crop_u8 reads them) composited in place: row b's face, faces[b] f32 [S, S, >= 3] (a view of
+    any pixel stride, channels 0..2 read), resampled to box b, blended with the edge ramp inv_ramp f32 [n, 2] and rounded to u8, in
+    row order (include/imm_compose.h: imm_compose_u8).  boxes i32 [n, 5], links i32 [n, 2] (generation.compose_links of THESE rows);
+    max_box_pixels: the largest box area of the rows."""
+    n = boxes.shape[0]
+    if photos.dtype != torch.uint8 or photos.dim() != 1 or not photos.is_contiguous():
+        raise ValueError('photos must be the flat contiguous u8 buffer, got %s %s' % (photos.dtype, tuple(photos.shape)))
+    if boxes.dtype != torch.int32 or tuple(boxes.shape) != (n, 5) or not boxes.is_contiguous():
+        raise ValueError('boxes must be contiguous int32 [n, 5], got %s %s' % (boxes.dtype, tuple(boxes.shape)))
+    if links.dtype != torch.int32 or tuple(links.shape) != (n, 2) or not links.is_contiguous():
+        raise ValueError('links must be contiguous int32 [n, 2], got %s %s' % (links.dtype, tuple(links.shape)))
+    if inv_ramp.dtype != torch.float32 or tuple(inv_ramp.shape) != (n, 2) or not inv_ramp.is_contiguous():
+        raise ValueError('inv_ramp must be contiguous f32 [n, 2], got %s %s' % (inv_ramp.dtype, tuple(inv_ramp.shape)))
+    S, ld = faces.shape[1], faces.stride(2)
+    if (faces.dtype != torch.float32 or faces.dim() != 4 or faces.shape[0] != n or faces.shape[2] != S or faces.shape[3] < 3 or
+            faces.stride(3) != 1 or faces.stride(1) != S * ld or faces.stride(0) != S * S * ld):
+        raise ValueError('faces must be f32 [n, S, S, >= 3] with dense pixels of one stride, got %s %s strides %s' % (
+            faces.dtype, tuple(faces.shape), tuple(faces.stride())))
+    call('imm_compose_u8', _p(photos), _p(offsets), _p(hw), int(hw.shape[0]), _p(boxes), _p(links), _p(inv_ramp), _p(faces), int(ld), n,
+         int(S), int(max_box_pixels), _s())
+
+
 def masked_sse_pool(a, b, batch, s, c, mask, S, partial, pool_a, pool_b):
     call('imm_masked_sse_pool', _p(a), _p(b), dtype_enum(a.dtype), batch, s, c, _p(mask), S, _p(partial), _p(pool_a), _p(pool_b), _s())
 
