@@ -23,7 +23,10 @@ same place of the photo):
     source photo                       s = (y0 + c_y sy, x0 + c_x sx),  geom (y0, x0, sy, sx) = keypoints.box_geometry
     value                              bilinear at s, taps floor(s) and floor(s) + 1, zeros outside the photo, f32 in [0, 255]
 
-Unweighted fits only; no reflection handling; no forward TPS point map (Alignment.to_aligned serves similarity and affine)."""
+LandmarkDetector.unalign carries pixels the other way: aligned faces (edited or generated in the canonical frame) are pasted back into
+their u8 photos through the inverse of the similarity or affine map (imm_unalign_maps, imm_unalign_u8; include/imm_unalign.h).
+
+Unweighted fits only; no reflection handling; no forward TPS point map (Alignment.to_aligned and unalign serve similarity and affine)."""
 import numpy as np
 
 MODELS = ('similarity', 'affine', 'tps')
@@ -208,14 +211,23 @@ class LandmarkTemplate(object):
         return tpl
 
 
+def unalign_inv_ramp(feather, out_size):
+    """The reciprocal of the paste's edge ramp, feather * So aligned pixels wide, as the f32 value imm_unalign_u8 takes; 2 where that
+    width is <= 0.5 pixels (every weight is then 1: a hard paste; feather == 0 always is).  feather: checked by the caller."""
+    ramp = float(feather) * int(out_size)
+    return 2.0 if ramp <= 0.5 else float(np.float32(1.0 / ramp))
+
+
 class Alignment(object):
     """What align(return_transform=True) returns next to the images: coef f32 [n, m3, 2] (the backward maps), geom f32 [n, 4]
     ((y0, x0, sy, sx) per row), mu f32 [n, K, 2] (tensors on the detector's device, or arrays), the model, lam, the template and the
-    output size."""
+    output size; for u8 photo input also rows int32 [n, 5], the box rows (image, y0, x0, y1, x1) the faces were cut from (a host
+    array; None for a tensor batch), which LandmarkDetector.unalign needs to find each row's photo."""
 
-    def __init__(self, coef, geom, mu, model, lam, template, out_size):
+    def __init__(self, coef, geom, mu, model, lam, template, out_size, rows=None):
         self.coef, self.geom, self.mu = coef, geom, mu
         self.model, self.lam, self.template, self.out_size = model, float(lam), template, int(out_size)
+        self.rows = None if rows is None else np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, 5)
 
     @staticmethod
     def _host(a):

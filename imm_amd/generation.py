@@ -20,6 +20,9 @@ repose() puts the generated face back where it came from: photos and face boxes 
 re-posed.  Per bucket the boxes are cut from the packed u8 photos (imm_resize_crop_u8 box mode), run through the appearance and render
 programs, and one imm_compose_u8 launch resamples the f32 predictions to the boxes' sizes and blends them over a device copy of the
 photos with a linear edge ramp (include/imm_compose.h): the f32 tiles never leave the prediction buffer.
+With a template (repose(..., template=, model=)) the generator sees every face in the framing it was trained on instead of a raw box
+crop: the face is aligned to the template from the original pixels (LandmarkDetector.align at So = S), encoded, rendered at a pose given
+in the ALIGNED frame, and pasted back through the inverse of its alignment map (imm_unalign_maps, imm_unalign_u8; include/imm_unalign.h).
 """
 import numpy as np
 import torch
@@ -113,6 +116,17 @@ def plan_repose(photos, poses, boxes, pose_boxes, feather, K):
         raise ValueError('poses must be landmarks [%d, %d, 2] or [1, %d, 2] (or a list of u8 pose photos), got %s' % (
             n, K, K, tuple(lm.shape)))
     return photos, rows, ('landmarks', lm.float()), feather
+
+
+def check_repose_template(template, model, K, S):
+    """repose(template=)'s template and model checked on the host: the similarity and affine maps are inverted, the tps map is not."""
+    from . import alignment as AL
+    AL.check_model(model)
+    if model == 'tps':
+        raise NotImplementedError('repose with a template serves the similarity and affine models; the tps map is not inverted')
+    if not isinstance(template, AL.LandmarkTemplate):
+        raise ValueError('template must be an alignment.LandmarkTemplate, got %r' % (type(template).__name__,))
+    template.check(K, S)
 
 
 def _split(names, get):
@@ -431,7 +445,7 @@ class ImageGenerator(object):
         out = out.view(n_a, n_p, self.S, self.S, 3)
         return (out, mu_p) if return_landmarks else out
 
-    def repose(self, photos, poses, boxes=None, pose_boxes=None, feather=0.125, return_faces=False):
+    def repose(self, photos, poses, boxes=None, pose_boxes=None, feather=0.125, return_faces=False, template=None, model='similarity'):
         """The photos with every box's face re-posed: a list of u8 device tensors [h_i, w_i, 3], one per photo, views of one packed
         buffer.  photos: a list of u8 arrays of any sizes (decode_u8's forms).  boxes: as keypoints() takes them, n rows; by default
         one whole-photo box per photo.  poses: landmarks f32 [n, K, 2] (or [1, K, 2] for all rows), or a list of u8 pose photos whose
@@ -439,7 +453,15 @@ class ImageGenerator(object):
         the paste fades into the photo (0: a hard paste).  return_faces=True: (photos, faces f32 [n, S, S, 3], landmarks f32 [n, K, 2]).
         Every row's crop is cut from the ORIGINAL pixels and the faces are composited into a device copy, in row order (a later box
         blends over an earlier paste, imm_compose_u8's rule): an overlapping later box never sees an earlier paste in its crop.  A
-        face is resampled bilinearly, without a pre-filter: a box much smaller than S x S point-samples its face."""
+        face is resampled bilinearly, without a pre-filter: a box much smaller than S x S point-samples its face.
+        template (an alignment.LandmarkTemplate of this model's K and S) with model 'similarity' | 'affine': every face is first
+        aligned to the template from the original u8 pixels (detector.align at So = S), so the generator sees the framing it was
+        trained on; it is encoded, rendered at its pose and pasted back through the inverse of its alignment map (imm_unalign_u8),
+        feather being a share of the ALIGNED frame's side.  The poses are then landmarks in the aligned frame; pose photos give
+        detector.detect(detector.align(pose_photos, template, pose_boxes, model)).  'tps' raises NotImplementedError (the tps map is
+        not inverted).  return_faces=True returns the aligned-frame renders and those landmarks."""
+        if template is not None:
+            return self._repose_aligned(photos, poses, boxes, pose_boxes, feather, return_faces, template, model)
         S = self.S
         photos, rows, pose, feather = plan_repose(photos, poses, boxes, pose_boxes, feather, self.K)
         n = len(rows)
@@ -477,6 +499,58 @@ class ImageGenerator(object):
                     faces[part].copy_(self._pred[:count, ..., :3])
         cur.wait_stream(self.stream)
         for t in (src, offs_d, hw_d, boxes_d, links_d, ramp_d):
+            t.record_stream(self.stream)
+        offs = [0]
+        for a in photos[:-1]:
+            offs.append(offs[-1] + ((a.size + 15) & ~15))
+        out = [canvas[o:o + a.size].view(a.shape) for o, a in zip(offs, photos)]
+        return (out, faces, lm.contiguous()) if return_faces else out
+
+    def _repose_aligned(self, photos, poses, boxes, pose_boxes, feather, return_faces, template, model):
+        """repose() with a template: align -> encode -> render -> paste through the inverse map.  The photos are packed once: the
+        detector's align() reads that buffer, and since every face is aligned before the first paste the same buffer is pasted into."""
+        from . import alignment as AL
+        from .inference import unalign_grid_pixels
+        S, det = self.S, self.detector
+        check_repose_template(template, model, self.K, S)
+        photos, rows, pose, feather = plan_repose(photos, poses, boxes, pose_boxes, feather, self.K)
+        n = len(rows)
+        if pose[0] == 'photos':
+            lm = det.detect(det.align(pose[1], template, pose[2], model))
+        else:
+            lm = pose[1].to(device=self.dev, dtype=torch.float32)
+        if lm.shape[0] != n:
+            lm = lm.expand(n, self.K, 2)
+        buckets = plan_buckets(n, self.max_batch)
+        links = np.concatenate([compose_links(rows[start:start + count]) for start, count, _b in buckets])
+        cur = torch.cuda.current_stream(self.dev)
+        with torch.cuda.device(self.dev):
+            canvas, offs_d, hw_d, boxes_d = pack_u8(photos, self.dev, rows)         # all photos, once per call
+            links_d = ops.to_device_pinned(links, self.dev)
+            aligned, al = det.align(photos, template, rows, model, return_transform=True, _packed=(canvas, offs_d, hw_d, boxes_d))
+            fwd = torch.empty(n, 6, device=self.dev)
+            bbox = torch.empty(n, 4, dtype=torch.int32, device=self.dev)
+            ops.unalign_maps(al.coef, al.geom, boxes_d, hw_d, S, S, fwd, bbox)      # the coefficients never leave the device
+            faces = torch.empty(n, S, S, 3, device=self.dev) if return_faces else None
+        inv_ramp = AL.unalign_inv_ramp(feather, S)
+        self.stream.wait_stream(cur)
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            for start, count, bucket in buckets:
+                self._ensure_capacity(bucket)
+                part = slice(start, start + count)
+                self._img[:count].copy_(aligned[part])
+                self._mu[:count].copy_(lm[part])
+                if count < bucket:
+                    self._img[count:bucket].zero_()
+                    self._mu[count:bucket].zero_()
+                self._run('appearance', bucket)
+                self._run('render', bucket)
+                ops.unalign_u8(canvas, offs_d, hw_d, boxes_d[part], links_d[part], fwd[part], bbox[part], inv_ramp, self._pred[:count],
+                               unalign_grid_pixels(photos, rows[part]))
+                if return_faces:
+                    faces[part].copy_(self._pred[:count, ..., :3])
+        cur.wait_stream(self.stream)
+        for t in (canvas, offs_d, hw_d, boxes_d, links_d, aligned, fwd, bbox):
             t.record_stream(self.stream)
         offs = [0]
         for a in photos[:-1]:

@@ -258,6 +258,48 @@ def stage_u8(images, dst, S, device, boxes=None):
     return src, offs_d, hw_d, boxes_d
 
 
+UNALIGN_MAX_ROWS = 65535      # rows of one imm_unalign_u8 launch (its grid's y dimension)
+
+
+def plan_unalign(photos, aligned_shape, alignment, feather):
+    """unalign()'s arguments checked on the host, before anything reaches the device: (photos as decoded u8 arrays, the alignment's
+    box rows int32 [n, 5], n, So, feather)."""
+    from .generation import check_feather
+    if alignment.model == 'tps':
+        raise NotImplementedError('unalign serves the similarity and affine models; the tps map is not inverted')
+    feather = check_feather(feather)
+    rows = getattr(alignment, 'rows', None)
+    if rows is None:
+        raise ValueError('the alignment holds no box rows: unalign needs what align(u8 photos, ..., return_transform=True) returns')
+    if not isinstance(photos, (list, tuple)):
+        raise ValueError('unalign needs the photos as the list of u8 arrays align() was given')
+    photos = decode_u8(photos)
+    n, So = len(rows), int(alignment.out_size)
+    shape = tuple(int(v) for v in aligned_shape)
+    if len(shape) != 4 or shape[1:3] != (So, So) or shape[3] < 3:
+        raise ValueError('aligned must be [n, %d, %d, >= 3] (the alignment\'s out_size), got %s' % (So, So, shape))
+    if shape[0] != n or len(alignment.coef) != n or len(alignment.geom) != n:
+        raise ValueError('%d aligned faces, %d coefficient rows and %d geometry rows for the alignment\'s %d box rows' % (
+            shape[0], len(alignment.coef), len(alignment.geom), n))
+    if n == 0:
+        raise ValueError('the alignment holds no rows')
+    if tuple(np.shape(alignment.coef)[1:]) != (3, 2):
+        raise ValueError('coef must be [n, 3, 2], got %s' % (tuple(np.shape(alignment.coef)),))
+    if rows[:, 0].min() < 0 or rows[:, 0].max() >= len(photos):
+        raise ValueError('the alignment\'s rows name photos 0..%d, %d photos were given' % (int(rows[:, 0].max()), len(photos)))
+    return photos, rows, n, So, feather
+
+
+def unalign_grid_pixels(photos, rows):
+    """The max_pixels of an imm_unalign_u8 launch over these box rows, from what the host knows: twice the largest box (an aligned face
+    covers about its box; its bounding box, once rotated, up to twice that), at most the largest photo the rows name.  It sizes the
+    grid only: a larger bounding box is still pasted whole."""
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, 5)
+    box = int(((rows[:, 3] - rows[:, 1]) * (rows[:, 4] - rows[:, 2])).max())
+    photo = max(int(photos[i].shape[0]) * int(photos[i].shape[1]) for i in set(rows[:, 0].tolist()))
+    return int(max(1, min(2 * max(box, 1), photo, 2 ** 31 - 1)))
+
+
 class _Launch(object):
     __slots__ = ('tag', 'name', 'family', 'fn')
 
@@ -578,7 +620,7 @@ class LandmarkDetector(object):
         cur.wait_stream(self.stream)
         return mu_out
 
-    def align(self, images, template, boxes=None, model='similarity', lam=0.0, out_size=None, return_transform=False):
+    def align(self, images, template, boxes=None, model='similarity', lam=0.0, out_size=None, return_transform=False, _packed=None):
         """Every face warped so that its landmarks land on the template: f32 [n, So, So, 3] in [0, 255] on the detector's device, one
         row per box (per image without boxes); with return_transform=True also an alignment.Alignment (coef, geom, mu, to_source,
         to_aligned).  images, boxes: as keypoints() takes them.  template: an alignment.LandmarkTemplate of this detector's K and S.
@@ -586,7 +628,9 @@ class LandmarkDetector(object):
         The landmarks come from detect()'s program on the S x S crop of each box; the backward map's coefficients are one more launch
         in that program (imm_align_coeffs) and the photo is then sampled ONCE, straight from the packed u8 pixels, through the map and
         the box geometry (imm_align_warp_u8) - the S x S crop is not resampled.  A tensor batch [N, S, S, 3] is its own source: the
-        staged f32 copy the detector reads is sampled in place of u8 photos, geometry (0, 0, 1, 1)."""
+        staged f32 copy the detector reads is sampled in place of u8 photos, geometry (0, 0, 1, 1).
+        _packed (internal; ImageGenerator.repose): pack_u8(images, device, rows) of exactly these u8 images and box rows, made by a
+        caller that needs the packed photos itself; the buckets then read that one buffer instead of packing their own photos."""
         from . import alignment as AL
         from . import keypoints as KP
         lam = AL.check_model(model, lam)
@@ -616,7 +660,10 @@ class LandmarkDetector(object):
             self._stager.copy(self._al_ft[:ft.size], torch.from_numpy(ft.reshape(-1)), ('al_ft', m3))
             for start, count, bucket in plan_buckets(N, self.max_batch):
                 self._ensure_capacity(bucket)
-                if u8:
+                if u8 and _packed is not None:
+                    src, offs_d, hw_d, boxes_d = _packed[0], _packed[1], _packed[2], _packed[3][start:start + count]
+                    ops.resize_crop_u8(src, offs_d, hw_d, 3, (self.S, self.S), (0, 0), (self.S, self.S), self._img[:count], boxes=boxes_d)
+                elif u8:
                     part = rows[start:start + count]
                     used, idx = np.unique(part[:, 0], return_inverse=True)
                     local = np.concatenate([idx.reshape(-1, 1).astype(np.int32), part[:, 1:]], axis=1)
@@ -635,5 +682,45 @@ class LandmarkDetector(object):
                     mu_out[start:start + count].copy_(self._mu[:count])
         cur.wait_stream(self.stream)
         if return_transform:
-            return out, AL.Alignment(coef_out, ops.to_device_pinned(geom, self.dev), mu_out, model, lam, template, So)
+            return out, AL.Alignment(coef_out, ops.to_device_pinned(geom, self.dev), mu_out, model, lam, template, So,
+                                     rows if u8 else None)
         return out
+
+    def unalign(self, photos, aligned, alignment, feather=0.125):
+        """align() run backwards: the photos with every row's aligned face pasted back where align() took it from: a list of u8 device
+        tensors [h_i, w_i, 3], one per photo, views of one packed buffer (as ImageGenerator.repose returns them).
+        photos: the list of u8 arrays align() was given.  aligned: f32 [n, So, So, >= 3] on the host or the device (channels 0..2 are
+        read; a device tensor with dense pixels of one stride is read in place), So == alignment.out_size: the aligned faces, edited
+        or generated in the canonical frame.  alignment: what align(photos, ..., return_transform=True) returned (similarity or
+        affine; the tps map is not inverted: NotImplementedError).  feather in [0, 0.5]: the share of the aligned frame's side over
+        which the paste fades into the photo (0: a hard paste).
+        The photos are packed once; imm_unalign_maps inverts the rows' maps on the device (the coefficients never come back to the
+        host) and imm_unalign_u8 pastes the rows in row order (a later row blends over an earlier paste), sampling each face
+        bilinearly, without a pre-filter: a face much smaller in the photo than So x So is point-sampled."""
+        from . import alignment as AL
+        from .generation import compose_links
+        photos, rows, n, So, feather = plan_unalign(photos, getattr(aligned, 'shape', np.shape(aligned)), alignment, feather)
+        faces = torch.as_tensor(aligned)
+        if faces.dtype != torch.float32:
+            faces = faces.float()
+        with torch.cuda.device(self.dev):                 # everything on the caller's stream: the detector's programs are not run
+            faces = faces.to(self.dev) if faces.is_cuda else ops.to_device_pinned(faces, self.dev)
+            ld = faces.stride(2)
+            if faces.stride(3) != 1 or ld < 3 or faces.stride(1) != So * ld or faces.stride(0) != So * So * ld:
+                faces = faces.contiguous()
+            coef, geom = (ops.to_device_pinned(torch.as_tensor(a), self.dev, torch.float32).contiguous()
+                          for a in (alignment.coef, alignment.geom))
+            canvas, offs_d, hw_d, boxes_d = pack_u8(photos, self.dev, rows)              # all photos, once per call
+            fwd = torch.empty(n, 6, device=self.dev)
+            bbox = torch.empty(n, 4, dtype=torch.int32, device=self.dev)
+            ops.unalign_maps(coef, geom, boxes_d, hw_d, self.S, So, fwd, bbox)
+            inv_ramp = AL.unalign_inv_ramp(feather, So)
+            for start in range(0, n, UNALIGN_MAX_ROWS):
+                part = slice(start, min(start + UNALIGN_MAX_ROWS, n))
+                links_d = ops.to_device_pinned(compose_links(rows[part]), self.dev)
+                ops.unalign_u8(canvas, offs_d, hw_d, boxes_d[part], links_d, fwd[part], bbox[part], inv_ramp, faces[part],
+                               unalign_grid_pixels(photos, rows[part]))
+        offs = [0]
+        for a in photos[:-1]:
+            offs.append(offs[-1] + ((a.size + 15) & ~15))
+        return [canvas[o:o + a.size].view(a.shape) for o, a in zip(offs, photos)]

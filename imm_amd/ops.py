@@ -750,6 +750,54 @@ def compose_u8(photos, offsets, hw, boxes, links, inv_ramp, faces, max_box_pixel
          int(S), int(max_box_pixels), _s())
 
 
+def unalign_maps(coef, geom, boxes, hw, image_size, out_size, fwd, bbox):
+    """fwd f32 [n, 6] (photo pixel -> aligned coordinate, m00 m01 m02 m10 m11 m12) and bbox i32 [n, 4] (half-open, in the row's photo)
+    from the backward maps of align(): coef f32 [n, 3, 2], geom f32 [n, 4], boxes i32 [n, 5] (the image index is read), hw i32
+    [images, 2] (include/imm_unalign.h: imm_unalign_maps).  Everything stays on the device."""
+    n = boxes.shape[0]
+    if boxes.dtype != torch.int32 or tuple(boxes.shape) != (n, 5) or not boxes.is_contiguous():
+        raise ValueError('boxes must be contiguous int32 [n, 5], got %s %s' % (boxes.dtype, tuple(boxes.shape)))
+    if coef.dtype != torch.float32 or tuple(coef.shape) != (n, 3, 2) or not coef.is_contiguous():
+        raise ValueError('coef must be contiguous f32 [n, 3, 2] (the similarity and affine models), got %s %s' % (
+            coef.dtype, tuple(coef.shape)))
+    if geom.dtype != torch.float32 or tuple(geom.shape) != (n, 4) or not geom.is_contiguous():
+        raise ValueError('geom must be contiguous f32 [n, 4], got %s %s' % (geom.dtype, tuple(geom.shape)))
+    if hw.dtype != torch.int32 or hw.dim() != 2 or hw.shape[1] != 2 or not hw.is_contiguous():
+        raise ValueError('hw must be contiguous int32 [images, 2], got %s %s' % (hw.dtype, tuple(hw.shape)))
+    if fwd.dtype != torch.float32 or tuple(fwd.shape) != (n, 6) or not fwd.is_contiguous():
+        raise ValueError('fwd must be contiguous f32 [n, 6], got %s %s' % (fwd.dtype, tuple(fwd.shape)))
+    if bbox.dtype != torch.int32 or tuple(bbox.shape) != (n, 4) or not bbox.is_contiguous():
+        raise ValueError('bbox must be contiguous int32 [n, 4], got %s %s' % (bbox.dtype, tuple(bbox.shape)))
+    call('imm_unalign_maps', _p(coef), _p(geom), _p(boxes), _p(hw), int(hw.shape[0]), n, int(image_size), int(out_size), _p(fwd),
+         _p(bbox), _s())
+
+
+def unalign_u8(photos, offsets, hw, boxes, links, fwd, bbox, inv_ramp, faces, max_pixels):
+    """The packed u8 photos (as resize_crop_u8 reads them) pasted into in place: row b's aligned face, faces[b] f32 [So, So, >= 3] (a
+    view of any pixel stride, channels 0..2 read), sampled through fwd[b] at every photo pixel of bbox[b] the map covers, blended with
+    the edge ramp of reciprocal width inv_ramp (a float) and rounded to u8, in row order (include/imm_unalign.h: imm_unalign_u8).
+    boxes i32 [n, 5] (the image index is read), links i32 [n, 2] (generation.compose_links of THESE rows), fwd f32 [n, 6] and bbox i32
+    [n, 4] from unalign_maps; max_pixels: the largest bbox area expected (it sizes the grid only)."""
+    n = boxes.shape[0]
+    if photos.dtype != torch.uint8 or photos.dim() != 1 or not photos.is_contiguous():
+        raise ValueError('photos must be the flat contiguous u8 buffer, got %s %s' % (photos.dtype, tuple(photos.shape)))
+    if boxes.dtype != torch.int32 or tuple(boxes.shape) != (n, 5) or not boxes.is_contiguous():
+        raise ValueError('boxes must be contiguous int32 [n, 5], got %s %s' % (boxes.dtype, tuple(boxes.shape)))
+    if links.dtype != torch.int32 or tuple(links.shape) != (n, 2) or not links.is_contiguous():
+        raise ValueError('links must be contiguous int32 [n, 2], got %s %s' % (links.dtype, tuple(links.shape)))
+    if fwd.dtype != torch.float32 or tuple(fwd.shape) != (n, 6) or not fwd.is_contiguous():
+        raise ValueError('fwd must be contiguous f32 [n, 6], got %s %s' % (fwd.dtype, tuple(fwd.shape)))
+    if bbox.dtype != torch.int32 or tuple(bbox.shape) != (n, 4) or not bbox.is_contiguous():
+        raise ValueError('bbox must be contiguous int32 [n, 4], got %s %s' % (bbox.dtype, tuple(bbox.shape)))
+    So, ld = faces.shape[1], faces.stride(2)
+    if (faces.dtype != torch.float32 or faces.dim() != 4 or faces.shape[0] != n or faces.shape[2] != So or faces.shape[3] < 3 or
+            faces.stride(3) != 1 or faces.stride(1) != So * ld or faces.stride(0) != So * So * ld):
+        raise ValueError('faces must be f32 [n, So, So, >= 3] with dense pixels of one stride, got %s %s strides %s' % (
+            faces.dtype, tuple(faces.shape), tuple(faces.stride())))
+    call('imm_unalign_u8', _p(photos), _p(offsets), _p(hw), int(hw.shape[0]), _p(boxes), _p(links), _p(fwd), _p(bbox), float(inv_ramp),
+         _p(faces), int(ld), n, int(So), int(max_pixels), _s())
+
+
 def masked_sse_pool(a, b, batch, s, c, mask, S, partial, pool_a, pool_b):
     call('imm_masked_sse_pool', _p(a), _p(b), dtype_enum(a.dtype), batch, s, c, _p(mask), S, _p(partial), _p(pool_a), _p(pool_b), _s())
 
