@@ -407,6 +407,9 @@ bool imm_halo_applicable(const imm_conv_desc* d) {
   if (d->hi != d->ho || d->wi != d->wo || d->ho % HALO_PH || d->wo % HALO_PW) return false;
   if (d->ho * d->wo < 64 * 64) return false;      // deep layers: the im2col kernels have more parallelism
   if (d->flags & 0xf00) return false;   // debug ablation bits select the im2col kernel
+  // this kernel's partial sums are (sum v, sum v^2): the batch-norm BACKWARD rows (sum v, sum v * mask_ref) that IMM_CONV_STATS |
+  // IMM_CONV_MASK asks for come from the kernels that have them (conv_halo2, conv_hdeep, im2col); no launch of the step sets both
+  if ((d->flags & IMM_CONV_STATS) && (d->flags & IMM_CONV_MASK)) return false;
   const int64_t xb = (int64_t)d->batch * d->hi * d->wi * d->ldx * 2;
   return xb < (1LL << 31);
 }

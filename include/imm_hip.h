@@ -13,6 +13,18 @@
  *     (imm_dtype BF16 or F16) unless a parameter says f32; channel counts that feed a
  *     convolution are multiples of 8 and padding channels hold zeros.
  *   - statistics, parameters, gradients of parameters, optimizer state: f32.
+ *   - a tensor passed as (pointer, c, ld) with ld > c is a VIEW into a wider buffer (the engine's concat buffer has two
+ *     writers with disjoint columns).  Every entry point reads channels [0, c) of an input pixel and nothing of [c, ld), and
+ *     writes channels [0, c) of an output pixel and nothing of [c, ld): those columns belong to the caller, whatever they
+ *     hold (NaN included).  For convolutions c is `ci` (the K-loop channels, zero padded by the caller up to ci) on the input
+ *     and `co` on the output and the mask.  This holds for imm_conv2d (all families, forward and data gradient), imm_conv2d_nol,
+ *     imm_conv2d_group, imm_conv2d_dgrad_s2, imm_conv_first, imm_conv2d_wgrad / _multi (x and dy), imm_colsum, imm_bn_apply_relu,
+ *     imm_bn_apply_fused (x_out and up2x_out), imm_bn_bwd_reduce / _reduce_up / _apply / _apply_fused, imm_upsample2x_fwd / _bwd /
+ *     _bwd_bn, imm_resize_ac_fwd / _bwd, imm_pose_head_fwd (feat, heat, gauss_out) and imm_pose_head_bwd (dgauss, dfeat).
+ *     Map height and width are independent everywhere: h != w is served by every entry point that takes both.
+ *     The exceptions OWN their whole output row and zero its tail: imm_image_loss_grad and imm_vgg_conv1_1_bwd write [3, lddp)
+ *     = 0, imm_softargmax_gauss_bwd / imm_pose_head_bwd write dheat [K, lddh) = 0, imm_pack_image_taps writes [3 kw, ld) = 0.
+ *     tests/test_geometry_gpu.py and tests/test_kernels_gpu.py assert all of this on NaN-filled, guarded buffers.
  */
 #ifndef IMM_HIP_H
 #define IMM_HIP_H

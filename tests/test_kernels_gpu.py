@@ -127,15 +127,31 @@ def check_family(ops, desc, dt, tag):
         assert key == CONV_VARIANT[tag], (tag, key)
 
 
-def run_conv(ops, x16, w, bias, k, stride, co, ci_pad, out_f32, extra_flags=0, mask=None, ldy=None):
+def wide(x, ld, c_zero=None, fill=float('nan')):
+    """[..., c] -> [..., ld] on the device between guard bands: [c, c_zero) zero (the padding channels a convolution's K loop reads),
+    [c_zero, ld) `fill` — columns of a wider buffer that belong to somebody else: NaN, so a kernel that reads them into a result
+    fails close()."""
+    c = x.shape[-1]
+    c_zero = c if c_zero is None else c_zero
+    out = torch.full(tuple(x.shape[:-1]) + (ld,), fill, dtype=x.dtype)
+    out[..., :c] = x
+    out[..., c:c_zero] = 0
+    return guarded.inp(out, DEV, depth=2)
+
+
+def run_conv(ops, x16, w, bias, k, stride, co, ci_pad, out_f32, extra_flags=0, mask=None, ldy=None, ldx=None):
+    """x16 [B, H, W, ci_real]: H and W are independent (the descriptor gets both).  ldx > ci_pad: the input rows are ldx wide, channels
+    [ci_real, ci_pad) zero and [ci_pad, ldx) NaN.  ldy above the minimum: the caller asserts untouched(y[..., co:]).  The mask's pixel
+    stride is its last dimension (pass wide(mask, ldmask) for ldmask > co)."""
     from imm_amd import _lib as L
     B, H, W, _ = x16.shape
     dt = x16.dtype
     ci_real = w.shape[2]
-    xd = padded(x16, ci_pad)
+    ldx = ldx or ci_pad
+    xd = padded(x16, ci_pad) if ldx == ci_pad else wide(x16, ldx, ci_pad)
     flags = extra_flags | (L.CONV_BIAS if bias is not None else 0) | (L.CONV_OUT_F32 if out_f32 else 0)
     ldy = ldy or ops.round_up(co, 8 if not out_f32 else 4)
-    desc = ops.fwd_desc(B, H, W, ci_pad, ci_pad, co, ldy, k, stride, flags, ldmask=(mask.shape[-1] if mask is not None else 0))
+    desc = ops.fwd_desc(B, H, W, ci_pad, ldx, co, ldy, k, stride, flags, ldmask=(mask.shape[-1] if mask is not None else 0))
     rows = ops.round_up(co, 128)
     wt = guarded.out((rows, desc.kpad), dt, DEV, fill=0)
     wd = w.float().to(DEV).contiguous()
@@ -1881,3 +1897,475 @@ def test_pinned_stager_and_to_device_pinned(ops):
     a_ref = a.astype(np.float32)
     a[:] = 0
     assert t.is_cuda and t.dtype == torch.float32 and torch.equal(t.cpu(), torch.from_numpy(a_ref))
+
+
+# ----------------------------------------------------------------------------------------------
+# geometry: non-square maps (both orientations) and row strides above the channel counts, every convolution family
+# ----------------------------------------------------------------------------------------------
+# Each family's square case of CONV_CASES with the pixel count kept, one side doubled and the other halved where the family's
+# predicate allows it (ho % 8, wo % 16, >= 64x64 pixels for the halo kernels, >= 100 workgroups for hdeep): patches per row then
+# differ from patches per column, so a kernel that uses ho where it means wo computes garbage here and passes every square case.
+# Each case runs with compact rows AND with ldx = ci_pad + 8, ldy = round_up(co, 8) + 8, ldmask = co + 8: input columns
+# [ci_pad, ldx) and mask columns [co, ldmask) are NaN, output columns [co, ldy) must stay untouched (include/imm_hip.h).
+GEOM_CONV_CASES = [
+    # B, H, W, ci_real, ci_pad, co, k, stride, out_f32, tag
+    (2, 32, 128, 64, 64, 64, 3, 1, False, 'halo_64_64_wide'), (2, 128, 32, 64, 64, 64, 3, 1, False, 'halo_64_64_tall'),
+    (1, 64, 256, 32, 32, 32, 3, 1, False, 'halo_32_32_wide'), (1, 256, 64, 32, 32, 32, 3, 1, False, 'halo_32_32_tall'),
+    (3, 32, 128, 32, 32, 9, 3, 1, True, 'halo_32_9_f32_wide'), (3, 128, 32, 32, 32, 9, 3, 1, True, 'halo_32_9_f32_tall'),
+    (2, 32, 128, 64, 64, 32, 3, 1, False, 'halo_64_32_wide'), (2, 128, 32, 64, 64, 32, 3, 1, False, 'halo_64_32_tall'),
+    (2, 64, 256, 32, 32, 64, 3, 2, False, 'halo_s2_wide'), (2, 256, 64, 32, 32, 64, 3, 2, False, 'halo_s2_tall'),
+    (1, 32, 128, 32, 32, 48, 3, 2, False, 'halo_s2_co48_wide'), (1, 128, 32, 32, 32, 48, 3, 2, False, 'halo_s2_co48_tall'),
+    (16, 32, 128, 64, 64, 128, 3, 1, False, 'hdeep_bn128_one_slice_wide'), (16, 128, 32, 64, 64, 128, 3, 1, False, 'hdeep_bn128_one_slice_tall'),
+    (13, 16, 64, 128, 128, 256, 3, 1, False, 'hdeep_bn64_two_slices_wide'), (13, 64, 16, 128, 128, 256, 3, 1, False, 'hdeep_bn64_two_slices_tall'),
+    (7, 32, 128, 192, 192, 128, 3, 1, False, 'hdeep_three_slices_wide'), (7, 128, 32, 192, 192, 128, 3, 1, False, 'hdeep_three_slices_tall'),
+    (20, 32, 128, 128, 128, 128, 3, 1, False, 'hdeep_persistent_ragged_wide'), (20, 128, 32, 128, 128, 128, 3, 1, False, 'hdeep_persistent_ragged_tall'),
+    (130, 16, 64, 128, 128, 64, 3, 1, False, 'hdeep_persistent_bn64_wide'), (130, 64, 16, 128, 128, 64, 3, 1, False, 'hdeep_persistent_bn64_tall'),
+    # 8x16 patches, 4 waves: the map is one patch high.  The tall twin (32 x 8 columns: wo % 16 != 0) is not an hdeep shape
+    (32, 8, 32, 128, 128, 256, 3, 1, False, 'hdeep_small_patch_wide'), (32, 32, 8, 128, 128, 256, 3, 1, False, 'hdeep_small_patch_tall_igemm64'),
+    # an 8 x 16 map passes ho % 8 and wo % 16 but is NOT the two-whole-images-per-workgroup form of 8x8 maps (variant digit 40000)
+    (32, 8, 16, 512, 512, 512, 3, 1, False, 'hdeep_8x16_not_map8'),
+    (32, 64, 32, 64, 64, 128, 3, 2, False, 's2f_tall'), (32, 32, 64, 64, 64, 128, 3, 2, False, 's2f_wide'),
+    (2, 32, 48, 3, 8, 32, 7, 1, False, 'first7x7_wide'), (2, 48, 32, 3, 8, 32, 7, 1, False, 'first7x7_tall'),
+    (1, 10, 14, 64, 64, 64, 3, 1, False, 'ragged_m100_wide'), (1, 14, 10, 64, 64, 64, 3, 1, False, 'ragged_m100_tall'),
+    (2, 8, 32, 32, 32, 32, 3, 1, False, 'enc3x3_wide'), (2, 32, 8, 32, 32, 32, 3, 1, False, 'enc3x3_tall'),
+    (2, 8, 32, 32, 32, 64, 3, 2, False, 'stride2_wide'), (2, 32, 8, 32, 32, 64, 3, 2, False, 'stride2_tall'),
+    (2, 8, 32, 256, 256, 10, 1, 1, True, 'pose1x1_wide'), (2, 32, 8, 256, 256, 10, 1, 1, True, 'pose1x1_tall'),
+    (2, 8, 32, 266, 288, 256, 3, 1, False, 'concat266_wide'), (2, 32, 8, 266, 288, 256, 3, 1, False, 'concat266_tall'),
+    (2, 8, 16, 512, 512, 512, 3, 1, False, 'vgg5_wide'), (2, 16, 8, 512, 512, 512, 3, 1, False, 'vgg5_tall'),
+]
+# (family, variant key) of the plain launch on a 256-CU part, as CONV_VARIANT: a case proves nothing about a kernel that did not run
+GEOM_CONV_VARIANT = {
+    'halo_64_64_wide': ('halo2', 406464),
+    'halo_64_64_tall': ('halo2', 406464),
+    'halo_32_32_wide': ('halo2', 403232),
+    'halo_32_32_tall': ('halo2', 403232),
+    'halo_32_9_f32_wide': ('halo', 303216),
+    'halo_32_9_f32_tall': ('halo', 303216),
+    'halo_64_32_wide': ('halo2', 406432),
+    'halo_64_32_tall': ('halo2', 406432),
+    'halo_s2_wide': ('halo', 313264),
+    'halo_s2_tall': ('halo', 313264),
+    'halo_s2_co48_wide': ('halo', 313264),
+    'halo_s2_co48_tall': ('halo', 313264),
+    'hdeep_bn128_one_slice_wide': ('hdeep6', 600000),
+    'hdeep_bn128_one_slice_tall': ('hdeep6', 600000),
+    'hdeep_bn64_two_slices_wide': ('hdeep', 520648),
+    'hdeep_bn64_two_slices_tall': ('hdeep', 520648),
+    'hdeep_three_slices_wide': ('hdeep', 520648),
+    'hdeep_three_slices_tall': ('hdeep', 520648),
+    'hdeep_persistent_ragged_wide': ('hdeep6', 600001),
+    'hdeep_persistent_ragged_tall': ('hdeep6', 600001),
+    'hdeep_persistent_bn64_wide': ('hdeep', 510648),
+    'hdeep_persistent_bn64_tall': ('hdeep', 510648),
+    'hdeep_small_patch_wide': ('hdeep', 520644),
+    'hdeep_small_patch_tall_igemm64': ('igemm64', 210404),
+    'hdeep_8x16_not_map8': ('hdeep', 520644),
+    's2f_tall': ('s2f', 700064),
+    's2f_wide': ('s2f', 700064),
+    'first7x7_wide': ('igemm', 100802),
+    'first7x7_tall': ('igemm', 100802),
+    'ragged_m100_wide': ('igemm64', 210404),
+    'ragged_m100_tall': ('igemm64', 210404),
+    'enc3x3_wide': ('igemm', 110802),
+    'enc3x3_tall': ('igemm', 110802),
+    'stride2_wide': ('igemm', 110404),
+    'stride2_tall': ('igemm', 110404),
+    'pose1x1_wide': ('igemm', 110801),
+    'pose1x1_tall': ('igemm', 110801),
+    'concat266_wide': ('igemm', 110404),
+    'concat266_tall': ('igemm', 110404),
+    'vgg5_wide': ('igemm64', 210404),
+    'vgg5_tall': ('igemm64', 210404),
+}
+
+
+def _geom_variant(ops, desc, dt, tag, what=''):
+    got = ops.conv2d_variant(desc, dt)
+    assert got == GEOM_CONV_VARIANT[tag], (tag, what, got)
+
+
+@pytest.mark.parametrize('case', GEOM_CONV_CASES, ids=[c[-1] for c in GEOM_CONV_CASES])
+@pytest.mark.parametrize('dt', [torch.bfloat16, torch.float16], ids=['bf16', 'f16'])
+def test_conv_forward_non_square_and_wide_strides(ops, case, dt):
+    """imm_conv2d forward: tolerances of test_conv_forward / test_conv_relu_stats_mask; one oracle convolution per case."""
+    from imm_amd import _lib as L
+    B, H, W, ci_real, ci_pad, co, k, stride, out_f32, tag = case
+    x = rnd((B, H, W, ci_real), 1, 1.0, dt)
+    w = rnd((k, k, ci_real, co), 2, 0.05, dt)
+    b = rnd((co,), 3, 0.5, torch.float32)
+    ref = O.conv2d_same(x.float(), w.float(), b, stride)
+    assert ref.shape[1] != ref.shape[2]
+    rt = 2e-3 if out_f32 else (1e-2 if dt == torch.bfloat16 else 2e-3)
+    at = 2e-3 if not out_f32 else 2e-4
+    ldx, ldy = ci_pad + 8, ops.round_up(co, 8) + 8
+    for what, kw in (('compact', {}), ('wide', dict(ldx=ldx, ldy=ldy))):
+        y, _, desc = run_conv(ops, x, w, b, k, stride, co, ci_pad, out_f32, **kw)
+        _geom_variant(ops, desc, dt, tag, what)
+        close(y[..., :co], ref, rt, at, 'conv_fwd/%s/%s' % (tag, what))
+        assert untouched(y[..., co:]), 'padding channels [co, ldy) belong to the caller: imm_conv2d must not write them (%s)' % what
+    if out_f32 or k != 3:
+        return
+    # epilogues, wide rows throughout: batch-norm partial sums; ReLU; ReLU-backward mask (stride 1: the data-gradient epilogue)
+    y, stats, desc = run_conv(ops, x, w, b, k, stride, co, ci_pad, False, extra_flags=L.CONV_STATS, ldx=ldx, ldy=ldy)
+    assert ops.conv2d_variant(desc, dt)[0] in (GEOM_CONV_VARIANT[tag][0], 'hdeep'), (tag, ops.conv2d_variant(desc, dt))   # hdeep6 has no sums
+    close(y[..., :co], ref, rt, at, 'conv+stats/y/' + tag)
+    assert untouched(y[..., co:])
+    s = stats.sum(dim=0).cpu()
+    close(s[0], ref.sum(dim=(0, 1, 2)), 1e-3, 1e-3, 'conv+stats/sum/' + tag)
+    close(s[1], (ref ** 2).sum(dim=(0, 1, 2)), 1e-3, 1e-3, 'conv+stats/sumsq/' + tag)
+    y2, _, _ = run_conv(ops, x, w, b, k, stride, co, ci_pad, False, extra_flags=L.CONV_RELU, ldx=ldx, ldy=ldy)
+    close(y2[..., :co], torch.relu(ref), rt, at, 'conv+relu/' + tag)
+    assert untouched(y2[..., co:])
+    if stride != 1:
+        return
+    mref = rnd(tuple(ref.shape), 7, 1.0, dt)
+    y3, st3, d3 = run_conv(ops, x, w, b, k, stride, co, ci_pad, False, extra_flags=L.CONV_MASK | L.CONV_STATS, mask=wide(mref, co + 8),
+                           ldx=ldx, ldy=ldy)
+    assert d3.ldmask == co + 8
+    # conv_halo2 takes a mask only at ci == co and conv_halo has no (sum v, sum v * mask_ref) rows: 64 -> 32 falls to the im2col kernel
+    fam_m = {'halo_64_32_wide': 'igemm', 'halo_64_32_tall': 'igemm', 'hdeep_bn128_one_slice_wide': 'hdeep', 'hdeep_bn128_one_slice_tall': 'hdeep',
+             'hdeep_persistent_ragged_wide': 'hdeep', 'hdeep_persistent_ragged_tall': 'hdeep'}.get(tag, GEOM_CONV_VARIANT[tag][0])
+    assert ops.conv2d_variant(d3, dt)[0] == fam_m, (tag, ops.conv2d_variant(d3, dt))
+    v = ref * (mref.float() > 0)
+    close(y3[..., :co], v, rt, at, 'conv+mask/' + tag)
+    assert untouched(y3[..., co:])
+    s3 = st3.sum(dim=0).cpu()
+    close(s3[0], v.sum(dim=(0, 1, 2)), 2e-3, 2e-3, 'bn-bwd sums/sum dz/' + tag)
+    close(s3[1], (v * mref.float()).sum(dim=(0, 1, 2)), 2e-3, 2e-3, 'bn-bwd sums/sum dz*out/' + tag)
+
+
+def test_conv_rejects_strides_below_the_channel_count(ops):
+    """A stride the descriptor cannot be served with fails with its IMM_REQUIRE message, in no family silently."""
+    from imm_amd import _lib as L
+    x = guarded.out((1, 64, 64, 64), torch.bfloat16, DEV, fill=0)
+    wt = guarded.out((128, 576), torch.bfloat16, DEV, fill=0)
+    y = guarded.out((1, 64, 64, 64), torch.bfloat16, DEV)
+    with pytest.raises(L.ImmHipError, match=r'conv: ldx=56 \(ci=64\) must be a multiple of 8'):
+        ops.conv2d(ops.fwd_desc(1, 64, 64, 64, 56, 64, 64, 3, 1, 0), x, wt, None, y)
+    with pytest.raises(L.ImmHipError, match=r'conv: ldx=68 \(ci=64\) must be a multiple of 8'):
+        ops.conv2d(ops.fwd_desc(1, 64, 64, 64, 68, 64, 64, 3, 1, 0), x, wt, None, y)
+    with pytest.raises(L.ImmHipError, match=r'conv: ldy=60 \(co=64\) must be a multiple of 4'):
+        ops.conv2d(ops.fwd_desc(1, 64, 64, 64, 64, 64, 60, 3, 1, 0), x, wt, None, y)
+    with pytest.raises(L.ImmHipError, match='conv: mask flag without mask/ldmask'):
+        ops.conv2d(ops.fwd_desc(1, 64, 64, 64, 64, 64, 64, 3, 1, L.CONV_MASK, ldmask=56), x, wt, None, y, None, x)
+    assert untouched(y)
+
+
+GEOM_DGRAD_CASES = [
+    # B, H, W, ci_real, ci_pad, co, co_pad, k, stride, tag          (H x W = the forward INPUT = dx)
+    (2, 8, 32, 32, 32, 32, 32, 3, 1, 'k3s1_wide'), (2, 32, 8, 32, 32, 32, 32, 3, 1, 'k3s1_tall'),
+    (2, 8, 32, 32, 32, 64, 64, 3, 2, 'k3s2_wide'), (2, 32, 8, 32, 32, 64, 64, 3, 2, 'k3s2_tall'),
+    (2, 8, 32, 256, 256, 10, 16, 1, 1, 'k1_co10_wide'), (2, 32, 8, 256, 256, 10, 16, 1, 1, 'k1_co10_tall'),
+    (1, 16, 64, 32, 32, 9, 16, 3, 1, 'k3_co9_wide'), (1, 64, 16, 32, 32, 9, 16, 3, 1, 'k3_co9_tall'),
+    (2, 8, 32, 266, 288, 256, 256, 3, 1, 'ci266_wide'), (2, 32, 8, 266, 288, 256, 256, 3, 1, 'ci266_tall'),
+    (2, 16, 64, 64, 64, 128, 128, 3, 2, 'k3s2_b_wide'), (2, 64, 16, 64, 64, 128, 128, 3, 2, 'k3s2_b_tall'),
+    (16, 16, 64, 128, 128, 256, 256, 3, 1, 'hdeep_256to128_wide'), (16, 64, 16, 128, 128, 256, 256, 3, 1, 'hdeep_256to128_tall'),
+    (32, 8, 32, 256, 256, 512, 512, 3, 1, 'hdeep_512to256_wide'), (16, 32, 16, 256, 256, 512, 512, 3, 1, 'hdeep_512to256_tall'),
+    (2, 32, 128, 64, 64, 64, 64, 3, 1, 'halo2_64_64_wide'), (2, 128, 32, 64, 64, 64, 64, 3, 1, 'halo2_64_64_tall'),
+]
+GEOM_DGRAD_VARIANT = {
+    'k3s1_wide': ('igemm', 110802),
+    'k3s1_tall': ('igemm', 110802),
+    'k3s2_wide': ('igemm', 110802),
+    'k3s2_tall': ('igemm', 110802),
+    'k1_co10_wide': ('igemm', 100404),
+    'k1_co10_tall': ('igemm', 100404),
+    'k3_co9_wide': ('igemm', 100802),
+    'k3_co9_tall': ('igemm', 100802),
+    'ci266_wide': ('igemm64', 210404),
+    'ci266_tall': ('igemm64', 210404),
+    'k3s2_b_wide': ('igemm64', 210404),
+    'k3s2_b_tall': ('igemm64', 210404),
+    'hdeep_256to128_wide': ('hdeep', 520644),
+    'hdeep_256to128_tall': ('hdeep', 520644),
+    'hdeep_512to256_wide': ('hdeep', 520644),
+    'hdeep_512to256_tall': ('hdeep', 520644),
+    'halo2_64_64_wide': ('halo2', 406464),
+    'halo2_64_64_tall': ('halo2', 406464),
+}
+
+
+@pytest.mark.parametrize('case', GEOM_DGRAD_CASES, ids=[c[-1] for c in GEOM_DGRAD_CASES])
+@pytest.mark.parametrize('dt', [torch.bfloat16, torch.float16], ids=['bf16', 'f16'])
+def test_conv_dgrad_non_square_and_wide_strides(ops, case, dt):
+    """imm_conv2d as a data gradient (test_conv_dgrad) on h != w maps, compact and with lddy = co_pad + 8, lddx = ci_pad + 8."""
+    B, H, W, ci_real, ci_pad, co, co_pad, k, stride, tag = case
+    w = rnd((k, k, ci_real, co), 11, 0.05, dt)
+    xr = torch.zeros(B, H, W, ci_real, requires_grad=True)
+    yref = O.conv2d_same(xr, w.float(), None, stride)
+    dy = rnd(tuple(yref.shape), 12, 1.0, dt)
+    (gx,) = torch.autograd.grad(yref, xr, dy.float())
+    rows = ops.round_up(ci_real, 128)
+    wd = w.float().to(DEV).contiguous()
+    for what, lddy, lddx in (('compact', co_pad, ci_pad), ('wide', co_pad + 8, ci_pad + 8)):
+        desc = ops.dgrad_desc(B, H, W, ci_real, lddx, co_pad, lddy, k, stride, 0)
+        got = ops.conv2d_variant(desc, dt)
+        assert got == GEOM_DGRAD_VARIANT[tag], (tag, what, got)
+        wt = guarded.out((rows, desc.kpad), dt, DEV, fill=0)
+        ops.pack_weights(wd, wt, 1, k, k, ci_real, co, co_pad, rows, desc.kpad)
+        dx = guarded.out((B, H, W, lddx), dt, DEV)
+        ops.conv2d(desc, wide(dy, lddy, co_pad), wt, None, dx)
+        torch.cuda.synchronize()
+        close(dx[..., :ci_real], gx, 1e-2 if dt == torch.bfloat16 else 2e-3, 2e-3, 'dgrad/%s/%s' % (tag, what))
+        assert untouched(dx[..., ci_real:]), 'padding channels [co, ldy) of imm_conv2d belong to the caller (%s)' % what
+
+
+S2D_GEOM_CASES = [
+    # B, h, w (dy), ci (dx channels), co (dy channels), lddx, tag
+    (2, 8, 32, 64, 128, 64, 'deep_wide'), (2, 32, 16, 64, 128, 72, 'deep_tall_lddx72'),
+    (2, 16, 64, 32, 64, 40, 'halo_form_wide_lddx40'), (2, 64, 16, 32, 64, 32, 'halo_form_tall'),
+    (3, 8, 16, 40, 64, 48, 'one_patch_dx40_lddx48'),
+]
+
+
+@pytest.mark.parametrize('case', S2D_GEOM_CASES, ids=[c[-1] for c in S2D_GEOM_CASES])
+@pytest.mark.parametrize('dt', [torch.bfloat16, torch.float16], ids=['bf16', 'f16'])
+def test_conv_dgrad_stride2_one_launch_non_square(ops, case, dt):
+    """imm_conv2d_dgrad_s2 (test_conv_dgrad_stride2_one_launch) on h != w gradients, with the output rows wider than c_dx.  lddy is
+    this entry point's channel count as well as its stride (include/imm_hip.h): it cannot be pulled apart."""
+    B, h, w_, ci, co, lddx, _tag = case
+    k = 3
+    w = rnd((k, k, ci, co), 13, 0.05, dt)
+    xr = torch.zeros(B, 2 * h, 2 * w_, ci, requires_grad=True)
+    yref = O.conv2d_same(xr, w.float(), None, 2)
+    assert tuple(yref.shape[1:3]) == (h, w_)
+    dy = rnd(tuple(yref.shape), 14, 1.0, dt)
+    (gx,) = torch.autograd.grad(yref, xr, dy.float())
+    assert ops.conv2d_dgrad_s2_supported(B, h, w_, co, ci, lddx)
+    rows = ops.round_up(ci, 128)
+    wt = guarded.out((rows, 9 * co), dt, DEV, fill=0)
+    ops.pack_weights(w.float().to(DEV).contiguous(), wt, 1, k, k, ci, co, co, rows, 9 * co)
+    dx = guarded.out((B, 2 * h, 2 * w_, lddx), dt, DEV)
+    ops.conv2d_dgrad_s2(dev(dy), co, wt, dx, lddx, ci, B, h, w_)
+    torch.cuda.synchronize()
+    close(dx[..., :ci], gx, 1e-2, 2e-3, 'dgrad_s2_one_launch')
+    assert untouched(dx[..., ci:])
+
+
+def test_conv_dgrad_stride2_one_launch_rejects_transposed_maps(ops):
+    """h % 8 and w % 16 are not interchangeable: a 16 x 8 gradient is refused with the entry point's message."""
+    from imm_amd import _lib as L
+    assert ops.conv2d_dgrad_s2_supported(2, 8, 16, 64, 32, 32) and not ops.conv2d_dgrad_s2_supported(2, 16, 8, 64, 32, 32)
+    dy = guarded.out((2, 16, 8, 64), torch.bfloat16, DEV, fill=0)
+    wt = guarded.out((128, 576), torch.bfloat16, DEV, fill=0)
+    dx = guarded.out((2, 32, 16, 32), torch.bfloat16, DEV)
+    with pytest.raises(L.ImmHipError, match='conv_dgrad_s2: batch 2, dy 16x8 x 64'):
+        ops.conv2d_dgrad_s2(dy, 64, wt, dx, 32, 32, 2, 16, 8)
+    assert untouched(dx)
+
+
+GEOM_WGRAD_CASES = [
+    # B, H, W, ci_real, ci_pad, co, lddy, k, stride, nsplit, tag
+    (2, 8, 32, 32, 32, 32, 32, 3, 1, 1, 'k3s1_split1_wide'), (2, 32, 8, 32, 32, 32, 32, 3, 1, 5, 'k3s1_split5_tall'),
+    (2, 8, 32, 32, 32, 64, 64, 3, 2, 2, 'k3s2_wide'), (2, 32, 8, 32, 32, 64, 64, 3, 2, 2, 'k3s2_tall'),
+    (2, 32, 48, 3, 8, 32, 32, 7, 1, 4, 'first7x7_wide'), (2, 48, 32, 3, 8, 32, 32, 7, 1, 4, 'first7x7_tall'),
+    (2, 8, 32, 256, 256, 10, 16, 1, 1, 2, 'pose1x1_wide'), (2, 32, 8, 256, 256, 10, 16, 1, 1, 2, 'pose1x1_tall'),
+    (1, 16, 64, 32, 32, 9, 16, 3, 1, 3, 'final9_wide'), (1, 64, 16, 32, 32, 9, 16, 3, 1, 3, 'final9_tall'),
+    (2, 8, 32, 266, 288, 256, 256, 3, 1, 2, 'concat266_wide'), (2, 32, 8, 266, 288, 256, 256, 3, 1, 2, 'concat266_tall'),
+    (2, 8, 32, 128, 128, 128, 128, 3, 1, 1, 'c128_wide'), (2, 32, 8, 128, 128, 128, 128, 3, 1, 1, 'c128_tall'),
+]
+
+
+@pytest.mark.parametrize('case', GEOM_WGRAD_CASES, ids=[c[-1] for c in GEOM_WGRAD_CASES])
+@pytest.mark.parametrize('dt', [torch.bfloat16, torch.float16], ids=['bf16', 'f16'])
+def test_conv_wgrad_non_square_and_wide_strides(ops, case, dt):
+    """imm_conv2d_wgrad (test_conv_wgrad) on h != w maps; compact rows, then ldx = ci_pad + 8 and lddy + 8 with NaN in the extra columns."""
+    B, H, W, ci_real, ci_pad, co, lddy, k, stride, nsplit, tag = case
+    x = rnd((B, H, W, ci_real), 21, 1.0, dt)
+    wr = torch.zeros(k, k, ci_real, co, requires_grad=True)
+    yref = O.conv2d_same(x.float(), wr, None, stride)
+    dy = rnd(tuple(yref.shape), 22, 1.0, dt)
+    (gw,) = torch.autograd.grad(yref, wr, dy.float())
+    for what, ldx, ldd in (('compact', ci_pad, lddy), ('wide', ci_pad + 8, lddy + 8)):
+        desc = ops.fwd_desc(B, H, W, ci_pad, ldx, co, ldd, k, stride, 0)
+        slab = guarded.out((nsplit, desc.kpad, co), torch.float32, DEV)
+        ops.conv2d_wgrad(desc, wide(x, ldx, ci_pad), wide(dy, ldd, lddy), ldd, slab, nsplit)
+        dw = guarded.out((k, k, ci_real, co), torch.float32, DEV)
+        ops.conv2d_wgrad_reduce(slab, nsplit, k, k, ci_pad, ci_real, co, desc.kpad, dw)
+        torch.cuda.synchronize()
+        close(dw, gw, 2e-3, 5e-4, 'wgrad/%s/%s' % (tag, what))
+
+
+GEOM_WGRAD_HALO_CASES = [
+    # B, H, W, ci, co, lddy, tag
+    (1, 64, 256, 32, 32, 32, 'h32_32_wide'), (1, 256, 64, 32, 32, 32, 'h32_32_tall'),
+    (2, 32, 128, 64, 64, 64, 'h64_64_wide'), (2, 128, 32, 64, 64, 64, 'h64_64_tall'),
+    (3, 32, 128, 32, 9, 32, 'h32_9_wide'), (3, 128, 32, 32, 9, 32, 'h32_9_tall'),
+    (5, 32, 128, 128, 64, 64, 'sliced_128_64_wide'), (5, 128, 32, 128, 64, 64, 'sliced_128_64_tall'),
+]
+
+
+@pytest.mark.parametrize('case', GEOM_WGRAD_HALO_CASES, ids=[c[-1] for c in GEOM_WGRAD_HALO_CASES])
+@pytest.mark.parametrize('dt', [torch.bfloat16, torch.float16], ids=['bf16', 'f16'])
+def test_conv_wgrad_halo_non_square_and_wide_strides(ops, case, dt):
+    """The LDS-halo filter gradient (test_conv_wgrad_halo) on h != w maps; then the same job with ldx = ci + 8 through whichever
+    kernel serves it (the variant is printed; a family may decline a wide stride, the parity check stays)."""
+    B, H, W, ci, co, lddy, tag = case
+    x = rnd((B, H, W, ci), 121, 1.0, dt)
+    wr = torch.zeros(3, 3, ci, co, requires_grad=True)
+    yref = O.conv2d_same(x.float(), wr, None, 1)
+    dy = rnd(tuple(yref.shape), 122, 1.0, dt)
+    (gw,) = torch.autograd.grad(yref, wr, dy.float())
+    desc = ops.fwd_desc(B, H, W, ci, ci, co, lddy, 3, 1, 0)
+    assert ops.conv2d_wgrad_variant(desc, lddy, dt)[0] // 100000 == 2, 'case should select the halo kernel'
+    for what, ldx in (('compact', ci), ('wide', ci + 8)):
+        d = ops.fwd_desc(B, H, W, ci, ldx, co, lddy, 3, 1, 0)
+        key = ops.conv2d_wgrad_variant(d, lddy, dt)[0]
+        nsplit = ops.conv2d_wgrad_splits(d, lddy) or 3
+        print('WGRAD_HALO_GEOM %s %s variant %d nsplit %d' % (tag, what, key, nsplit))
+        assert key // 100000 == 2, (tag, what, key)
+        slab = guarded.out((nsplit, d.kpad, co), torch.float32, DEV)
+        ops.conv2d_wgrad(d, wide(x, ldx), wide(dy, lddy, lddy), lddy, slab, nsplit)
+        dw = guarded.out((3, 3, ci, co), torch.float32, DEV)
+        ops.conv2d_wgrad_reduce(slab, nsplit, 3, 3, ci, ci, co, d.kpad, dw)
+        torch.cuda.synchronize()
+        close(dw, gw, 2e-3, 5e-4, 'wgrad_halo/%s/%s' % (tag, what))
+
+
+@pytest.mark.parametrize('dt', [torch.bfloat16, torch.float16], ids=['bf16', 'f16'])
+@pytest.mark.parametrize('B,H,W', [(2, 32, 128), (2, 128, 32)], ids=['wide', 'tall'])
+def test_conv_wgrad_halo_7x1_first_layer_non_square(ops, B, H, W, dt):
+    """test_conv_wgrad_halo_7x1_first_layer on h != w images, alone and as a member of a multi-problem launch with ldx = ci + 8."""
+    ci, co = 32, 32
+    x = rnd((B, H, W, ci), 131, 1.0, dt)
+    x[..., 21:] = 0
+    wr = torch.zeros(7, 1, ci, co, requires_grad=True)
+    yref = O.conv2d_same(x.float(), wr, None, 1)
+    dy = rnd(tuple(yref.shape), 132, 1.0, dt)
+    (gw,) = torch.autograd.grad(yref, wr, dy.float())
+    desc = ops.fwd_desc(B, H, W, ci, ci, co, co, 7, 1, 0, kw=1)
+    key, wps, _units, pcu = ops.conv2d_wgrad_variant(desc, co, dt)
+    assert key // 100000 == 2 and wps == 1 and pcu == 2, key
+    nsplit = ops.conv2d_wgrad_splits(desc, co)
+    assert nsplit > 0
+    dyd = dev(dy)
+    for ns, multi, ldx in ((nsplit, False, ci), (7, True, ci + 8), (3, False, ci + 8)):
+        d = ops.fwd_desc(B, H, W, ci, ldx, co, co, 7, 1, 0, kw=1)
+        xd = wide(x, ldx)
+        slab = guarded.out((ns, d.kpad, co), torch.float32, DEV)
+        if multi:
+            ops.conv2d_wgrad_multi(ops.WgradMulti([(d, xd, dyd, co, slab, ns)], dt))
+        else:
+            ops.conv2d_wgrad(d, xd, dyd, co, slab, ns)
+        dw = guarded.out((7, 1, ci, co), torch.float32, DEV)
+        ops.conv2d_wgrad_reduce(slab, ns, 7, 1, ci, ci, co, d.kpad, dw)
+        torch.cuda.synchronize()
+        close(dw, gw, 2e-3, 5e-4, 'wgrad_halo_7x1/%d%s/ldx%d' % (ns, 'm' if multi else '', ldx))
+
+
+@pytest.mark.parametrize('dt', [torch.bfloat16, torch.float16], ids=['bf16', 'f16'])
+@pytest.mark.parametrize('B,H,W,co', [(2, 64, 256, 64), (2, 256, 64, 64), (1, 32, 128, 48)], ids=['wide', 'tall', 'wide_co48'])
+def test_conv_wgrad_halo_stride2_non_square(ops, B, H, W, co, dt):
+    """test_conv_wgrad_halo_stride2 on h != w images, alone and as a member of a multi-problem launch with ldx = ci + 8."""
+    ci = 32
+    x = rnd((B, H, W, ci), 141, 1.0, dt)
+    wr = torch.zeros(3, 3, ci, co, requires_grad=True)
+    yref = O.conv2d_same(x.float(), wr, None, 2)
+    dy = rnd(tuple(yref.shape[:3]) + (64,), 142, 1.0, dt)
+    dy[..., co:] = 0
+    (gw,) = torch.autograd.grad(yref, wr, dy[..., :co].float())
+    desc = ops.fwd_desc(B, H, W, ci, ci, co, 64, 3, 2, 0)
+    key, wps, _units, pcu = ops.conv2d_wgrad_variant(desc, 64, dt)
+    assert key == 200000 + 20000 + 3264 and wps == 1 and pcu == 1, key
+    nsplit = ops.conv2d_wgrad_splits(desc, 64)
+    assert nsplit > 0
+    dyd = dev(dy)
+    for ns, multi, ldx in ((nsplit, False, ci), (5, True, ci + 8), (3, False, ci + 8)):
+        d = ops.fwd_desc(B, H, W, ci, ldx, co, 64, 3, 2, 0)
+        xd = wide(x, ldx)
+        slab = guarded.out((ns, d.kpad, co), torch.float32, DEV)
+        if multi:
+            ops.conv2d_wgrad_multi(ops.WgradMulti([(d, xd, dyd, 64, slab, ns)], dt))
+        else:
+            ops.conv2d_wgrad(d, xd, dyd, 64, slab, ns)
+        dw = guarded.out((3, 3, ci, co), torch.float32, DEV)
+        ops.conv2d_wgrad_reduce(slab, ns, 3, 3, ci, ci, co, d.kpad, dw)
+        torch.cuda.synchronize()
+        close(dw, gw, 2e-3, 5e-4, 'wgrad_halo_s2/%d%s/ldx%d' % (ns, 'm' if multi else '', ldx))
+
+
+@pytest.mark.parametrize('dt', [torch.bfloat16, torch.float16], ids=['bf16', 'f16'])
+@pytest.mark.parametrize('B,H,W,ci,co,stride,out_f32', [(2, 32, 128, 32, 32, 1, False), (2, 128, 32, 64, 64, 1, False),
+                                                       (2, 64, 256, 32, 64, 2, False), (1, 128, 32, 32, 9, 1, True)],
+                         ids=['s1_wide', 's1_tall_64_64', 's2_wide', 'f32_head_tall'])
+def test_conv_norm_on_load_non_square_and_wide_strides(ops, B, H, W, ci, co, stride, out_f32, dt):
+    """imm_conv2d_nol (test_conv_norm_on_load) with the raw tensor in rows of ci + 8 (NaN beyond ci), ldy above the minimum, h != w:
+    against the oracle convolution of the normalised tensor that imm_bn_apply_relu stores."""
+    from imm_amd import _lib as L
+    raw = rnd((B, H, W, ci), 900, 1.0, dt)
+    g = torch.Generator().manual_seed(901)
+    scale = dev((torch.randn(ci, generator=g) * 0.8 + 0.3))
+    shift = dev((torch.randn(ci, generator=g) * 0.7 + 0.4))
+    ldx, ldy = ci + 8, ops.round_up(co, 8) + 8
+    yw = wide(raw, ldx)
+    out = guarded.out((B, H, W, ci), dt, DEV)
+    ops.bn_apply_relu(yw, B * H * W, ci, ldx, scale, shift, True, out, ci)
+    w = rnd((3, 3, ci, co), 902, 0.05, dt)
+    bias = rnd((co,), 903, 0.1, torch.float32).float()
+    flags = L.CONV_BIAS | L.CONV_STATS | (L.CONV_OUT_F32 if out_f32 else 0)
+    desc = ops.fwd_desc(B, H, W, ci, ldx, co, ldy, 3, stride, flags)
+    assert ops.conv2d_nol_supported(desc)
+    rows = ops.round_up(co, 128)
+    wt = guarded.out((rows, desc.kpad), dt, DEV, fill=0)
+    ops.pack_weights(w.float().to(DEV).contiguous(), wt, 0, 3, 3, ci, co, ci, rows, desc.kpad)
+    z = guarded.out((B, desc.ho, desc.wo, ldy), torch.float32 if out_f32 else dt, DEV)
+    st = guarded.out((ops.conv2d_nol_stats_blocks(desc), 2, co), torch.float32, DEV)
+    ops.conv2d_nol(desc, yw, scale, shift, True, wt, dev(bias), z, st)
+    torch.cuda.synchronize()
+    zo = O.conv2d_same(out.float().cpu(), w.float(), bias, stride)
+    close(z[..., :co], zo, 1e-2 if not out_f32 else 2e-3, 2e-3, 'conv_nol vs oracle')
+    assert untouched(z[..., co:]), 'padding channels [co, ldy) belong to the caller'
+    s = st.sum(0).cpu()
+    close(s[0], zo.sum(dim=(0, 1, 2)), 1e-3, 1e-3, 'conv_nol/sum')
+    close(s[1], (zo ** 2).sum(dim=(0, 1, 2)), 1e-3, 1e-3, 'conv_nol/sumsq')
+
+
+@pytest.mark.parametrize('B,H,W,ci,co', [(2, 16, 64, 64, 128), (2, 64, 16, 64, 128), (3, 8, 32, 32, 64), (3, 32, 8, 128, 256)],
+                         ids=['grouped_wide', 'grouped_tall', 'grouped_128x32_wide', 'grouped_deep_tall'])
+def test_conv_group_non_square_and_wide_strides(ops, B, H, W, ci, co):
+    """imm_conv2d_group (the four parity classes of a stride-2 data gradient) on h != w maps with lddy = co + 8 and lddx = ci + 8,
+    against autograd of the oracle convolution (tolerance of test_conv_dgrad_stride2_parity_classes)."""
+    k, dt = 3, torch.bfloat16
+    w = rnd((k, k, ci, co), 401, 0.05)
+    xr = torch.zeros(B, H, W, ci, requires_grad=True)
+    yref = O.conv2d_same(xr, w.float(), None, 2)
+    dy = rnd(tuple(yref.shape), 402)
+    (gx,) = torch.autograd.grad(yref, xr, dy.float())
+    lddy, lddx = co + 8, ci + 8
+    classes = ops.dgrad_s2_class_descs(B, H, W, ci, lddx, co, lddy, k)
+    assert classes is not None and len(classes) == 4
+    rows = ops.round_up(ci, 128)
+    wts = []
+    for d, mode in classes:
+        wt = guarded.out((rows, d.kpad), dt, DEV, fill=0)
+        ops.pack_weights(w.float().to(DEV).contiguous(), wt, mode, k, k, ci, co, co, rows, d.kpad)
+        wts.append(wt)
+    got = guarded.out((B, H, W, lddx), dt, DEV)
+    ops.conv2d_group(ops.ConvGroup([d for d, _m in classes], wts), wide(dy, lddy), got)
+    torch.cuda.synchronize()
+    close(got[..., :ci], gx, 1e-2, 2e-3, 'conv_group')
+    assert untouched(got[..., ci:])
+
+
+@pytest.mark.parametrize('dt', [torch.bfloat16, torch.float16], ids=['bf16', 'f16'])
+@pytest.mark.parametrize('B,S,co,ldy', [(2, 64, 32, 40), (3, 32, 20, 32)], ids=['co32_ldy40', 'co20_ldy32'])
+def test_first_conv_from_the_f32_image_wide_strides(ops, B, S, co, ldy, dt):
+    """imm_conv_first (test_first_conv_from_the_f32_image) with ldy above round_up(co, 8)."""
+    from imm_amd import _lib as L
+    g = torch.Generator().manual_seed(77)
+    src = torch.rand(B, S, S, 3, generator=g) * 255
+    w = rnd((7, 7, 3, co), 57, 0.01, torch.float32)
+    bias = rnd((co,), 59, 0.5, torch.float32)
+    assert ops.conv_first_supported(B, S, co, ldy)
+    wt = guarded.out((128, 224), dt, DEV, fill=0)
+    ops.pack_weights(w.to(DEV).contiguous(), wt, 0, 7, 1, 21, co, 32, 128, 224)
+    y = guarded.out((B, S, S, ldy), dt, DEV)
+    stats = guarded.out((ops.conv_first_stats_blocks(B, S), 2, co), torch.float32, DEV)
+    ops.conv_first(dev(src), wt, dev(bias), y, ldy, stats, B, S, co, L.CONV_BIAS | L.CONV_STATS)
+    torch.cuda.synchronize()
+    ref = O.conv2d_same(src.to(dt).float(), w.to(dt).float(), bias, 1)
+    close(y[..., :co], ref, 1e-2, 2e-3, 'conv_first vs oracle')
+    assert untouched(y[..., co:])
+    st = stats.sum(0).cpu()
+    close(st[0], ref.sum(dim=(0, 1, 2)), 1e-3, 1e-3, 'conv_first/sum')
+    close(st[1], (ref ** 2).sum(dim=(0, 1, 2)), 1e-3, 1e-3, 'conv_first/sumsq')

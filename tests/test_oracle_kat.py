@@ -355,3 +355,152 @@ def test_cost_moving_average_is_the_biased_tf110_shadow():
     for _ in range(50):
         st, avg = O.cost_ema_update(st, [3.25])
     assert abs(avg[0] - 3.25 * (1 - 0.99 ** 50)) < 1e-9
+
+
+# ---- non-square maps: the oracle at the shapes tests/test_geometry_gpu.py leans on, against direct f64 loops ----------------------
+# Each loop below is written from the TF 1.10 op definition (not from oracle/np_ref.py, whose helpers are square-only in places):
+# height and width are never interchangeable in them, so an oracle that used the wrong extent on one axis cannot agree.
+def _conv_same_loops(x, w, b, s):
+    """tf.nn.conv2d SAME: per axis n_out = ceil(n/s), pad_total = max((n_out-1)*s + k - n, 0), pad_before = pad_total // 2."""
+    B, H, W, Ci = x.shape
+    kh, kw, _, Co = w.shape
+    ho, wo = -(-H // s), -(-W // s)
+    pt = max((ho - 1) * s + kh - H, 0) // 2
+    pl = max((wo - 1) * s + kw - W, 0) // 2
+    y = np.zeros((B, ho, wo, Co), np.float64)
+    for oy in range(ho):
+        for ox in range(wo):
+            for ky in range(kh):
+                iy = oy * s + ky - pt
+                if iy < 0 or iy >= H:
+                    continue
+                for kx in range(kw):
+                    ix = ox * s + kx - pl
+                    if ix < 0 or ix >= W:
+                        continue
+                    y[:, oy, ox] += x[:, iy, ix].astype(np.float64) @ w[ky, kx].astype(np.float64)
+    return y + (0 if b is None else b.astype(np.float64))
+
+
+def _resize_loops(x, oh, ow, ac):
+    """tf.image.resize_bilinear: src = dst * (in-1)/(out-1) with align_corners (out > 1), else dst * in/out; lo = floor(src),
+    hi = min(lo + 1, in - 1); columns are interpolated within the top and the bottom row, then the rows."""
+    B, H, W, C = x.shape
+    sy = (H - 1) / (oh - 1) if ac and oh > 1 else H / oh
+    sx = (W - 1) / (ow - 1) if ac and ow > 1 else W / ow
+    y = np.zeros((B, oh, ow, C), np.float64)
+    xd = x.astype(np.float64)
+    for Y in range(oh):
+        fy = Y * sy
+        y0 = int(math.floor(fy)); y1 = min(y0 + 1, H - 1); ly = fy - y0
+        for X in range(ow):
+            fx = X * sx
+            x0 = int(math.floor(fx)); x1 = min(x0 + 1, W - 1); lx = fx - x0
+            top = xd[:, y0, x0] + (xd[:, y0, x1] - xd[:, y0, x0]) * lx
+            bot = xd[:, y1, x0] + (xd[:, y1, x1] - xd[:, y1, x0]) * lx
+            y[:, Y, X] = top + (bot - top) * ly
+    return y
+
+
+@pytest.mark.parametrize('k,s,h,w', [(3, 1, 5, 8), (3, 1, 8, 5), (3, 2, 6, 9), (3, 2, 9, 6), (3, 2, 7, 4), (7, 1, 4, 9), (7, 2, 6, 5),
+                                     (1, 1, 3, 7)])
+def test_conv_same_on_non_square_maps(k, s, h, w):
+    """S1 per axis: stride 1 and 2, odd and even sides, tall and wide; the 3 x 2-stride (6, 9) case pads 0|1 rows and 1|1 columns."""
+    rng = np.random.default_rng(100 * k + 10 * s + h)
+    x = rng.standard_normal((2, h, w, 3)).astype(np.float32)
+    wt = rng.standard_normal((k, k, 3, 4)).astype(np.float32)
+    b = rng.standard_normal(4).astype(np.float32)
+    y = O.conv2d_same(t(x), t(wt), t(b), s).numpy()
+    assert y.shape == (2, -(-h // s), -(-w // s), 4)
+    np.testing.assert_allclose(y, _conv_same_loops(x, wt, b, s), rtol=1e-5, atol=1e-5)
+
+
+def test_conv_same_non_square_kernel_and_delta():
+    """A 7x1 kernel (the tap-unrolled first layer) pads rows only; a delta at (1, 4) of a 4x6 map through an index kernel."""
+    rng = np.random.default_rng(17)
+    x = rng.standard_normal((1, 6, 10, 2)).astype(np.float32)
+    wt = rng.standard_normal((7, 1, 2, 3)).astype(np.float32)
+    np.testing.assert_allclose(O.conv2d_same(t(x), t(wt)).numpy(), _conv_same_loops(x, wt, None, 1), rtol=1e-5, atol=1e-5)
+    d = torch.zeros(1, 4, 6, 1); d[0, 1, 4, 0] = 1.0
+    w9 = torch.arange(9, dtype=torch.float32).reshape(3, 3, 1, 1)
+    y = O.conv2d_same(d, w9)[0, :, :, 0]
+    # out[oy][ox] = w[1 + 1 - oy][1 + 4 - ox]
+    assert y.shape == (4, 6) and y[0, 3] == 8.0 and y[2, 5] == 0.0 and y[1, 4] == 4.0 and y[0, 5] == 6.0 and float(y[3].abs().max()) == 0.0
+
+
+@pytest.mark.parametrize('ac', [False, True], ids=['legacy', 'align_corners'])
+@pytest.mark.parametrize('hw,ohw', [((4, 6), (8, 12)), ((6, 4), (12, 8)), ((8, 12), (4, 6)), ((12, 8), (6, 4)), ((8, 16), (4, 4)),
+                                    ((5, 3), (3, 7))])
+def test_resize_on_non_square_maps(hw, ohw, ac):
+    """S2 / S3 with independent row and column ratios (the (8, 16) -> (4, 4) case: 2 and 4; (5, 3) -> (3, 7): down and up)."""
+    rng = np.random.default_rng(hw[0] * 31 + ohw[1])
+    x = rng.standard_normal((2, hw[0], hw[1], 3)).astype(np.float32)
+    y = O.resize_bilinear(t(x), ohw[0], ohw[1], ac).numpy()
+    assert y.shape == (2, ohw[0], ohw[1], 3)
+    np.testing.assert_allclose(y, _resize_loops(x, ohw[0], ohw[1], ac), rtol=1e-5, atol=1e-6)
+
+
+def test_resize_non_square_ramp_closed_form():
+    """f(y, x) = 10 y + x on 3 x 5 -> 5 x 9 with align_corners: src_y = Y / 2, src_x = X / 2, a ramp stays a ramp on each axis."""
+    g = (10 * np.arange(3, dtype=np.float32)[:, None] + np.arange(5, dtype=np.float32)[None]).reshape(1, 3, 5, 1)
+    got = O.resize_bilinear(t(g), 5, 9, True)[0, :, :, 0].numpy()
+    np.testing.assert_allclose(got, 10 * (np.arange(5) / 2.0)[:, None] + (np.arange(9) / 2.0)[None], atol=1e-6)
+
+
+@pytest.mark.parametrize('h,w', [(4, 6), (6, 4), (2, 8)])
+def test_max_pool_on_non_square_maps(h, w):
+    rng = np.random.default_rng(h * 7 + w)
+    x = rng.standard_normal((2, h, w, 3)).astype(np.float32)
+    ref = np.zeros((2, h // 2, w // 2, 3), np.float32)
+    for Y in range(h // 2):
+        for X in range(w // 2):
+            ref[:, Y, X] = np.maximum(np.maximum(x[:, 2 * Y, 2 * X], x[:, 2 * Y, 2 * X + 1]),
+                                      np.maximum(x[:, 2 * Y + 1, 2 * X], x[:, 2 * Y + 1, 2 * X + 1]))
+    got = O.max_pool2(t(x)).numpy()
+    assert got.shape == ref.shape
+    np.testing.assert_array_equal(got, ref)
+
+
+@pytest.mark.parametrize('h,w', [(4, 7), (7, 4), (16, 32)])
+def test_softargmax_on_non_square_maps(h, w):
+    """imm_model.py:252-264: the row profile is softmax over h of the mean over w (and the other way round), coordinates are
+    linspace(-1, 1, h) and linspace(-1, 1, w); py is [B, h, K], px [B, w, K]."""
+    rng = np.random.default_rng(h + 3 * w)
+    heat = (rng.standard_normal((2, h, w, 3)) * 3).astype(np.float32)
+    mu, py, px = O.soft_argmax(t(heat))
+    assert mu.shape == (2, 3, 2) and py.shape == (2, h, 3) and px.shape == (2, w, 3)
+    hd = heat.astype(np.float64)
+    for b in range(2):
+        for k in range(3):
+            rows = np.array([sum(hd[b, i, j, k] for j in range(w)) / w for i in range(h)])
+            cols = np.array([sum(hd[b, i, j, k] for i in range(h)) / h for j in range(w)])
+            pr = np.exp(rows - rows.max()); pr /= pr.sum()
+            pc = np.exp(cols - cols.max()); pc /= pc.sum()
+            np.testing.assert_allclose(py[b, :, k].numpy(), pr, atol=1e-6)
+            np.testing.assert_allclose(px[b, :, k].numpy(), pc, atol=1e-6)
+            my = sum(pr[i] * (-1 + 2 * i / (h - 1)) for i in range(h))
+            mx = sum(pc[j] * (-1 + 2 * j / (w - 1)) for j in range(w))
+            assert abs(float(mu[b, k, 0]) - my) < 2e-6 and abs(float(mu[b, k, 1]) - mx) < 2e-6
+
+
+@pytest.mark.parametrize('mode', ['rot', 'flat', 'ankush'])
+@pytest.mark.parametrize('h,w', [(4, 9), (9, 4)])
+def test_gaussian_maps_on_non_square_maps(h, w, mode):
+    """imm_model.py:34-78 with shape_hw = [h, w]: y runs over linspace(-1, 1, h), x over linspace(-1, 1, w); output [B, h, w, K]."""
+    rng = np.random.default_rng(h * 5 + w)
+    mu = rng.uniform(-0.9, 0.9, (2, 3, 2)).astype(np.float32)
+    g = O.gaussian_maps(t(mu), [h, w], 10.0, mode).numpy()
+    assert g.shape == (2, h, w, 3)
+    ref = np.zeros((2, h, w, 3), np.float64)
+    for b in range(2):
+        for k in range(3):
+            for i in range(h):
+                for j in range(w):
+                    dy = float(mu[b, k, 0]) - (-1 + 2 * i / (h - 1)); dx = float(mu[b, k, 1]) - (-1 + 2 * j / (w - 1))
+                    if mode == 'rot':
+                        ref[b, i, j, k] = math.exp(-(dy * dy + dx * dx) * 100.0)
+                    elif mode == 'flat':
+                        ref[b, i, j, k] = math.exp(-((dy * dy + dx * dx) * 100.0 + 1e-5) ** 0.25)
+                    else:
+                        ref[b, i, j, k] = math.exp(-math.sqrt(1e-4 + abs(dy * 10.0))) * math.exp(-math.sqrt(1e-4 + abs(dx * 10.0)))
+    np.testing.assert_allclose(g, ref, rtol=2e-5, atol=1e-6)
