@@ -256,7 +256,7 @@ __global__ __launch_bounds__(BN * 4) void conv_s2f_kernel(const S2fArgs ha) {
 
   // ---- epilogue: lane = pixel (row 4 wm + i, col frow), 8 consecutive channels; bias is in the accumulators ----------------------
   // ReLU on the f32 value before the 16-bit store (the batch-norm-folded detector's conv + bias + ReLU); the partial sums are of
-  // the stored value, as in conv_common.h
+  // that f32 value, before the rounding of the store, as in conv_common.h (the contract at imm_conv2d in include/imm_hip.h)
   const bool f_stats = a.flags & IMM_CONV_STATS, f_relu = a.flags & IMM_CONV_RELU;
   const int nb = n0 + wn * 32 + q * 8;
   const int64_t m_first = ((int64_t)img * a.ho + y0 + wm * 4) * a.wo + x0 + frow;

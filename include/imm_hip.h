@@ -170,7 +170,11 @@ int imm_conv2d_dgrad_s2(const void* dy, int lddy, const void* wt, int kpad, void
  * with n_mblocks = imm_conv_stats_blocks(desc).  Replaces tf.nn.conv2d+bias_add (nn_utils.py:100,108),
  * vgg conv+bias+relu (vgg16.py:182-189,230) and their data gradients.
  * Epilogue order: + bias, ReLU, mask (IMM_CONV_MASK: v = 0 where mask_ref <= 0, mask_ref 16-bit [pixels][ldmask] with the
- * geometry of y), store, partial sums.  IMM_CONV_STATS alone: rows of (sum v, sum v^2) — the batch statistics of a forward
+ * geometry of y), store, partial sums.  v is the f32 value after bias, ReLU and mask.  The 16-bit store is ONE round-to-nearest-
+ * even of that v (no truncation, no intermediate 16-bit value before the bias is added); an f32 store is v itself.  The partial
+ * sums are taken from the f32 v BEFORE the 16-bit rounding, in every kernel family, so that the batch statistics of a layer do not
+ * depend on which family served it.  tests/test_exact_gpu.py holds every family to both, bit for bit, on integer data whose
+ * accumulators are exact.  IMM_CONV_STATS alone: rows of (sum v, sum v^2) — the batch statistics of a forward
  * convolution.  IMM_CONV_STATS | IMM_CONV_MASK: rows of (sum v, sum v * mask_ref) — the batch-norm BACKWARD sums (sum dz,
  * sum dz * out) of the conv+BN+ReLU block whose output gradient this data gradient produces (mask_ref = that block's stored
  * activation `out`), which replaces a separate reduction pass over dz (tf.gradients of nn_utils.py:201-209).
