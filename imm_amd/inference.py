@@ -30,6 +30,7 @@ import torch
 from . import _lib as L
 from . import ops
 from .engine import BN_EPS, encoder_spec
+from .tracking import OneEuro
 
 POSE_SCOPE = 'model/pose_encoder'
 MAX_LANDMARKS = 64            # the soft-argmax / pose-head kernels' limit
@@ -619,6 +620,26 @@ class LandmarkDetector(object):
                 mu_out[start:start + count].copy_(self._mu[:count])
         cur.wait_stream(self.stream)
         return mu_out
+
+    def track(self, frames, boxes, regressor=None, box_smooth=0.5, one_euro=OneEuro(), fps=25.0, chunk_frames=32):
+        """The faces of a clip followed from its first frame: a tracking.Track (mu, points, points_smooth [T, F, K, 2], boxes int32
+        [T, F, 4], flags [T, F], keypoints [T, F, M, 2] with a regressor) on the detector's device.
+        frames: a list of T u8 HWC arrays of any sizes.  boxes: the faces of frames[0], rows (0, y0, x0, y1, x1) or (y0, x0, y1, x1),
+        as keypoints.check_boxes takes them; at most max_batch of them.  box_smooth in (0, 1]: the weight of a frame's measurement in
+        the box filter.  one_euro: a tracking.OneEuro (the default: OneEuro()), or None for points_smooth == points.  fps: the clip's
+        frame rate (the filter's time step).  chunk_frames: frames packed and uploaded at a time.
+        Per frame, on the detector's stream: imm_resize_crop_u8 with the box rows the frame before left in device memory, the bucket's
+        captured program (with the keypoint epilogue, given a regressor), imm_track_step (include/imm_track.h) and a device copy of the
+        landmarks.  Between the first and the last frame's launches nothing is copied to the host and the stream is not synchronised."""
+        from . import tracking as TR
+        frames, rows, beta, _consts, chunk = TR.plan_track(frames, boxes, self.max_batch, box_smooth, one_euro, fps, chunk_frames)
+        return TR.FaceTracker(self, regressor, beta, one_euro, fps, capacity=len(frames)).run(frames, rows, chunk)
+
+    def tracker(self, regressor=None, box_smooth=0.5, one_euro=OneEuro(), fps=25.0):
+        """A tracking.FaceTracker for live input: .start(frame, boxes), .step(frame), .result() -> the Track of the frames seen so far.
+        The launches of track(), with one-frame uploads."""
+        from . import tracking as TR
+        return TR.FaceTracker(self, regressor, box_smooth, one_euro, fps)
 
     def align(self, images, template, boxes=None, model='similarity', lam=0.0, out_size=None, return_transform=False, _packed=None):
         """Every face warped so that its landmarks land on the template: f32 [n, So, So, 3] in [0, 255] on the detector's device, one

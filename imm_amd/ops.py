@@ -798,6 +798,27 @@ def unalign_u8(photos, offsets, hw, boxes, links, fwd, bbox, inv_ramp, faces, ma
          _p(faces), int(ld), n, int(So), int(max_pixels), _s())
 
 
+def track_step(mu, boxes, hw, state, image_size, next_image, init, box_smooth, min_cutoff, beta, d_cutoff, c, te, filter_off, points,
+               points_smooth, boxes_next, geom_next, flags):
+    """One frame of face tracking (include/imm_track.h: imm_track_step): mu f32 [F, K, 2] and the rows boxes i32 [F, 5] this frame was
+    cut with -> points, points_smooth f32 [F, K, 2] (source pixels), the next frame's rows boxes_next i32 [F, 5] (image index
+    next_image) with their geometry geom_next f32 [F, 4], and flags i32 [F]; state f64 [F, 5 + 6 K] (tracking.state_size) is read
+    and written.  hw i32 [images, 2]: the sizes of the photos `boxes` index.  c = 2 pi / fps and te = 1 / fps come from the host."""
+    F, K = mu.shape[0], mu.shape[1]
+    for name, t, dt, shape in (('mu', mu, torch.float32, (F, K, 2)), ('boxes', boxes, torch.int32, (F, 5)),
+                               ('state', state, torch.float64, (F, 5 + 6 * K)), ('points', points, torch.float32, (F, K, 2)),
+                               ('points_smooth', points_smooth, torch.float32, (F, K, 2)), ('boxes_next', boxes_next, torch.int32, (F, 5)),
+                               ('geom_next', geom_next, torch.float32, (F, 4)), ('flags', flags, torch.int32, (F,))):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError('%s must be contiguous %s %s, got %s %s' % (name, str(dt).replace('torch.', ''), list(shape), t.dtype,
+                                                                         tuple(t.shape)))
+    if hw.dtype != torch.int32 or hw.dim() != 2 or hw.shape[1] != 2 or not hw.is_contiguous():
+        raise ValueError('hw must be contiguous int32 [images, 2], got %s %s' % (hw.dtype, tuple(hw.shape)))
+    call('imm_track_step', _p(mu), _p(boxes), _p(hw), _p(state), int(K), int(image_size), int(F), int(hw.shape[0]), int(next_image),
+         int(init), float(box_smooth), float(min_cutoff), float(beta), float(d_cutoff), float(c), float(te), int(bool(filter_off)),
+         _p(points), _p(points_smooth), _p(boxes_next), _p(geom_next), _p(flags), _s())
+
+
 def masked_sse_pool(a, b, batch, s, c, mask, S, partial, pool_a, pool_b):
     call('imm_masked_sse_pool', _p(a), _p(b), dtype_enum(a.dtype), batch, s, c, _p(mask), S, _p(partial), _p(pool_a), _p(pool_b), _s())
 

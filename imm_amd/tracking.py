@@ -1,0 +1,300 @@
+"""Face tracking: the boxes follow the landmarks from frame to frame.
+
+Every program of the detector works on a face box per row.  For a clip the caller has the boxes of its first frame only; here the
+box of every later frame comes from the landmarks of the frame before it, on the device:
+
+    tr = det.track(frames, boxes)                       # frames: T u8 HWC arrays, boxes: the faces of frames[0]
+    tr.points, tr.points_smooth                         # f32 [T, F, K, 2] source pixels (y, x); tr.boxes int32 [T, F, 4]; tr.lost
+    live = det.tracker(); live.start(frame0, boxes); live.step(frame1); ...; live.result()
+
+Per frame, on the detector's stream: imm_resize_crop_u8 with the box rows in device memory, the captured pose program of the bucket,
+imm_track_step (include/imm_track.h states the rule once: landmarks -> source pixels -> similarity fit of the first frame's shape ->
+box filter -> the next frame's box row and geometry -> One-Euro filter of the points), and a device copy of the landmarks into the
+result.  Nothing comes back to the host between a clip's first and last launch.
+
+This module holds the host side: OneEuro (the filter's constants), plan_track (every argument checked before anything reaches the
+device), the state layout, Track (the result) and FaceTracker (the launches).  It imports without a GPU."""
+import math
+
+import numpy as np
+import torch
+
+from . import keypoints as KP
+
+STATE_HEAD = 5                # h0, w0, cy, cx, s in front of z0, xhat, dxhat (include/imm_track.h)
+FLAG_LOST, FLAG_OUTSIDE = 1, 2
+
+
+def state_size(K):
+    """f64 values of one face's state: (h0, w0, cy, cx, s), then z0, xhat, dxhat [K, 2] each."""
+    return STATE_HEAD + 6 * int(K)
+
+
+def state_views(state, K):
+    """One face's (or [F, ..] faces') state split into named views: h0w0 [.., 2], box [.., 3] = (cy, cx, s), z0, xhat, dxhat [.., K, 2]."""
+    K = int(K)
+    lead = state.shape[:-1]
+    part = lambda i: state[..., STATE_HEAD + 2 * K * i:STATE_HEAD + 2 * K * (i + 1)].reshape(lead + (K, 2))
+    return {'h0w0': state[..., 0:2], 'box': state[..., 2:5], 'z0': part(0), 'xhat': part(1), 'dxhat': part(2)}
+
+
+class OneEuro(object):
+    """The constants of the One-Euro filter (Casiez, Roussel, Vogel 2012) of the tracked points: the cutoff of the low-pass is
+    min_cutoff + beta * |speed| Hz, the speed (in box heights per second) itself low-passed at d_cutoff Hz.  Conventional values;
+    they are not tuned against video here."""
+
+    def __init__(self, min_cutoff=1.0, beta=0.05, d_cutoff=1.0):
+        self.min_cutoff, self.beta, self.d_cutoff = float(min_cutoff), float(beta), float(d_cutoff)
+        for name in ('min_cutoff', 'd_cutoff'):
+            v = getattr(self, name)
+            if not (math.isfinite(v) and v > 0):
+                raise ValueError('%s must be finite and positive, got %r' % (name, v))
+        if not (math.isfinite(self.beta) and self.beta >= 0):
+            raise ValueError('beta must be finite and >= 0, got %r' % (self.beta,))
+
+    def __repr__(self):
+        return 'OneEuro(min_cutoff=%g, beta=%g, d_cutoff=%g)' % (self.min_cutoff, self.beta, self.d_cutoff)
+
+
+def filter_constants(one_euro, fps):
+    """(min_cutoff, beta, d_cutoff, c, te, filter_off) as imm_track_step takes them: c = 2 pi / fps and te = 1 / fps formed here in f64,
+    so no transcendental constant is formed on the device.  one_euro None: the filter is off (neutral constants are passed)."""
+    fps = float(fps)
+    if not (math.isfinite(fps) and fps > 0):
+        raise ValueError('fps must be finite and positive, got %r' % (fps,))
+    off = one_euro is None
+    oe = OneEuro() if off else one_euro
+    if not isinstance(oe, OneEuro):
+        raise ValueError('one_euro must be a tracking.OneEuro or None, got %r' % (one_euro,))
+    return oe.min_cutoff, oe.beta, oe.d_cutoff, 2.0 * math.pi / fps, 1.0 / fps, int(off)
+
+
+def check_box_smooth(box_smooth):
+    b = float(box_smooth)
+    if not (0.0 < b <= 1.0):
+        raise ValueError('box_smooth must lie in (0, 1], got %r' % (box_smooth,))
+    return b
+
+
+def check_first_boxes(boxes, what='frame 0'):
+    """The faces of a clip's first frame as int32 rows [F, 5] (0, y0, x0, y1, x1): keypoints.check_boxes against that one frame.
+    Rows of four values are all faces of that frame.  ValueError for a row naming another frame."""
+    rows = [list(b) for b in boxes]
+    if rows and all(len(r) == 4 for r in rows):
+        rows = [[0] + r for r in rows]
+    try:
+        return KP.check_boxes(rows, 1)
+    except ValueError as e:
+        if 'names image' in str(e):
+            raise ValueError('%s: every box row must name %s (image index 0)' % (e, what))
+        raise
+
+
+def plan_track(frames, boxes, n_faces_max, box_smooth=0.5, one_euro=OneEuro(), fps=25.0, chunk_frames=32):
+    """track()'s arguments checked on the host, before anything reaches the device: (frames as decoded u8 arrays, box rows int32
+    [F, 5], box_smooth, filter constants (filter_constants), chunk_frames).  n_faces_max: the detector's max_batch."""
+    from .inference import decode_u8
+    if not isinstance(frames, (list, tuple)):
+        raise ValueError('track needs the frames as a list of u8 HWC arrays (a tensor batch holds no photo to cut boxes from)')
+    if len(frames) == 0:
+        raise ValueError('no frames')
+    try:
+        frames = decode_u8(frames)
+    except TypeError as e:
+        raise ValueError(str(e))
+    rows = check_first_boxes(boxes)
+    if len(rows) > int(n_faces_max):
+        raise ValueError('%d faces, the detector\'s max_batch is %d' % (len(rows), int(n_faces_max)))
+    chunk = int(chunk_frames)
+    if chunk < 1:
+        raise ValueError('chunk_frames must be >= 1, got %r' % (chunk_frames,))
+    return frames, rows, check_box_smooth(box_smooth), filter_constants(one_euro, fps), chunk
+
+
+class Track(object):
+    """What tracking returns, T frames by F faces, tensors on the detector's device (or the host after .cpu()):
+    mu f32 [T, F, K, 2] the landmarks (y, x) in [-1, 1] of each frame's box; points f32 [T, F, K, 2] the same in source pixels;
+    points_smooth f32 [T, F, K, 2] after the One-Euro filter; boxes int32 [T, F, 4] the box (y0, x0, y1, x1) each frame was cut
+    with; flags int32 [T, F] (bit 0 lost, bit 1 the next box left the photo); keypoints f32 [T, F, M, 2] with a regressor, else None."""
+
+    def __init__(self, mu, points, points_smooth, boxes, flags, keypoints=None):
+        self.mu, self.points, self.points_smooth, self.boxes, self.flags, self.keypoints = mu, points, points_smooth, boxes, flags, keypoints
+
+    def __len__(self):
+        return int(self.mu.shape[0])
+
+    @property
+    def lost(self):
+        """bool [T, F]: the fit of that frame was unusable (a non-finite landmark, a degenerate shape); the box was kept."""
+        return (self.flags & FLAG_LOST) != 0
+
+    @property
+    def outside(self):
+        """bool [T, F]: the box made from that frame does not intersect the photo the frame was cut from."""
+        return (self.flags & FLAG_OUTSIDE) != 0
+
+    def cpu(self):
+        from . import ops
+        get = lambda t: None if t is None else ops.download(t.contiguous())
+        return Track(get(self.mu), get(self.points), get(self.points_smooth), get(self.boxes), get(self.flags), get(self.keypoints))
+
+
+class FaceTracker(object):
+    """Tracking of live input: start(frame, boxes) with the faces of the first frame, then step(frame) per frame; result() is the
+    Track of the frames seen so far (views of the tracker's buffers).  LandmarkDetector.track is start + step over a clip with the
+    frames uploaded chunk_frames at a time.
+    Every frame is issued on the detector's stream without a device -> host copy and without synchronising that stream; the host
+    waits only for its own uploads, on a side stream.  With a regressor the geometry rows of the detector (the keypoint epilogue's
+    input) are written by each frame for the next one: keypoints() or align() calls on the same detector between two steps of such a
+    tracker overwrite them."""
+
+    def __init__(self, detector, regressor=None, box_smooth=0.5, one_euro=OneEuro(), fps=25.0, capacity=64):
+        self.det = detector
+        self.reg = regressor
+        if regressor is not None:
+            regressor.check(detector.K, detector.S)
+            regressor.epilogue_weights()
+        self.box_smooth = check_box_smooth(box_smooth)
+        self.consts = filter_constants(one_euro, fps)
+        self.capacity = max(1, int(capacity))
+        self.t = 0
+        self.F = 0
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    def _alloc(self, cap):
+        det, F, K = self.det, self.F, self.det.K
+        dev = det.dev
+        bufs = {'mu': torch.empty(cap, F, K, 2, device=dev), 'points': torch.empty(cap, F, K, 2, device=dev),
+                'smooth': torch.empty(cap, F, K, 2, device=dev), 'flags': torch.empty(cap, F, dtype=torch.int32, device=dev),
+                'boxes': torch.zeros(cap + 1, F, 5, dtype=torch.int32, device=dev)}
+        if self.reg is not None:
+            bufs['kp'] = torch.empty(cap, F, self.reg.M, 2, device=dev)
+        return bufs
+
+    def _grow(self):
+        """Twice the frames (device copies on the detector's stream, which is current; the old buffers stay valid for results handed
+        out).  The new buffers are read on the caller's stream later: the allocator is told."""
+        old, t = self._bufs, self.t
+        self.capacity *= 2
+        new = self._alloc(self.capacity)
+        for k, v in old.items():
+            n = t + 1 if k == 'boxes' else t
+            new[k][:n].copy_(v[:n])
+            new[k].record_stream(self._cur)
+        self._bufs = new
+
+    def _upload(self, frames):
+        """Decoded u8 frames packed into one device buffer on the upload stream: (src, offsets, hw, count).  The detector's stream
+        waits for the copies on the device."""
+        from .inference import pack_u8
+        det = self.det
+        up = getattr(det, '_upload_stream', None)
+        if up is None:
+            up = det._upload_stream = torch.cuda.Stream(device=det.dev)
+        with torch.cuda.device(det.dev), torch.cuda.stream(up):
+            src, offs_d, hw_d, _ = pack_u8(frames, det.dev)
+        det.stream.wait_stream(up)
+        for t in (src, offs_d, hw_d):
+            t.record_stream(det.stream)
+        return src, offs_d, hw_d, len(frames)
+
+    def _begin(self, rows):
+        """Buffers, the first frame's box rows and geometry, the regressor's weights and the bucket's captured program: everything
+        that is not a per-frame launch.  Called with the caller's stream current."""
+        from . import ops
+        from .inference import plan_buckets
+        det = self.det
+        self.F = F = len(rows)
+        if F > det.max_batch:
+            raise ValueError('%d faces, the detector\'s max_batch is %d' % (F, det.max_batch))
+        self.bucket = plan_buckets(F, det.max_batch)[0][2]
+        self.M = None if self.reg is None else self.reg.M
+        self.t = 0
+        with torch.cuda.device(det.dev):
+            self._bufs = self._alloc(self.capacity)
+            self._state = torch.zeros(F, state_size(det.K), dtype=torch.float64, device=det.dev)
+            cur = torch.cuda.current_stream(det.dev)
+            det.stream.wait_stream(cur)
+            with torch.cuda.stream(det.stream):
+                det._ensure_capacity(self.bucket)
+                det._stager.copy(self._bufs['boxes'][0], torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)), ('track_rows', F))
+                if self.reg is not None:
+                    w, b = self.reg.epilogue_weights()
+                    det._stager.copy(det._kp_w[:w.size], torch.from_numpy(w.reshape(-1)), ('kp_w', self.M))
+                    det._stager.copy(det._kp_b[:b.size], torch.from_numpy(b), ('kp_b', self.M))
+                    det._stager.copy(det._geom[:F], torch.from_numpy(KP.box_geometry(rows, det.S)), ('geom', F))
+                key = self.bucket if self.M is None else (self.bucket, int(self.M))
+                if det.use_graph and key not in det._graphs:
+                    det._run(self.bucket, self.M)              # capture (and its synchronisation) ahead of the first frame
+
+    def _advance(self, src, offs_d, hw_d, next_image):
+        """The launches of one frame whose photo the current box rows index in (src, offs_d, hw_d); the detector's stream is current."""
+        from . import ops
+        det, t, F, bucket, M = self.det, self.t, self.F, self.bucket, self.M
+        if t == self.capacity:
+            self._grow()
+        b = self._bufs
+        rows = b['boxes'][t]
+        S = det.S
+        det._ensure_capacity(bucket)
+        ops.resize_crop_u8(src, offs_d, hw_d, 3, (S, S), (0, 0), (S, S), det._img[:F], boxes=rows)
+        if F < bucket:
+            det._img[F:bucket].zero_()
+        det._run(bucket, M)
+        mc, be, dc, c, te, off = self.consts
+        ops.track_step(det._mu[:F], rows, hw_d, self._state, S, next_image, 1 if t == 0 else 0, self.box_smooth, mc, be, dc, c, te, off,
+                       b['points'][t], b['smooth'][t], b['boxes'][t + 1], det._geom[:F], b['flags'][t])
+        b['mu'][t].copy_(det._mu[:F])
+        if M is not None:
+            b['kp'][t].copy_(det._kp[:F * M * 2].view(F, M, 2))
+        self.t = t + 1
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    def start(self, frame, boxes):
+        """The first frame of a clip and its faces (keypoints.check_boxes rows naming this frame, or (y0, x0, y1, x1) per face)."""
+        frames, rows, _b, _c, _n = plan_track([frame], boxes, self.det.max_batch)
+        self._begin(rows)
+        return self._step(frames[0])
+
+    def step(self, frame):
+        """The next frame, cut with the boxes the frame before it left on the device."""
+        from .inference import decode_u8
+        if self.F == 0:
+            raise RuntimeError('start(frame, boxes) comes first')
+        try:
+            frame = decode_u8([frame])[0]
+        except TypeError as e:
+            raise ValueError(str(e))
+        return self._step(frame)
+
+    def _step(self, frame):
+        det = self.det
+        cur = self._cur = torch.cuda.current_stream(det.dev)
+        det.stream.wait_stream(cur)
+        src, offs_d, hw_d, _n = self._upload([frame])
+        with torch.cuda.device(det.dev), torch.cuda.stream(det.stream):
+            self._advance(src, offs_d, hw_d, 0)
+        cur.wait_stream(det.stream)
+        return self
+
+    def run(self, frames, rows, chunk_frames):
+        """track(): every frame of a checked clip, uploaded chunk_frames at a time; the caller's stream waits once, at the end."""
+        det = self.det
+        self._begin(rows)
+        cur = self._cur = torch.cuda.current_stream(det.dev)
+        det.stream.wait_stream(cur)
+        for c0 in range(0, len(frames), chunk_frames):
+            src, offs_d, hw_d, count = self._upload(frames[c0:c0 + chunk_frames])
+            with torch.cuda.device(det.dev), torch.cuda.stream(det.stream):
+                for i in range(count):
+                    self._advance(src, offs_d, hw_d, i + 1 if i + 1 < count else 0)
+        cur.wait_stream(det.stream)
+        return self.result()
+
+    def result(self):
+        """The Track of the frames seen so far."""
+        if self.F == 0:
+            raise RuntimeError('start(frame, boxes) comes first')
+        b, t = self._bufs, self.t
+        return Track(b['mu'][:t], b['points'][:t], b['smooth'][:t], b['boxes'][:t, :, 1:], b['flags'][:t],
+                     b['kp'][:t] if self.reg is not None else None)

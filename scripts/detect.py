@@ -9,7 +9,13 @@ image, the convert_landmarks convention of scripts/test.py) and `sizes` [N, 2] (
 With --regressor (a file written by scripts/test.py --save-regressor) it also holds the regressed annotated points of every face:
 `keypoints` [F, M, 2] ((y, x) pixels of the source image), `boxes` [F, 4] ((y0, x0, y1, x1) source pixels, half-open) and `owner`
 [F] (the index into `files` of each face's image).  The faces are the rows of --boxes, a CSV (`file, y0, x0, y1, x1` per line) or
-JSON ([[file, y0, x0, y1, x1], ...]) file, in its order; without --boxes, one face per image, the whole image."""
+JSON ([[file, y0, x0, y1, x1], ...]) file, in its order; without --boxes, one face per image, the whole image.
+With --track the images of the folder, in sorted order, are the frames of one clip and --boxes holds the faces of its FIRST frame
+(every row names that file; no regressor needed).  The boxes of the later frames follow the landmarks on the GPU
+(LandmarkDetector.tracker, imm_amd/tracking.py), and the file holds per frame and face: `mu`, `landmarks` [T, F, K, 2], `points` and
+`points_smooth` [T, F, K, 2] ((y, x) source pixels, raw and after the One-Euro filter; --no-filter makes them equal), `boxes`
+[T, F, 4] (the box each frame was cut with), `flags` [T, F] (bit 0: lost, bit 1: the box left the photo) and, with --regressor,
+`keypoints` [T, F, M, 2].  --fps is the clip's frame rate, --box-smooth the weight of a frame in the box filter."""
 from __future__ import print_function
 
 import argparse
@@ -54,6 +60,34 @@ def read_boxes(path, files):
     return np.array(owner, dtype=np.int64), np.array(boxes, dtype=np.int64).reshape(-1, 4)
 
 
+def track(args, det, reg, files):
+    """--track: the folder as one clip, the faces of its first frame followed through it."""
+    from imm_amd.tracking import OneEuro
+    if not args.boxes:
+        raise ValueError('--track needs --boxes with the faces of the first frame')
+    owner, boxes = read_boxes(args.boxes, files)
+    if len(owner) == 0 or (owner != 0).any():
+        raise ValueError('%s: with --track every row names the first frame, %s' % (args.boxes, files[0]))
+    live = det.tracker(regressor=reg, box_smooth=args.box_smooth, one_euro=None if args.no_filter else OneEuro(), fps=args.fps)
+    sizes = []
+    for i, f in enumerate(files):                       # one decoded frame on the host at a time
+        im = decode_image(osp.join(args.images_dir, f))
+        sizes.append(im.shape[:2])
+        if i == 0:
+            live.start(im, boxes.tolist())
+        else:
+            live.step(im)
+    tr = live.result().cpu()
+    mu = tr.mu.numpy()
+    out = dict(files=np.array(files), mu=mu, landmarks=((mu + 1) / 2.0) * args.im_size, sizes=np.array(sizes, dtype=np.int32),
+               points=tr.points.numpy(), points_smooth=tr.points_smooth.numpy(), boxes=tr.boxes.numpy(), flags=tr.flags.numpy())
+    if reg is not None:
+        out['keypoints'] = tr.keypoints.numpy()
+    np.savez(args.out, **out)
+    print('%d frames, %d faces tracked, %d landmarks each -> %s (%d lost)' % (mu.shape[0], mu.shape[1], mu.shape[2], args.out,
+                                                                               int(tr.lost.sum())))
+
+
 def main(args):
     config = load_configs(args.configs)
     torch.cuda.set_device(0)
@@ -64,6 +98,8 @@ def main(args):
     det = LandmarkDetector.from_checkpoint(config.model, args.checkpoint, image_size=args.im_size, max_batch=args.batch_size,
                                            dtype=dtype, device='cuda:0')
     reg = LandmarkRegressor.load(args.regressor, detector=det) if args.regressor else None
+    if args.track:
+        return track(args, det, reg, files)
     if args.boxes and reg is None:
         raise ValueError('--boxes needs --regressor')
     owner, boxes = read_boxes(args.boxes, files) if args.boxes else (None, None)
@@ -142,4 +178,9 @@ if __name__ == '__main__':
                         help='regressor .npz of scripts/test.py --save-regressor: also write the annotated points of every face')
     parser.add_argument('--boxes', type=str, default=None,
                         help='CSV or JSON face boxes, one row `file, y0, x0, y1, x1` per face (default: each whole image)')
+    parser.add_argument('--track', action='store_true',
+                        help='the folder is one clip (frames in sorted order): follow the faces of --boxes, given for its first frame')
+    parser.add_argument('--fps', type=float, default=25.0, help='--track: the frame rate of the clip')
+    parser.add_argument('--box-smooth', type=float, default=0.5, help='--track: the weight of a frame in the box filter, in (0, 1]')
+    parser.add_argument('--no-filter', action='store_true', help='--track: no One-Euro filter (points_smooth equals points)')
     main(parser.parse_args())

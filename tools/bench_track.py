@@ -1,0 +1,144 @@
+"""Frames/s of face tracking: LandmarkDetector.track (the box of every frame made on the GPU from the landmarks of the frame before,
+imm_track_step) against the loop a user writes without it: per frame landmarks([frame], boxes), .cpu(), and the box update of
+include/imm_track.h in vectorised numpy on the host.  64 frames of 512 x 384 at F = 1, 4, 16 faces, S = 128, K = 10, bf16; writes
+the table to profiles/track_bench.txt.
+
+Both sides are wall-clock times of the whole clip (the loop synchronises every frame by construction, so stream events would not
+see its host share), from the call to a final synchronisation.  After untimed warm-up runs of both, the two sides alternate, one
+clip each per window; the table gives the median and the range over the windows.
+Usage: python tools/bench_track.py [--faces 1 4 16] [--frames 64] [--windows 7]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from imm_amd.models.imm_model import IMMModel             # noqa: E402
+from imm_amd.tracking import OneEuro                      # noqa: E402
+from bench_detect import model_config                     # noqa: E402
+
+OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'track_bench.txt')
+
+
+class HostTracker(object):
+    """The box update on the host, vectorised over the faces: the rule of include/imm_track.h in numpy f64 (not its bit-exact
+    restatement, which tests/track_reference.py is: numpy's own summation order)."""
+
+    def __init__(self, S, beta, one_euro, fps):
+        self.S, self.beta, self.oe, self.c, self.te, self.state = S, beta, one_euro, 2 * np.pi / fps, 1.0 / fps, None
+
+    def alpha(self, fc):
+        return 1.0 / (1.0 + 1.0 / (self.c * fc))
+
+    def update(self, mu, rows):
+        b = rows[:, 1:].astype(np.float64)
+        side = np.stack([b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], 1)
+        scale = (side.astype(np.float32) / np.float32(self.S)).astype(np.float64)
+        p = b[:, None, :2] + (mu.astype(np.float64) + 1.0) * 0.5 * self.S * scale[:, None]
+        centre = (b[:, :2] + b[:, 2:]) * 0.5
+        if self.state is None:
+            self.state = dict(z0=p - centre[:, None], side=side, c=centre.copy(), s=np.ones(len(b)), xhat=p.copy(), dxhat=np.zeros_like(p))
+        st = self.state
+        z = st['z0'][..., 0] + 1j * st['z0'][..., 1]
+        q = p[..., 0] + 1j * p[..., 1]
+        sc = z - z.mean(1, keepdims=True)
+        den = (np.abs(sc) ** 2).sum(1)
+        with np.errstate(all='ignore'):
+            a = (np.conj(sc) * (q - q.mean(1, keepdims=True))).sum(1) / den
+            m = q.mean(1) - a * z.mean(1)
+            ms = np.abs(a)
+            ok = np.isfinite(mu).all((1, 2)) & (den != 0) & np.isfinite(m) & np.isfinite(ms) & (ms > 0)
+            st['c'][ok] += self.beta * (np.stack([m.real, m.imag], 1) - st['c'])[ok]
+            st['s'][ok] += self.beta * (ms - st['s'])[ok]
+            hw = np.clip(np.rint(st['s'][:, None] * st['side']), 2, 2 ** 22)
+            o = np.clip(np.rint(st['c'] - hw * 0.5), -2 ** 23, 2 ** 23)
+            if self.oe is not None:
+                dx = (p - st['xhat']) / (self.te * side[:, :1, None])
+                dh = st['dxhat'] + self.alpha(self.oe.d_cutoff) * (dx - st['dxhat'])
+                xh = st['xhat'] + self.alpha(self.oe.min_cutoff + self.oe.beta * np.abs(dh)) * (p - st['xhat'])
+                st['dxhat'][ok], st['xhat'][ok] = dh[ok], xh[ok]
+        nxt = np.concatenate([np.zeros((len(b), 1)), o, o + hw], 1).astype(np.int32)
+        return p, (st['xhat'].copy() if self.oe is not None else p), nxt
+
+
+def user_loop(det, frames, boxes, beta, one_euro, fps):
+    rows = np.array([(0,) + tuple(b) for b in boxes], dtype=np.int32)
+    host = HostTracker(det.S, beta, one_euro, fps)
+    out = []
+    for f in frames:
+        mu = det.landmarks([f], rows.tolist()).cpu().numpy()
+        p, smooth, rows = host.update(mu, rows)
+        out.append((mu, p, smooth))
+    return out
+
+
+def wall_ms(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def main(args):
+    torch.cuda.set_device(0)
+    dev = 'cuda:0'
+    S, K, T = 128, 10, args.frames
+    rng = np.random.RandomState(0)
+    frames = [rng.randint(0, 256, size=(512, 384, 3)).astype(np.uint8) for _ in range(T)]
+    props = torch.cuda.get_device_properties(0)
+    lines = ['device: %s (%s, %d CUs)' % (props.name, props.gcnArchName, props.multi_processor_count),
+             'S %d, K %d, bf16; %d u8 frames of 512 x 384, F faces of 160 x 128 px; box_smooth 0.5, OneEuro(), 25 fps' % (S, K, T),
+             'wall-clock ms per clip, the two sides alternating, median (min .. max) of %d windows after %d warm-up clips each' % (
+                 args.windows, args.warmup),
+             'loop  = per frame: landmarks([frame], boxes), .cpu(), the box update in numpy on the host',
+             'track = LandmarkDetector.track(frames, boxes, chunk_frames=32)',
+             '%4s %30s %30s %12s %12s %8s' % ('F', 'loop ms', 'track ms', 'loop fr/s', 'track fr/s', 'ratio')]
+    rows = []
+    for F in args.faces:
+        boxes = [(20 + 19 * (i % 16), 10 + 13 * (i % 16), 180 + 19 * (i % 16), 138 + 13 * (i % 16)) for i in range(F)]
+        model = IMMModel(model_config(K), dtype=torch.bfloat16, device=dev)
+        x = torch.zeros(max(F, 2), S, S, 3, device=dev)
+        model.build({'image': x, 'future_image': x}, training_pl=False, build_loss=False)
+        det = model.landmark_detector(S, max_batch=max(F, 1))
+        oe = OneEuro()
+        loop = lambda: user_loop(det, frames, boxes, 0.5, oe, 25.0)
+        track = lambda: det.track(frames, boxes, box_smooth=0.5, one_euro=oe, fps=25.0, chunk_frames=32)
+        for _ in range(args.warmup):
+            loop()
+            track()
+        t_loop, t_track = [], []
+        for _ in range(args.windows):
+            t_loop.append(wall_ms(loop))
+            t_track.append(wall_ms(track))
+        ml, mt = float(np.median(t_loop)), float(np.median(t_track))
+        row = {'faces': F, 'frames': T, 'loop_ms': ml, 'track_ms': mt, 'loop_ms_all': t_loop, 'track_ms_all': t_track,
+               'loop_frames_per_s': T / ml * 1e3, 'track_frames_per_s': T / mt * 1e3, 'loop_over_track': ml / mt}
+        rows.append(row)
+        fmt = lambda v: '%8.2f (%7.2f .. %7.2f)' % (float(np.median(v)), min(v), max(v))
+        lines.append('%4d %30s %30s %12.0f %12.0f %8.2f' % (F, fmt(t_loop), fmt(t_track), row['loop_frames_per_s'],
+                                                            row['track_frames_per_s'], row['loop_over_track']))
+        print(lines[-1], flush=True)
+        del det, model
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write(text)
+    print(json.dumps({'image_size': S, 'n_maps': K, 'dtype': 'bf16', 'rows': rows}))
+
+
+if __name__ == '__main__':
+    p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    p.add_argument('--faces', type=int, nargs='+', default=[1, 4, 16])
+    p.add_argument('--frames', type=int, default=64)
+    p.add_argument('--windows', type=int, default=7)
+    p.add_argument('--warmup', type=int, default=2)
+    p.add_argument('--out', type=str, default=OUT)
+    main(p.parse_args())
