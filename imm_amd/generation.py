@@ -34,6 +34,7 @@ from .inference import (LandmarkDetector, _Launch, alloc_encoder_weights, as_ima
                         encoder_act_elems, fold_batch_norm, folded_encoder_program, pack_folded_encoder, pack_u8, plan_buckets,
                         read_variables, stage_u8)
 from .keypoints import check_boxes
+from .tracking import OneEuro
 
 IMAGE_SCOPE = 'model/image_encoder'
 RENDER_SCOPE = 'model/renderer'
@@ -505,6 +506,27 @@ class ImageGenerator(object):
             offs.append(offs[-1] + ((a.size + 15) & ~15))
         out = [canvas[o:o + a.size].view(a.shape) for o, a in zip(offs, photos)]
         return (out, faces, lm.contiguous()) if return_faces else out
+
+    def reenact(self, photos, frames, driver_box, boxes=None, motion='relative', rigid=True, gain=1.0, smooth=True, feather=0.125,
+                paste=True, box_smooth=0.5, one_euro=OneEuro(), fps=25.0, chunk_frames=32, return_faces=False, template=None, model=None):
+        """A driving clip animates the faces of still photos: a reenact.Reenactment (landmarks f32 [T, n, K, 2] the poses rendered,
+        flags int32 [T, n] / held, faces f32 [T, n, S, S, 3] with return_faces=True, frames[t][i] photo i at frame t as u8 [h_i, w_i, 3]
+        with paste=True, track the driver's tracking.Track) on the generator's device.
+        photos / boxes: as repose() takes them, n rows, n <= max_batch.  frames / driver_box: a clip, a list of T u8 HWC arrays, and the
+        ONE driving face (y0, x0, y1, x1) of its first frame, as detector.track takes them (box_smooth, one_euro, fps, chunk_frames
+        likewise).  motion 'relative': the driver's motion since its first frame is added to each face's own landmarks; 'absolute': the
+        driver's shape itself is laid over each face.  rigid=False: the driver's head motion (turn, size, shift) is divided out first, so
+        only its expression moves the faces.  gain in [0, 4] scales the motion (0: the faces' own poses).  smooth=False reads the
+        tracker's raw points instead of its One-Euro filtered ones.  feather: as in repose().
+        The photos are uploaded, cut and encoded once; per frame the tracker's launches, imm_retarget (include/imm_retarget.h states
+        the rule), the captured render program and one imm_compose_u8 launch are queued, and nothing returns to the host between the
+        clip's first and last launch (imm_amd/reenact.py).  A face whose rule has no usable answer on a frame, and every face on a frame
+        that lost the driver, keeps its pose of the frame before (flags bit 0).  template= (re-enactment in the aligned frame), model=
+        (tps, affine) and several drivers are not implemented and raise."""
+        from . import reenact as RE
+        plan = RE.plan_reenact(photos, frames, driver_box, boxes, self.max_batch, motion, rigid, gain, smooth, feather, paste, box_smooth,
+                               one_euro, fps, chunk_frames, template, model)
+        return RE.run(self, plan, return_faces)
 
     def _repose_aligned(self, photos, poses, boxes, pose_boxes, feather, return_faces, template, model):
         """repose() with a template: align -> encode -> render -> paste through the inverse map.  The photos are packed once: the

@@ -819,6 +819,22 @@ def track_step(mu, boxes, hw, state, image_size, next_image, init, box_smooth, m
          _p(points), _p(points_smooth), _p(boxes_next), _p(geom_next), _p(flags), _s())
 
 
+def retarget(q, anchor, driver_flags, m, prev, init, relative, rigid, gain, out, flags):
+    """One frame of re-enactment (include/imm_retarget.h: imm_retarget): the driver's points q f32 [K, 2] of this frame, the anchor f64
+    [K, 2] (set to q with init) and the driver's track_step flags i32 [1] -> the poses out f32 [n, K, 2] of the source faces with the
+    landmarks m f32 [n, K, 2], and flags i32 [n] (bit 0: held, out = prev f32 [n, K, 2]).  out may be prev."""
+    n, K = m.shape[0], m.shape[1]
+    for name, t, dt, shape in (('q', q, torch.float32, (K, 2)), ('anchor', anchor, torch.float64, (K, 2)),
+                               ('driver_flags', driver_flags, torch.int32, (1,)), ('m', m, torch.float32, (n, K, 2)),
+                               ('prev', prev, torch.float32, (n, K, 2)), ('out', out, torch.float32, (n, K, 2)),
+                               ('flags', flags, torch.int32, (n,))):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError('%s must be contiguous %s %s, got %s %s' % (name, str(dt).replace('torch.', ''), list(shape), t.dtype,
+                                                                         tuple(t.shape)))
+    call('imm_retarget', _p(q), _p(anchor), _p(driver_flags), _p(m), _p(prev), int(K), int(n), int(init), int(bool(relative)),
+         int(bool(rigid)), float(gain), _p(out), _p(flags), _s())
+
+
 def masked_sse_pool(a, b, batch, s, c, mask, S, partial, pool_a, pool_b):
     call('imm_masked_sse_pool', _p(a), _p(b), dtype_enum(a.dtype), batch, s, c, _p(mask), S, _p(partial), _p(pool_a), _p(pool_b), _s())
 

@@ -1,0 +1,209 @@
+"""Re-enactment: a tracked driving clip animates the faces of still photos.
+
+    r = gen.reenact(photos, frames, driver_box, boxes)     # photos: u8 arrays, boxes: their n faces; frames: T u8 arrays,
+    r.frames[t][i]                                         # driver_box: the ONE driving face of frames[0]; photo i at frame t, u8
+    r.landmarks, r.flags, r.held, r.faces, r.track         # f32 [T, n, K, 2], int32 [T, n], bool [T, n], f32 [T, n, S, S, 3], a Track
+
+Once per call the photos are packed and uploaded, the n boxes cut (imm_resize_crop_u8), the appearance stage of the generator run (its
+features stay in the joint buffer: the render stage writes the Gaussian-map channels only) and the faces' own landmarks m detected.
+Per frame, without anything returning to the host between the clip's first and last launch:
+
+    detector's stream     the tracker's frame (FaceTracker._advance with the one driver face: crop, pose program, imm_track_step, copy)
+                          imm_retarget: that frame's points_smooth (or points) and flags -> landmarks[t]; a held face keeps landmarks[t - 1]
+    generator's stream    waits for the detector's; landmarks[t] -> the render stage's input; the captured render program of the bucket;
+                          the packed photos copied into slot t of the result and one imm_compose_u8 launch into it
+
+include/imm_retarget.h states once how a driver's landmarks become the pose of a different face: the similarity of the driver's
+first-frame shape onto the face's own landmarks carries the driver's motion since its first frame ('relative') or its shape itself
+('absolute') into the face's box; rigid=False first divides the driver's head motion out, so that only its expression moves the face.
+
+This module holds the host side: plan_reenact (every argument checked before anything reaches the device), Reenactment (the result)
+and run (the launches).  It imports without a GPU."""
+import math
+
+import numpy as np
+import torch
+
+from . import tracking as TR
+
+MOTIONS = ('relative', 'absolute')
+FLAG_HELD = 1
+GAIN_MAX = 4.0
+
+
+def check_motion(motion):
+    if motion not in MOTIONS:
+        raise ValueError('motion must be one of %s, got %r' % (', '.join(repr(m) for m in MOTIONS), motion))
+    return motion
+
+
+def check_gain(gain):
+    g = float(gain)
+    if not (math.isfinite(g) and 0.0 <= g <= GAIN_MAX):
+        raise ValueError('gain must be finite and lie in [0, %g], got %r' % (GAIN_MAX, gain))
+    return g
+
+
+def check_driver_box(driver_box):
+    """The ONE driving face of the clip's first frame as an int32 row [1, 5]: (y0, x0, y1, x1), (0, y0, x0, y1, x1) or a list of one such."""
+    box = driver_box
+    if isinstance(box, np.ndarray):
+        box = box.tolist()
+    if isinstance(box, (list, tuple)) and len(box) in (4, 5) and all(np.isscalar(v) for v in box):
+        box = [box]
+    if not isinstance(box, (list, tuple)):
+        raise ValueError('driver_box must be the box (y0, x0, y1, x1) of the one driving face of frames[0], got %r' % (driver_box,))
+    if len(box) != 1:
+        raise ValueError('%d driver faces: re-enactment follows ONE driving face (several drivers are not implemented); give the box '
+                         '(y0, x0, y1, x1) of that face in frames[0]' % len(box))
+    return TR.check_first_boxes(box, 'frames[0]')
+
+
+class ReenactPlan(object):
+    """reenact()'s checked arguments."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def plan_reenact(photos, frames, driver_box, boxes=None, max_batch=128, motion='relative', rigid=True, gain=1.0, smooth=True,
+                 feather=0.125, paste=True, box_smooth=0.5, one_euro=TR.OneEuro(), fps=25.0, chunk_frames=32, template=None, model=None):
+    """reenact()'s arguments checked on the host, before anything reaches the device: a ReenactPlan of the photos as decoded u8 arrays,
+    their box rows int32 [n, 5], the frames as decoded u8 arrays, the driver's row int32 [1, 5], and the checked settings."""
+    from .generation import NEEDS_U8, check_feather
+    from .inference import decode_u8
+    from .keypoints import check_boxes
+    if template is not None:
+        raise NotImplementedError('reenact with a template (re-enactment in the aligned frame) is not implemented: the faces are '
+                                  'rendered in their raw box crops')
+    if model is not None:
+        raise NotImplementedError('reenact carries the driver\'s motion over with a similarity; model=%r (the tps and affine models) '
+                                  'is not implemented' % (model,))
+    motion, gain, feather = check_motion(motion), check_gain(gain), check_feather(feather)
+    if not isinstance(photos, (list, tuple)):
+        raise ValueError(NEEDS_U8)
+    if len(photos) == 0:
+        raise ValueError('no photos')
+    try:
+        photos = decode_u8(photos)
+    except TypeError as e:
+        raise ValueError(str(e))
+    rows = check_boxes([(0, 0, a.shape[0], a.shape[1]) for a in photos] if boxes is None else boxes, len(photos))
+    if len(rows) > int(max_batch):
+        raise ValueError('%d faces, the generator\'s max_batch is %d' % (len(rows), int(max_batch)))
+    drow = check_driver_box(driver_box)
+    frames, drow, beta, consts, chunk = TR.plan_track(frames, drow, max_batch, box_smooth, one_euro, fps, chunk_frames)
+    return ReenactPlan(photos=photos, rows=rows, frames=frames, driver_row=drow, relative=motion == 'relative', rigid=bool(rigid), gain=gain,
+                       smooth=bool(smooth), feather=feather, paste=bool(paste), box_smooth=beta, one_euro=one_euro, fps=float(fps),
+                       chunk_frames=chunk)
+
+
+class Reenactment(object):
+    """What reenact returns, T frames by n source faces, tensors on the generator's device:
+    landmarks f32 [T, n, K, 2] the poses rendered ((y, x) in [-1, 1] of each face's box); flags int32 [T, n] (bit 0 held: the pose of
+    the frame before was kept); faces f32 [T, n, S, S, 3] the generated faces, or None; frames: with paste, frames[t][i] is photo i at
+    frame t, u8 [h_i, w_i, 3], views of one [T, packed] device buffer, else None; track: the driver's tracking.Track."""
+
+    def __init__(self, landmarks, flags, faces, frames, track):
+        self.landmarks, self.flags, self.faces, self.frames, self.track = landmarks, flags, faces, frames, track
+
+    def __len__(self):
+        return int(self.landmarks.shape[0])
+
+    @property
+    def held(self):
+        """bool [T, n]: the driver was lost on that frame or the rule had no usable answer for that face; its pose was kept."""
+        return (self.flags & FLAG_HELD) != 0
+
+
+def check_render_keeps_features(gen, bucket):
+    """The appearance features of a bucket survive its render stage: the stage's first launch writes the Gaussian maps into the joint
+    buffer's channels [8f, 8f + K) and every later one writes an activation or the prediction buffer."""
+    prog = gen.program('render', bucket)
+    if prog[0].tag != 'gauss' or any(l.tag not in ('conv', 'upsample') for l in prog[1:]):
+        raise RuntimeError('the render stage of this generator writes more of the joint buffer than the Gaussian maps: %s' % (
+            [l.tag for l in prog],))
+
+
+def run(gen, plan, return_faces=False):
+    """The launches of reenact() for a checked plan (see the module docstring); called with the caller's stream current."""
+    from . import ops
+    from .generation import compose_inv_ramp, compose_links
+    from .inference import pack_u8, plan_buckets
+    det, S, K, dev = gen.detector, gen.S, gen.K, gen.dev
+    photos, rows, frames = plan.photos, plan.rows, plan.frames
+    n, T = len(rows), len(frames)
+    bucket = plan_buckets(n, gen.max_batch)[0][2]
+    area = (rows[:, 3] - rows[:, 1]).astype(np.int64) * (rows[:, 4] - rows[:, 2]).astype(np.int64)
+    max_pixels = int(min(area.max(), 2 ** 31 - 1))
+    cur = torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev):
+        src, offs_d, hw_d, boxes_d = pack_u8(photos, dev, rows)                     # all photos, once per call
+        shared = [src, offs_d, hw_d, boxes_d]
+        if plan.paste:
+            links_d = ops.to_device_pinned(compose_links(rows), dev)
+            ramp_d = ops.to_device_pinned(compose_inv_ramp(rows, plan.feather), dev)
+            canvas = torch.empty(T, src.numel(), dtype=torch.uint8, device=dev)
+            shared += [links_d, ramp_d, canvas]
+        m = torch.empty(n, K, 2, device=dev)
+        lm = torch.empty(T, n, K, 2, device=dev)
+        flags = torch.empty(T, n, dtype=torch.int32, device=dev)
+        anchor = torch.zeros(K, 2, dtype=torch.float64, device=dev)
+        faces = torch.empty(T, n, S, S, 3, device=dev) if return_faces else None
+        shared += [m, lm, flags, anchor] + ([faces] if return_faces else [])
+        # once per call, on the detector's stream: the faces' own landmarks (detector.landmarks(photos, boxes), from the packed photos)
+        det.stream.wait_stream(cur)
+        with torch.cuda.stream(det.stream):
+            det._ensure_capacity(bucket)
+            ops.resize_crop_u8(src, offs_d, hw_d, 3, (S, S), (0, 0), (S, S), det._img[:n], boxes=boxes_d)
+            if n < bucket:
+                det._img[n:bucket].zero_()
+            det._run(bucket)
+            m.copy_(det._mu[:n])
+        # once per call, on the generator's stream: the appearance of every face, which stays in the joint buffer
+        gen.stream.wait_stream(cur)
+        with torch.cuda.stream(gen.stream):
+            gen._ensure_capacity(bucket)
+            check_render_keeps_features(gen, bucket)
+            ops.resize_crop_u8(src, offs_d, hw_d, 3, (S, S), (0, 0), (S, S), gen._img[:n], boxes=boxes_d)
+            if n < bucket:
+                gen._img[n:bucket].zero_()
+            gen._mu[:bucket].zero_()
+            if gen.use_graph and ('render', bucket) not in gen._graphs:
+                gen._run('render', bucket)                     # capture (and its synchronisation) ahead of the first frame
+            gen._run('appearance', bucket)
+    tracker = TR.FaceTracker(det, None, plan.box_smooth, plan.one_euro, plan.fps, capacity=T)
+    tracker._begin(plan.driver_row)
+    tracker._cur = cur
+    det.stream.wait_stream(cur)
+    which = 'smooth' if plan.smooth else 'points'
+    for c0 in range(0, T, plan.chunk_frames):
+        fsrc, foffs_d, fhw_d, count = tracker._upload(frames[c0:c0 + plan.chunk_frames])
+        for i in range(count):
+            t = c0 + i
+            with torch.cuda.device(dev), torch.cuda.stream(det.stream):
+                tracker._advance(fsrc, foffs_d, fhw_d, i + 1 if i + 1 < count else 0)
+                b = tracker._bufs                              # per-frame slots: nothing a later frame overwrites is read below
+                ops.retarget(b[which][t, 0], anchor, b['flags'][t], m, lm[t - 1] if t else m, int(t == 0), plan.relative, plan.rigid,
+                             plan.gain, lm[t], flags[t])
+            gen.stream.wait_stream(det.stream)
+            with torch.cuda.device(dev), torch.cuda.stream(gen.stream):
+                gen._mu[:n].copy_(lm[t])
+                gen._run('render', bucket)
+                if plan.paste:
+                    canvas[t].copy_(src)
+                    ops.compose_u8(canvas[t], offs_d, hw_d, boxes_d, links_d, ramp_d, gen._pred[:n], max_pixels)
+                if return_faces:
+                    faces[t].copy_(gen._pred[:n, ..., :3])
+    cur.wait_stream(det.stream)
+    cur.wait_stream(gen.stream)
+    for x in shared:
+        x.record_stream(det.stream)
+        x.record_stream(gen.stream)
+    out = None
+    if plan.paste:
+        offs = [0]
+        for a in photos[:-1]:
+            offs.append(offs[-1] + ((a.size + 15) & ~15))
+        out = [[canvas[t, o:o + a.size].view(a.shape) for o, a in zip(offs, photos)] for t in range(T)]
+    return Reenactment(lm, flags, faces, out, tracker.result())
