@@ -707,6 +707,71 @@ class LandmarkDetector(object):
                                      rows if u8 else None)
         return out
 
+    def warp(self, photos, poses, boxes=None, pose_boxes=None, feather=0.125, anchors=2, lam=0.0, strength=1.0, return_transform=False):
+        """The photos with every box's face re-posed from the photo's OWN pixels: a list of u8 device tensors [h_i, w_i, 3], one per
+        photo, views of one packed buffer (as ImageGenerator.repose returns them); nothing is rendered.
+        photos, boxes, poses, pose_boxes: as ImageGenerator.repose takes them (a list of u8 arrays; n box rows, by default one
+        whole-photo box per photo; landmarks f32 [n, K, 2] or [1, K, 2] in the box frame, or a list of u8 pose photos whose landmarks
+        are detector.landmarks(poses, pose_boxes)).  Per row a thin-plate spline is fitted on the device (imm_warp_fit) that carries the
+        target landmarks back to the face's own landmarks and `anchors` points per side of the box border (corners included; 0: none)
+        to themselves; every pixel of the box then takes the original photo's value at the place the spline sends it to, bilinearly,
+        faded into the photo over `feather` of the box side (imm_warp_u8; include/imm_warp.h states the rule).  lam >= 0 smooths the
+        spline (0: it interpolates), strength scales the motion (0: the photo itself; 1: the pose).  K + 4 * anchors must lie in
+        [3, 80]; host poses whose control points lie closer than 1e-6 are refused.  Rows are applied in row order, each sampling the ORIGINAL pixels: an overlapping later box blends over an earlier
+        one.  A row without a usable fit (coincident control points, a landmark that is not finite) leaves its box alone.
+        Per bucket: imm_resize_crop_u8 from the original pixels, the captured pose program, imm_warp_fit reading the pose head's
+        landmarks in place, imm_warp_u8, all on the detector's stream; nothing returns to the host.
+        return_transform=True: (photos, a warping.PhotoWarp: coef, ctrl, rows, mu, poses, flags, to_source)."""
+        from . import warping as WP
+        from .generation import compose_inv_ramp, compose_links
+        S, K = self.S, self.K
+        photos, rows, pose, feather, m, lam, strength, M = WP.plan_warp(photos, poses, boxes, pose_boxes, feather, K, anchors, lam, strength)
+        n = len(rows)
+        if pose[0] == 'photos':
+            lm = self.landmarks(pose[1], pose[2])
+        else:
+            lm = pose[1].to(device=self.dev, dtype=torch.float32)
+        lm = (lm.expand(n, K, 2) if lm.shape[0] != n else lm).contiguous()
+        buckets = plan_buckets(n, self.max_batch)
+        links = np.concatenate([compose_links(rows[start:start + count]) for start, count, _b in buckets])
+        area = (rows[:, 3] - rows[:, 1]).astype(np.int64) * (rows[:, 4] - rows[:, 2]).astype(np.int64)
+        cur = torch.cuda.current_stream(self.dev)
+        with torch.cuda.device(self.dev):
+            src, offs_d, hw_d, boxes_d = pack_u8(photos, self.dev, rows)            # all photos, once per call
+            canvas = src.clone()
+            links_d = ops.to_device_pinned(links, self.dev)
+            ramp_d = ops.to_device_pinned(compose_inv_ramp(rows, feather), self.dev)
+            anchors_d = ops.to_device_pinned(WP.warp_anchors(m).astype(np.float32), self.dev) if m else None
+            coef = torch.empty(n, M + 3, 2, device=self.dev)
+            ctrl = torch.empty(n, M, 2, device=self.dev)
+            flags = torch.empty(n, dtype=torch.int32, device=self.dev)
+            mu_out = torch.empty(n, K, 2, device=self.dev) if return_transform else None
+        self.stream.wait_stream(cur)
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            for start, count, bucket in buckets:
+                self._ensure_capacity(bucket)
+                part = slice(start, start + count)
+                ops.resize_crop_u8(src, offs_d, hw_d, 3, (S, S), (0, 0), (S, S), self._img[:count], boxes=boxes_d[part])
+                if count < bucket:
+                    self._img[count:bucket].zero_()
+                self._run(bucket)
+                ops.warp_fit(lm[part], self._mu[:count], anchors_d, strength, lam, coef[part], ctrl[part], flags[part])
+                ops.warp_u8(src, canvas, offs_d, hw_d, boxes_d[part], links_d[part], ramp_d[part], ctrl[part], coef[part],
+                            int(min(area[part].max(), 2 ** 31 - 1)))
+                if return_transform:
+                    mu_out[part].copy_(self._mu[:count])
+        cur.wait_stream(self.stream)
+        for t in (src, canvas, offs_d, hw_d, boxes_d, links_d, ramp_d, anchors_d, lm, coef, ctrl, flags, mu_out):
+            if t is not None:
+                t.record_stream(self.stream)
+        offs = [0]
+        for a in photos[:-1]:
+            offs.append(offs[-1] + ((a.size + 15) & ~15))
+        out = [canvas[o:o + a.size].view(a.shape) for o, a in zip(offs, photos)]
+        if return_transform:
+            return out, WP.PhotoWarp(coef, ctrl, rows, mu_out, lm, flags, strength, lam, m)
+        return out
+
     def unalign(self, photos, aligned, alignment, feather=0.125):
         """align() run backwards: the photos with every row's aligned face pasted back where align() took it from: a list of u8 device
         tensors [h_i, w_i, 3], one per photo, views of one packed buffer (as ImageGenerator.repose returns them).

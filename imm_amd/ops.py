@@ -835,6 +835,67 @@ def retarget(q, anchor, driver_flags, m, prev, init, relative, rigid, gain, out,
          int(bool(rigid)), float(gain), _p(out), _p(flags), _s())
 
 
+WARP_MAX_POINTS = 80          # control points of a warp spline: landmarks + border anchors
+
+
+def _check_tensors(specs):
+    for name, t, dt, shape in specs:
+        if t.dtype != dt or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise ValueError('%s must be contiguous %s %s, got %s %s' % (name, str(dt).replace('torch.', ''), list(shape), t.dtype,
+                                                                         tuple(t.shape)))
+
+
+def warp_fit(poses, mu, anchors, strength, lam, coef, ctrl, flags):
+    """The per-face thin-plate spline of LandmarkDetector.warp (include/imm_warp.h: imm_warp_fit): poses f32 [n, K, 2] (the target
+    landmarks) and mu f32 [n, K, 2] (the faces' own) with the border anchors f32 [A, 2] (None or empty: no anchors) -> coef f32
+    [n, K + A + 3, 2], ctrl f32 [n, K + A, 2] and flags i32 [n] (bit 0: no usable fit, the row's coefficients are NaN)."""
+    if poses.dim() != 3 or poses.shape[2] != 2:
+        raise ValueError('poses must be f32 [n, K, 2], got %s' % (tuple(poses.shape),))
+    n, K = int(poses.shape[0]), int(poses.shape[1])
+    A = 0 if anchors is None else int(anchors.shape[0])
+    M = K + A
+    if n < 1 or n > 65535 or K < 1 or A % 4 or not 3 <= M <= WARP_MAX_POINTS:
+        raise ValueError('warp_fit serves 1..65535 rows of K >= 1 landmarks and A = 4 m anchors with 3 <= K + A <= %d, got n = %d, K = %d, '
+                         'A = %d' % (WARP_MAX_POINTS, n, K, A))
+    specs = [('poses', poses, torch.float32, (n, K, 2)), ('mu', mu, torch.float32, (n, K, 2)), ('coef', coef, torch.float32, (n, M + 3, 2)),
+             ('ctrl', ctrl, torch.float32, (n, M, 2)), ('flags', flags, torch.int32, (n,))]
+    if A:
+        specs.append(('anchors', anchors, torch.float32, (A, 2)))
+    _check_tensors(specs)
+    strength, lam = float(strength), float(lam)
+    if strength - strength != 0.0:
+        raise ValueError('strength must be finite, got %r' % (strength,))
+    if not (lam >= 0.0 and lam - lam == 0.0):
+        raise ValueError('lam must be finite and >= 0, got %r' % (lam,))
+    call('imm_warp_fit', _p(poses), _p(mu), _p(anchors) if A else None, K, A, n, strength, lam, _p(coef), _p(ctrl), _p(flags), _s())
+
+
+def warp_u8(src, dst, offsets, hw, boxes, links, inv_ramp, ctrl, coef, max_box_pixels):
+    """The packed u8 photos dst (a copy of src, as resize_crop_u8 reads them) warped in place: every pixel of row b's box takes the
+    ORIGINAL photo's (src, read only) value at the place the row's spline (ctrl f32 [n, M, 2], coef f32 [n, M + 3, 2] from warp_fit)
+    sends it to, blended with the edge ramp inv_ramp f32 [n, 2] and rounded to u8, in row order (include/imm_warp.h: imm_warp_u8).
+    boxes i32 [n, 5], links i32 [n, 2] (generation.compose_links of THESE rows); max_box_pixels: the largest box area of the rows."""
+    if boxes.dim() != 2 or ctrl.dim() != 3:
+        raise ValueError('boxes must be int32 [n, 5] and ctrl f32 [n, M, 2], got %s and %s' % (tuple(boxes.shape), tuple(ctrl.shape)))
+    n, M = int(boxes.shape[0]), int(ctrl.shape[1])
+    for name, t in (('src', src), ('dst', dst)):
+        if t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError('%s must be the flat contiguous u8 buffer, got %s %s' % (name, t.dtype, tuple(t.shape)))
+    if src.numel() != dst.numel() or src.data_ptr() == dst.data_ptr():
+        raise ValueError('dst must be a copy of src (same size, another buffer): every row samples the original pixels')
+    if n < 1 or n > 65535 or not 3 <= M <= WARP_MAX_POINTS:
+        raise ValueError('warp_u8 serves 1..65535 rows of 3 <= M <= %d control points, got n = %d, M = %d' % (WARP_MAX_POINTS, n, M))
+    _check_tensors([('boxes', boxes, torch.int32, (n, 5)), ('links', links, torch.int32, (n, 2)), ('inv_ramp', inv_ramp, torch.float32, (n, 2)),
+                    ('ctrl', ctrl, torch.float32, (n, M, 2)), ('coef', coef, torch.float32, (n, M + 3, 2)),
+                    ('offsets', offsets, torch.int64, (hw.shape[0],))])
+    if hw.dtype != torch.int32 or hw.dim() != 2 or hw.shape[1] != 2 or not hw.is_contiguous():
+        raise ValueError('hw must be contiguous int32 [images, 2], got %s %s' % (hw.dtype, tuple(hw.shape)))
+    if int(max_box_pixels) < 1:
+        raise ValueError('max_box_pixels must be positive, got %r' % (max_box_pixels,))
+    call('imm_warp_u8', _p(src), _p(dst), _p(offsets), _p(hw), int(hw.shape[0]), _p(boxes), _p(links), _p(inv_ramp), _p(ctrl), _p(coef), M, n,
+         int(max_box_pixels), _s())
+
+
 def masked_sse_pool(a, b, batch, s, c, mask, S, partial, pool_a, pool_b):
     call('imm_masked_sse_pool', _p(a), _p(b), dtype_enum(a.dtype), batch, s, c, _p(mask), S, _p(partial), _p(pool_a), _p(pool_b), _s())
 
