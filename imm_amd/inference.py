@@ -772,6 +772,109 @@ class LandmarkDetector(object):
             return out, WP.PhotoWarp(coef, ctrl, rows, mu_out, lm, flags, strength, lam, m)
         return out
 
+    def morph(self, photos, donors, boxes=None, donor_boxes=None, shape=0.5, texture=None, feather=0.125, anchors=2, lam=0.0,
+              landmarks=None, donor_landmarks=None, return_transform=False):
+        """The photos with every box's face blended with a donor's face, in shape and in texture, from the pixels of the two
+        photographs: a list of u8 device tensors [h_i, w_i, 3], one per photo, views of one packed buffer (what warp returns); nothing
+        is rendered.
+        photos, boxes: as warp takes them.  donors, donor_boxes: the donor faces in the same forms (a list of u8 arrays; box rows, by
+        default one whole-photo box per donor photo): one donor row per face, or ONE for all.  shape and texture: a number or one per
+        row, in [0, 1].  shape moves the landmarks from the face's own (0) to the donor's (1), each in the frame of its box; texture
+        mixes the pixels from the face's own (0) to the donor's (1); texture=None: texture = shape, the morph at that point.  shape = 0,
+        texture = 1 swaps the donor's face in, in place; texture = 0 is warp towards the blended pose.  feather, anchors, lam: as warp
+        takes them.  landmarks, donor_landmarks: f32 [n, K, 2], the faces' own and the donors' landmarks where the caller has them
+        (annotated, or from an earlier call); that side's pose program is then skipped.
+        Per row the blended landmarks p = (1 - shape) mu + shape mu_donor and the anchors are the control points of two splines fitted by
+        ONE imm_warp_fit launch: p -> mu in the face's box, p -> mu_donor in the donor's box.  Every pixel of the box takes the original
+        photo's value at the first place and the donor photo's value at the second, bilinearly, mixed by texture and faded into the photo
+        (imm_morph_u8; include/imm_morph.h states the rule).  Rows are applied in row order.  A row without a usable fit on either side
+        leaves its box alone.
+        Both photo lists are packed and uploaded once; the donors' landmarks are detector.landmarks(donors, donor_boxes).  Per bucket:
+        imm_resize_crop_u8 from the original pixels and the captured pose program (unless landmarks is given), imm_morph_poses,
+        imm_warp_fit over twice the rows, imm_morph_u8, all on the detector's stream; nothing returns to the host.
+        return_transform=True: (photos, a morphing.PhotoMorph: coef_a, coef_b, ctrl, rows, donor_rows, mu, donor_mu, poses, flags,
+        to_source, to_donor)."""
+        from . import morphing as MP
+        from . import warping as WP
+        from .generation import compose_inv_ramp, compose_links
+        S, K = self.S, self.K
+        photos, rows, donors, drows, drows_given, shape, texture, feather, m, lam, M, lm_a, lm_b = MP.plan_morph(
+            photos, donors, boxes, donor_boxes, shape, texture, feather, K, anchors, lam, landmarks, donor_landmarks)
+        n = len(rows)
+        if lm_b is None:
+            lm_b = self.landmarks(donors, drows_given)
+        else:
+            lm_b = lm_b.to(device=self.dev, dtype=torch.float32)
+        lm_b = (lm_b.expand(n, K, 2) if lm_b.shape[0] != n else lm_b).contiguous()
+        if lm_a is not None:
+            lm_a = lm_a.to(device=self.dev, dtype=torch.float32).contiguous()
+        buckets = plan_buckets(n, self.max_batch)
+        links = np.concatenate([compose_links(rows[start:start + count]) for start, count, _b in buckets])
+        area = (rows[:, 3] - rows[:, 1]).astype(np.int64) * (rows[:, 4] - rows[:, 2]).astype(np.int64)
+        cur = torch.cuda.current_stream(self.dev)
+        with torch.cuda.device(self.dev):
+            src, offs_d, hw_d, boxes_d = pack_u8(photos, self.dev, rows)            # all photos, once per call
+            don, doffs_d, dhw_d, dboxes_d = pack_u8(donors, self.dev, drows)        # all donor photos, once per call
+            canvas = src.clone()
+            links_d = ops.to_device_pinned(links, self.dev)
+            ramp_d = ops.to_device_pinned(compose_inv_ramp(rows, feather), self.dev)
+            shape_d = ops.to_device_pinned(shape, self.dev)
+            texture_d = ops.to_device_pinned(texture, self.dev)
+            anchors_d = ops.to_device_pinned(WP.warp_anchors(m).astype(np.float32), self.dev) if m else None
+            coef_a = torch.empty(n, M + 3, 2, device=self.dev)
+            coef_b = torch.empty(n, M + 3, 2, device=self.dev)
+            ctrl = torch.empty(n, M, 2, device=self.dev)
+            flags = torch.empty(n, dtype=torch.int32, device=self.dev)
+            poses = torch.empty(n, K, 2, device=self.dev) if return_transform else None
+            mu_out = torch.empty(n, K, 2, device=self.dev) if return_transform and lm_a is None else None
+            # one bucket's scratch: the inputs and outputs of the fit over 2 * count rows
+            B = max(count for _s, count, _b in buckets)
+            poses2, mu2 = torch.empty(2 * B * K * 2, device=self.dev), torch.empty(2 * B * K * 2, device=self.dev)
+            coef2, ctrl2 = torch.empty(2 * B * (M + 3) * 2, device=self.dev), torch.empty(2 * B * M * 2, device=self.dev)
+            flags2 = torch.empty(2 * B, dtype=torch.int32, device=self.dev)
+        self.stream.wait_stream(cur)
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            for start, count, bucket in buckets:
+                part = slice(start, start + count)
+                if lm_a is None:
+                    self._ensure_capacity(bucket)
+                    ops.resize_crop_u8(src, offs_d, hw_d, 3, (S, S), (0, 0), (S, S), self._img[:count], boxes=boxes_d[part])
+                    if count < bucket:
+                        self._img[count:bucket].zero_()
+                    self._run(bucket)
+                    own = self._mu[:count]
+                else:
+                    own = lm_a[part]
+                p2, m2 = poses2[:2 * count * K * 2].view(2, count, K, 2), mu2[:2 * count * K * 2].view(2, count, K, 2)
+                c2, t2 = coef2[:2 * count * (M + 3) * 2].view(2, count, M + 3, 2), ctrl2[:2 * count * M * 2].view(2, count, M, 2)
+                f2 = flags2[:2 * count].view(2, count)
+                ops.morph_poses(own, lm_b[part], shape_d[part], p2, m2)
+                ops.warp_fit(p2.view(2 * count, K, 2), m2.view(2 * count, K, 2), anchors_d, 1.0, lam, c2.view(2 * count, M + 3, 2),
+                             t2.view(2 * count, M, 2), f2.view(2 * count))
+                coef_a[part].copy_(c2[0])
+                coef_b[part].copy_(c2[1])
+                ctrl[part].copy_(t2[0])
+                torch.bitwise_or(f2[0], f2[1], out=flags[part])
+                ops.morph_u8(src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, boxes_d[part], dboxes_d[part], links_d[part], ramp_d[part],
+                             texture_d[part], t2[0], c2[0], c2[1], int(min(area[part].max(), 2 ** 31 - 1)))
+                if return_transform:
+                    poses[part].copy_(p2[0])
+                    if mu_out is not None:
+                        mu_out[part].copy_(own)
+        cur.wait_stream(self.stream)
+        for t in (src, don, canvas, offs_d, hw_d, boxes_d, doffs_d, dhw_d, dboxes_d, links_d, ramp_d, shape_d, texture_d, anchors_d, lm_a,
+                  lm_b, coef_a, coef_b, ctrl, flags, poses, mu_out, poses2, mu2, coef2, ctrl2, flags2):
+            if t is not None:
+                t.record_stream(self.stream)
+        offs = [0]
+        for a in photos[:-1]:
+            offs.append(offs[-1] + ((a.size + 15) & ~15))
+        out = [canvas[o:o + a.size].view(a.shape) for o, a in zip(offs, photos)]
+        if return_transform:
+            return out, MP.PhotoMorph(coef_a, coef_b, ctrl, rows, drows, mu_out if lm_a is None else lm_a, lm_b, poses, flags, shape,
+                                      texture, lam, m)
+        return out
+
     def unalign(self, photos, aligned, alignment, feather=0.125):
         """align() run backwards: the photos with every row's aligned face pasted back where align() took it from: a list of u8 device
         tensors [h_i, w_i, 3], one per photo, views of one packed buffer (as ImageGenerator.repose returns them).

@@ -1,0 +1,139 @@
+"""Two faces blended in shape and texture from their own pixels: the host side of LandmarkDetector.morph (include/imm_morph.h states
+the rule).
+
+transfer(), repose() with pose photos and reenact() bring a second face into a photograph through the generator: a 300-pixel face comes
+back as an up-sampled 128-pixel render.  morph() works on the pixels of the two photographs instead.  Per row there is a face of its
+own (a box in one of the photos) and a donor face (a box in one of the donor photos), and two numbers in [0, 1]: `shape` moves the
+landmarks from the face's own (0) to the donor's (1), `texture` mixes the pixels from the face's own (0) to the donor's (1).  The blended
+landmarks p are the control points (with warp()'s border anchors) of TWO displacement splines, fitted by one imm_warp_fit launch: one
+carries p back to the face's own landmarks, the other to the donor's, so every pixel of the box finds its place in both photographs and
+takes the mix of what lies there.  shape = texture = t is the morph at t, shape = 0 with texture = 1 the donor's face swapped in place,
+texture = 0 warp() towards the blended pose.
+
+Here: the pose blend in the kernel's f32 order, the argument checks of morph() and PhotoMorph, what morph(return_transform=True) returns.
+Nothing here needs a GPU."""
+import numpy as np
+
+from .warping import _host, check_spline, displacement
+
+MAX_ROWS = 32767               # rows of one morph() call: imm_warp_fit takes 2 n <= 65535 rows
+
+
+def blend_poses(mu_a, mu_b, shape):
+    """p = (1 - s) * mu_a + s * mu_b, f32 [n, K, 2], in imm_morph_poses' order (numpy rounds every f32 operation separately): mu_a, mu_b
+    [n, K, 2] and shape [n] are read as f32.  s = 0 gives mu_a and s = 1 gives mu_b as values; a NaN input gives NaN."""
+    a, b = np.asarray(mu_a, dtype=np.float32), np.asarray(mu_b, dtype=np.float32)
+    s = np.asarray(shape, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 2 or b.shape != a.shape or s.shape != a.shape[:1]:
+        raise ValueError('mu_a and mu_b must be [n, K, 2] and shape [n], got %s, %s and %s' % (a.shape, b.shape, s.shape))
+    s = s[:, None, None]
+    with np.errstate(invalid='ignore', over='ignore'):
+        wa = np.float32(1.0) - s
+        ta, tb = wa * a, s * b
+        return ta + tb
+
+
+def _share(value, n, name):
+    """A scalar or [n] in [0, 1] -> f32 [n]."""
+    v = np.asarray(value, dtype=np.float64)
+    if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != n):
+        raise ValueError('%s must be a number or one per row [%d], got shape %s' % (name, n, v.shape))
+    v = np.broadcast_to(v, (n,))
+    if not (np.isfinite(v).all() and (v >= 0.0).all() and (v <= 1.0).all()):
+        raise ValueError('%s must be finite and lie in [0, 1] (0: the face itself, 1: the donor), got %r' % (name, value))
+    return np.ascontiguousarray(v, dtype=np.float32)
+
+
+def _given_landmarks(lm, counts, K, name):
+    """landmarks= / donor_landmarks=: f32 [n, K, 2] (or one of the other counts allowed) as a tensor; a host tensor must be finite (a device
+    tensor is not read back: its rows are judged by the fit)."""
+    import torch
+    t = torch.as_tensor(lm)
+    if t.dim() != 3 or tuple(t.shape[1:]) != (K, 2) or t.shape[0] not in counts:
+        raise ValueError('%s must be [%s, %d, 2], got %s' % (name, ' or '.join(str(c) for c in counts), K, tuple(t.shape)))
+    t = t.float()
+    if not t.is_cuda and not bool(torch.isfinite(t).all()):
+        raise ValueError('%s must be finite' % name)
+    return t
+
+
+def plan_morph(photos, donors, boxes, donor_boxes, shape, texture, feather, K, anchors=2, lam=0.0, landmarks=None, donor_landmarks=None):
+    """morph()'s arguments checked on the host, before anything reaches the device: (photos as decoded u8 arrays, box rows int32 [n, 5],
+    donor photos as decoded u8 arrays, donor box rows int32 [n, 5] (ONE donor row is repeated for every face), the donor rows as given
+    (what detector.landmarks(donors, .) is asked for), shape f32 [n], texture f32 [n], feather, m, lam, M, landmarks, donor_landmarks).
+    photos / boxes and donors / donor_boxes in generation.plan_repose's forms (lists of u8 arrays; box rows, by default one whole-photo
+    box per photo).  texture=None: texture = shape.  landmarks / donor_landmarks: None or f32 [n, K, 2] tensors (donor_landmarks may have
+    one row when there is one donor row)."""
+    from .generation import NEEDS_U8, check_feather
+    from .inference import decode_u8
+    from .keypoints import check_boxes
+    m, lam, _strength, M = check_spline(anchors, lam, 1.0, K)
+    feather = check_feather(feather)
+    for name, ims in (('photos', photos), ('donors', donors)):
+        if not isinstance(ims, (list, tuple)) or not len(ims):
+            raise ValueError('%s: %s' % (name, NEEDS_U8))
+    photos, donors = decode_u8(photos), decode_u8(donors)
+    rows = check_boxes([(0, 0, a.shape[0], a.shape[1]) for a in photos] if boxes is None else boxes, len(photos))
+    drows = check_boxes([(0, 0, a.shape[0], a.shape[1]) for a in donors] if donor_boxes is None else donor_boxes, len(donors))
+    n, n_d = len(rows), len(drows)
+    if n > MAX_ROWS:
+        raise ValueError('a morph serves at most %d rows a call (one fit over twice as many), got %d' % (MAX_ROWS, n))
+    if n_d not in (n, 1):
+        raise ValueError('%d donors for %d faces: give one per face, or one for all' % (n_d, n))
+    shape = _share(shape, n, 'shape')
+    texture = shape.copy() if texture is None else _share(texture, n, 'texture')
+    if landmarks is not None:
+        landmarks = _given_landmarks(landmarks, (n,), K, 'landmarks')
+    if donor_landmarks is not None:
+        donor_landmarks = _given_landmarks(donor_landmarks, (n,) if n_d == n else (n, 1), K, 'donor_landmarks')
+    full = np.ascontiguousarray(np.broadcast_to(drows, (n, 5)) if n_d != n else drows, dtype=np.int32)
+    return photos, rows, donors, full, drows, shape, texture, feather, m, lam, M, landmarks, donor_landmarks
+
+
+class PhotoMorph(object):
+    """What morph(return_transform=True) returns: the two splines of every row.  coef_a and coef_b f32 [n, M + 3, 2] (device tensors, the
+    halves of imm_warp_fit's output: target frame -> own frame, target frame -> donor frame) on the shared control points ctrl f32
+    [n, M, 2]; rows and donor_rows int32 [n, 5] (host); mu and donor_mu f32 [n, K, 2] (the faces' own and the donors' landmarks), poses
+    f32 [n, K, 2] (their blend, the target), flags int32 [n] (the OR of the two fits' flags; bit 0: no usable fit, the box was left
+    alone), shape and texture f32 [n] (host), and the call's lam and anchors."""
+
+    def __init__(self, coef_a, coef_b, ctrl, rows, donor_rows, mu, donor_mu, poses, flags, shape, texture, lam, anchors):
+        self.coef_a, self.coef_b, self.ctrl = coef_a, coef_b, ctrl
+        self.rows, self.donor_rows = np.asarray(rows, dtype=np.int32), np.asarray(donor_rows, dtype=np.int32)
+        self.mu, self.donor_mu, self.poses, self.flags = mu, donor_mu, poses, flags
+        self.shape, self.texture = np.asarray(shape, dtype=np.float32), np.asarray(texture, dtype=np.float32)
+        self.lam, self.anchors = float(lam), int(anchors)
+
+    def _frame(self, points_px):
+        pts = np.asarray(points_px, dtype=np.float64)
+        n = len(self.rows)
+        if pts.ndim != 3 or pts.shape[0] != n or pts.shape[2] != 2:
+            raise ValueError('points_px must be [%d, P, 2], got %s' % (n, pts.shape))
+        org = self.rows[:, 1:3].astype(np.float64)
+        half = (self.rows[:, 3:5] - self.rows[:, 1:3]).astype(np.float64) / 2.0
+        return pts, org, half
+
+    def to_source(self, points_px):
+        """points_px [n, P, 2]: (y, x) photo pixels of the RESULT, row b's in the photo of row b -> f64 [n, P, 2], the pixels of the
+        ORIGINAL photo whose values the morph took there (the kernel's map sA, in f64 from the f32 coefficients; blending and clamping
+        apart)."""
+        pts, org, half = self._frame(points_px)
+        coef, ctrl = _host(self.coef_a), _host(self.ctrl)
+        out = np.empty_like(pts)
+        for b in range(len(self.rows)):
+            q = (pts[b] - org[b]) / half[b] - 1.0
+            out[b] = pts[b] + half[b] * displacement(coef[b], ctrl[b], q)
+        return out
+
+    def to_donor(self, points_px):
+        """points_px [n, P, 2] as to_source takes them -> f64 [n, P, 2], the pixels of row b's DONOR photo whose values the morph mixed in
+        there (the kernel's map sB: the donor-frame point q + DB(q) in the pixels of the donor box)."""
+        pts, org, half = self._frame(points_px)
+        coef, ctrl = _host(self.coef_b), _host(self.ctrl)
+        dorg = self.donor_rows[:, 1:3].astype(np.float64)
+        dhalf = (self.donor_rows[:, 3:5] - self.donor_rows[:, 1:3]).astype(np.float64) / 2.0
+        out = np.empty_like(pts)
+        for b in range(len(self.rows)):
+            q = (pts[b] - org[b]) / half[b] - 1.0
+            out[b] = dorg[b] + ((q + displacement(coef[b], ctrl[b], q)) + 1.0) * dhalf[b]
+        return out

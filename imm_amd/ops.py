@@ -896,6 +896,69 @@ def warp_u8(src, dst, offsets, hw, boxes, links, inv_ramp, ctrl, coef, max_box_p
          int(max_box_pixels), _s())
 
 
+MORPH_MAX_ROWS = 32767        # rows of one morph: the fit that follows imm_morph_poses takes twice as many
+
+
+def morph_poses(mu_a, mu_b, shape, poses2, mu2):
+    """The pose blend of LandmarkDetector.morph (include/imm_morph.h: imm_morph_poses): mu_a, mu_b f32 [n, K, 2] (the faces' own and
+    their donors' landmarks) and shape f32 [n] -> poses2 f32 [2, n, K, 2] (p = (1 - s) mu_a + s mu_b, twice) and mu2 f32 [2, n, K, 2]
+    ((mu_a, mu_b)): viewed as [2 n, K, 2], the poses and mu of ONE warp_fit over 2 n rows."""
+    if mu_a.dim() != 3 or mu_a.shape[2] != 2:
+        raise ValueError('mu_a must be f32 [n, K, 2], got %s' % (tuple(mu_a.shape),))
+    n, K = int(mu_a.shape[0]), int(mu_a.shape[1])
+    if n < 1 or n > MORPH_MAX_ROWS or K < 1 or K > WARP_MAX_POINTS:
+        raise ValueError('morph_poses serves 1..%d rows of 1..%d landmarks, got n = %d, K = %d' % (MORPH_MAX_ROWS, WARP_MAX_POINTS, n, K))
+    _check_tensors([('mu_a', mu_a, torch.float32, (n, K, 2)), ('mu_b', mu_b, torch.float32, (n, K, 2)), ('shape', shape, torch.float32, (n,)),
+                    ('poses2', poses2, torch.float32, (2, n, K, 2)), ('mu2', mu2, torch.float32, (2, n, K, 2))])
+    for name, t in (('mu_a', mu_a), ('mu_b', mu_b), ('shape', shape)):
+        for oname, o in (('poses2', poses2), ('mu2', mu2)):
+            if _overlap(t, o):
+                raise ValueError('%s overlaps %s: the outputs are written while the inputs are read' % (name, oname))
+    if _overlap(poses2, mu2):
+        raise ValueError('poses2 overlaps mu2')
+    call('imm_morph_poses', _p(mu_a), _p(mu_b), _p(shape), K, n, _p(poses2), _p(mu2), _s())
+
+
+def _overlap(a, b):
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def morph_u8(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b,
+             max_box_pixels):
+    """The packed u8 photos dst (a copy of src) morphed in place (include/imm_morph.h: imm_morph_u8): every pixel of row b's box takes
+    the mix, by texture f32 [n], of the ORIGINAL photo's value (src, read only) at the place the row's spline coef_a sends it to and of
+    the donor photo's value (donor, a second packed buffer with donor_offsets / donor_hw, read only; it may be src) at the place coef_b
+    sends it to inside the donor box (donor_boxes i32 [n, 5]), blended with the edge ramp inv_ramp f32 [n, 2] and rounded to u8, in row
+    order.  ctrl f32 [n, M, 2], coef_a / coef_b f32 [n, M + 3, 2]: the halves of ONE warp_fit over the 2 n rows of morph_poses.  boxes,
+    links, max_box_pixels as warp_u8 takes them."""
+    if boxes.dim() != 2 or ctrl.dim() != 3:
+        raise ValueError('boxes must be int32 [n, 5] and ctrl f32 [n, M, 2], got %s and %s' % (tuple(boxes.shape), tuple(ctrl.shape)))
+    n, M = int(boxes.shape[0]), int(ctrl.shape[1])
+    for name, t in (('src', src), ('dst', dst), ('donor', donor)):
+        if t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError('%s must be the flat contiguous u8 buffer, got %s %s' % (name, t.dtype, tuple(t.shape)))
+    if src.numel() != dst.numel() or _overlap(src, dst):
+        raise ValueError('dst must be a copy of src (same size, another buffer): every row samples the original pixels')
+    if _overlap(donor, dst):
+        raise ValueError('the donor buffer is read only: it may be src, never dst')
+    if n < 1 or n > 65535 or not 3 <= M <= WARP_MAX_POINTS:
+        raise ValueError('morph_u8 serves 1..65535 rows of 3 <= M <= %d control points, got n = %d, M = %d' % (WARP_MAX_POINTS, n, M))
+    for name, t in (('hw', hw), ('donor_hw', donor_hw)):
+        if t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != 2 or t.shape[0] < 1 or not t.is_contiguous():
+            raise ValueError('%s must be contiguous int32 [images, 2], got %s %s' % (name, t.dtype, tuple(t.shape)))
+    _check_tensors([('boxes', boxes, torch.int32, (n, 5)), ('donor_boxes', donor_boxes, torch.int32, (n, 5)), ('links', links, torch.int32, (n, 2)),
+                    ('inv_ramp', inv_ramp, torch.float32, (n, 2)), ('texture', texture, torch.float32, (n,)),
+                    ('ctrl', ctrl, torch.float32, (n, M, 2)), ('coef_a', coef_a, torch.float32, (n, M + 3, 2)),
+                    ('coef_b', coef_b, torch.float32, (n, M + 3, 2)), ('offsets', offsets, torch.int64, (hw.shape[0],)),
+                    ('donor_offsets', donor_offsets, torch.int64, (donor_hw.shape[0],))])
+    if int(max_box_pixels) < 1:
+        raise ValueError('max_box_pixels must be positive, got %r' % (max_box_pixels,))
+    call('imm_morph_u8', _p(src), _p(dst), _p(offsets), _p(hw), int(hw.shape[0]), _p(donor), _p(donor_offsets), _p(donor_hw),
+         int(donor_hw.shape[0]), _p(boxes), _p(donor_boxes), _p(links), _p(inv_ramp), _p(texture), _p(ctrl), _p(coef_a), _p(coef_b), M, n,
+         int(max_box_pixels), _s())
+
+
 def masked_sse_pool(a, b, batch, s, c, mask, S, partial, pool_a, pool_b):
     call('imm_masked_sse_pool', _p(a), _p(b), dtype_enum(a.dtype), batch, s, c, _p(mask), S, _p(partial), _p(pool_a), _p(pool_b), _s())
 

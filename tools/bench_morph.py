@@ -1,0 +1,134 @@
+"""Faces/s of LandmarkDetector.morph (u8 photos, donor photos and face boxes in, the photos out with every face blended with its donor's
+in shape and texture, from the pixels of the two photographs) at S = 128, bf16, K = 10, the default 2 anchors per side (M = 18 control
+points) and one bucket of B = 64 rows, with what a caller had to do before alongside, for orientation only: two LandmarkDetector.warp
+calls (the photos and the donor photos, each towards a common pose), both results copied to the host and the boxes cross-dissolved
+there in numpy.  Writes the table to profiles/morph_bench.txt.
+
+  morph     detector.morph(photos, donors, boxes, donor_boxes, shape=0.5): pack + copy of both photo lists, a device copy to morph into,
+            the donors' landmarks (their pack, crop and pose program), the box crop, the pose program's graph, imm_morph_poses, one
+            imm_warp_fit over 2 B rows and one imm_morph_u8 launch
+  dissolve  two detector.warp calls, .cpu() of both results, then per face 0.5 * box + 0.5 * donor box in numpy (the common part of the
+            two boxes; a real cross-dissolve would also have to resample one box to the other's size)
+  pack      what comes before any kernel of morph: both photo lists packed on the host, copied to the device, one of them copied once
+            more there (inference.pack_u8 twice and a clone)
+  poses, fit, u8   imm_morph_poses, imm_warp_fit over 2 B rows and imm_morph_u8 alone, on the buffers of one morph() call
+All are timed with HIP events on the caller's stream, alternated window by window in the same run (median over the windows of the mean
+per-call time).  The photos and the donor photos are about 512 x 384 (sizes vary by a few pixels) with one box of about 250 x 250 each.
+An untrained model's landmarks sit in a small cloud, so lam = 1 keeps the systems regular; what the kernels cost does not depend on it.
+Usage: python tools/bench_morph.py [--batch 64] [--windows 7] [--reps 10] [--anchors 2]"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+
+OUT = os.path.join(ROOT, 'profiles', 'morph_bench.txt')
+S, K = 128, 10
+LAM = 1.0
+
+
+def main(args):
+    import torch
+    from bench_detect import timed_ms
+    from bench_repose import make_generator, scene
+    from bench_warp import grid_poses
+    from imm_amd import ops
+    from imm_amd.generation import compose_inv_ramp, compose_links
+    from imm_amd.inference import pack_u8, plan_buckets
+    from imm_amd.keypoints import check_boxes
+    from imm_amd.warping import warp_anchors
+    B, m = args.batch, args.anchors
+    M = K + 4 * m
+    photos, boxes, _lm = scene(B)
+    donors, dboxes, _lm = scene(B, seed=1)
+    model, gen = make_generator(B)
+    det = gen.detector
+    assert len(plan_buckets(B, B)) == 1
+    props = torch.cuda.get_device_properties(0)
+    mid = torch.from_numpy(grid_poses(B)).cuda()
+    rows, drows = check_boxes(boxes, B), check_boxes(dboxes, B)
+    out, pm = det.morph(photos, donors, boxes, dboxes, shape=0.5, anchors=m, lam=LAM, return_transform=True)
+    torch.cuda.synchronize()
+    flagged = int((pm.flags != 0).sum())
+    changed = sum(int((o.cpu().numpy() != p).any(axis=2).sum()) for o, p in zip(out, photos))
+
+    def dissolve():
+        a = det.warp(photos, mid, boxes, anchors=m, lam=LAM)
+        b = det.warp(donors, mid, dboxes, anchors=m, lam=LAM)
+        res = []
+        for (i, y0, x0, y1, x1), (j, v0, u0, v1, u1) in zip(boxes, dboxes):
+            pa, pb = a[i].cpu().numpy(), b[j].cpu().numpy()
+            fa, fb = pa[max(y0, 0):y1, max(x0, 0):x1], pb[max(v0, 0):v1, max(u0, 0):u1]
+            h, w = min(fa.shape[0], fb.shape[0]), min(fa.shape[1], fb.shape[1])
+            fa[:h, :w] = np.rint(0.5 * fa[:h, :w].astype(np.float32) + 0.5 * fb[:h, :w].astype(np.float32)).astype(np.uint8)
+            res.append(pa)
+        return res
+
+    # the three kernels alone, on the buffers of that call
+    src, offs_d, hw_d, boxes_d = pack_u8(photos, 'cuda:0', rows)
+    don, doffs_d, dhw_d, dboxes_d = pack_u8(donors, 'cuda:0', drows)
+    canvas = src.clone()
+    links_d = ops.to_device_pinned(compose_links(rows), 'cuda:0')
+    ramp_d = ops.to_device_pinned(compose_inv_ramp(rows, 0.125), 'cuda:0')
+    shape_d = ops.to_device_pinned(pm.shape, 'cuda:0')
+    texture_d = ops.to_device_pinned(pm.texture, 'cuda:0')
+    area = int(((rows[:, 3] - rows[:, 1]) * (rows[:, 4] - rows[:, 2])).max())
+    anchors_d = ops.to_device_pinned(warp_anchors(m).astype(np.float32), 'cuda:0') if m else None
+    poses2, mu2 = torch.empty(2, B, K, 2, device='cuda:0'), torch.empty(2, B, K, 2, device='cuda:0')
+    coef2, ctrl2 = torch.empty(2 * B, M + 3, 2, device='cuda:0'), torch.empty(2 * B, M, 2, device='cuda:0')
+    flags2 = torch.empty(2 * B, dtype=torch.int32, device='cuda:0')
+    ops.morph_poses(pm.mu, pm.donor_mu, shape_d, poses2, mu2)
+    fns = {'morph': lambda: det.morph(photos, donors, boxes, dboxes, shape=0.5, anchors=m, lam=LAM), 'dissolve': dissolve,
+           'pack': lambda: (pack_u8(photos, 'cuda:0', rows)[0].clone(), pack_u8(donors, 'cuda:0', drows)),
+           'poses': lambda: ops.morph_poses(pm.mu, pm.donor_mu, shape_d, poses2, mu2),
+           'fit': lambda: ops.warp_fit(poses2.view(2 * B, K, 2), mu2.view(2 * B, K, 2), anchors_d, 1.0, LAM, coef2, ctrl2, flags2),
+           'u8': lambda: ops.morph_u8(src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, boxes_d, dboxes_d, links_d, ramp_d, texture_d, pm.ctrl,
+                                      pm.coef_a, pm.coef_b, area)}
+    ms = {k: [] for k in fns}
+    for k, fn in fns.items():
+        timed_ms(fn, 2, 1, args.warmup)
+    for _ in range(args.windows):                                   # alternated: one window of each, again and again
+        for k, fn in fns.items():
+            ms[k].append(timed_ms(fn, args.reps, 1, 0))
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    spread = {k: (float(np.min(v)), float(np.max(v))) for k, v in ms.items()}
+    px = 0
+    for i, y0, x0, y1, x1 in boxes:
+        h, w = photos[i].shape[:2]
+        px += max(0, min(y1, h) - max(y0, 0)) * max(0, min(x1, w) - max(x0, 0))
+    lines = ['device: %s (%s, %d CUs)' % (props.name, props.gcnArchName, props.multi_processor_count),
+             'S = %d, K = %d, anchors = %d (M = %d control points), lam = %g, bf16, one bucket of B = %d rows; %d u8 photos and %d donor photos of '
+             'about 512 x 384 (%.1f MB + %.1f MB packed), one box of about 250 x 250 each (%.2f M box pixels in all); ms per call: median '
+             '(min .. max) of %d alternated windows x %d calls' % (S, K, m, M, LAM, B, B, B, sum(p.size for p in photos) / 1e6,
+                                                                   sum(p.size for p in donors) / 1e6, px / 1e6, args.windows, args.reps),
+             'rows without a usable fit: %d of %d; photo pixels the morph changed: %d' % (flagged, B, changed),
+             '%-8s %10s %22s %12s' % ('call', 'ms', '(min .. max)', 'faces/s')]
+    for k in ('morph', 'dissolve', 'pack', 'poses', 'fit', 'u8'):
+        lines.append('%-8s %10.3f %22s %12s' % (k, med[k], '(%.3f .. %.3f)' % spread[k],
+                                                '%.0f' % (B / med[k] * 1e3) if k in ('morph', 'dissolve') else '-'))
+    lines.append('imm_morph_u8: %.1f ps per box pixel at %d logarithms each (%.2f G log/s); imm_warp_fit: %.1f us per launch of %d systems of '
+                 '%d x %d; imm_morph_poses: %.1f us' % (med['u8'] * 1e9 / px, M, px * M / med['u8'] / 1e6, med['fit'] * 1e3, 2 * B, M + 3, M + 3,
+                                                        med['poses'] * 1e3))
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write(text)
+    print(json.dumps({'batch': B, 'anchors': m, 'morph_ms': med['morph'], 'dissolve_ms': med['dissolve'], 'pack_ms': med['pack'],
+                      'poses_ms': med['poses'], 'fit_ms': med['fit'], 'u8_ms': med['u8'], 'flagged': flagged}))
+
+
+if __name__ == '__main__':
+    p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    p.add_argument('--batch', type=int, default=64)
+    p.add_argument('--windows', type=int, default=7)
+    p.add_argument('--reps', type=int, default=10)
+    p.add_argument('--warmup', type=int, default=3)
+    p.add_argument('--anchors', type=int, default=2, help='anchor points per side of the box frame')
+    p.add_argument('--out', type=str, default=OUT)
+    main(p.parse_args())
