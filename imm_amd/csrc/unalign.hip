@@ -12,18 +12,11 @@
 //
 // imm_unalign_maps: one thread per row, f64, every operation rounded separately, in the order written below (the numpy restatement
 // of the tests follows it line by line), rounded once to f32.  It also writes the row's bounding box in the photo.
-// imm_unalign_u8: compose_u8_kernel's shape.  One thread = one photo pixel (its three bytes) of one row's bounding box; blockIdx.y is
-// the row.  Overlapping rows of one photo are resolved without atomics through the links of imm_compose_u8: the thread of (row b,
-// pixel) skips the pixel if its own map does not cover it or if an earlier row of this launch covers it in the same photo;
-// otherwise it alone owns the pixel: it reads it once, walks b and the later rows of the photo that cover it, keeps the running value
-// in a register with the per-row rint, and writes it once.  "Covers" is the quad test above with the other row's map, so every thread
-// that looks at a pixel decides its owner from the same f32 arithmetic.  Every pixel has one writer and no reader but that writer.
-// The photo accesses are byte-wide for compose.hip's reason (rows start at any byte, a quad's edge falls inside any dword); the faces
-// are gathered through L2.  Algorithmic bytes: 6 per covered photo pixel (3 read, 3 written) plus each face once.
-// Nothing outside the packed buffer or the faces is addressed whatever the device buffers hold: the bounding box is clipped to the
-// photo again here, a covered coordinate lies in [0, So - 1] (its taps are clamped all the same), and the link walks step strictly
-// downwards / upwards inside [0, n).
-#include "common.h"
+// imm_unalign_u8: the paste skeleton of paste_common.h, which states the launch shape, the ownership of a pixel and the addressing
+// argument, over the row's bounding box.  "Covers" is the quad test above with a row's own map, so every thread that looks at a pixel
+// decides its owner from the same f32 arithmetic; a covered coordinate lies in [0, So - 1] (its taps are clamped all the same).  The
+// faces are gathered through L2.  Algorithmic bytes: 6 per covered photo pixel (3 read, 3 written) plus each face once.
+#include "paste_common.h"
 
 __global__ __launch_bounds__(64) void unalign_maps_kernel(const float* __restrict__ coef, const float* __restrict__ geom,
                                                           const int32_t* __restrict__ boxes, const int32_t* __restrict__ hw, int n_images,
@@ -96,96 +89,58 @@ extern "C" int imm_unalign_maps(const float* coef, const float* geom, const int3
   return 0;
 }
 
-struct UnalignMap {
+struct UnalignRow {
   float m00, m01, m02, m10, m11, m12;
+  const float* face;
 };
 
-__device__ __forceinline__ UnalignMap unalign_map(const float* __restrict__ fwd, int j) {
-  const float* m = fwd + (int64_t)j * 6;
-  return UnalignMap{m[0], m[1], m[2], m[3], m[4], m[5]};
-}
+struct UnalignPolicy {
+  typedef UnalignRow Row;
+  const float *fwd, *faces;
+  float inv_ramp, edge;
+  int ld, So;
+  Row own;
 
-// the aligned-frame coordinate of photo pixel (r, c) and the quad test; a NaN map covers nothing
-__device__ __forceinline__ bool unalign_covers(const UnalignMap& q, float r, float c, float edge, float& fi, float& fj) {
+  __device__ __forceinline__ Row row(int j) const {
+    const float* m = fwd + (int64_t)j * 6;
+    return Row{m[0], m[1], m[2], m[3], m[4], m[5], faces + (int64_t)j * So * So * ld};
+  }
+  // the aligned-frame coordinate of photo pixel (r, c)
+  __device__ __forceinline__ void coord(const Row& q, int r, int c, float& fi, float& fj) const {
 #pragma clang fp contract(off)
-  fi = (q.m00 * r + q.m01 * c) + q.m02;
-  fj = (q.m10 * r + q.m11 * c) + q.m12;
-  return fi >= 0.f && fi <= edge && fj >= 0.f && fj <= edge;
-}
+    const float rf = (float)r, cf = (float)c;
+    fi = (q.m00 * rf + q.m01 * cf) + q.m02;
+    fj = (q.m10 * rf + q.m11 * cf) + q.m12;
+  }
+  // the quad test; a NaN map covers nothing
+  __device__ __forceinline__ bool covers(const Row& q, int r, int c) const {
+    float fi, fj;
+    coord(q, r, c, fi, fj);
+    return fi >= 0.f && fi <= edge && fj >= 0.f && fj <= edge;
+  }
+  __device__ __forceinline__ void apply(const Row& q, int r, int c, float (&v)[3]) const {
+#pragma clang fp contract(off)
+    float fi, fj, g[3];
+    coord(q, r, c, fi, fj);
+    paste_sample_face(q.face, So, ld, fi, fj, g);
+    const float wy = fminf(1.f, (fminf(fi, edge - fi) + 0.5f) * inv_ramp);
+    const float wx = fminf(1.f, (fminf(fj, edge - fj) + 0.5f) * inv_ramp);
+    paste_blend(v, g, wy * wx);
+  }
+};
 
 __global__ __launch_bounds__(256) void unalign_u8_kernel(uint8_t* __restrict__ photos, const int64_t* __restrict__ offs,
                                                          const int32_t* __restrict__ hw, int n_images,
                                                          const int32_t* __restrict__ boxes, const int32_t* __restrict__ links,
                                                          const float* __restrict__ fwd, const int32_t* __restrict__ bbox, float inv_ramp,
                                                          const float* __restrict__ faces, int ld, int n, int So) {
-#pragma clang fp contract(off)   // every operation rounded separately: bit-identical to the f32 host restatement in the same order
   const int b = blockIdx.y;
-  const int img = boxes[5 * b];
-  if (img < 0 || img >= n_images) return;
-  const int sh = hw[2 * img], sw = hw[2 * img + 1];
-  // the row's bounding box, clipped to the photo once more
-  const int cy0 = max(bbox[4 * b], 0), cx0 = max(bbox[4 * b + 1], 0), cy1 = min(bbox[4 * b + 2], sh), cx1 = min(bbox[4 * b + 3], sw);
-  const int cw = cx1 - cx0, chh = cy1 - cy0;
-  if (cw <= 0 || chh <= 0) return;
-  const int64_t area = (int64_t)cw * chh;
-  const UnalignMap own = unalign_map(fwd, b);
-  const float edge = (float)(So - 1);
-  uint8_t* photo = photos + offs[img];
-  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < area; p += (int64_t)gridDim.x * 256) {
-    const int pr = (int)(p / cw);
-    const int r = cy0 + pr, c = cx0 + (int)(p - (int64_t)pr * cw);
-    const float rf = (float)r, cf = (float)c;
-    float fi, fj;
-    if (!unalign_covers(own, rf, cf, edge, fi, fj)) continue;
-    // an earlier row of this launch that covers (r, c) in the same photo owns the pixel.  The chain must step strictly downwards
-    // (upwards below): device data cannot make the walk leave [0, n) or loop.
-    bool owned = true;
-    for (int j = links[2 * b], last = b; j >= 0 && j < last; last = j, j = links[2 * j]) {
-      float ui, uj;
-      if (boxes[5 * j] == img && unalign_covers(unalign_map(fwd, j), rf, cf, edge, ui, uj)) {
-        owned = false;
-        break;
-      }
-    }
-    if (!owned) continue;
-    uint8_t* px = photo + ((int64_t)r * sw + c) * 3;
-    float v0 = (float)px[0], v1 = (float)px[1], v2 = (float)px[2];
-    bool hit = true;                                     // row b covers the pixel: fi, fj hold its coordinate
-    for (int j = b;;) {
-      if (hit) {
-        const int yl = min(max((int)floorf(fi), 0), So - 1), xl = min(max((int)floorf(fj), 0), So - 1);
-        const int yh = min(yl + 1, So - 1), xh = min(xl + 1, So - 1);
-        const float ty = fi - (float)yl, tx = fj - (float)xl;
-        const float wy = fminf(1.f, (fminf(fi, edge - fi) + 0.5f) * inv_ramp);
-        const float wx = fminf(1.f, (fminf(fj, edge - fj) + 0.5f) * inv_ramp);
-        const float a = wy * wx;
-        const float* f = faces + (int64_t)j * So * So * ld;
-        const float* tlp = f + ((int64_t)yl * So + xl) * ld;
-        const float* trp = f + ((int64_t)yl * So + xh) * ld;
-        const float* blp = f + ((int64_t)yh * So + xl) * ld;
-        const float* brp = f + ((int64_t)yh * So + xh) * ld;
-        float v[3] = {v0, v1, v2};
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-          const float tl = tlp[ch], tr = trp[ch], bl = blp[ch], br = brp[ch];
-          const float top = tl + (tr - tl) * tx;
-          const float bot = bl + (br - bl) * tx;
-          float g = top + (bot - top) * ty;
-          g = fminf(fmaxf(g, 0.f), 255.f);
-          const float d = g - v[ch];
-          const float m = a * d;
-          // in contract the sum is already in [0, 255]; the clamp keeps weights outside [0, 1] from wrapping the byte
-          v[ch] = fminf(fmaxf(rintf(v[ch] + m), 0.f), 255.f);
-        }
-        v0 = v[0]; v1 = v[1]; v2 = v[2];
-      }
-      const int nx = links[2 * j + 1];
-      if (nx <= j || nx >= n) break;
-      j = nx;
-      hit = boxes[5 * j] == img && unalign_covers(unalign_map(fwd, j), rf, cf, edge, fi, fj);      // a foreign row covers nothing
-    }
-    px[0] = (uint8_t)v0; px[1] = (uint8_t)v1; px[2] = (uint8_t)v2;
-  }
+  PastePhoto ph;
+  if (!paste_photo(boxes, offs, hw, n_images, b, ph)) return;
+  UnalignPolicy pol{fwd, faces, inv_ramp, (float)(So - 1), ld, So};
+  pol.own = pol.row(b);
+  // the row's bounding box, which paste_rows clips to the photo once more
+  paste_rows(pol, PasteBox{bbox[4 * b], bbox[4 * b + 1], bbox[4 * b + 2], bbox[4 * b + 3]}, ph, photos + ph.off, boxes, links, n);
 }
 
 extern "C" int imm_unalign_u8(uint8_t* photos, const int64_t* offsets, const int32_t* hw, int n_images, const int32_t* boxes,
@@ -196,10 +151,8 @@ extern "C" int imm_unalign_u8(uint8_t* photos, const int64_t* offsets, const int
   IMM_REQUIRE(out_size > 0 && out_size <= 8192 && ld >= 3, "unalign_u8: 0 < out_size <= 8192, ld >= 3 (got %d, %d)", out_size, ld);
   IMM_REQUIRE(inv_ramp > 0.f && inv_ramp <= 3.0e38f, "unalign_u8: inv_ramp must be positive and finite (got %g)", (double)inv_ramp);
   IMM_REQUIRE(max_pixels > 0, "unalign_u8: max_pixels > 0 (got %d)", max_pixels);
-  // the grid is sized by the caller's largest bounding box; a row with more pixels than that is still covered (grid-stride loop)
-  const int blocks = (int)((((int64_t)max_pixels + 255) / 256 < 65536) ? ((int64_t)max_pixels + 255) / 256 : 65536);
-  hipLaunchKernelGGL(unalign_u8_kernel, dim3(blocks, n), dim3(256), 0, (hipStream_t)stream, photos, offsets, hw, n_images, boxes, links,
-                     fwd, bbox, inv_ramp, faces, ld, n, out_size);
+  hipLaunchKernelGGL(unalign_u8_kernel, dim3(paste_grid_x(max_pixels), n), dim3(256), 0, (hipStream_t)stream, photos, offsets, hw, n_images,
+                     boxes, links, fwd, bbox, inv_ramp, faces, ld, n, out_size);
   IMM_CHECK_LAUNCH("imm_unalign_u8");
   return 0;
 }

@@ -32,7 +32,7 @@ from . import ops
 from .engine import encoder_spec, n_renderer_out, render_sizes, renderer_spec, trainable_spec
 from .inference import (LandmarkDetector, _Launch, alloc_encoder_weights, as_image_batch, bucket_sizes, check_limits, decode_u8,
                         encoder_act_elems, fold_batch_norm, folded_encoder_program, pack_folded_encoder, pack_u8, plan_buckets,
-                        read_variables, stage_u8)
+                        read_variables, stage_u8, unpack_u8)
 from .keypoints import check_boxes
 from .tracking import OneEuro
 
@@ -77,6 +77,16 @@ def compose_links(rows):
             links[last[img], 1] = b
         last[img] = b
     return links
+
+
+def bucket_links(rows, buckets):
+    """compose_links of every bucket (start, count, _) of rows on its own, concatenated: int32 [n, 2], one launch per bucket."""
+    return np.concatenate([compose_links(rows[start:start + count]) for start, count, _b in buckets])
+
+
+def box_areas(rows):
+    """int64 [n]: the pixels of every box row (image, y0, x0, y1, x1)."""
+    return (rows[:, 3] - rows[:, 1]).astype(np.int64) * (rows[:, 4] - rows[:, 2]).astype(np.int64)
 
 
 def check_feather(feather):
@@ -473,8 +483,8 @@ class ImageGenerator(object):
         if lm.shape[0] != n:
             lm = lm.expand(n, self.K, 2)
         buckets = plan_buckets(n, self.max_batch)
-        links = np.concatenate([compose_links(rows[start:start + count]) for start, count, _b in buckets])
-        area = (rows[:, 3] - rows[:, 1]).astype(np.int64) * (rows[:, 4] - rows[:, 2]).astype(np.int64)
+        links = bucket_links(rows, buckets)
+        area = box_areas(rows)
         cur = torch.cuda.current_stream(self.dev)
         with torch.cuda.device(self.dev):
             src, offs_d, hw_d, boxes_d = pack_u8(photos, self.dev, rows)            # all photos, once per call
@@ -501,10 +511,7 @@ class ImageGenerator(object):
         cur.wait_stream(self.stream)
         for t in (src, offs_d, hw_d, boxes_d, links_d, ramp_d):
             t.record_stream(self.stream)
-        offs = [0]
-        for a in photos[:-1]:
-            offs.append(offs[-1] + ((a.size + 15) & ~15))
-        out = [canvas[o:o + a.size].view(a.shape) for o, a in zip(offs, photos)]
+        out = unpack_u8(canvas, photos)
         return (out, faces, lm.contiguous()) if return_faces else out
 
     def reenact(self, photos, frames, driver_box, boxes=None, motion='relative', rigid=True, gain=1.0, smooth=True, feather=0.125,
@@ -544,7 +551,7 @@ class ImageGenerator(object):
         if lm.shape[0] != n:
             lm = lm.expand(n, self.K, 2)
         buckets = plan_buckets(n, self.max_batch)
-        links = np.concatenate([compose_links(rows[start:start + count]) for start, count, _b in buckets])
+        links = bucket_links(rows, buckets)
         cur = torch.cuda.current_stream(self.dev)
         with torch.cuda.device(self.dev):
             canvas, offs_d, hw_d, boxes_d = pack_u8(photos, self.dev, rows)         # all photos, once per call
@@ -574,8 +581,5 @@ class ImageGenerator(object):
         cur.wait_stream(self.stream)
         for t in (canvas, offs_d, hw_d, boxes_d, links_d, aligned, fwd, bbox):
             t.record_stream(self.stream)
-        offs = [0]
-        for a in photos[:-1]:
-            offs.append(offs[-1] + ((a.size + 15) & ~15))
-        out = [canvas[o:o + a.size].view(a.shape) for o, a in zip(offs, photos)]
+        out = unpack_u8(canvas, photos)
         return (out, faces, lm.contiguous()) if return_faces else out

@@ -229,16 +229,27 @@ def decode_u8(images):
     return decoded
 
 
+def packed_offsets(decoded):
+    """Where pack_u8 puts each of the decoded images (16-byte aligned starts): (offsets i64 [count], the bytes they take)."""
+    offs = np.zeros(len(decoded), dtype=np.int64)
+    total = 0
+    for i, a in enumerate(decoded):
+        offs[i] = total
+        total += (a.size + 15) & ~15
+    return offs, total
+
+
+def unpack_u8(packed, decoded):
+    """The images of a buffer laid out as pack_u8(decoded) lays it out: a list of views [h_i, w_i, 3], one per image."""
+    return [packed[o:o + a.size].view(a.shape) for o, a in zip(packed_offsets(decoded)[0].tolist(), decoded)]
+
+
 def pack_u8(images, device, boxes=None):
     """Pack u8 HWC images back to back (16-byte aligned starts, like the data loader) into one device buffer: (src u8, offsets i64
     [count], hw i32 [count, 2], boxes i32 [n, 5] or None), what imm_resize_crop_u8 and imm_align_warp_u8 read."""
     decoded = decode_u8(images)
     count = len(decoded)
-    offs = np.zeros(count, dtype=np.int64)
-    total = 0
-    for i, a in enumerate(decoded):
-        offs[i] = total
-        total += (a.size + 15) & ~15
+    offs, total = packed_offsets(decoded)
     packed = np.zeros(max(total, 16), dtype=np.uint8)
     for a, o in zip(decoded, offs):
         packed[o:o + a.size] = a.reshape(-1)
@@ -723,7 +734,7 @@ class LandmarkDetector(object):
         landmarks in place, imm_warp_u8, all on the detector's stream; nothing returns to the host.
         return_transform=True: (photos, a warping.PhotoWarp: coef, ctrl, rows, mu, poses, flags, to_source)."""
         from . import warping as WP
-        from .generation import compose_inv_ramp, compose_links
+        from .generation import box_areas, bucket_links, compose_inv_ramp
         S, K = self.S, self.K
         photos, rows, pose, feather, m, lam, strength, M = WP.plan_warp(photos, poses, boxes, pose_boxes, feather, K, anchors, lam, strength)
         n = len(rows)
@@ -733,8 +744,8 @@ class LandmarkDetector(object):
             lm = pose[1].to(device=self.dev, dtype=torch.float32)
         lm = (lm.expand(n, K, 2) if lm.shape[0] != n else lm).contiguous()
         buckets = plan_buckets(n, self.max_batch)
-        links = np.concatenate([compose_links(rows[start:start + count]) for start, count, _b in buckets])
-        area = (rows[:, 3] - rows[:, 1]).astype(np.int64) * (rows[:, 4] - rows[:, 2]).astype(np.int64)
+        links = bucket_links(rows, buckets)
+        area = box_areas(rows)
         cur = torch.cuda.current_stream(self.dev)
         with torch.cuda.device(self.dev):
             src, offs_d, hw_d, boxes_d = pack_u8(photos, self.dev, rows)            # all photos, once per call
@@ -764,10 +775,7 @@ class LandmarkDetector(object):
         for t in (src, canvas, offs_d, hw_d, boxes_d, links_d, ramp_d, anchors_d, lm, coef, ctrl, flags, mu_out):
             if t is not None:
                 t.record_stream(self.stream)
-        offs = [0]
-        for a in photos[:-1]:
-            offs.append(offs[-1] + ((a.size + 15) & ~15))
-        out = [canvas[o:o + a.size].view(a.shape) for o, a in zip(offs, photos)]
+        out = unpack_u8(canvas, photos)
         if return_transform:
             return out, WP.PhotoWarp(coef, ctrl, rows, mu_out, lm, flags, strength, lam, m)
         return out
@@ -796,7 +804,7 @@ class LandmarkDetector(object):
         to_source, to_donor)."""
         from . import morphing as MP
         from . import warping as WP
-        from .generation import compose_inv_ramp, compose_links
+        from .generation import box_areas, bucket_links, compose_inv_ramp
         S, K = self.S, self.K
         photos, rows, donors, drows, drows_given, shape, texture, feather, m, lam, M, lm_a, lm_b = MP.plan_morph(
             photos, donors, boxes, donor_boxes, shape, texture, feather, K, anchors, lam, landmarks, donor_landmarks)
@@ -809,8 +817,8 @@ class LandmarkDetector(object):
         if lm_a is not None:
             lm_a = lm_a.to(device=self.dev, dtype=torch.float32).contiguous()
         buckets = plan_buckets(n, self.max_batch)
-        links = np.concatenate([compose_links(rows[start:start + count]) for start, count, _b in buckets])
-        area = (rows[:, 3] - rows[:, 1]).astype(np.int64) * (rows[:, 4] - rows[:, 2]).astype(np.int64)
+        links = bucket_links(rows, buckets)
+        area = box_areas(rows)
         cur = torch.cuda.current_stream(self.dev)
         with torch.cuda.device(self.dev):
             src, offs_d, hw_d, boxes_d = pack_u8(photos, self.dev, rows)            # all photos, once per call
@@ -866,10 +874,7 @@ class LandmarkDetector(object):
                   lm_b, coef_a, coef_b, ctrl, flags, poses, mu_out, poses2, mu2, coef2, ctrl2, flags2):
             if t is not None:
                 t.record_stream(self.stream)
-        offs = [0]
-        for a in photos[:-1]:
-            offs.append(offs[-1] + ((a.size + 15) & ~15))
-        out = [canvas[o:o + a.size].view(a.shape) for o, a in zip(offs, photos)]
+        out = unpack_u8(canvas, photos)
         if return_transform:
             return out, MP.PhotoMorph(coef_a, coef_b, ctrl, rows, drows, mu_out if lm_a is None else lm_a, lm_b, poses, flags, shape,
                                       texture, lam, m)
@@ -909,7 +914,4 @@ class LandmarkDetector(object):
                 links_d = ops.to_device_pinned(compose_links(rows[part]), self.dev)
                 ops.unalign_u8(canvas, offs_d, hw_d, boxes_d[part], links_d, fwd[part], bbox[part], inv_ramp, faces[part],
                                unalign_grid_pixels(photos, rows[part]))
-        offs = [0]
-        for a in photos[:-1]:
-            offs.append(offs[-1] + ((a.size + 15) & ~15))
-        return [canvas[o:o + a.size].view(a.shape) for o, a in zip(offs, photos)]
+        return unpack_u8(canvas, photos)

@@ -727,25 +727,35 @@ def align_warp_u8(src, offsets, hw, boxes, geom, coef, basis_t, image_size, dst,
          n, int(image_size), So, _p(dst), dst.stride(2) if ld_dst is None else ld_dst, _s())
 
 
+def _check_tensors(specs):
+    """(name, tensor, dtype, shape) each: a ValueError that names the first tensor that is not contiguous with that dtype and shape; a
+    dimension given as None is free (hw i32 [images, 2], a flat packed buffer u8 [bytes])."""
+    for name, t, dt, shape in specs:
+        if (t.dtype != dt or t.dim() != len(shape) or any(s is not None and s != d for s, d in zip(shape, t.shape)) or
+                not t.is_contiguous()):
+            raise ValueError('%s must be contiguous %s [%s], got %s %s' % (name, str(dt).replace('torch.', ''), ', '.join(
+                'any' if s is None else str(s) for s in shape), t.dtype, tuple(t.shape)))
+
+
+def _check_faces(faces, n):
+    """faces f32 [n, S, S, >= 3] with dense pixels of one stride -> (S, that stride)."""
+    S, ld = faces.shape[1], faces.stride(2)
+    if (faces.dtype != torch.float32 or faces.dim() != 4 or faces.shape[0] != n or faces.shape[2] != S or faces.shape[3] < 3 or
+            faces.stride(3) != 1 or faces.stride(1) != S * ld or faces.stride(0) != S * S * ld):
+        raise ValueError('faces must be f32 [n, S, S, >= 3] with dense pixels of one stride, got %s %s strides %s' % (
+            faces.dtype, tuple(faces.shape), tuple(faces.stride())))
+    return S, ld
+
+
 def compose_u8(photos, offsets, hw, boxes, links, inv_ramp, faces, max_box_pixels):
     """The packed u8 photos (as resize_crop_u8 reads them) composited in place: row b's face, faces[b] f32 [S, S, >= 3] (a view of
     any pixel stride, channels 0..2 read), resampled to box b, blended with the edge ramp inv_ramp f32 [n, 2] and rounded to u8, in
     row order (include/imm_compose.h: imm_compose_u8).  boxes i32 [n, 5], links i32 [n, 2] (generation.compose_links of THESE rows);
     max_box_pixels: the largest box area of the rows."""
     n = boxes.shape[0]
-    if photos.dtype != torch.uint8 or photos.dim() != 1 or not photos.is_contiguous():
-        raise ValueError('photos must be the flat contiguous u8 buffer, got %s %s' % (photos.dtype, tuple(photos.shape)))
-    if boxes.dtype != torch.int32 or tuple(boxes.shape) != (n, 5) or not boxes.is_contiguous():
-        raise ValueError('boxes must be contiguous int32 [n, 5], got %s %s' % (boxes.dtype, tuple(boxes.shape)))
-    if links.dtype != torch.int32 or tuple(links.shape) != (n, 2) or not links.is_contiguous():
-        raise ValueError('links must be contiguous int32 [n, 2], got %s %s' % (links.dtype, tuple(links.shape)))
-    if inv_ramp.dtype != torch.float32 or tuple(inv_ramp.shape) != (n, 2) or not inv_ramp.is_contiguous():
-        raise ValueError('inv_ramp must be contiguous f32 [n, 2], got %s %s' % (inv_ramp.dtype, tuple(inv_ramp.shape)))
-    S, ld = faces.shape[1], faces.stride(2)
-    if (faces.dtype != torch.float32 or faces.dim() != 4 or faces.shape[0] != n or faces.shape[2] != S or faces.shape[3] < 3 or
-            faces.stride(3) != 1 or faces.stride(1) != S * ld or faces.stride(0) != S * S * ld):
-        raise ValueError('faces must be f32 [n, S, S, >= 3] with dense pixels of one stride, got %s %s strides %s' % (
-            faces.dtype, tuple(faces.shape), tuple(faces.stride())))
+    _check_tensors([('photos', photos, torch.uint8, (None,)), ('boxes', boxes, torch.int32, (n, 5)), ('links', links, torch.int32, (n, 2)),
+                    ('inv_ramp', inv_ramp, torch.float32, (n, 2))])
+    S, ld = _check_faces(faces, n)
     call('imm_compose_u8', _p(photos), _p(offsets), _p(hw), int(hw.shape[0]), _p(boxes), _p(links), _p(inv_ramp), _p(faces), int(ld), n,
          int(S), int(max_box_pixels), _s())
 
@@ -755,19 +765,9 @@ def unalign_maps(coef, geom, boxes, hw, image_size, out_size, fwd, bbox):
     from the backward maps of align(): coef f32 [n, 3, 2], geom f32 [n, 4], boxes i32 [n, 5] (the image index is read), hw i32
     [images, 2] (include/imm_unalign.h: imm_unalign_maps).  Everything stays on the device."""
     n = boxes.shape[0]
-    if boxes.dtype != torch.int32 or tuple(boxes.shape) != (n, 5) or not boxes.is_contiguous():
-        raise ValueError('boxes must be contiguous int32 [n, 5], got %s %s' % (boxes.dtype, tuple(boxes.shape)))
-    if coef.dtype != torch.float32 or tuple(coef.shape) != (n, 3, 2) or not coef.is_contiguous():
-        raise ValueError('coef must be contiguous f32 [n, 3, 2] (the similarity and affine models), got %s %s' % (
-            coef.dtype, tuple(coef.shape)))
-    if geom.dtype != torch.float32 or tuple(geom.shape) != (n, 4) or not geom.is_contiguous():
-        raise ValueError('geom must be contiguous f32 [n, 4], got %s %s' % (geom.dtype, tuple(geom.shape)))
-    if hw.dtype != torch.int32 or hw.dim() != 2 or hw.shape[1] != 2 or not hw.is_contiguous():
-        raise ValueError('hw must be contiguous int32 [images, 2], got %s %s' % (hw.dtype, tuple(hw.shape)))
-    if fwd.dtype != torch.float32 or tuple(fwd.shape) != (n, 6) or not fwd.is_contiguous():
-        raise ValueError('fwd must be contiguous f32 [n, 6], got %s %s' % (fwd.dtype, tuple(fwd.shape)))
-    if bbox.dtype != torch.int32 or tuple(bbox.shape) != (n, 4) or not bbox.is_contiguous():
-        raise ValueError('bbox must be contiguous int32 [n, 4], got %s %s' % (bbox.dtype, tuple(bbox.shape)))
+    # coef [n, 3, 2]: the similarity and affine models
+    _check_tensors([('boxes', boxes, torch.int32, (n, 5)), ('coef', coef, torch.float32, (n, 3, 2)), ('geom', geom, torch.float32, (n, 4)),
+                    ('hw', hw, torch.int32, (None, 2)), ('fwd', fwd, torch.float32, (n, 6)), ('bbox', bbox, torch.int32, (n, 4))])
     call('imm_unalign_maps', _p(coef), _p(geom), _p(boxes), _p(hw), int(hw.shape[0]), n, int(image_size), int(out_size), _p(fwd),
          _p(bbox), _s())
 
@@ -779,21 +779,9 @@ def unalign_u8(photos, offsets, hw, boxes, links, fwd, bbox, inv_ramp, faces, ma
     boxes i32 [n, 5] (the image index is read), links i32 [n, 2] (generation.compose_links of THESE rows), fwd f32 [n, 6] and bbox i32
     [n, 4] from unalign_maps; max_pixels: the largest bbox area expected (it sizes the grid only)."""
     n = boxes.shape[0]
-    if photos.dtype != torch.uint8 or photos.dim() != 1 or not photos.is_contiguous():
-        raise ValueError('photos must be the flat contiguous u8 buffer, got %s %s' % (photos.dtype, tuple(photos.shape)))
-    if boxes.dtype != torch.int32 or tuple(boxes.shape) != (n, 5) or not boxes.is_contiguous():
-        raise ValueError('boxes must be contiguous int32 [n, 5], got %s %s' % (boxes.dtype, tuple(boxes.shape)))
-    if links.dtype != torch.int32 or tuple(links.shape) != (n, 2) or not links.is_contiguous():
-        raise ValueError('links must be contiguous int32 [n, 2], got %s %s' % (links.dtype, tuple(links.shape)))
-    if fwd.dtype != torch.float32 or tuple(fwd.shape) != (n, 6) or not fwd.is_contiguous():
-        raise ValueError('fwd must be contiguous f32 [n, 6], got %s %s' % (fwd.dtype, tuple(fwd.shape)))
-    if bbox.dtype != torch.int32 or tuple(bbox.shape) != (n, 4) or not bbox.is_contiguous():
-        raise ValueError('bbox must be contiguous int32 [n, 4], got %s %s' % (bbox.dtype, tuple(bbox.shape)))
-    So, ld = faces.shape[1], faces.stride(2)
-    if (faces.dtype != torch.float32 or faces.dim() != 4 or faces.shape[0] != n or faces.shape[2] != So or faces.shape[3] < 3 or
-            faces.stride(3) != 1 or faces.stride(1) != So * ld or faces.stride(0) != So * So * ld):
-        raise ValueError('faces must be f32 [n, So, So, >= 3] with dense pixels of one stride, got %s %s strides %s' % (
-            faces.dtype, tuple(faces.shape), tuple(faces.stride())))
+    _check_tensors([('photos', photos, torch.uint8, (None,)), ('boxes', boxes, torch.int32, (n, 5)), ('links', links, torch.int32, (n, 2)),
+                    ('fwd', fwd, torch.float32, (n, 6)), ('bbox', bbox, torch.int32, (n, 4))])
+    So, ld = _check_faces(faces, n)
     call('imm_unalign_u8', _p(photos), _p(offsets), _p(hw), int(hw.shape[0]), _p(boxes), _p(links), _p(fwd), _p(bbox), float(inv_ramp),
          _p(faces), int(ld), n, int(So), int(max_pixels), _s())
 
@@ -805,15 +793,10 @@ def track_step(mu, boxes, hw, state, image_size, next_image, init, box_smooth, m
     next_image) with their geometry geom_next f32 [F, 4], and flags i32 [F]; state f64 [F, 5 + 6 K] (tracking.state_size) is read
     and written.  hw i32 [images, 2]: the sizes of the photos `boxes` index.  c = 2 pi / fps and te = 1 / fps come from the host."""
     F, K = mu.shape[0], mu.shape[1]
-    for name, t, dt, shape in (('mu', mu, torch.float32, (F, K, 2)), ('boxes', boxes, torch.int32, (F, 5)),
-                               ('state', state, torch.float64, (F, 5 + 6 * K)), ('points', points, torch.float32, (F, K, 2)),
-                               ('points_smooth', points_smooth, torch.float32, (F, K, 2)), ('boxes_next', boxes_next, torch.int32, (F, 5)),
-                               ('geom_next', geom_next, torch.float32, (F, 4)), ('flags', flags, torch.int32, (F,))):
-        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-            raise ValueError('%s must be contiguous %s %s, got %s %s' % (name, str(dt).replace('torch.', ''), list(shape), t.dtype,
-                                                                         tuple(t.shape)))
-    if hw.dtype != torch.int32 or hw.dim() != 2 or hw.shape[1] != 2 or not hw.is_contiguous():
-        raise ValueError('hw must be contiguous int32 [images, 2], got %s %s' % (hw.dtype, tuple(hw.shape)))
+    _check_tensors([('mu', mu, torch.float32, (F, K, 2)), ('boxes', boxes, torch.int32, (F, 5)), ('state', state, torch.float64, (F, 5 + 6 * K)),
+                    ('points', points, torch.float32, (F, K, 2)), ('points_smooth', points_smooth, torch.float32, (F, K, 2)),
+                    ('boxes_next', boxes_next, torch.int32, (F, 5)), ('geom_next', geom_next, torch.float32, (F, 4)),
+                    ('flags', flags, torch.int32, (F,)), ('hw', hw, torch.int32, (None, 2))])
     call('imm_track_step', _p(mu), _p(boxes), _p(hw), _p(state), int(K), int(image_size), int(F), int(hw.shape[0]), int(next_image),
          int(init), float(box_smooth), float(min_cutoff), float(beta), float(d_cutoff), float(c), float(te), int(bool(filter_off)),
          _p(points), _p(points_smooth), _p(boxes_next), _p(geom_next), _p(flags), _s())
@@ -824,25 +807,14 @@ def retarget(q, anchor, driver_flags, m, prev, init, relative, rigid, gain, out,
     [K, 2] (set to q with init) and the driver's track_step flags i32 [1] -> the poses out f32 [n, K, 2] of the source faces with the
     landmarks m f32 [n, K, 2], and flags i32 [n] (bit 0: held, out = prev f32 [n, K, 2]).  out may be prev."""
     n, K = m.shape[0], m.shape[1]
-    for name, t, dt, shape in (('q', q, torch.float32, (K, 2)), ('anchor', anchor, torch.float64, (K, 2)),
-                               ('driver_flags', driver_flags, torch.int32, (1,)), ('m', m, torch.float32, (n, K, 2)),
-                               ('prev', prev, torch.float32, (n, K, 2)), ('out', out, torch.float32, (n, K, 2)),
-                               ('flags', flags, torch.int32, (n,))):
-        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-            raise ValueError('%s must be contiguous %s %s, got %s %s' % (name, str(dt).replace('torch.', ''), list(shape), t.dtype,
-                                                                         tuple(t.shape)))
+    _check_tensors([('q', q, torch.float32, (K, 2)), ('anchor', anchor, torch.float64, (K, 2)), ('driver_flags', driver_flags, torch.int32, (1,)),
+                    ('m', m, torch.float32, (n, K, 2)), ('prev', prev, torch.float32, (n, K, 2)), ('out', out, torch.float32, (n, K, 2)),
+                    ('flags', flags, torch.int32, (n,))])
     call('imm_retarget', _p(q), _p(anchor), _p(driver_flags), _p(m), _p(prev), int(K), int(n), int(init), int(bool(relative)),
          int(bool(rigid)), float(gain), _p(out), _p(flags), _s())
 
 
 WARP_MAX_POINTS = 80          # control points of a warp spline: landmarks + border anchors
-
-
-def _check_tensors(specs):
-    for name, t, dt, shape in specs:
-        if t.dtype != dt or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-            raise ValueError('%s must be contiguous %s %s, got %s %s' % (name, str(dt).replace('torch.', ''), list(shape), t.dtype,
-                                                                         tuple(t.shape)))
 
 
 def warp_fit(poses, mu, anchors, strength, lam, coef, ctrl, flags):
@@ -878,18 +850,14 @@ def warp_u8(src, dst, offsets, hw, boxes, links, inv_ramp, ctrl, coef, max_box_p
     if boxes.dim() != 2 or ctrl.dim() != 3:
         raise ValueError('boxes must be int32 [n, 5] and ctrl f32 [n, M, 2], got %s and %s' % (tuple(boxes.shape), tuple(ctrl.shape)))
     n, M = int(boxes.shape[0]), int(ctrl.shape[1])
-    for name, t in (('src', src), ('dst', dst)):
-        if t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
-            raise ValueError('%s must be the flat contiguous u8 buffer, got %s %s' % (name, t.dtype, tuple(t.shape)))
+    _check_tensors([('src', src, torch.uint8, (None,)), ('dst', dst, torch.uint8, (None,))])
     if src.numel() != dst.numel() or src.data_ptr() == dst.data_ptr():
         raise ValueError('dst must be a copy of src (same size, another buffer): every row samples the original pixels')
     if n < 1 or n > 65535 or not 3 <= M <= WARP_MAX_POINTS:
         raise ValueError('warp_u8 serves 1..65535 rows of 3 <= M <= %d control points, got n = %d, M = %d' % (WARP_MAX_POINTS, n, M))
     _check_tensors([('boxes', boxes, torch.int32, (n, 5)), ('links', links, torch.int32, (n, 2)), ('inv_ramp', inv_ramp, torch.float32, (n, 2)),
                     ('ctrl', ctrl, torch.float32, (n, M, 2)), ('coef', coef, torch.float32, (n, M + 3, 2)),
-                    ('offsets', offsets, torch.int64, (hw.shape[0],))])
-    if hw.dtype != torch.int32 or hw.dim() != 2 or hw.shape[1] != 2 or not hw.is_contiguous():
-        raise ValueError('hw must be contiguous int32 [images, 2], got %s %s' % (hw.dtype, tuple(hw.shape)))
+                    ('hw', hw, torch.int32, (None, 2)), ('offsets', offsets, torch.int64, (hw.shape[0],))])
     if int(max_box_pixels) < 1:
         raise ValueError('max_box_pixels must be positive, got %r' % (max_box_pixels,))
     call('imm_warp_u8', _p(src), _p(dst), _p(offsets), _p(hw), int(hw.shape[0]), _p(boxes), _p(links), _p(inv_ramp), _p(ctrl), _p(coef), M, n,
@@ -935,18 +903,16 @@ def morph_u8(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor
     if boxes.dim() != 2 or ctrl.dim() != 3:
         raise ValueError('boxes must be int32 [n, 5] and ctrl f32 [n, M, 2], got %s and %s' % (tuple(boxes.shape), tuple(ctrl.shape)))
     n, M = int(boxes.shape[0]), int(ctrl.shape[1])
-    for name, t in (('src', src), ('dst', dst), ('donor', donor)):
-        if t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
-            raise ValueError('%s must be the flat contiguous u8 buffer, got %s %s' % (name, t.dtype, tuple(t.shape)))
+    _check_tensors([('src', src, torch.uint8, (None,)), ('dst', dst, torch.uint8, (None,)), ('donor', donor, torch.uint8, (None,))])
     if src.numel() != dst.numel() or _overlap(src, dst):
         raise ValueError('dst must be a copy of src (same size, another buffer): every row samples the original pixels')
     if _overlap(donor, dst):
         raise ValueError('the donor buffer is read only: it may be src, never dst')
     if n < 1 or n > 65535 or not 3 <= M <= WARP_MAX_POINTS:
         raise ValueError('morph_u8 serves 1..65535 rows of 3 <= M <= %d control points, got n = %d, M = %d' % (WARP_MAX_POINTS, n, M))
-    for name, t in (('hw', hw), ('donor_hw', donor_hw)):
-        if t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != 2 or t.shape[0] < 1 or not t.is_contiguous():
-            raise ValueError('%s must be contiguous int32 [images, 2], got %s %s' % (name, t.dtype, tuple(t.shape)))
+    _check_tensors([('hw', hw, torch.int32, (None, 2)), ('donor_hw', donor_hw, torch.int32, (None, 2))])
+    if hw.shape[0] < 1 or donor_hw.shape[0] < 1:
+        raise ValueError('hw and donor_hw must hold at least one image, got %s and %s' % (tuple(hw.shape), tuple(donor_hw.shape)))
     _check_tensors([('boxes', boxes, torch.int32, (n, 5)), ('donor_boxes', donor_boxes, torch.int32, (n, 5)), ('links', links, torch.int32, (n, 2)),
                     ('inv_ramp', inv_ramp, torch.float32, (n, 2)), ('texture', texture, torch.float32, (n,)),
                     ('ctrl', ctrl, torch.float32, (n, M, 2)), ('coef_a', coef_a, torch.float32, (n, M + 3, 2)),

@@ -128,13 +128,13 @@ def check_render_keeps_features(gen, bucket):
 def run(gen, plan, return_faces=False):
     """The launches of reenact() for a checked plan (see the module docstring); called with the caller's stream current."""
     from . import ops
-    from .generation import compose_inv_ramp, compose_links
-    from .inference import pack_u8, plan_buckets
+    from .generation import box_areas, compose_inv_ramp, compose_links
+    from .inference import pack_u8, plan_buckets, unpack_u8
     det, S, K, dev = gen.detector, gen.S, gen.K, gen.dev
     photos, rows, frames = plan.photos, plan.rows, plan.frames
     n, T = len(rows), len(frames)
     bucket = plan_buckets(n, gen.max_batch)[0][2]
-    area = (rows[:, 3] - rows[:, 1]).astype(np.int64) * (rows[:, 4] - rows[:, 2]).astype(np.int64)
+    area = box_areas(rows)
     max_pixels = int(min(area.max(), 2 ** 31 - 1))
     cur = torch.cuda.current_stream(dev)
     with torch.cuda.device(dev):
@@ -202,8 +202,5 @@ def run(gen, plan, return_faces=False):
         x.record_stream(gen.stream)
     out = None
     if plan.paste:
-        offs = [0]
-        for a in photos[:-1]:
-            offs.append(offs[-1] + ((a.size + 15) & ~15))
-        out = [[canvas[t, o:o + a.size].view(a.shape) for o, a in zip(offs, photos)] for t in range(T)]
+        out = [unpack_u8(canvas[t], photos) for t in range(T)]
     return Reenactment(lm, flags, faces, out, tracker.result())

@@ -47,9 +47,9 @@ def dev(ops, a):
     return ops.to_device_pinned(np.ascontiguousarray(a), DEV)
 
 
-def run_compose(ops, photos, rows, faces, feather, launches=None):
+def run_compose(ops, photos, rows, faces, feather, launches=None, max_pixels=None):
     """imm_compose_u8 over the packed photos in a guarded buffer, the rows issued as the given launches (lists of row indices, in
-    order; default: one launch of all rows).  Returns (the whole buffer as a host array, the packed input buffer)."""
+    order; default: one launch of all rows), the grid sized by max_pixels (default: the launch's largest box).  Returns (the whole buffer as a host array, the packed input buffer)."""
     buf, offs, hw = R.pack(photos)
     guarded.reset()
     canvas = guarded.out(buf.shape, torch.uint8, DEV, fill=torch.from_numpy(buf))
@@ -57,7 +57,7 @@ def run_compose(ops, photos, rows, faces, feather, launches=None):
     faces_d = guarded.inp(torch.from_numpy(faces), DEV)
     for part in ([list(range(len(rows)))] if launches is None else launches):
         sub = rows[part]
-        area = int(((sub[:, 3] - sub[:, 1]) * (sub[:, 4] - sub[:, 2])).max())
+        area = int(((sub[:, 3] - sub[:, 1]) * (sub[:, 4] - sub[:, 2])).max()) if max_pixels is None else max_pixels
         assert part == list(range(part[0], part[-1] + 1))                 # consecutive rows: their faces are a leading-dimension slice
         ops.compose_u8(canvas, offs_d, hw_d, dev(ops, sub), dev(ops, G.compose_links(sub)), dev(ops, G.compose_inv_ramp(sub, feather)),
                        faces_d[part[0]:part[-1] + 1], area)
@@ -105,6 +105,17 @@ def test_compose_split_invariance(ops):
         apart, _ = run_compose(ops, photos, rows, faces, feather, [list(range(0, 5)), list(range(5, 9)), list(range(9, n))])
         assert np.array_equal(one, pairs) and np.array_equal(one, apart), feather
     assert all(sum(i in part for i in R.OVERLAPPING) == 1 for part in (range(0, 5), range(5, 9), range(9, n)))
+
+
+def test_compose_one_block_per_row(ops):
+    """The grid-size argument set to 1: ONE block of 256 threads per row carries every box through the grid-stride loop, and the bytes
+    are those of a grid as large as the largest box."""
+    photos, rows, faces = R.kernel_case(ld=4)
+    assert ((rows[:, 3] - rows[:, 1]) * (rows[:, 4] - rows[:, 2])).max() > 2 * 256
+    for feather in (0.0, 0.125):
+        full, _ = run_compose(ops, photos, rows, faces, feather)
+        one, _ = run_compose(ops, photos, rows, faces, feather, max_pixels=1)
+        assert np.array_equal(one, full), feather
 
 
 def test_compose_identity(ops):

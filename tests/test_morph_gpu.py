@@ -79,10 +79,11 @@ def device_fit(ops, mu_a, mu_b, shape, m, lam):
     return poses2[0], coef[:n], coef[n:], ctrl[:n], flags[:n] | flags[n:]
 
 
-def run_morph(ops, photos, rows, donors, drows, ctrl, coef_a, coef_b, texture, feather, launches=None, links=None, donor_is_src=False):
+def run_morph(ops, photos, rows, donors, drows, ctrl, coef_a, coef_b, texture, feather, launches=None, links=None, donor_is_src=False,
+              max_pixels=None):
     """imm_morph_u8 over the packed photos; source, donor and canvas in guarded buffers, the rows issued as the given launches (lists of
-    consecutive row indices, in order; default: one launch of all rows).  donor_is_src: the donor buffer IS the source buffer (donors
-    must be the photos).  Returns (the whole canvas as a host array, the packed input)."""
+    consecutive row indices, in order; default: one launch of all rows), the grid sized by max_pixels (default: the launch's largest box).
+    donor_is_src: the donor buffer IS the source buffer (donors must be the photos).  Returns (the whole canvas as a host array, the packed input)."""
     buf, offs, hw = CR.pack(photos)
     dbuf, doffs, dhw = CR.pack(donors)
     guarded.reset()
@@ -98,7 +99,7 @@ def run_morph(ops, photos, rows, donors, drows, ctrl, coef_a, coef_b, texture, f
         assert part == list(range(part[0], part[-1] + 1))
         sl = slice(part[0], part[-1] + 1)
         sub = rows[sl]
-        area = int(max(1, ((sub[:, 3] - sub[:, 1]) * (sub[:, 4] - sub[:, 2])).max()))
+        area = int(max(1, ((sub[:, 3] - sub[:, 1]) * (sub[:, 4] - sub[:, 2])).max())) if max_pixels is None else max_pixels
         lk = G.compose_links(sub) if links is None else links[sl]
         ops.morph_u8(src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, dev(ops, sub), dev(ops, drows[sl]), dev(ops, lk), dev(ops, ramp[sl]),
                      tex_d[sl], ctrl_d[sl], ca_d[sl], cb_d[sl], area)
@@ -262,6 +263,18 @@ def test_morph_split_invariance(ops):
     order = [i for i in range(n) if i not in WR.OVERLAPPING] + list(WR.OVERLAPPING)[::-1]
     rev, _c = R.morph_f32(photos, rows[order], donors, full[order], ctrl[order], coef_a[order], coef_b[order], texture[order], ramp[order])
     assert not all(np.array_equal(a, b) for a, b in zip(fwd, rev))
+
+
+def test_morph_one_block_per_row(ops):
+    """The grid-size argument set to 1: ONE block of 256 threads per row carries every box through the grid-stride loop, and the bytes
+    are those of a grid as large as the largest box."""
+    photos, rows, donors, drows, mu_a, mu_b, shape, texture = R.kernel_case(10, 2)
+    _poses, coef_a, coef_b, ctrl, _flags = device_fit(ops, mu_a, mu_b, shape, 2, 0.0)
+    assert ((rows[:, 3] - rows[:, 1]) * (rows[:, 4] - rows[:, 2])).max() > 2 * 256
+    for feather in (0.0, 0.125):
+        full, _ = run_morph(ops, photos, rows, donors, drows, ctrl, coef_a, coef_b, texture, feather)
+        one, _ = run_morph(ops, photos, rows, donors, drows, ctrl, coef_a, coef_b, texture, feather, max_pixels=1)
+        assert np.array_equal(one, full), feather
 
 
 # ----------------------------------------------------------------------------------------------------------------------------

@@ -58,9 +58,9 @@ def run_maps(ops, coef, geom, boxes, hw, Si, So):
     return fwd.cpu().numpy(), bbox.cpu().numpy()
 
 
-def run_paste(ops, photos, boxes, fwd32, bbox, faces, feather, launches=None, So=SK):
+def run_paste(ops, photos, boxes, fwd32, bbox, faces, feather, launches=None, So=SK, max_pixels=None):
     """imm_unalign_u8 over the packed photos in a guarded buffer, the rows issued as the given launches (lists of consecutive row indices,
-    in order; default: one launch of all rows).  Returns (the whole buffer as a host array, the packed input buffer)."""
+    in order; default: one launch of all rows), the grid sized by max_pixels (default: the launch's largest bbox).  Returns (the whole buffer as a host array, the packed input buffer)."""
     buf, offs, hw = CR.pack(photos)
     guarded.reset()
     canvas = guarded.out(buf.shape, torch.uint8, DEV, fill=torch.from_numpy(buf))
@@ -70,7 +70,7 @@ def run_paste(ops, photos, boxes, fwd32, bbox, faces, feather, launches=None, So
     for part in ([list(range(len(boxes)))] if launches is None else launches):
         assert part == list(range(part[0], part[-1] + 1))                 # consecutive rows: their faces are a leading-dimension slice
         sl = slice(part[0], part[-1] + 1)
-        area = int(max(1, ((bbox[sl, 2] - bbox[sl, 0]) * (bbox[sl, 3] - bbox[sl, 1])).max()))
+        area = int(max(1, ((bbox[sl, 2] - bbox[sl, 0]) * (bbox[sl, 3] - bbox[sl, 1])).max())) if max_pixels is None else max_pixels
         ops.unalign_u8(canvas, offs_d, hw_d, dev(ops, boxes[sl]), dev(ops, G.compose_links(boxes[sl])), dev(ops, fwd32[sl]), dev(ops, bbox[sl]),
                        inv, faces_d[sl], area)
     torch.cuda.synchronize()
@@ -166,6 +166,18 @@ def test_unalign_split_invariance(ops):
         assert np.array_equal(one, two) and np.array_equal(one, each), feather
     # the two-launch split parts the three mutually overlapping rows
     assert sum(i < 4 for i in R.OVERLAPPING) == 2
+
+
+def test_unalign_one_block_per_row(ops):
+    """The grid-size argument set to 1: ONE block of 256 threads per row carries every box through the grid-stride loop, and the bytes
+    are those of a grid as large as the largest box."""
+    photos, boxes, coef, geom, faces = R.kernel_case(ld=12)
+    fwd32, bbox, _B, _t = case_maps(photos, boxes, coef, geom)
+    assert ((bbox[:, 2] - bbox[:, 0]) * (bbox[:, 3] - bbox[:, 1])).max() > 2 * 256
+    for feather in (0.0, 0.125):
+        full, _ = run_paste(ops, photos, boxes, fwd32, bbox, faces, feather)
+        one, _ = run_paste(ops, photos, boxes, fwd32, bbox, faces, feather, max_pixels=1)
+        assert np.array_equal(one, full), feather
 
 
 def test_unalign_identity(ops):

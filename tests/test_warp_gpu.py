@@ -59,9 +59,10 @@ def run_fit(ops, poses, mu, m, strength=1.0, lam=0.0):
     return coef.cpu().numpy(), ctrl.cpu().numpy(), flags.cpu().numpy()
 
 
-def run_warp(ops, photos, rows, ctrl, coef, feather, launches=None, links=None):
+def run_warp(ops, photos, rows, ctrl, coef, feather, launches=None, links=None, max_pixels=None):
     """imm_warp_u8 over the packed photos, source and canvas in guarded buffers, the rows issued as the given launches (lists of
-    consecutive row indices, in order; default: one launch of all rows).  Returns (the whole canvas as a host array, the packed input)."""
+    consecutive row indices, in order; default: one launch of all rows), the grid sized by max_pixels (default: the launch's largest box).
+    Returns (the whole canvas as a host array, the packed input)."""
     buf, offs, hw = CR.pack(photos)
     guarded.reset()
     src = guarded.inp(torch.from_numpy(buf), DEV)
@@ -74,7 +75,7 @@ def run_warp(ops, photos, rows, ctrl, coef, feather, launches=None, links=None):
         assert part == list(range(part[0], part[-1] + 1))
         sl = slice(part[0], part[-1] + 1)
         sub = rows[sl]
-        area = int(max(1, ((sub[:, 3] - sub[:, 1]) * (sub[:, 4] - sub[:, 2])).max()))
+        area = int(max(1, ((sub[:, 3] - sub[:, 1]) * (sub[:, 4] - sub[:, 2])).max())) if max_pixels is None else max_pixels
         lk = G.compose_links(sub) if links is None else links[sl]
         ops.warp_u8(src, canvas, offs_d, hw_d, dev(ops, sub), dev(ops, lk), dev(ops, ramp[sl]), ctrl_d[sl], coef_d[sl], area)
     torch.cuda.synchronize()
@@ -212,6 +213,18 @@ def test_warp_split_invariance(ops):
     order = [i for i in range(n) if i not in R.OVERLAPPING] + list(R.OVERLAPPING)[::-1]
     rev = R.warp_f32(photos, rows[order], ctrl[order], coef[order], ramp[order])
     assert not all(np.array_equal(a, b) for a, b in zip(fwd, rev))
+
+
+def test_warp_one_block_per_row(ops):
+    """The grid-size argument set to 1: ONE block of 256 threads per row carries every box through the grid-stride loop, and the bytes
+    are those of a grid as large as the largest box."""
+    photos, rows, mu, poses = R.kernel_case(10, 2)
+    coef, ctrl, _flags = run_fit(ops, poses, mu, 2)
+    assert ((rows[:, 3] - rows[:, 1]) * (rows[:, 4] - rows[:, 2])).max() > 2 * 256
+    for feather in (0.0, 0.125):
+        full, _ = run_warp(ops, photos, rows, ctrl, coef, feather)
+        one, _ = run_warp(ops, photos, rows, ctrl, coef, feather, max_pixels=1)
+        assert np.array_equal(one, full), feather
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
