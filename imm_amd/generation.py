@@ -29,10 +29,10 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .engine import encoder_spec, n_renderer_out, render_sizes, renderer_spec, trainable_spec
-from .inference import (LandmarkDetector, _Launch, alloc_encoder_weights, as_image_batch, bucket_sizes, check_limits, decode_u8,
-                        encoder_act_elems, fold_batch_norm, folded_encoder_program, pack_folded_encoder, pack_u8, plan_buckets,
-                        read_variables, stage_u8, unpack_u8)
+from .engine import n_renderer_out, render_sizes, renderer_spec, trainable_spec
+from .inference import (NEEDS_U8, BucketRunner, LandmarkDetector, _Launch, alloc_encoder_weights, as_image_batch, check_limits,
+                        decode_u8, fold_batch_norm, folded_encoder_program, pack_folded_encoder, pack_u8, photo_boxes, plan_buckets,
+                        pose_landmarks, read_variables, unalign_grid_pixels, unpack_u8)
 from .keypoints import check_boxes
 from .tracking import OneEuro
 
@@ -59,9 +59,6 @@ def plan_pairs(n_a, n_p, max_batch):
         idx = np.arange(start, start + count)
         out.append((start, count, bucket, idx // n_p, idx % n_p))
     return out
-
-
-NEEDS_U8 = 'boxes need the images as a list of u8 arrays (a tensor batch is already S x S)'
 
 
 def compose_links(rows):
@@ -144,21 +141,41 @@ def _split(names, get):
     return {n: get[n] for n in names}
 
 
-class ImageGenerator(object):
+class PasteSetup(object):
+    """What a call that pastes faces into its photos puts on the device once, on the caller's current stream: the photos packed with
+    their box rows (src, offs_d, hw_d, boxes_d: pack_u8), canvas (a copy of src to paste into; None with clone=False, for a caller
+    that keeps canvases of its own), links_d (bucket_links: one launch per bucket) and ramp_d (compose_inv_ramp); area: box_areas on
+    the host."""
+
+    def __init__(self, photos, rows, buckets, feather, device, clone=True):
+        self.area = box_areas(rows)
+        links = bucket_links(rows, buckets)
+        with torch.cuda.device(device):
+            self.src, self.offs_d, self.hw_d, self.boxes_d = pack_u8(photos, device, rows)
+            self.canvas = self.src.clone() if clone else None
+            self.links_d = ops.to_device_pinned(links, device)
+            self.ramp_d = ops.to_device_pinned(compose_inv_ramp(rows, feather), device)
+
+    def tensors(self):
+        """The device tensors, for record_stream."""
+        return self.src, self.canvas, self.offs_d, self.hw_d, self.boxes_d, self.links_d, self.ramp_d
+
+    def packed(self, part):
+        """The rows `part` (a slice) as BucketRunner._stage takes them."""
+        return self.src, self.offs_d, self.hw_d, self.boxes_d[part]
+
+    def max_pixels(self, part):
+        """The grid argument of a paste launch over the rows `part`: its largest box."""
+        return int(min(self.area[part].max(), 2 ** 31 - 1))
+
+
+class ImageGenerator(BucketRunner):
     """reconstruct(x, y) / render(x, landmarks) / transfer(appearance, poses) of a trained model (see the module docstring).
     `model` is an IMMModel whose variables exist; the generator reads them, never writes them, and refresh() re-reads them."""
+    what = 'generator'
 
     def __init__(self, model, image_size=128, max_batch=128, use_graph=True):
-        eng = getattr(model, '_master', None) or getattr(model, 'engine', None)
-        if eng is None:
-            raise RuntimeError('the model has no variables yet: build, train or restore it first '
-                               '(or use ImageGenerator.from_checkpoint)')
-        self._model = model
-        self._static = None
-        self._check(model._config, model.dtype, image_size)
-        self.detector = LandmarkDetector(model, image_size=image_size, max_batch=max_batch, use_graph=use_graph)
-        self._setup(model._config, model.dtype, eng.dev, image_size, max_batch, use_graph)
-        self.refresh(detector=False)
+        super(ImageGenerator, self).__init__(model, image_size, max_batch, use_graph)
 
     @classmethod
     def from_checkpoint(cls, config, path, image_size=128, max_batch=128, dtype=torch.bfloat16, device=None, use_graph=True):
@@ -167,15 +184,7 @@ class ImageGenerator(object):
         cls._check(config, dtype, image_size)
         pnames, snames = generator_names(config, int(image_size))
         get = read_variables(path, pnames + snames, 'generator')
-        gen = cls.__new__(cls)
-        gen._model = None
-        gen._static = (_split(pnames, get), _split(snames, get))
-        if device is None:
-            device = 'cuda:%d' % torch.cuda.current_device()
-        gen.detector = LandmarkDetector._from_variables(config, gen._static, image_size, max_batch, dtype, device, use_graph)
-        gen._setup(config, dtype, torch.device(device), image_size, max_batch, use_graph)
-        gen.refresh(detector=False)
-        return gen
+        return cls._from_variables(config, (_split(pnames, get), _split(snames, get)), image_size, max_batch, dtype, device, use_graph)
 
     # ------------------------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -186,22 +195,17 @@ class ImageGenerator(object):
             raise NotImplementedError('renderer starts at 16x16 (min_res 16, renderer_stride 2): got %d' % s16)
 
     def _setup(self, cfg, dtype, device, image_size, max_batch, use_graph):
-        S, K, nf = check_limits(cfg, dtype, image_size, 'generator')
-        L.load()
-        self.cfg, self.dt, self.dev, self.S, self.K, self.nf = cfg, dtype, torch.device(device), S, K, nf
-        self.max_batch = int(max_batch)
-        bucket_sizes(self.max_batch)
-        self.use_graph = bool(use_graph)
-        self.He = S // 8
-        self.C8 = 8 * nf
-        self.Cj = ops.round_up(self.C8 + K, 64)      # the engine's joint width: whole 64-channel K slices, zero padded
-        self.inv_std = 1.0 / float(cfg.gauss_std)
-        self.spec = encoder_spec(nf)
+        self._check(cfg, dtype, image_size)
+        if self._model is not None:
+            self.detector = LandmarkDetector(self._model, image_size=image_size, max_batch=max_batch, use_graph=use_graph)
+        else:
+            self.detector = LandmarkDetector._from_variables(cfg, self._static, image_size, max_batch, dtype, device, use_graph)
+        super(ImageGenerator, self)._setup(cfg, dtype, device, image_size, max_batch, use_graph)
+        self.C8 = 8 * self.nf
+        self.Cj = ops.round_up(self.C8 + self.K, 64)      # the engine's joint width: whole 64-channel K slices, zero padded
         self.n_out = n_renderer_out(cfg)
-        self.rspec = renderer_spec(cfg, S, self.n_out)
+        self.rspec = renderer_spec(cfg, self.S, self.n_out)
         self.ldp = ops.round_up(self.n_out, 4)
-        self.stream = torch.cuda.Stream(device=self.dev)
-        self._stager = ops.PinnedStager()
         with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
             self.wt_im, self.bias_im = alloc_encoder_weights(self.spec, dtype, self.dev)
             self.wt_r, self.bias_r = [], []
@@ -210,40 +214,35 @@ class ImageGenerator(object):
                 self.wt_r.append(torch.zeros(ops.round_up(co, 128), ops.round_up(k * k * ci_pad, 32), dtype=dtype, device=self.dev))
                 self.bias_r.append(torch.zeros(co, dtype=torch.float32, device=self.dev))
                 ci_pad = co
-        self._cap = 0
-        self._graphs = {}
+
+    def _names(self):
+        return generator_names(self.cfg, self.S)
 
     def refresh(self, detector=True):
         """(Re-)read the variables (the model's current ones, or the checkpoint's), fold the batch norms and re-pack the filters
         in place: captured programs stay valid.  detector=True refreshes gen.detector too."""
-        if self._static is not None:
-            params, state = self._static
-        else:
-            eng = getattr(self._model, '_master', None) or self._model.engine
-            pnames, snames = generator_names(self.cfg, self.S)
-            params = {n: ops.download(eng.pview[n]) for n in pnames}
-            state = {n: ops.download(eng.state[n]) for n in snames}
+        variables = self._variables()
         if detector:
             self.detector.refresh()
-        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
-            pack_folded_encoder(params, state, IMAGE_SCOPE, self.spec, self.wt_im, self.bias_im, self.dev)
-            ci_real, ci_pad = self.C8 + self.K, self.Cj
-            for i, (k, ci, co, bn, _up) in enumerate(self.rspec):
-                sc = '%s/conv_%d' % (RENDER_SCOPE, i + 1)
-                w, b = params[sc + '/w'].double().numpy(), params[sc + '/b'].double().numpy()
-                if bn:
-                    w, b = fold_batch_norm(w, b, params[sc + '/gamma'], params[sc + '/beta'], state[sc + '/moving_mean'],
-                                           state[sc + '/moving_variance'])
-                if w.shape != (k, k, ci, co) or ci != ci_real:
-                    raise ValueError('%s/w: shape %s != %s' % (sc, w.shape, (k, k, ci_real, co)))
-                w_dev = torch.empty(w.shape, dtype=torch.float32, device=self.dev)
-                ops.upload(w_dev, torch.from_numpy(w.astype(np.float32)), sc + '/w (folded)' if bn else sc + '/w')
-                rows, kpad = self.wt_r[i].shape
-                ops.pack_weights(w_dev, self.wt_r[i], 0, k, k, ci_real, co, ci_pad, rows, kpad)
-                ops.upload(self.bias_r[i], torch.from_numpy(b.astype(np.float32)), sc + '/b (folded)' if bn else sc + '/b')
-                ci_real, ci_pad = co, co
-            self.stream.synchronize()
+        self._repack(*variables)
+
+    def _pack(self, params, state):
+        pack_folded_encoder(params, state, IMAGE_SCOPE, self.spec, self.wt_im, self.bias_im, self.dev)
+        ci_real, ci_pad = self.C8 + self.K, self.Cj
+        for i, (k, ci, co, bn, _up) in enumerate(self.rspec):
+            sc = '%s/conv_%d' % (RENDER_SCOPE, i + 1)
+            w, b = params[sc + '/w'].double().numpy(), params[sc + '/b'].double().numpy()
+            if bn:
+                w, b = fold_batch_norm(w, b, params[sc + '/gamma'], params[sc + '/beta'], state[sc + '/moving_mean'],
+                                       state[sc + '/moving_variance'])
+            if w.shape != (k, k, ci, co) or ci != ci_real:
+                raise ValueError('%s/w: shape %s != %s' % (sc, w.shape, (k, k, ci_real, co)))
+            w_dev = torch.empty(w.shape, dtype=torch.float32, device=self.dev)
+            ops.upload(w_dev, torch.from_numpy(w.astype(np.float32)), sc + '/w (folded)' if bn else sc + '/w')
+            rows, kpad = self.wt_r[i].shape
+            ops.pack_weights(w_dev, self.wt_r[i], 0, k, k, ci_real, co, ci_pad, rows, kpad)
+            ops.upload(self.bias_r[i], torch.from_numpy(b.astype(np.float32)), sc + '/b (folded)' if bn else sc + '/b')
+            ci_real, ci_pad = co, co
 
     # ------------------------------------------------------------------------------------------------------------------------
     def _render_act_elems(self, batch):
@@ -256,30 +255,12 @@ class ImageGenerator(object):
                 n = max(n, batch * H * H * co)
         return n
 
-    def _ensure_capacity(self, batch):
-        """Buffers of one bucket, sized for the largest bucket run so far (smaller buckets use leading views)."""
-        if batch <= self._cap:
-            return
-        self.stream.synchronize()
-        self._graphs = {}                              # they address the old buffers
-        S, K = self.S, self.K
-        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
-            self._img = torch.zeros(batch, S, S, 3, device=self.dev)
-            self._xin = None
-            n_act = encoder_act_elems(self.spec, S, batch)
-            self._act = [torch.zeros(n_act, dtype=self.dt, device=self.dev) for _ in range(2)]
-            self._joint = torch.zeros(batch, 16, 16, self.Cj, dtype=self.dt, device=self.dev)    # padding channels stay zero
-            self._mu = torch.zeros(batch, K, 2, device=self.dev)
-            n_r = self._render_act_elems(batch)
-            self._ract = [torch.zeros(n_r, dtype=self.dt, device=self.dev) for _ in range(2)]
-            self._pred = torch.zeros(batch, S, S, self.ldp, device=self.dev)
-        self._cap = batch
-
-    def _xin_for(self, batch):
-        if self._xin is None or self._xin.shape[0] < batch:
-            with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
-                self._xin = torch.zeros(self._cap, self.S, self.S, 32, dtype=self.dt, device=self.dev)
-        return self._xin[:batch]
+    def _alloc(self, batch):
+        self._joint = torch.zeros(batch, 16, 16, self.Cj, dtype=self.dt, device=self.dev)    # padding channels stay zero
+        self._mu = torch.zeros(batch, self.K, 2, device=self.dev)
+        n_r = self._render_act_elems(batch)
+        self._ract = [torch.zeros(n_r, dtype=self.dt, device=self.dev) for _ in range(2)]
+        self._pred = torch.zeros(batch, self.S, self.S, self.ldp, device=self.dev)
 
     def program(self, stage, batch):
         """The launches of one bucket of a stage: [_Launch(tag, name, family, fn)].  stage 'appearance': image rows
@@ -331,52 +312,24 @@ class ImageGenerator(object):
 
     def _run(self, stage, batch):
         """Issue the (graph of the) program of one stage and bucket on the generator's stream."""
-        if not self.use_graph:
-            for l in self.program(stage, batch):
-                l.fn()
-            return
-        g = self._graphs.get((stage, batch))
-        if g is None:
-            prog = self.program(stage, batch)
-            for l in prog:                 # warm-up outside capture (code-object loading, LDS attribute calls)
-                l.fn()
-            self.stream.synchronize()
-            g = ops.Graph()
-            g.capture_begin()
-            for l in prog:
-                l.fn()
-            g.capture_end()
-            self._graphs[(stage, batch)] = g
-        g.launch()
+        self._launch((stage, batch), lambda: self.program(stage, batch))
+
+    def _capture(self, stage, batch):
+        """Make sure _run(stage, batch) finds its graph captured (BucketRunner._launch, ahead=True)."""
+        self._launch((stage, batch), lambda: self.program(stage, batch), ahead=True)
 
     # ------------------------------------------------------------------------------------------------------------------------
     def _rows(self, images, boxes):
         """(images, u8, rows): detect()'s input forms, and with boxes (u8 photos only; keypoints.check_boxes) the photos decoded and
         the box rows int32 [n, 5] that take the images' place; rows is None without boxes."""
-        images, u8 = as_image_batch(images, self.S)
         if boxes is None:
-            return images, u8, None
-        if not u8:
-            raise ValueError(NEEDS_U8)
-        images = decode_u8(images)
-        return images, u8, check_boxes(boxes, len(images))
+            return as_image_batch(images, self.S) + (None,)
+        return photo_boxes(images, boxes, self.S)
 
-    def _encode(self, images, u8, start, count, bucket, rows=None):
+    def _encode(self, images, rows, start, count, bucket):
         """Appearance stage of images [start, start + count) into joint rows [0, count) (bucket `bucket`, tail zero images).  With
         rows (int32 [n, 5] boxes over u8 photos) the rows [start, start + count) take the images' place, cut and resized on the GPU."""
-        self._ensure_capacity(bucket)
-        if rows is not None:
-            # the photos this bucket's boxes cut from, packed once each; box rows renumbered into that list (as keypoints() does)
-            part = rows[start:start + count]
-            used, idx = np.unique(part[:, 0], return_inverse=True)
-            local = np.concatenate([idx.reshape(-1, 1).astype(np.int32), part[:, 1:]], axis=1)
-            stage_u8([images[i] for i in used], self._img[:count], self.S, self.dev, boxes=local)
-        elif u8:
-            stage_u8(images[start:start + count], self._img[:count], self.S, self.dev)
-        else:
-            self._stager.copy(self._img[:count], images[start:start + count], ('images', count))
-        if count < bucket:
-            self._img[count:bucket].zero_()
+        self._stage_rows(images, rows, start, count, bucket)
         self._run('appearance', bucket)
 
     def _landmarks(self, landmarks, n):
@@ -385,25 +338,26 @@ class ImageGenerator(object):
             raise ValueError('landmarks must be [%d, %d, 2], got %s' % (n, self.K, tuple(lm.shape)))
         return lm.to(device=self.dev, dtype=torch.float32)
 
+    def _stage_mu(self, lm, count, bucket):
+        """The render stage's input rows of one bucket: _mu[:count] = lm, the tail zero."""
+        self._mu[:count].copy_(lm)
+        if count < bucket:
+            self._mu[count:bucket].zero_()
+
     def render(self, images, landmarks, boxes=None):
         """images (detect()'s forms, N of them) rendered at landmarks f32 [N, K, 2] ((y, x) in [-1, 1]): f32 [N, S, S, 3],
         unclipped, in the 0..255 scale of future_im_pred.  boxes (as keypoints() takes them, u8 photos only): the N rows are the
         boxes, cut from their photos with zero padding and resized to S x S on the GPU."""
-        images, u8, rows = self._rows(images, boxes)
+        images, _u8, rows = self._rows(images, boxes)
         N = len(images) if rows is None else len(rows)
-        cur = torch.cuda.current_stream(self.dev)
         lm = self._landmarks(landmarks, N)
         out = torch.empty(N, self.S, self.S, 3, device=self.dev)
-        self.stream.wait_stream(cur)
-        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+        with self._forked():
             for start, count, bucket in plan_buckets(N, self.max_batch):
-                self._encode(images, u8, start, count, bucket, rows)
-                self._mu[:count].copy_(lm[start:start + count])
-                if count < bucket:
-                    self._mu[count:bucket].zero_()
+                self._encode(images, rows, start, count, bucket)
+                self._stage_mu(lm[start:start + count], count, bucket)
                 self._run('render', bucket)
                 out[start:start + count].copy_(self._pred[:count, ..., :3])
-        cur.wait_stream(self.stream)
         return out
 
     def reconstruct(self, images, future_images, boxes=None, pose_boxes=None):
@@ -424,7 +378,7 @@ class ImageGenerator(object):
         rendered in buckets, their joint rows gathered from the stored features.  return_landmarks=True: (images, the poses'
         landmarks f32 [P, K, 2] it rendered at).  boxes / pose_boxes (u8 photos only): the A appearance rows / the P pose rows are
         the boxes of those photos."""
-        appearance, u8, rows = self._rows(appearance, boxes)
+        appearance, _u8, rows = self._rows(appearance, boxes)
         n_a = len(appearance) if rows is None else len(rows)
         if pose_boxes is None:
             mu_p = self.detector.detect(poses)
@@ -433,26 +387,22 @@ class ImageGenerator(object):
                 raise ValueError(NEEDS_U8)
             mu_p = self.detector.landmarks(poses, pose_boxes)
         n_p = mu_p.shape[0]
-        cur = torch.cuda.current_stream(self.dev)
         out = torch.empty(n_a * n_p, self.S, self.S, 3, device=self.dev)
-        self.stream.wait_stream(cur)
-        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+        with self._forked():
             feats = torch.empty(n_a, 16, 16, self.C8, dtype=self.dt, device=self.dev)
             for start, count, bucket in plan_buckets(n_a, self.max_batch):
-                self._encode(appearance, u8, start, count, bucket, rows)
+                self._encode(appearance, rows, start, count, bucket)
                 feats[start:start + count].copy_(self._joint[:count, ..., :self.C8])
             for start, count, bucket, a_idx, p_idx in plan_pairs(n_a, n_p, self.max_batch):
                 self._ensure_capacity(bucket)
                 a_idx = torch.from_numpy(a_idx).to(self.dev)
                 p_idx = torch.from_numpy(p_idx).to(self.dev)
                 self._joint[:count, ..., :self.C8].copy_(feats.index_select(0, a_idx))
-                self._mu[:count].copy_(mu_p.index_select(0, p_idx))
                 if count < bucket:
                     self._joint[count:bucket, ..., :self.C8].zero_()
-                    self._mu[count:bucket].zero_()
+                self._stage_mu(mu_p.index_select(0, p_idx), count, bucket)
                 self._run('render', bucket)
                 out[start:start + count].copy_(self._pred[:count, ..., :3])
-        cur.wait_stream(self.stream)
         out = out.view(n_a, n_p, self.S, self.S, 3)
         return (out, mu_p) if return_landmarks else out
 
@@ -476,42 +426,22 @@ class ImageGenerator(object):
         S = self.S
         photos, rows, pose, feather = plan_repose(photos, poses, boxes, pose_boxes, feather, self.K)
         n = len(rows)
-        if pose[0] == 'photos':
-            lm = self.detector.landmarks(pose[1], pose[2])
-        else:
-            lm = pose[1].to(device=self.dev, dtype=torch.float32)
-        if lm.shape[0] != n:
-            lm = lm.expand(n, self.K, 2)
+        lm = pose_landmarks(self.detector, pose, n)
         buckets = plan_buckets(n, self.max_batch)
-        links = bucket_links(rows, buckets)
-        area = box_areas(rows)
-        cur = torch.cuda.current_stream(self.dev)
-        with torch.cuda.device(self.dev):
-            src, offs_d, hw_d, boxes_d = pack_u8(photos, self.dev, rows)            # all photos, once per call
-            canvas = src.clone()
-            links_d = ops.to_device_pinned(links, self.dev)
-            ramp_d = ops.to_device_pinned(compose_inv_ramp(rows, feather), self.dev)
-            faces = torch.empty(n, S, S, 3, device=self.dev) if return_faces else None
-        self.stream.wait_stream(cur)
-        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+        ps = PasteSetup(photos, rows, buckets, feather, self.dev)                   # all photos, once per call
+        faces = torch.empty(n, S, S, 3, device=self.dev) if return_faces else None
+        with self._forked(*ps.tensors()):
             for start, count, bucket in buckets:
-                self._ensure_capacity(bucket)
                 part = slice(start, start + count)
-                ops.resize_crop_u8(src, offs_d, hw_d, 3, (S, S), (0, 0), (S, S), self._img[:count], boxes=boxes_d[part])
-                self._mu[:count].copy_(lm[part])
-                if count < bucket:
-                    self._img[count:bucket].zero_()
-                    self._mu[count:bucket].zero_()
+                self._stage(count, bucket, packed=ps.packed(part))
+                self._stage_mu(lm[part], count, bucket)
                 self._run('appearance', bucket)
                 self._run('render', bucket)
-                ops.compose_u8(canvas, offs_d, hw_d, boxes_d[part], links_d[part], ramp_d[part], self._pred[:count],
-                               int(min(area[part].max(), 2 ** 31 - 1)))
+                ops.compose_u8(ps.canvas, ps.offs_d, ps.hw_d, ps.boxes_d[part], ps.links_d[part], ps.ramp_d[part], self._pred[:count],
+                               ps.max_pixels(part))
                 if return_faces:
                     faces[part].copy_(self._pred[:count, ..., :3])
-        cur.wait_stream(self.stream)
-        for t in (src, offs_d, hw_d, boxes_d, links_d, ramp_d):
-            t.record_stream(self.stream)
-        out = unpack_u8(canvas, photos)
+        out = unpack_u8(ps.canvas, photos)
         return (out, faces, lm.contiguous()) if return_faces else out
 
     def reenact(self, photos, frames, driver_box, boxes=None, motion='relative', rigid=True, gain=1.0, smooth=True, feather=0.125,
@@ -539,20 +469,13 @@ class ImageGenerator(object):
         """repose() with a template: align -> encode -> render -> paste through the inverse map.  The photos are packed once: the
         detector's align() reads that buffer, and since every face is aligned before the first paste the same buffer is pasted into."""
         from . import alignment as AL
-        from .inference import unalign_grid_pixels
         S, det = self.S, self.detector
         check_repose_template(template, model, self.K, S)
         photos, rows, pose, feather = plan_repose(photos, poses, boxes, pose_boxes, feather, self.K)
         n = len(rows)
-        if pose[0] == 'photos':
-            lm = det.detect(det.align(pose[1], template, pose[2], model))
-        else:
-            lm = pose[1].to(device=self.dev, dtype=torch.float32)
-        if lm.shape[0] != n:
-            lm = lm.expand(n, self.K, 2)
+        lm = pose_landmarks(det, pose, n, lambda p, b: det.detect(det.align(p, template, b, model)))
         buckets = plan_buckets(n, self.max_batch)
         links = bucket_links(rows, buckets)
-        cur = torch.cuda.current_stream(self.dev)
         with torch.cuda.device(self.dev):
             canvas, offs_d, hw_d, boxes_d = pack_u8(photos, self.dev, rows)         # all photos, once per call
             links_d = ops.to_device_pinned(links, self.dev)
@@ -562,24 +485,16 @@ class ImageGenerator(object):
             ops.unalign_maps(al.coef, al.geom, boxes_d, hw_d, S, S, fwd, bbox)      # the coefficients never leave the device
             faces = torch.empty(n, S, S, 3, device=self.dev) if return_faces else None
         inv_ramp = AL.unalign_inv_ramp(feather, S)
-        self.stream.wait_stream(cur)
-        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+        with self._forked(canvas, offs_d, hw_d, boxes_d, links_d, aligned, fwd, bbox):
             for start, count, bucket in buckets:
-                self._ensure_capacity(bucket)
                 part = slice(start, start + count)
-                self._img[:count].copy_(aligned[part])
-                self._mu[:count].copy_(lm[part])
-                if count < bucket:
-                    self._img[count:bucket].zero_()
-                    self._mu[count:bucket].zero_()
+                self._stage(count, bucket, aligned[part])
+                self._stage_mu(lm[part], count, bucket)
                 self._run('appearance', bucket)
                 self._run('render', bucket)
                 ops.unalign_u8(canvas, offs_d, hw_d, boxes_d[part], links_d[part], fwd[part], bbox[part], inv_ramp, self._pred[:count],
                                unalign_grid_pixels(photos, rows[part]))
                 if return_faces:
                     faces[part].copy_(self._pred[:count, ..., :3])
-        cur.wait_stream(self.stream)
-        for t in (canvas, offs_d, hw_d, boxes_d, links_d, aligned, fwd, bbox):
-            t.record_stream(self.stream)
         out = unpack_u8(canvas, photos)
         return (out, faces, lm.contiguous()) if return_faces else out

@@ -24,12 +24,15 @@ of images is then 10 launches, captured into a HIP graph per power-of-two batch 
 No statistics, no batch-norm launches, nothing written back to the model: parameters, moving statistics, loss normalisers,
 step counters stay bit-identical.  Eval-mode batch norm is per sample, so the zero-padded tail of a bucket cannot change a result.
 """
+import contextlib
+
 import numpy as np
 import torch
 
 from . import _lib as L
 from . import ops
 from .engine import BN_EPS, encoder_spec
+from .keypoints import box_geometry, check_boxes
 from .tracking import OneEuro
 
 POSE_SCOPE = 'model/pose_encoder'
@@ -312,6 +315,47 @@ def unalign_grid_pixels(photos, rows):
     return int(max(1, min(2 * max(box, 1), photo, 2 ** 31 - 1)))
 
 
+NEEDS_U8 = 'boxes need the images as a list of u8 arrays (a tensor batch is already S x S)'
+
+
+def local_rows(part):
+    """The box rows int32 [n, 5] of one bucket renumbered into the photos they use: (used, local) with `used` the sorted indices of
+    those photos (each packed once) and `local` the rows with column 0 indexing into `used`."""
+    used, idx = np.unique(part[:, 0], return_inverse=True)
+    return used, np.concatenate([idx.reshape(-1, 1).astype(np.int32), part[:, 1:]], axis=1)
+
+
+def photo_boxes(images, boxes, S):
+    """keypoints()'s input forms resolved: (images, u8, rows).  A list of u8 photos comes back decoded, with its box rows int32 [n, 5]
+    (keypoints.check_boxes; one whole-photo box per photo without boxes).  A tensor batch [N, S, S, 3] takes no boxes and has no rows."""
+    images, u8 = as_image_batch(images, S)
+    if not u8:
+        if boxes is not None:
+            raise ValueError(NEEDS_U8)
+        return images, False, None
+    images = decode_u8(images)
+    return images, True, check_boxes([(0, 0, a.shape[0], a.shape[1]) for a in images] if boxes is None else boxes, len(images))
+
+
+def photo_rows(images, boxes, S):
+    """photo_boxes and the rows' geometry f32 [n, 4] (keypoints.box_geometry; (0, 0, 1, 1) per image of a tensor batch):
+    (images, u8, rows, geom)."""
+    images, u8, rows = photo_boxes(images, boxes, S)
+    geom = box_geometry(rows, S) if u8 else np.tile(np.array([0, 0, 1, 1], np.float32), (len(images), 1))
+    return images, u8, rows, geom
+
+
+def pose_landmarks(detector, pose, n, from_photos=None):
+    """A pose source as generation.plan_repose returns it -> landmarks f32 [n, K, 2] on the detector's device: ('landmarks', tensor
+    [n or 1, K, 2]) is moved there, ('photos', u8 photos, boxes) goes through from_photos(photos, boxes) (default: detector.landmarks);
+    one row is expanded (a view) to n."""
+    if pose[0] == 'photos':
+        lm = (from_photos or detector.landmarks)(pose[1], pose[2])
+    else:
+        lm = pose[1].to(device=detector.dev, dtype=torch.float32)
+    return lm.expand(n, detector.K, 2) if lm.shape[0] != n else lm
+
+
 class _Launch(object):
     __slots__ = ('tag', 'name', 'family', 'fn')
 
@@ -319,43 +363,36 @@ class _Launch(object):
         self.tag, self.name, self.family, self.fn = tag, name, family, fn
 
 
-class LandmarkDetector(object):
-    """Unsupervised landmarks of a trained model: detect(images) -> mu f32 [N, K, 2], (y, x) in [-1, 1] (= the eval path's
-    `gauss_yx`).  `model` is an IMMModel whose variables exist (trained, restored, or built once); the detector reads them,
-    never writes them, and refresh() re-reads them after further training."""
+class BucketRunner(object):
+    """What LandmarkDetector and ImageGenerator share: a folded encoder run in power-of-two batch buckets on the object's own stream.
+    It owns the construction state (cfg, dt, dev, S, K, nf, max_batch, use_graph, He, inv_std, spec, stream, _stager), the buffers of
+    one bucket sized for the largest bucket run so far (_img, _xin, _act; the subclass's in _alloc), the graph cache (_graphs, dropped
+    whenever the buffers are reallocated), the staging of a bucket's input rows (_stage) and the fork to the object's stream and back
+    (_forked).  A subclass says what it reads (_names), how it packs it (_pack), what else a bucket needs (_alloc) and its launches
+    (program, _run) and the word for itself in error messages (what)."""
 
-    def __init__(self, model, image_size=128, max_batch=256, use_graph=True):
+    def __init__(self, model, image_size, max_batch, use_graph):
         eng = getattr(model, '_master', None) or getattr(model, 'engine', None)
         if eng is None:
             raise RuntimeError('the model has no variables yet: build, train or restore it first '
-                               '(or use LandmarkDetector.from_checkpoint)')
-        self._model = model
-        self._static = None
+                               '(or use %s.from_checkpoint)' % type(self).__name__)
+        self._model, self._static = model, None
         self._setup(model._config, model.dtype, eng.dev, image_size, max_batch, use_graph)
-        self.refresh()
-
-    @classmethod
-    def from_checkpoint(cls, config, path, image_size=128, max_batch=256, dtype=torch.bfloat16, device=None, use_graph=True):
-        """A detector straight from a checkpoint (`.pt` file or TensorFlow bundle prefix), without a training engine.
-        config: the `model:` block of the experiment config (config.model)."""
-        return cls._from_variables(config, read_checkpoint(path, int(config.n_filters)), image_size, max_batch, dtype, device,
-                                   use_graph)
+        self._repack(*self._variables())
 
     @classmethod
     def _from_variables(cls, config, static, image_size, max_batch, dtype, device, use_graph):
-        """A detector over host variables (params, state) that it keeps for refresh()."""
-        det = cls.__new__(cls)
-        det._model = None
-        det._static = static
+        """An object over host variables (params, state) that it keeps for refresh()."""
+        obj = cls.__new__(cls)
+        obj._model, obj._static = None, static
         if device is None:
             device = 'cuda:%d' % torch.cuda.current_device()
-        det._setup(config, dtype, torch.device(device), image_size, max_batch, use_graph)
-        det.refresh()
-        return det
+        obj._setup(config, dtype, torch.device(device), image_size, max_batch, use_graph)
+        obj._repack(*obj._variables())
+        return obj
 
-    # ------------------------------------------------------------------------------------------------------------------------
     def _setup(self, cfg, dtype, device, image_size, max_batch, use_graph):
-        S, K, nf = check_limits(cfg, dtype, image_size)
+        S, K, nf = check_limits(cfg, dtype, image_size, self.what)
         L.load()
         self.cfg, self.dt, self.dev, self.S, self.K, self.nf = cfg, dtype, torch.device(device), S, K, nf
         self.max_batch = int(max_batch)
@@ -364,15 +401,151 @@ class LandmarkDetector(object):
         self.He = S // 8
         self.inv_std = 1.0 / float(cfg.gauss_std)
         self.spec = encoder_spec(nf)
+        self.stream = torch.cuda.Stream(device=self.dev)
+        self._stager = ops.PinnedStager()
+        self._cap = 0
+        self._graphs = {}
+
+    def _variables(self):
+        """(params, state) of _names() as host tensors: the stored checkpoint's, or the live engine's current ones."""
+        if self._static is not None:
+            return self._static
+        eng = getattr(self._model, '_master', None) or self._model.engine
+        pnames, snames = self._names()
+        return {n: ops.download(eng.pview[n]) for n in pnames}, {n: ops.download(eng.state[n]) for n in snames}
+
+    def _repack(self, params, state):
+        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            self._pack(params, state)
+            self.stream.synchronize()
+
+    def refresh(self):
+        """(Re-)read the variables (the model's current ones, or the checkpoint's), fold the batch norms and re-pack the filters
+        in place: captured programs stay valid."""
+        self._repack(*self._variables())
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    def _ensure_capacity(self, batch):
+        """Buffers of one bucket, sized for the largest bucket run so far (smaller buckets use leading views).  Allocated with the
+        object's stream current: the caching allocator ties a block to the stream it was allocated on."""
+        if batch <= self._cap:
+            return
+        self.stream.synchronize()
+        self._graphs = {}                              # they address the old buffers
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            self._img = torch.zeros(batch, self.S, self.S, 3, device=self.dev)
+            self._xin = None
+            n_act = encoder_act_elems(self.spec, self.S, batch)
+            self._act = [torch.zeros(n_act, dtype=self.dt, device=self.dev) for _ in range(2)]
+            self._alloc(batch)
+        self._cap = batch
+
+    def _xin_for(self, batch):
+        if self._xin is None or self._xin.shape[0] < batch:
+            with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+                self._xin = torch.zeros(self._cap, self.S, self.S, 32, dtype=self.dt, device=self.dev)
+        return self._xin[:batch]
+
+    def _launch(self, key, program, ahead=False):
+        """Issue the launches program() returns (those with a fn) on the current stream: one by one without use_graph, else as the
+        graph cached under `key`, captured on a miss.  ahead=True only makes sure of the cache (a miss captures, with its
+        synchronisation, and launches once; a hit and use_graph=False do nothing): what a caller does ahead of a clip's first frame."""
+        if ahead and (not self.use_graph or key in self._graphs):
+            return
+        if not self.use_graph:
+            for l in program():
+                if l.fn is not None:
+                    l.fn()
+            return
+        g = self._graphs.get(key)
+        if g is None:
+            prog = [l for l in program() if l.fn is not None]
+            for l in prog:                 # warm-up outside capture (code-object loading, LDS attribute calls)
+                l.fn()
+            self.stream.synchronize()
+            g = ops.Graph()
+            g.capture_begin()
+            for l in prog:
+                l.fn()
+            g.capture_end()
+            self._graphs[key] = g
+        g.launch()
+
+    def _stage(self, count, bucket, images=None, boxes=None, packed=None):
+        """The input rows of one bucket (current stream): _img[:count] filled, _img[count:bucket] zeroed.  images: a float batch
+        [count, S, S, 3] (host or device), or a list of u8 photos resized on the GPU, with boxes (int32 [count, 5] rows over that list)
+        cut and resized per box; or packed = (src, offs_d, hw_d, boxes_d), pack_u8's tensors with this bucket's count box rows.  Returns
+        the packed tensors (None for a float batch)."""
+        self._ensure_capacity(bucket)
+        S, dst = self.S, self._img[:count]
+        if packed is not None:
+            ops.resize_crop_u8(packed[0], packed[1], packed[2], 3, (S, S), (0, 0), (S, S), dst, boxes=packed[3])
+        elif isinstance(images, (list, tuple)):
+            packed = stage_u8(images, dst, S, self.dev, boxes=boxes)
+        else:
+            self._stager.copy(dst, images, ('images', count))
+        if count < bucket:
+            self._img[count:bucket].zero_()
+        return packed
+
+    def _stage_rows(self, images, rows, start, count, bucket):
+        """_stage of rows [start, start + count) of a call: of the images themselves (rows None), or of box rows int32 [n, 5] over u8
+        photos: the photos these rows cut from, packed once each."""
+        if rows is None:
+            return self._stage(count, bucket, images[start:start + count])
+        used, local = local_rows(rows[start:start + count])
+        return self._stage(count, bucket, [images[i] for i in used], local)
+
+    def _fork(self):
+        """The object's stream waits for the caller's current stream, which is returned."""
+        cur = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(cur)
+        return cur
+
+    def _join(self, cur, *record):
+        """The caller's stream waits for the object's; the tensors in `record` (None skipped), allocated on the caller's stream and
+        used on the object's, are made known to the allocator."""
+        cur.wait_stream(self.stream)
+        for t in record:
+            if t is not None:
+                t.record_stream(self.stream)
+
+    @contextlib.contextmanager
+    def _forked(self, *record):
+        """with self._forked(tensors...): the body runs with the object's device and stream current, between _fork and _join."""
+        cur = self._fork()
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            yield cur
+        self._join(cur, *record)
+
+
+class LandmarkDetector(BucketRunner):
+    """Unsupervised landmarks of a trained model: detect(images) -> mu f32 [N, K, 2], (y, x) in [-1, 1] (= the eval path's
+    `gauss_yx`).  `model` is an IMMModel whose variables exist (trained, restored, or built once); the detector reads them,
+    never writes them, and refresh() re-reads them after further training."""
+    what = 'detector'
+
+    def __init__(self, model, image_size=128, max_batch=256, use_graph=True):
+        super(LandmarkDetector, self).__init__(model, image_size, max_batch, use_graph)
+
+    @classmethod
+    def from_checkpoint(cls, config, path, image_size=128, max_batch=256, dtype=torch.bfloat16, device=None, use_graph=True):
+        """A detector straight from a checkpoint (`.pt` file or TensorFlow bundle prefix), without a training engine.
+        config: the `model:` block of the experiment config (config.model)."""
+        return cls._from_variables(config, read_checkpoint(path, int(config.n_filters)), image_size, max_batch, dtype, device,
+                                   use_graph)
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    def _setup(self, cfg, dtype, device, image_size, max_batch, use_graph):
+        super(LandmarkDetector, self)._setup(cfg, dtype, device, image_size, max_batch, use_graph)
+        K, He, C = self.K, self.He, 8 * self.nf
         if self.spec[0][0] != 7 or self.spec[0][1] != 3:
             raise NotImplementedError('first encoder layer must be 7x7 over RGB')
         self.ldh = ops.round_up(K, 4)
-        C, He = 8 * nf, self.He
         # the one-launch pose head (imm_pose_head_fwd), under the engine's conditions; else the 1x1 convolution + soft-argmax pair
         self.fused_head = (C % 32 == 0 and (He * He) % 16 == 0 and 4 * (He * He * K + 2 * He * K + 2 * K) <= 158 * 1024 and
                            4 * ((2 + 2 * He) * K + 516) + He * He * ops.round_up(K, 32) * 2 <= 158 * 1024)
-        self.stream = torch.cuda.Stream(device=self.dev)
-        self._stager = ops.PinnedStager()
         with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
             # packed filters and folded biases (shared by every bucket)
             self.wt, self.bias = alloc_encoder_weights(self.spec, dtype, self.dev)
@@ -386,57 +559,28 @@ class LandmarkDetector(object):
             # [m3, So * So] are made on first use, per (template, So)
             self._al_ft = torch.zeros(2 * K * 2 * ops.MAX_ALIGN_M3, device=self.dev)
         self._al_basis = {}
-        self._cap = 0
-        self._graphs = {}
 
-    def refresh(self):
-        """(Re-)read the variables (the model's current ones, or the checkpoint's), fold the batch norms and re-pack the filters
-        in place: captured programs stay valid."""
-        if self._static is not None:
-            params, state = self._static
-        else:
-            eng = getattr(self._model, '_master', None) or self._model.engine
-            pnames, snames = pose_encoder_names(self.nf)
-            params = {n: ops.download(eng.pview[n]) for n in pnames}
-            state = {n: ops.download(eng.state[n]) for n in snames}
-        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
-            pack_folded_encoder(params, state, POSE_SCOPE, self.spec, self.wt, self.bias, self.dev)
-            C = 8 * self.nf
-            w_dev = torch.empty(1, 1, C, self.K, dtype=torch.float32, device=self.dev)
-            ops.upload(w_dev, params[POSE_SCOPE + '/conv_1/w'], POSE_SCOPE + '/conv_1/w')
-            rows, kpad = self.wt_head.shape
-            ops.pack_weights(w_dev, self.wt_head, 0, 1, 1, C, self.K, C, rows, kpad)
-            ops.upload(self.bias_head, params[POSE_SCOPE + '/conv_1/b'], POSE_SCOPE + '/conv_1/b')
-            self.stream.synchronize()
+    def _names(self):
+        return pose_encoder_names(self.nf)
 
-    # ------------------------------------------------------------------------------------------------------------------------
-    def _ensure_capacity(self, batch):
-        """Activations of one bucket, sized for the largest bucket run so far (smaller buckets use leading views)."""
-        if batch <= self._cap:
-            return
-        self.stream.synchronize()
-        self._graphs = {}                              # they address the old buffers
-        S, K, He, nf = self.S, self.K, self.He, self.nf
-        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
-            self._img = torch.zeros(batch, S, S, 3, device=self.dev)
-            self._xin = None
-            n_act = encoder_act_elems(self.spec, S, batch)
-            self._act = [torch.zeros(n_act, dtype=self.dt, device=self.dev) for _ in range(2)]
-            self._heat = torch.zeros(batch, He, He, self.ldh, device=self.dev)
-            self._mu = torch.zeros(batch, K, 2, device=self.dev)
-            self._py = torch.zeros(batch, He, K, device=self.dev)
-            self._px = torch.zeros(batch, He, K, device=self.dev)
-            self._geom = torch.zeros(batch, 4, device=self.dev)                        # keypoints(): (y0, x0, sy, sx) per row
-            self._kp = torch.zeros(batch * ops.MAX_KEYPOINTS * 2, device=self.dev)     # keypoints(): [batch, M, 2]
-            self._al_coef = torch.zeros(batch * ops.MAX_ALIGN_M3 * 2, device=self.dev)  # align(): [batch, m3, 2]
-        self._cap = batch
+    def _pack(self, params, state):
+        pack_folded_encoder(params, state, POSE_SCOPE, self.spec, self.wt, self.bias, self.dev)
+        C = 8 * self.nf
+        w_dev = torch.empty(1, 1, C, self.K, dtype=torch.float32, device=self.dev)
+        ops.upload(w_dev, params[POSE_SCOPE + '/conv_1/w'], POSE_SCOPE + '/conv_1/w')
+        rows, kpad = self.wt_head.shape
+        ops.pack_weights(w_dev, self.wt_head, 0, 1, 1, C, self.K, C, rows, kpad)
+        ops.upload(self.bias_head, params[POSE_SCOPE + '/conv_1/b'], POSE_SCOPE + '/conv_1/b')
 
-    def _xin_for(self, batch):
-        if self._xin is None or self._xin.shape[0] < batch:
-            with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
-                self._xin = torch.zeros(self._cap, self.S, self.S, 32, dtype=self.dt, device=self.dev)
-        return self._xin[:batch]
+    def _alloc(self, batch):
+        K, He = self.K, self.He
+        self._heat = torch.zeros(batch, He, He, self.ldh, device=self.dev)
+        self._mu = torch.zeros(batch, K, 2, device=self.dev)
+        self._py = torch.zeros(batch, He, K, device=self.dev)
+        self._px = torch.zeros(batch, He, K, device=self.dev)
+        self._geom = torch.zeros(batch, 4, device=self.dev)                        # keypoints(): (y0, x0, sy, sx) per row
+        self._kp = torch.zeros(batch * ops.MAX_KEYPOINTS * 2, device=self.dev)     # keypoints(): [batch, M, 2]
+        self._al_coef = torch.zeros(batch * ops.MAX_ALIGN_M3 * 2, device=self.dev)  # align(): [batch, m3, 2]
 
     def program(self, batch, u8=False, kp_m=None, align=None):
         """The launches of one bucket: [_Launch(tag, name, family, fn)].  tag: 'resize' | 'pack_image' | 'conv' | 'pose_head'
@@ -486,60 +630,37 @@ class LandmarkDetector(object):
             prog.append(_Launch('align_warp', 'align/warp', 'align', None))     # issued by align() with the call's pixels
         return prog
 
-    def _run(self, batch, kp_m=None, align=None):
-        """Issue the (graph of the) program of bucket `batch` (with the keypoint epilogue of M = kp_m points, or with align()'s
-        coefficient launch) on the detector's stream."""
-        if not self.use_graph:
-            for l in self.program(batch, kp_m=kp_m, align=align):
-                if l.fn is not None:
-                    l.fn()
-            return
+    def _keyed(self, batch, kp_m=None, align=None):
         key = batch if kp_m is None else (batch, int(kp_m))
         if align is not None:
             key = (batch, 'align', int(align[1]))
-        g = self._graphs.get(key)
-        if g is None:
-            prog = [l for l in self.program(batch, kp_m=kp_m, align=align) if l.fn is not None]
-            for l in prog:                 # warm-up outside capture (code-object loading, LDS attribute calls)
-                l.fn()
-            self.stream.synchronize()
-            g = ops.Graph()
-            g.capture_begin()
-            for l in prog:
-                l.fn()
-            g.capture_end()
-            self._graphs[key] = g
-        g.launch()
+        return key, lambda: self.program(batch, kp_m=kp_m, align=align)
+
+    def _run(self, batch, kp_m=None, align=None):
+        """Issue the (graph of the) program of bucket `batch` (with the keypoint epilogue of M = kp_m points, or with align()'s
+        coefficient launch) on the detector's stream."""
+        self._launch(*self._keyed(batch, kp_m, align))
+
+    def _capture(self, batch, kp_m=None):
+        """Make sure _run(batch, kp_m) finds its graph captured (_launch, ahead=True)."""
+        self._launch(*self._keyed(batch, kp_m), ahead=True)
 
     # ------------------------------------------------------------------------------------------------------------------------
-    def _stage_u8(self, images, count):
-        """Resize u8 images of any sizes on the GPU into the first `count` rows of the input buffer."""
-        stage_u8(images[:count], self._img[:count], self.S, self.dev)
-
     def detect(self, images, heatmaps=False):
         """images: NHWC float [N, S, S, 3] with values in [0, 255] (host or device), or a list of u8 HWC arrays of any sizes
         (resized to S x S on the GPU).  Returns mu f32 [N, K, 2] on the detector's device, and with heatmaps=True also the pose
         head's heat maps f32 [N, S/8, S/8, K]."""
-        images, u8 = as_image_batch(images, self.S)
+        images, _u8 = as_image_batch(images, self.S)
         N, K, He = len(images), self.K, self.He
-        cur = torch.cuda.current_stream(self.dev)
         mu_out = torch.empty(N, K, 2, device=self.dev)
         heat_out = torch.empty(N, He, He, K, device=self.dev) if heatmaps else None
-        self.stream.wait_stream(cur)
-        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+        with self._forked():
             for start, count, bucket in plan_buckets(N, self.max_batch):
-                self._ensure_capacity(bucket)
-                if u8:
-                    self._stage_u8(images[start:start + count], count)
-                else:
-                    self._stager.copy(self._img[:count], images[start:start + count], ('images', count))
-                if count < bucket:
-                    self._img[count:bucket].zero_()
+                self._stage_rows(images, None, start, count, bucket)
                 self._run(bucket)
                 mu_out[start:start + count].copy_(self._mu[:count])
                 if heatmaps:
                     heat_out[start:start + count].copy_(self._heat[:count, ..., :K])
-        cur.wait_stream(self.stream)
         return (mu_out, heat_out) if heatmaps else mu_out
 
     def keypoints(self, images, regressor, boxes=None, return_mu=False):
@@ -550,45 +671,23 @@ class LandmarkDetector(object):
         pixels (keypoints.check_boxes); each box is cut from its image with zero padding where it leaves it and resized to S x S on
         the GPU.  Without boxes, u8 images are resized whole (the points scale back by h / S, w / S) and a tensor batch is already
         the S x S frame."""
-        from . import keypoints as KP
         regressor.check(self.K, self.S)
         w, b = regressor.epilogue_weights()
         M = regressor.M
-        images, u8 = as_image_batch(images, self.S)
-        if u8:
-            images = decode_u8(images)
-            rows = KP.check_boxes([(0, 0, a.shape[0], a.shape[1]) for a in images] if boxes is None else boxes, len(images))
-            geom = KP.box_geometry(rows, self.S)
-        else:
-            if boxes is not None:
-                raise ValueError('boxes need the images as a list of u8 arrays (a tensor batch is already S x S)')
-            geom = np.tile(np.array([0, 0, 1, 1], np.float32), (len(images), 1))
+        images, _u8, rows, geom = photo_rows(images, boxes, self.S)
         N, K = len(geom), self.K
-        cur = torch.cuda.current_stream(self.dev)
         kp_out = torch.empty(N, M, 2, device=self.dev)
         mu_out = torch.empty(N, K, 2, device=self.dev) if return_mu else None
-        self.stream.wait_stream(cur)
-        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+        with self._forked():
             self._stager.copy(self._kp_w[:w.size], torch.from_numpy(w.reshape(-1)), ('kp_w', M))
             self._stager.copy(self._kp_b[:b.size], torch.from_numpy(b), ('kp_b', M))
             for start, count, bucket in plan_buckets(N, self.max_batch):
-                self._ensure_capacity(bucket)
-                if u8:
-                    # the images this bucket's boxes cut from, packed once each; box rows renumbered into that list
-                    part = rows[start:start + count]
-                    used, idx = np.unique(part[:, 0], return_inverse=True)
-                    local = np.concatenate([idx.reshape(-1, 1).astype(np.int32), part[:, 1:]], axis=1)
-                    stage_u8([images[i] for i in used], self._img[:count], self.S, self.dev, boxes=local)
-                else:
-                    self._stager.copy(self._img[:count], images[start:start + count], ('images', count))
-                if count < bucket:
-                    self._img[count:bucket].zero_()
+                self._stage_rows(images, rows, start, count, bucket)
                 self._stager.copy(self._geom[:count], torch.from_numpy(geom[start:start + count]), ('geom', count))
                 self._run(bucket, M)
                 kp_out[start:start + count].copy_(self._kp[:count * M * 2].view(count, M, 2))
                 if return_mu:
                     mu_out[start:start + count].copy_(self._mu[:count])
-        cur.wait_stream(self.stream)
         return (kp_out, mu_out) if return_mu else kp_out
 
     def _align_basis(self, template, model, So):
@@ -606,30 +705,16 @@ class LandmarkDetector(object):
     def landmarks(self, images, boxes=None):
         """detect() per face box: mu f32 [n, K, 2] of the rows keypoints() and align() would work on (one per box, cut with zero
         padding and resized to S x S on the GPU; one per image without boxes)."""
-        from . import keypoints as KP
-        images, u8 = as_image_batch(images, self.S)
+        images, u8, rows = photo_boxes(images, boxes, self.S)
         if not u8:
-            if boxes is not None:
-                raise ValueError('boxes need the images as a list of u8 arrays (a tensor batch is already S x S)')
             return self.detect(images)
-        images = decode_u8(images)
-        rows = KP.check_boxes([(0, 0, a.shape[0], a.shape[1]) for a in images] if boxes is None else boxes, len(images))
         N = len(rows)
-        cur = torch.cuda.current_stream(self.dev)
         mu_out = torch.empty(N, self.K, 2, device=self.dev)
-        self.stream.wait_stream(cur)
-        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+        with self._forked():
             for start, count, bucket in plan_buckets(N, self.max_batch):
-                self._ensure_capacity(bucket)
-                part = rows[start:start + count]
-                used, idx = np.unique(part[:, 0], return_inverse=True)
-                local = np.concatenate([idx.reshape(-1, 1).astype(np.int32), part[:, 1:]], axis=1)
-                stage_u8([images[i] for i in used], self._img[:count], self.S, self.dev, boxes=local)
-                if count < bucket:
-                    self._img[count:bucket].zero_()
+                self._stage_rows(images, rows, start, count, bucket)
                 self._run(bucket)
                 mu_out[start:start + count].copy_(self._mu[:count])
-        cur.wait_stream(self.stream)
         return mu_out
 
     def track(self, frames, boxes, regressor=None, box_smooth=0.5, one_euro=OneEuro(), fps=25.0, chunk_frames=32):
@@ -664,7 +749,6 @@ class LandmarkDetector(object):
         _packed (internal; ImageGenerator.repose): pack_u8(images, device, rows) of exactly these u8 images and box rows, made by a
         caller that needs the packed photos itself; the buckets then read that one buffer instead of packing their own photos."""
         from . import alignment as AL
-        from . import keypoints as KP
         lam = AL.check_model(model, lam)
         template.check(self.K, self.S)
         So = self.S if out_size is None else int(out_size)
@@ -672,39 +756,20 @@ class LandmarkDetector(object):
             raise ValueError('out_size must be in [1, 8192], got %d' % So)
         K, m3 = self.K, AL.n_basis(model, self.K)
         ft = np.ascontiguousarray(template.fit_matrix(model, lam).T, dtype=np.float32)             # [2K, 2 m3]
-        images, u8 = as_image_batch(images, self.S)
-        if u8:
-            images = decode_u8(images)
-            rows = KP.check_boxes([(0, 0, a.shape[0], a.shape[1]) for a in images] if boxes is None else boxes, len(images))
-            geom = KP.box_geometry(rows, self.S)
-        else:
-            if boxes is not None:
-                raise ValueError('boxes need the images as a list of u8 arrays (a tensor batch is already S x S)')
-            geom = np.tile(np.array([0, 0, 1, 1], np.float32), (len(images), 1))
+        images, u8, rows, geom = photo_rows(images, boxes, self.S)
         N = len(geom)
-        cur = torch.cuda.current_stream(self.dev)
         out = torch.empty(N, So, So, 3, device=self.dev)
         coef_out = torch.empty(N, m3, 2, device=self.dev) if return_transform else None
         mu_out = torch.empty(N, K, 2, device=self.dev) if return_transform else None
-        self.stream.wait_stream(cur)
-        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+        with self._forked():
             basis = self._align_basis(template, model, So)
             self._stager.copy(self._al_ft[:ft.size], torch.from_numpy(ft.reshape(-1)), ('al_ft', m3))
             for start, count, bucket in plan_buckets(N, self.max_batch):
-                self._ensure_capacity(bucket)
                 if u8 and _packed is not None:
-                    src, offs_d, hw_d, boxes_d = _packed[0], _packed[1], _packed[2], _packed[3][start:start + count]
-                    ops.resize_crop_u8(src, offs_d, hw_d, 3, (self.S, self.S), (0, 0), (self.S, self.S), self._img[:count], boxes=boxes_d)
-                elif u8:
-                    part = rows[start:start + count]
-                    used, idx = np.unique(part[:, 0], return_inverse=True)
-                    local = np.concatenate([idx.reshape(-1, 1).astype(np.int32), part[:, 1:]], axis=1)
-                    src, offs_d, hw_d, boxes_d = stage_u8([images[i] for i in used], self._img[:count], self.S, self.dev, boxes=local)
+                    packed = self._stage(count, bucket, packed=tuple(_packed[:3]) + (_packed[3][start:start + count],))
                 else:
-                    self._stager.copy(self._img[:count], images[start:start + count], ('images', count))
-                    src, offs_d, hw_d, boxes_d = self._img[:count], None, None, None
-                if count < bucket:
-                    self._img[count:bucket].zero_()
+                    packed = self._stage_rows(images, rows, start, count, bucket)
+                src, offs_d, hw_d, boxes_d = packed if u8 else (self._img[:count], None, None, None)
                 self._stager.copy(self._geom[:count], torch.from_numpy(geom[start:start + count]), ('geom', count))
                 self._run(bucket, align=(model, m3))
                 coef = self._al_coef[:bucket * m3 * 2].view(bucket, m3, 2)[:count]
@@ -712,10 +777,8 @@ class LandmarkDetector(object):
                 if return_transform:
                     coef_out[start:start + count].copy_(coef)
                     mu_out[start:start + count].copy_(self._mu[:count])
-        cur.wait_stream(self.stream)
         if return_transform:
-            return out, AL.Alignment(coef_out, ops.to_device_pinned(geom, self.dev), mu_out, model, lam, template, So,
-                                     rows if u8 else None)
+            return out, AL.Alignment(coef_out, ops.to_device_pinned(geom, self.dev), mu_out, model, lam, template, So, rows)
         return out
 
     def warp(self, photos, poses, boxes=None, pose_boxes=None, feather=0.125, anchors=2, lam=0.0, strength=1.0, return_transform=False):
@@ -734,48 +797,30 @@ class LandmarkDetector(object):
         landmarks in place, imm_warp_u8, all on the detector's stream; nothing returns to the host.
         return_transform=True: (photos, a warping.PhotoWarp: coef, ctrl, rows, mu, poses, flags, to_source)."""
         from . import warping as WP
-        from .generation import box_areas, bucket_links, compose_inv_ramp
-        S, K = self.S, self.K
+        from .generation import PasteSetup
+        K = self.K
         photos, rows, pose, feather, m, lam, strength, M = WP.plan_warp(photos, poses, boxes, pose_boxes, feather, K, anchors, lam, strength)
         n = len(rows)
-        if pose[0] == 'photos':
-            lm = self.landmarks(pose[1], pose[2])
-        else:
-            lm = pose[1].to(device=self.dev, dtype=torch.float32)
-        lm = (lm.expand(n, K, 2) if lm.shape[0] != n else lm).contiguous()
+        lm = pose_landmarks(self, pose, n).contiguous()
         buckets = plan_buckets(n, self.max_batch)
-        links = bucket_links(rows, buckets)
-        area = box_areas(rows)
-        cur = torch.cuda.current_stream(self.dev)
+        ps = PasteSetup(photos, rows, buckets, feather, self.dev)                   # all photos, once per call
         with torch.cuda.device(self.dev):
-            src, offs_d, hw_d, boxes_d = pack_u8(photos, self.dev, rows)            # all photos, once per call
-            canvas = src.clone()
-            links_d = ops.to_device_pinned(links, self.dev)
-            ramp_d = ops.to_device_pinned(compose_inv_ramp(rows, feather), self.dev)
             anchors_d = ops.to_device_pinned(WP.warp_anchors(m).astype(np.float32), self.dev) if m else None
             coef = torch.empty(n, M + 3, 2, device=self.dev)
             ctrl = torch.empty(n, M, 2, device=self.dev)
             flags = torch.empty(n, dtype=torch.int32, device=self.dev)
             mu_out = torch.empty(n, K, 2, device=self.dev) if return_transform else None
-        self.stream.wait_stream(cur)
-        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+        with self._forked(*ps.tensors(), anchors_d, lm, coef, ctrl, flags, mu_out):
             for start, count, bucket in buckets:
-                self._ensure_capacity(bucket)
                 part = slice(start, start + count)
-                ops.resize_crop_u8(src, offs_d, hw_d, 3, (S, S), (0, 0), (S, S), self._img[:count], boxes=boxes_d[part])
-                if count < bucket:
-                    self._img[count:bucket].zero_()
+                self._stage(count, bucket, packed=ps.packed(part))
                 self._run(bucket)
                 ops.warp_fit(lm[part], self._mu[:count], anchors_d, strength, lam, coef[part], ctrl[part], flags[part])
-                ops.warp_u8(src, canvas, offs_d, hw_d, boxes_d[part], links_d[part], ramp_d[part], ctrl[part], coef[part],
-                            int(min(area[part].max(), 2 ** 31 - 1)))
+                ops.warp_u8(ps.src, ps.canvas, ps.offs_d, ps.hw_d, ps.boxes_d[part], ps.links_d[part], ps.ramp_d[part], ctrl[part],
+                            coef[part], ps.max_pixels(part))
                 if return_transform:
                     mu_out[part].copy_(self._mu[:count])
-        cur.wait_stream(self.stream)
-        for t in (src, canvas, offs_d, hw_d, boxes_d, links_d, ramp_d, anchors_d, lm, coef, ctrl, flags, mu_out):
-            if t is not None:
-                t.record_stream(self.stream)
-        out = unpack_u8(canvas, photos)
+        out = unpack_u8(ps.canvas, photos)
         if return_transform:
             return out, WP.PhotoWarp(coef, ctrl, rows, mu_out, lm, flags, strength, lam, m)
         return out
@@ -804,28 +849,18 @@ class LandmarkDetector(object):
         to_source, to_donor)."""
         from . import morphing as MP
         from . import warping as WP
-        from .generation import box_areas, bucket_links, compose_inv_ramp
-        S, K = self.S, self.K
+        from .generation import PasteSetup
+        K = self.K
         photos, rows, donors, drows, drows_given, shape, texture, feather, m, lam, M, lm_a, lm_b = MP.plan_morph(
             photos, donors, boxes, donor_boxes, shape, texture, feather, K, anchors, lam, landmarks, donor_landmarks)
         n = len(rows)
-        if lm_b is None:
-            lm_b = self.landmarks(donors, drows_given)
-        else:
-            lm_b = lm_b.to(device=self.dev, dtype=torch.float32)
-        lm_b = (lm_b.expand(n, K, 2) if lm_b.shape[0] != n else lm_b).contiguous()
+        lm_b = pose_landmarks(self, ('photos', donors, drows_given) if lm_b is None else ('landmarks', lm_b), n).contiguous()
         if lm_a is not None:
             lm_a = lm_a.to(device=self.dev, dtype=torch.float32).contiguous()
         buckets = plan_buckets(n, self.max_batch)
-        links = bucket_links(rows, buckets)
-        area = box_areas(rows)
-        cur = torch.cuda.current_stream(self.dev)
+        ps = PasteSetup(photos, rows, buckets, feather, self.dev)                   # all photos, once per call
         with torch.cuda.device(self.dev):
-            src, offs_d, hw_d, boxes_d = pack_u8(photos, self.dev, rows)            # all photos, once per call
             don, doffs_d, dhw_d, dboxes_d = pack_u8(donors, self.dev, drows)        # all donor photos, once per call
-            canvas = src.clone()
-            links_d = ops.to_device_pinned(links, self.dev)
-            ramp_d = ops.to_device_pinned(compose_inv_ramp(rows, feather), self.dev)
             shape_d = ops.to_device_pinned(shape, self.dev)
             texture_d = ops.to_device_pinned(texture, self.dev)
             anchors_d = ops.to_device_pinned(WP.warp_anchors(m).astype(np.float32), self.dev) if m else None
@@ -840,15 +875,12 @@ class LandmarkDetector(object):
             poses2, mu2 = torch.empty(2 * B * K * 2, device=self.dev), torch.empty(2 * B * K * 2, device=self.dev)
             coef2, ctrl2 = torch.empty(2 * B * (M + 3) * 2, device=self.dev), torch.empty(2 * B * M * 2, device=self.dev)
             flags2 = torch.empty(2 * B, dtype=torch.int32, device=self.dev)
-        self.stream.wait_stream(cur)
-        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+        with self._forked(*ps.tensors(), don, doffs_d, dhw_d, dboxes_d, shape_d, texture_d, anchors_d, lm_a, lm_b, coef_a, coef_b, ctrl,
+                          flags, poses, mu_out, poses2, mu2, coef2, ctrl2, flags2):
             for start, count, bucket in buckets:
                 part = slice(start, start + count)
                 if lm_a is None:
-                    self._ensure_capacity(bucket)
-                    ops.resize_crop_u8(src, offs_d, hw_d, 3, (S, S), (0, 0), (S, S), self._img[:count], boxes=boxes_d[part])
-                    if count < bucket:
-                        self._img[count:bucket].zero_()
+                    self._stage(count, bucket, packed=ps.packed(part))
                     self._run(bucket)
                     own = self._mu[:count]
                 else:
@@ -863,18 +895,13 @@ class LandmarkDetector(object):
                 coef_b[part].copy_(c2[1])
                 ctrl[part].copy_(t2[0])
                 torch.bitwise_or(f2[0], f2[1], out=flags[part])
-                ops.morph_u8(src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, boxes_d[part], dboxes_d[part], links_d[part], ramp_d[part],
-                             texture_d[part], t2[0], c2[0], c2[1], int(min(area[part].max(), 2 ** 31 - 1)))
+                ops.morph_u8(ps.src, ps.canvas, ps.offs_d, ps.hw_d, don, doffs_d, dhw_d, ps.boxes_d[part], dboxes_d[part], ps.links_d[part],
+                             ps.ramp_d[part], texture_d[part], t2[0], c2[0], c2[1], ps.max_pixels(part))
                 if return_transform:
                     poses[part].copy_(p2[0])
                     if mu_out is not None:
                         mu_out[part].copy_(own)
-        cur.wait_stream(self.stream)
-        for t in (src, don, canvas, offs_d, hw_d, boxes_d, doffs_d, dhw_d, dboxes_d, links_d, ramp_d, shape_d, texture_d, anchors_d, lm_a,
-                  lm_b, coef_a, coef_b, ctrl, flags, poses, mu_out, poses2, mu2, coef2, ctrl2, flags2):
-            if t is not None:
-                t.record_stream(self.stream)
-        out = unpack_u8(canvas, photos)
+        out = unpack_u8(ps.canvas, photos)
         if return_transform:
             return out, MP.PhotoMorph(coef_a, coef_b, ctrl, rows, drows, mu_out if lm_a is None else lm_a, lm_b, poses, flags, shape,
                                       texture, lam, m)

@@ -128,54 +128,46 @@ def check_render_keeps_features(gen, bucket):
 def run(gen, plan, return_faces=False):
     """The launches of reenact() for a checked plan (see the module docstring); called with the caller's stream current."""
     from . import ops
-    from .generation import box_areas, compose_inv_ramp, compose_links
+    from .generation import PasteSetup
     from .inference import pack_u8, plan_buckets, unpack_u8
     det, S, K, dev = gen.detector, gen.S, gen.K, gen.dev
     photos, rows, frames = plan.photos, plan.rows, plan.frames
     n, T = len(rows), len(frames)
-    bucket = plan_buckets(n, gen.max_batch)[0][2]
-    area = box_areas(rows)
-    max_pixels = int(min(area.max(), 2 ** 31 - 1))
-    cur = torch.cuda.current_stream(dev)
+    buckets = plan_buckets(n, gen.max_batch)                   # one: n <= max_batch
+    bucket = buckets[0][2]
     with torch.cuda.device(dev):
-        src, offs_d, hw_d, boxes_d = pack_u8(photos, dev, rows)                     # all photos, once per call
-        shared = [src, offs_d, hw_d, boxes_d]
         if plan.paste:
-            links_d = ops.to_device_pinned(compose_links(rows), dev)
-            ramp_d = ops.to_device_pinned(compose_inv_ramp(rows, plan.feather), dev)
-            canvas = torch.empty(T, src.numel(), dtype=torch.uint8, device=dev)
-            shared += [links_d, ramp_d, canvas]
+            ps = PasteSetup(photos, rows, buckets, plan.feather, dev, clone=False)      # all photos, once per call
+            packed, max_pixels = ps.packed(slice(None)), ps.max_pixels(slice(None))
+            canvas = torch.empty(T, ps.src.numel(), dtype=torch.uint8, device=dev)
+            shared = [ps.links_d, ps.ramp_d, canvas]
+        else:
+            packed, shared = pack_u8(photos, dev, rows), []
+        src, offs_d, hw_d, boxes_d = packed
         m = torch.empty(n, K, 2, device=dev)
         lm = torch.empty(T, n, K, 2, device=dev)
         flags = torch.empty(T, n, dtype=torch.int32, device=dev)
         anchor = torch.zeros(K, 2, dtype=torch.float64, device=dev)
         faces = torch.empty(T, n, S, S, 3, device=dev) if return_faces else None
-        shared += [m, lm, flags, anchor] + ([faces] if return_faces else [])
+        shared += list(packed) + [m, lm, flags, anchor, faces]
         # once per call, on the detector's stream: the faces' own landmarks (detector.landmarks(photos, boxes), from the packed photos)
-        det.stream.wait_stream(cur)
+        cur = det._fork()
         with torch.cuda.stream(det.stream):
-            det._ensure_capacity(bucket)
-            ops.resize_crop_u8(src, offs_d, hw_d, 3, (S, S), (0, 0), (S, S), det._img[:n], boxes=boxes_d)
-            if n < bucket:
-                det._img[n:bucket].zero_()
+            det._stage(n, bucket, packed=packed)
             det._run(bucket)
             m.copy_(det._mu[:n])
         # once per call, on the generator's stream: the appearance of every face, which stays in the joint buffer
-        gen.stream.wait_stream(cur)
+        gen._fork()
         with torch.cuda.stream(gen.stream):
             gen._ensure_capacity(bucket)
             check_render_keeps_features(gen, bucket)
-            ops.resize_crop_u8(src, offs_d, hw_d, 3, (S, S), (0, 0), (S, S), gen._img[:n], boxes=boxes_d)
-            if n < bucket:
-                gen._img[n:bucket].zero_()
+            gen._stage(n, bucket, packed=packed)
             gen._mu[:bucket].zero_()
-            if gen.use_graph and ('render', bucket) not in gen._graphs:
-                gen._run('render', bucket)                     # capture (and its synchronisation) ahead of the first frame
+            gen._capture('render', bucket)                     # capture (and its synchronisation) ahead of the first frame
             gen._run('appearance', bucket)
     tracker = TR.FaceTracker(det, None, plan.box_smooth, plan.one_euro, plan.fps, capacity=T)
     tracker._begin(plan.driver_row)
-    tracker._cur = cur
-    det.stream.wait_stream(cur)
+    tracker._cur = det._fork()
     which = 'smooth' if plan.smooth else 'points'
     for c0 in range(0, T, plan.chunk_frames):
         fsrc, foffs_d, fhw_d, count = tracker._upload(frames[c0:c0 + plan.chunk_frames])
@@ -192,14 +184,11 @@ def run(gen, plan, return_faces=False):
                 gen._run('render', bucket)
                 if plan.paste:
                     canvas[t].copy_(src)
-                    ops.compose_u8(canvas[t], offs_d, hw_d, boxes_d, links_d, ramp_d, gen._pred[:n], max_pixels)
+                    ops.compose_u8(canvas[t], offs_d, hw_d, boxes_d, ps.links_d, ps.ramp_d, gen._pred[:n], max_pixels)
                 if return_faces:
                     faces[t].copy_(gen._pred[:n, ..., :3])
-    cur.wait_stream(det.stream)
-    cur.wait_stream(gen.stream)
-    for x in shared:
-        x.record_stream(det.stream)
-        x.record_stream(gen.stream)
+    det._join(cur, *shared)
+    gen._join(cur, *shared)
     out = None
     if plan.paste:
         out = [unpack_u8(canvas[t], photos) for t in range(T)]

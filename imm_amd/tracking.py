@@ -201,7 +201,6 @@ class FaceTracker(object):
     def _begin(self, rows):
         """Buffers, the first frame's box rows and geometry, the regressor's weights and the bucket's captured program: everything
         that is not a per-frame launch.  Called with the caller's stream current."""
-        from . import ops
         from .inference import plan_buckets
         det = self.det
         self.F = F = len(rows)
@@ -213,8 +212,7 @@ class FaceTracker(object):
         with torch.cuda.device(det.dev):
             self._bufs = self._alloc(self.capacity)
             self._state = torch.zeros(F, state_size(det.K), dtype=torch.float64, device=det.dev)
-            cur = torch.cuda.current_stream(det.dev)
-            det.stream.wait_stream(cur)
+            det._fork()
             with torch.cuda.stream(det.stream):
                 det._ensure_capacity(self.bucket)
                 det._stager.copy(self._bufs['boxes'][0], torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)), ('track_rows', F))
@@ -223,9 +221,7 @@ class FaceTracker(object):
                     det._stager.copy(det._kp_w[:w.size], torch.from_numpy(w.reshape(-1)), ('kp_w', self.M))
                     det._stager.copy(det._kp_b[:b.size], torch.from_numpy(b), ('kp_b', self.M))
                     det._stager.copy(det._geom[:F], torch.from_numpy(KP.box_geometry(rows, det.S)), ('geom', F))
-                key = self.bucket if self.M is None else (self.bucket, int(self.M))
-                if det.use_graph and key not in det._graphs:
-                    det._run(self.bucket, self.M)              # capture (and its synchronisation) ahead of the first frame
+                det._capture(self.bucket, self.M)              # capture (and its synchronisation) ahead of the first frame
 
     def _advance(self, src, offs_d, hw_d, next_image):
         """The launches of one frame whose photo the current box rows index in (src, offs_d, hw_d); the detector's stream is current."""
@@ -235,14 +231,10 @@ class FaceTracker(object):
             self._grow()
         b = self._bufs
         rows = b['boxes'][t]
-        S = det.S
-        det._ensure_capacity(bucket)
-        ops.resize_crop_u8(src, offs_d, hw_d, 3, (S, S), (0, 0), (S, S), det._img[:F], boxes=rows)
-        if F < bucket:
-            det._img[F:bucket].zero_()
+        det._stage(F, bucket, packed=(src, offs_d, hw_d, rows))
         det._run(bucket, M)
         mc, be, dc, c, te, off = self.consts
-        ops.track_step(det._mu[:F], rows, hw_d, self._state, S, next_image, 1 if t == 0 else 0, self.box_smooth, mc, be, dc, c, te, off,
+        ops.track_step(det._mu[:F], rows, hw_d, self._state, det.S, next_image, 1 if t == 0 else 0, self.box_smooth, mc, be, dc, c, te, off,
                        b['points'][t], b['smooth'][t], b['boxes'][t + 1], det._geom[:F], b['flags'][t])
         b['mu'][t].copy_(det._mu[:F])
         if M is not None:
@@ -268,27 +260,19 @@ class FaceTracker(object):
         return self._step(frame)
 
     def _step(self, frame):
-        det = self.det
-        cur = self._cur = torch.cuda.current_stream(det.dev)
-        det.stream.wait_stream(cur)
-        src, offs_d, hw_d, _n = self._upload([frame])
-        with torch.cuda.device(det.dev), torch.cuda.stream(det.stream):
+        with self.det._forked() as self._cur:
+            src, offs_d, hw_d, _n = self._upload([frame])
             self._advance(src, offs_d, hw_d, 0)
-        cur.wait_stream(det.stream)
         return self
 
     def run(self, frames, rows, chunk_frames):
         """track(): every frame of a checked clip, uploaded chunk_frames at a time; the caller's stream waits once, at the end."""
-        det = self.det
         self._begin(rows)
-        cur = self._cur = torch.cuda.current_stream(det.dev)
-        det.stream.wait_stream(cur)
-        for c0 in range(0, len(frames), chunk_frames):
-            src, offs_d, hw_d, count = self._upload(frames[c0:c0 + chunk_frames])
-            with torch.cuda.device(det.dev), torch.cuda.stream(det.stream):
+        with self.det._forked() as self._cur:
+            for c0 in range(0, len(frames), chunk_frames):
+                src, offs_d, hw_d, count = self._upload(frames[c0:c0 + chunk_frames])
                 for i in range(count):
                     self._advance(src, offs_d, hw_d, i + 1 if i + 1 < count else 0)
-        cur.wait_stream(det.stream)
         return self.result()
 
     def result(self):

@@ -133,3 +133,40 @@ def test_scripts_expose_the_detector():
                              stderr=subprocess.PIPE, timeout=300)
         assert out.returncode == 0, out.stderr.decode()[-1500:]
         assert flag in out.stdout.decode()
+
+
+def test_local_rows_renumbers_into_the_photos_used():
+    from imm_amd.inference import local_rows
+    part = np.array([(5, 1, 2, 30, 40), (2, -3, 0, 9, 8), (5, 7, 7, 20, 21), (9, 0, 0, 4, 4)], dtype=np.int32)
+    used, local = local_rows(part)
+    assert used.tolist() == [2, 5, 9] and local[:, 0].tolist() == [1, 0, 1, 2]
+    assert local.dtype == np.int32 and np.array_equal(local[:, 1:], part[:, 1:])
+    used, local = local_rows(part[3:])
+    assert used.tolist() == [9] and local.dtype == np.int32 and np.array_equal(local, [(0, 0, 0, 4, 4)])
+    already = np.array([(0, 1, 1, 5, 5), (1, 0, 0, 3, 3), (1, 2, 2, 6, 6), (2, 0, 1, 2, 3)], dtype=np.int32)
+    used, local = local_rows(already)
+    assert used.tolist() == [0, 1, 2] and local.dtype == np.int32 and np.array_equal(local, already)
+
+
+def test_photo_rows_resolves_photos_and_boxes():
+    from imm_amd.inference import photo_rows
+    from imm_amd.keypoints import box_geometry, check_boxes
+    rng = np.random.RandomState(0)
+    photos = [rng.randint(0, 256, size=(20, 30, 3)).astype(np.uint8), rng.randint(0, 256, size=(17, 9)).astype(np.uint8),
+              rng.randint(0, 256, size=(8, 12, 1)).astype(np.uint8)]
+    images, u8, rows, geom = photo_rows(photos, None, 64)
+    whole = check_boxes([(0, 0, 20, 30), (0, 0, 17, 9), (0, 0, 8, 12)], 3)
+    assert u8 and np.array_equal(rows, whole) and rows.dtype == whole.dtype and np.array_equal(geom, box_geometry(whole, 64))
+    assert [a.shape for a in images] == [(20, 30, 3), (17, 9, 3), (8, 12, 3)] and all(a.dtype == np.uint8 for a in images)
+    assert np.array_equal(images[0], photos[0])
+    for c in range(3):
+        assert np.array_equal(images[1][:, :, c], photos[1]) and np.array_equal(images[2][:, :, c], photos[2][:, :, 0])
+    boxes = [(2, 1, 1, 7, 9), (0, -4, 3, 10, 40)]
+    images, u8, rows, geom = photo_rows(photos, boxes, 64)
+    assert u8 and np.array_equal(rows, check_boxes(boxes, 3)) and np.array_equal(geom, box_geometry(rows, 64))
+    batch = torch.zeros(5, 64, 64, 3)
+    images, u8, rows, geom = photo_rows(batch, None, 64)
+    assert not u8 and rows is None and images.shape == (5, 64, 64, 3)
+    assert geom.dtype == np.float32 and np.array_equal(geom, np.tile(np.float32([0, 0, 1, 1]), (5, 1)))
+    with pytest.raises(ValueError, match=re.escape('boxes need the images as a list of u8 arrays (a tensor batch is already S x S)')):
+        photo_rows(batch, [(0, 0, 10, 10)] * 5, 64)
