@@ -15,6 +15,9 @@
 // byte taps per pixel, no logarithm.  Rows met on a link walk read their ctrl and coef through L2.
 // A row is ACTIVE when its donor image index lies in [0, n_donor_images) and its donor box has H > 0 and W > 0; a row that is not writes
 // nothing and owns nothing (the walks pass over it), so the rows of a call give the same bytes however they are split into launches.
+// imm_morph_colour_u8 (include/imm_colour.h) is the same kernel in a second, compile-time instantiation: the donor's sample takes
+// gB * G + O per channel in front of the mix, (G, O) = gain[b][ch] f32 [n, 3, 2].  The block's own row keeps its six floats in LDS, rows met
+// on a link walk read theirs through L2; gain reaches no address.  imm_morph_u8's instantiation carries none of it.
 #include "paste_common.h"
 
 __global__ __launch_bounds__(256) void morph_poses_kernel(const float* __restrict__ mu_a, const float* __restrict__ mu_b,
@@ -40,10 +43,15 @@ struct MorphRow {
   int dimg;                   // the donor photo, -1: the row is not active
 };
 
+struct MorphColourRow : MorphRow {
+  const float* g;             // its gain [3][2]: (G, O) per channel
+};
+
+template <bool COLOUR>
 struct MorphPolicy {
-  typedef MorphRow Row;
+  typedef typename std::conditional<COLOUR, MorphColourRow, MorphRow>::type Row;
   const int32_t *boxes, *dboxes;
-  const float *inv_ramp, *texture, *ctrl, *coef_a, *coef_b;
+  const float *inv_ramp, *texture, *ctrl, *coef_a, *coef_b, *gain;
   const uint8_t* sp;          // the row's photo in the ORIGINAL buffer
   const uint8_t* donor;
   const int64_t* doffs;
@@ -51,9 +59,10 @@ struct MorphPolicy {
   int sh, sw, n_donor, M;
   Row own;
 
-  // row j with its arrays at ct, ca, cb
-  __device__ __forceinline__ Row row(int j, const float* ct, const float* ca, const float* cb) const {
+  // row j with its arrays at ct, ca, cb (and its gain at g)
+  __device__ __forceinline__ Row row(int j, const float* ct, const float* ca, const float* cb, const float* g) const {
     Row q;
+    if constexpr (COLOUR) q.g = g;
     q.s = spline_row(boxes, inv_ramp, j, ct);
     q.ca = ca; q.cb = cb;
     q.tex = texture[j];
@@ -66,10 +75,12 @@ struct MorphPolicy {
     return q;
   }
   __device__ __forceinline__ Row row(int j) const {
-    return row(j, ctrl + (int64_t)j * 2 * M, coef_a + (int64_t)j * 2 * (M + 3), coef_b + (int64_t)j * 2 * (M + 3));
+    return row(j, ctrl + (int64_t)j * 2 * M, coef_a + (int64_t)j * 2 * (M + 3), coef_b + (int64_t)j * 2 * (M + 3),
+               COLOUR ? gain + (int64_t)j * 6 : nullptr);
   }
   __device__ __forceinline__ bool covers(const Row& q, int r, int c) const { return q.dimg >= 0 && paste_inside(q.s.box, r, c); }
-  // the row's own photo sampled at (r, c) + (H/2, W/2) DA, the donor photo at the donor box's image of q + DB, mixed by tex
+  // the row's own photo sampled at (r, c) + (H/2, W/2) DA, the donor photo at the donor box's image of q + DB (COLOUR: times its gain,
+  // plus its offset), mixed by tex
   __device__ __forceinline__ void apply(const Row& q, int r, int c, float (&v)[3]) const {
 #pragma clang fp contract(off)
     const float* const cf[2] = {q.ca, q.cb};
@@ -80,6 +91,13 @@ struct MorphPolicy {
     if (!(isfinite(ay) && isfinite(ax) && isfinite(by) && isfinite(bx))) return;
     paste_sample_photo(sp, sh, sw, ay, ax, ga);
     paste_sample_photo(donor + doffs[q.dimg], dhw[2 * q.dimg], dhw[2 * q.dimg + 1], by, bx, gb);
+    if constexpr (COLOUR) {
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        const float sc = gb[ch] * q.g[2 * ch];
+        gb[ch] = sc + q.g[2 * ch + 1];
+      }
+    }
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
       const float e = gb[ch] - ga[ch];
@@ -90,6 +108,7 @@ struct MorphPolicy {
   }
 };
 
+template <bool COLOUR>
 __global__ __launch_bounds__(256) void morph_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                        const int64_t* __restrict__ offs, const int32_t* __restrict__ hw, int n_images,
                                                        const uint8_t* __restrict__ donor, const int64_t* __restrict__ doffs,
@@ -97,20 +116,25 @@ __global__ __launch_bounds__(256) void morph_u8_kernel(const uint8_t* __restrict
                                                        const int32_t* __restrict__ dboxes, const int32_t* __restrict__ links,
                                                        const float* __restrict__ inv_ramp, const float* __restrict__ texture,
                                                        const float* __restrict__ ctrl, const float* __restrict__ coef_a,
-                                                       const float* __restrict__ coef_b, int M, int n) {
+                                                       const float* __restrict__ coef_b, const float* __restrict__ gain, int M, int n) {
   __shared__ float ct_s[2 * SPLINE_MAX_M];
   __shared__ float ca_s[2 * SPLINE_MAX_N];
   __shared__ float cb_s[2 * SPLINE_MAX_N];
+  __shared__ float g_s[COLOUR ? 6 : 1];                             // (without COLOUR: never referenced, takes no LDS)
   const int b = blockIdx.y;
   PastePhoto ph;
   if (!paste_photo(boxes, offs, hw, n_images, b, ph)) return;      // uniform over the block: no barrier is skipped by part of it
-  MorphPolicy pol{boxes, dboxes, inv_ramp, texture, ctrl, coef_a, coef_b, src + ph.off, donor, doffs, dhw, ph.sh, ph.sw, n_donor, M};
-  pol.own = pol.row(b, ct_s, ca_s, cb_s);
+  MorphPolicy<COLOUR> pol{boxes, dboxes, inv_ramp, texture, ctrl, coef_a, coef_b, gain, src + ph.off, donor, doffs, dhw, ph.sh, ph.sw, n_donor,
+                          M};
+  pol.own = pol.row(b, ct_s, ca_s, cb_s, g_s);
   if (pol.own.dimg < 0) return;                                    // not active: uniform as well
   for (int i = threadIdx.x; i < 2 * M; i += 256) ct_s[i] = ctrl[(int64_t)b * 2 * M + i];
   for (int i = threadIdx.x; i < 2 * (M + 3); i += 256) {
     ca_s[i] = coef_a[(int64_t)b * 2 * (M + 3) + i];
     cb_s[i] = coef_b[(int64_t)b * 2 * (M + 3) + i];
+  }
+  if constexpr (COLOUR) {
+    if (threadIdx.x < 6) g_s[threadIdx.x] = gain[(int64_t)b * 6 + threadIdx.x];
   }
   __syncthreads();
   paste_rows(pol, pol.own.s.box, ph, dst + ph.off, boxes, links, n);
@@ -128,21 +152,49 @@ extern "C" int imm_morph_poses(const float* mu_a, const float* mu_b, const float
   return 0;
 }
 
+// the checks and the launch of imm_morph_u8 and imm_morph_colour_u8 (gain != nullptr: the COLOUR instantiation)
+static int morph_launch(const char* name, const uint8_t* src, uint8_t* dst, const int64_t* offsets, const int32_t* hw, int n_images,
+                        const uint8_t* donor, const int64_t* donor_offsets, const int32_t* donor_hw, int n_donor_images, const int32_t* boxes,
+                        const int32_t* donor_boxes, const int32_t* links, const float* inv_ramp, const float* texture, const float* ctrl,
+                        const float* coef_a, const float* coef_b, const float* gain, int M, int n, int max_box_pixels, void* stream) {
+  IMM_REQUIRE(src && dst && offsets && hw && donor && donor_offsets && donor_hw && boxes && donor_boxes && links && inv_ramp && texture &&
+                  ctrl && coef_a && coef_b, "%s: null pointer", name);
+  IMM_REQUIRE(src != dst, "%s: dst must be a copy of src, not src itself (every row samples the original pixels)", name);
+  IMM_REQUIRE(donor != dst, "%s: the donor buffer is read only and must not be dst", name);
+  IMM_REQUIRE(n > 0 && n <= 65535 && n_images > 0 && n_donor_images > 0,
+              "%s: 0 < n <= 65535 rows, n_images > 0, n_donor_images > 0 (got %d, %d, %d)", name, n, n_images, n_donor_images);
+  IMM_REQUIRE(M >= 3 && M <= SPLINE_MAX_M, "%s: 3 <= M <= %d control points (got %d)", name, SPLINE_MAX_M, M);
+  IMM_REQUIRE(max_box_pixels > 0, "%s: max_box_pixels > 0 (got %d)", name, max_box_pixels);
+  const dim3 grid(paste_grid_x(max_box_pixels), n);
+  if (gain)
+    hipLaunchKernelGGL(morph_u8_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, offsets, hw, n_images, donor, donor_offsets,
+                       donor_hw, n_donor_images, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b, gain, M, n);
+  else
+    hipLaunchKernelGGL(morph_u8_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, offsets, hw, n_images, donor, donor_offsets,
+                       donor_hw, n_donor_images, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b, gain, M, n);
+  return 0;
+}
+
 extern "C" int imm_morph_u8(const uint8_t* src, uint8_t* dst, const int64_t* offsets, const int32_t* hw, int n_images, const uint8_t* donor,
                             const int64_t* donor_offsets, const int32_t* donor_hw, int n_donor_images, const int32_t* boxes,
                             const int32_t* donor_boxes, const int32_t* links, const float* inv_ramp, const float* texture, const float* ctrl,
                             const float* coef_a, const float* coef_b, int M, int n, int max_box_pixels, void* stream) {
-  IMM_REQUIRE(src && dst && offsets && hw && donor && donor_offsets && donor_hw && boxes && donor_boxes && links && inv_ramp && texture &&
-                  ctrl && coef_a && coef_b, "morph_u8: null pointer");
-  IMM_REQUIRE(src != dst, "morph_u8: dst must be a copy of src, not src itself (every row samples the original pixels)");
-  IMM_REQUIRE(donor != dst, "morph_u8: the donor buffer is read only and must not be dst");
-  IMM_REQUIRE(n > 0 && n <= 65535 && n_images > 0 && n_donor_images > 0,
-              "morph_u8: 0 < n <= 65535 rows, n_images > 0, n_donor_images > 0 (got %d, %d, %d)", n, n_images, n_donor_images);
-  IMM_REQUIRE(M >= 3 && M <= SPLINE_MAX_M, "morph_u8: 3 <= M <= %d control points (got %d)", SPLINE_MAX_M, M);
-  IMM_REQUIRE(max_box_pixels > 0, "morph_u8: max_box_pixels > 0 (got %d)", max_box_pixels);
-  hipLaunchKernelGGL(morph_u8_kernel, dim3(paste_grid_x(max_box_pixels), n), dim3(256), 0, (hipStream_t)stream, src, dst, offsets, hw, n_images,
-                     donor, donor_offsets, donor_hw, n_donor_images, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b, M,
-                     n);
+  const int rc = morph_launch("morph_u8", src, dst, offsets, hw, n_images, donor, donor_offsets, donor_hw, n_donor_images, boxes, donor_boxes,
+                              links, inv_ramp, texture, ctrl, coef_a, coef_b, nullptr, M, n, max_box_pixels, stream);
+  if (rc) return rc;
   IMM_CHECK_LAUNCH("imm_morph_u8");
+  return 0;
+}
+
+extern "C" int imm_morph_colour_u8(const uint8_t* src, uint8_t* dst, const int64_t* offsets, const int32_t* hw, int n_images,
+                                   const uint8_t* donor, const int64_t* donor_offsets, const int32_t* donor_hw, int n_donor_images,
+                                   const int32_t* boxes, const int32_t* donor_boxes, const int32_t* links, const float* inv_ramp,
+                                   const float* texture, const float* ctrl, const float* coef_a, const float* coef_b, const float* gain, int M,
+                                   int n, int max_box_pixels, void* stream) {
+  IMM_REQUIRE(gain, "morph_colour_u8: null pointer");
+  const int rc = morph_launch("morph_colour_u8", src, dst, offsets, hw, n_images, donor, donor_offsets, donor_hw, n_donor_images, boxes,
+                              donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b, gain, M, n, max_box_pixels, stream);
+  if (rc) return rc;
+  IMM_CHECK_LAUNCH("imm_morph_colour_u8");
   return 0;
 }

@@ -826,7 +826,7 @@ class LandmarkDetector(BucketRunner):
         return out
 
     def morph(self, photos, donors, boxes=None, donor_boxes=None, shape=0.5, texture=None, feather=0.125, anchors=2, lam=0.0,
-              landmarks=None, donor_landmarks=None, return_transform=False):
+              landmarks=None, donor_landmarks=None, return_transform=False, colour=0.0, max_gain=2.0):
         """The photos with every box's face blended with a donor's face, in shape and in texture, from the pixels of the two
         photographs: a list of u8 device tensors [h_i, w_i, 3], one per photo, views of one packed buffer (what warp returns); nothing
         is rendered.
@@ -845,15 +845,22 @@ class LandmarkDetector(BucketRunner):
         Both photo lists are packed and uploaded once; the donors' landmarks are detector.landmarks(donors, donor_boxes).  Per bucket:
         imm_resize_crop_u8 from the original pixels and the captured pose program (unless landmarks is given), imm_morph_poses,
         imm_warp_fit over twice the rows, imm_morph_u8, all on the detector's stream; nothing returns to the host.
+        colour: a number or one per row in [0, 1], how far the donor's pixels take the face's tone (0, the default: not at all, today's
+        launches and bytes; 1: the donor region's mean and spread per channel become the face region's).  The regions are the ellipses
+        inscribed in the two boxes as they lie in their photographs; the ratio of the spreads is kept in [1 / max_gain, max_gain]
+        (max_gain finite, >= 1).  With any colour > 0, once per call in front of the buckets: imm_colour_stats_u8 over the faces' rows
+        and over the donors' rows, imm_colour_gain; and per bucket imm_morph_colour_u8 in place of imm_morph_u8 (include/imm_colour.h
+        states the rule).
         return_transform=True: (photos, a morphing.PhotoMorph: coef_a, coef_b, ctrl, rows, donor_rows, mu, donor_mu, poses, flags,
-        to_source, to_donor)."""
+        to_source, to_donor, colour_gain, colour_flags)."""
         from . import morphing as MP
         from . import warping as WP
-        from .generation import PasteSetup
+        from .generation import PasteSetup, box_areas
         K = self.K
-        photos, rows, donors, drows, drows_given, shape, texture, feather, m, lam, M, lm_a, lm_b = MP.plan_morph(
-            photos, donors, boxes, donor_boxes, shape, texture, feather, K, anchors, lam, landmarks, donor_landmarks)
+        photos, rows, donors, drows, drows_given, shape, texture, feather, m, lam, M, lm_a, lm_b, colour, max_gain = MP.plan_morph(
+            photos, donors, boxes, donor_boxes, shape, texture, feather, K, anchors, lam, landmarks, donor_landmarks, colour, max_gain)
         n = len(rows)
+        matched = bool(colour.any())
         lm_b = pose_landmarks(self, ('photos', donors, drows_given) if lm_b is None else ('landmarks', lm_b), n).contiguous()
         if lm_a is not None:
             lm_a = lm_a.to(device=self.dev, dtype=torch.float32).contiguous()
@@ -875,8 +882,17 @@ class LandmarkDetector(BucketRunner):
             poses2, mu2 = torch.empty(2 * B * K * 2, device=self.dev), torch.empty(2 * B * K * 2, device=self.dev)
             coef2, ctrl2 = torch.empty(2 * B * (M + 3) * 2, device=self.dev), torch.empty(2 * B * M * 2, device=self.dev)
             flags2 = torch.empty(2 * B, dtype=torch.int32, device=self.dev)
+            gain = cflags = colour_d = sums2 = None
+            if matched:
+                colour_d = ops.to_device_pinned(colour, self.dev)
+                sums2 = torch.empty(2, n, 7, dtype=torch.int64, device=self.dev)
+                gain, cflags = torch.empty(n, 3, 2, device=self.dev), torch.empty(n, dtype=torch.int32, device=self.dev)
         with self._forked(*ps.tensors(), don, doffs_d, dhw_d, dboxes_d, shape_d, texture_d, anchors_d, lm_a, lm_b, coef_a, coef_b, ctrl,
-                          flags, poses, mu_out, poses2, mu2, coef2, ctrl2, flags2):
+                          flags, poses, mu_out, poses2, mu2, coef2, ctrl2, flags2, colour_d, sums2, gain, cflags):
+            if matched:                                                             # once per call, all rows
+                ops.colour_stats_u8(ps.src, ps.offs_d, ps.hw_d, ps.boxes_d, int(ps.area.max()), sums2[0])
+                ops.colour_stats_u8(don, doffs_d, dhw_d, dboxes_d, int(box_areas(drows).max()), sums2[1])
+                ops.colour_gain(sums2[0], sums2[1], colour_d, max_gain, gain, cflags)
             for start, count, bucket in buckets:
                 part = slice(start, start + count)
                 if lm_a is None:
@@ -895,8 +911,13 @@ class LandmarkDetector(BucketRunner):
                 coef_b[part].copy_(c2[1])
                 ctrl[part].copy_(t2[0])
                 torch.bitwise_or(f2[0], f2[1], out=flags[part])
-                ops.morph_u8(ps.src, ps.canvas, ps.offs_d, ps.hw_d, don, doffs_d, dhw_d, ps.boxes_d[part], dboxes_d[part], ps.links_d[part],
-                             ps.ramp_d[part], texture_d[part], t2[0], c2[0], c2[1], ps.max_pixels(part))
+                if matched:
+                    ops.morph_colour_u8(ps.src, ps.canvas, ps.offs_d, ps.hw_d, don, doffs_d, dhw_d, ps.boxes_d[part], dboxes_d[part],
+                                        ps.links_d[part], ps.ramp_d[part], texture_d[part], t2[0], c2[0], c2[1], gain[part],
+                                        ps.max_pixels(part))
+                else:
+                    ops.morph_u8(ps.src, ps.canvas, ps.offs_d, ps.hw_d, don, doffs_d, dhw_d, ps.boxes_d[part], dboxes_d[part],
+                                 ps.links_d[part], ps.ramp_d[part], texture_d[part], t2[0], c2[0], c2[1], ps.max_pixels(part))
                 if return_transform:
                     poses[part].copy_(p2[0])
                     if mu_out is not None:
@@ -904,8 +925,30 @@ class LandmarkDetector(BucketRunner):
         out = unpack_u8(ps.canvas, photos)
         if return_transform:
             return out, MP.PhotoMorph(coef_a, coef_b, ctrl, rows, drows, mu_out if lm_a is None else lm_a, lm_b, poses, flags, shape,
-                                      texture, lam, m)
+                                      texture, lam, m, colour, max_gain, gain, cflags)
         return out
+
+    def colour_stats(self, photos, boxes=None):
+        """The statistics colour matching works from, per box row and channel: (count int64 [n], mean f64 [n, 3], standard deviation f64
+        [n, 3]) on the host.  photos, boxes: as morph takes them (a list of u8 arrays; box rows, by default one whole-photo box per
+        photo).  The region of a row is the pixels of its box that lie in its photo and in the ellipse inscribed in the box
+        (include/imm_colour.h); a row without such a pixel, or with a box of more than 2^30 pixels, has count 0 and NaN.  One
+        imm_colour_stats_u8 launch on the caller's stream, the kernel morph(colour > 0) runs; the sums come back as integers and the
+        moments are formed on the host in imm_colour_gain's order."""
+        from . import morphing as MP
+        from .generation import NEEDS_U8, box_areas
+        from .keypoints import check_boxes
+        if not isinstance(photos, (list, tuple)) or not len(photos):
+            raise ValueError('photos: %s' % NEEDS_U8)
+        photos = decode_u8(photos)
+        rows = check_boxes([(0, 0, a.shape[0], a.shape[1]) for a in photos] if boxes is None else boxes, len(photos))
+        if len(rows) > 65535:
+            raise ValueError('colour_stats serves at most 65535 rows a call, got %d' % len(rows))
+        with torch.cuda.device(self.dev):
+            src, offs_d, hw_d, boxes_d = pack_u8(photos, self.dev, rows)
+            sums = torch.empty(len(rows), 7, dtype=torch.int64, device=self.dev)
+            ops.colour_stats_u8(src, offs_d, hw_d, boxes_d, int(box_areas(rows).max()), sums)
+            return MP.colour_moments(sums.cpu().numpy())
 
     def unalign(self, photos, aligned, alignment, feather=0.125):
         """align() run backwards: the photos with every row's aligned face pasted back where align() took it from: a list of u8 device

@@ -10,6 +10,10 @@ carries p back to the face's own landmarks, the other to the donor's, so every p
 takes the mix of what lies there.  shape = texture = t is the morph at t, shape = 0 with texture = 1 the donor's face swapped in place,
 texture = 0 warp() towards the blended pose.
 
+morph(colour=...) adds colour matching (include/imm_colour.h states the rule): per row and channel the mean and the spread of the face's
+pixels and of the donor's pixels, each over the ellipse inscribed in its box, give a gain and an offset that the donor's sample takes in
+front of the mix, so that a donor photographed in other light arrives in the face's tone.
+
 Here: the pose blend in the kernel's f32 order, the argument checks of morph() and PhotoMorph, what morph(return_transform=True) returns.
 Nothing here needs a GPU."""
 import numpy as np
@@ -17,6 +21,7 @@ import numpy as np
 from .warping import _host, check_spline, displacement
 
 MAX_ROWS = 32767               # rows of one morph() call: imm_warp_fit takes 2 n <= 65535 rows
+COLOUR_MAX_AREA = 1 << 30      # H * W of a box whose colour statistics are taken: imm_colour_stats_u8's integer ellipse test stays in 64 bits
 
 
 def blend_poses(mu_a, mu_b, shape):
@@ -57,10 +62,24 @@ def _given_landmarks(lm, counts, K, name):
     return t
 
 
-def plan_morph(photos, donors, boxes, donor_boxes, shape, texture, feather, K, anchors=2, lam=0.0, landmarks=None, donor_landmarks=None):
+def check_max_gain(max_gain):
+    """max_gain of morph(colour=...): finite and >= 1 -> float."""
+    try:
+        g = float(max_gain)
+    except (TypeError, ValueError):
+        raise ValueError('max_gain must be a number, got %r' % (max_gain,))
+    if not (g >= 1.0 and g - g == 0.0):
+        raise ValueError('max_gain must be finite and >= 1 (the ratio of the spreads is kept in [1 / max_gain, max_gain]), got %r' % (max_gain,))
+    return g
+
+
+def plan_morph(photos, donors, boxes, donor_boxes, shape, texture, feather, K, anchors=2, lam=0.0, landmarks=None, donor_landmarks=None,
+               colour=0.0, max_gain=2.0):
     """morph()'s arguments checked on the host, before anything reaches the device: (photos as decoded u8 arrays, box rows int32 [n, 5],
     donor photos as decoded u8 arrays, donor box rows int32 [n, 5] (ONE donor row is repeated for every face), the donor rows as given
-    (what detector.landmarks(donors, .) is asked for), shape f32 [n], texture f32 [n], feather, m, lam, M, landmarks, donor_landmarks).
+    (what detector.landmarks(donors, .) is asked for), shape f32 [n], texture f32 [n], feather, m, lam, M, landmarks, donor_landmarks,
+    colour f32 [n], max_gain).  colour: a number or one per row in [0, 1]; with any colour > 0 a box of more than 2^30 pixels on either
+    side is refused (imm_colour_stats_u8 would count nothing there).
     photos / boxes and donors / donor_boxes in generation.plan_repose's forms (lists of u8 arrays; box rows, by default one whole-photo
     box per photo).  texture=None: texture = shape.  landmarks / donor_landmarks: None or f32 [n, K, 2] tensors (donor_landmarks may have
     one row when there is one donor row)."""
@@ -87,7 +106,25 @@ def plan_morph(photos, donors, boxes, donor_boxes, shape, texture, feather, K, a
     if donor_landmarks is not None:
         donor_landmarks = _given_landmarks(donor_landmarks, (n,) if n_d == n else (n, 1), K, 'donor_landmarks')
     full = np.ascontiguousarray(np.broadcast_to(drows, (n, 5)) if n_d != n else drows, dtype=np.int32)
-    return photos, rows, donors, full, drows, shape, texture, feather, m, lam, M, landmarks, donor_landmarks
+    colour, max_gain = _share(colour, n, 'colour'), check_max_gain(max_gain)
+    if colour.any():
+        for name, rw in (('boxes', rows), ('donor_boxes', full)):
+            area = (rw[:, 3].astype(np.int64) - rw[:, 1]) * (rw[:, 4].astype(np.int64) - rw[:, 2])
+            if (area > COLOUR_MAX_AREA).any():
+                raise ValueError('%s: row %d has %d pixels; colour matching serves boxes of at most 2^30' % (
+                    name, int(np.argmax(area > COLOUR_MAX_AREA)), int(area.max())))
+    return photos, rows, donors, full, drows, shape, texture, feather, m, lam, M, landmarks, donor_landmarks, colour, max_gain
+
+
+def colour_moments(sums):
+    """imm_colour_stats_u8's sums [n, 7] (read as unsigned) -> (count int64 [n], mean f64 [n, 3], standard deviation f64 [n, 3]) on the
+    host, in imm_colour_gain's order of operations: m = S1 / N, sd = sqrt(max(S2 / N - m * m, 0)).  A row without pixels: count 0, NaN."""
+    s = np.ascontiguousarray(sums).view(np.uint64) if np.asarray(sums).dtype == np.int64 else np.asarray(sums, dtype=np.uint64)
+    N = s[:, 6].astype(np.float64)[:, None]
+    with np.errstate(all='ignore'):
+        m, q = s[:, 0:3].astype(np.float64) / N, s[:, 3:6].astype(np.float64) / N
+        sd = np.sqrt(np.maximum(q - m * m, 0.0))
+    return s[:, 6].astype(np.int64), m, sd
 
 
 class PhotoMorph(object):
@@ -95,14 +132,21 @@ class PhotoMorph(object):
     halves of imm_warp_fit's output: target frame -> own frame, target frame -> donor frame) on the shared control points ctrl f32
     [n, M, 2]; rows and donor_rows int32 [n, 5] (host); mu and donor_mu f32 [n, K, 2] (the faces' own and the donors' landmarks), poses
     f32 [n, K, 2] (their blend, the target), flags int32 [n] (the OR of the two fits' flags; bit 0: no usable fit, the box was left
-    alone), shape and texture f32 [n] (host), and the call's lam and anchors."""
+    alone), shape and texture f32 [n] (host), and the call's lam and anchors.  With colour matching (morph(colour > 0)): colour f32 [n]
+    (host), max_gain, colour_gain f32 [n, 3, 2] (device: (gain, offset) per channel, what the donor's samples were taken through) and
+    colour_flags int32 [n] (device; bit 0: a region without pixels, the row got (1, 0)); without it colour_gain and colour_flags are
+    None."""
 
-    def __init__(self, coef_a, coef_b, ctrl, rows, donor_rows, mu, donor_mu, poses, flags, shape, texture, lam, anchors):
+    def __init__(self, coef_a, coef_b, ctrl, rows, donor_rows, mu, donor_mu, poses, flags, shape, texture, lam, anchors, colour=None,
+                 max_gain=None, colour_gain=None, colour_flags=None):
         self.coef_a, self.coef_b, self.ctrl = coef_a, coef_b, ctrl
         self.rows, self.donor_rows = np.asarray(rows, dtype=np.int32), np.asarray(donor_rows, dtype=np.int32)
         self.mu, self.donor_mu, self.poses, self.flags = mu, donor_mu, poses, flags
         self.shape, self.texture = np.asarray(shape, dtype=np.float32), np.asarray(texture, dtype=np.float32)
         self.lam, self.anchors = float(lam), int(anchors)
+        self.colour = np.zeros(len(self.rows), dtype=np.float32) if colour is None else np.asarray(colour, dtype=np.float32)
+        self.max_gain = None if max_gain is None else float(max_gain)
+        self.colour_gain, self.colour_flags = colour_gain, colour_flags
 
     def _frame(self, points_px):
         pts = np.asarray(points_px, dtype=np.float64)

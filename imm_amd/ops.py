@@ -892,14 +892,9 @@ def _overlap(a, b):
     return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
 
 
-def morph_u8(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b,
-             max_box_pixels):
-    """The packed u8 photos dst (a copy of src) morphed in place (include/imm_morph.h: imm_morph_u8): every pixel of row b's box takes
-    the mix, by texture f32 [n], of the ORIGINAL photo's value (src, read only) at the place the row's spline coef_a sends it to and of
-    the donor photo's value (donor, a second packed buffer with donor_offsets / donor_hw, read only; it may be src) at the place coef_b
-    sends it to inside the donor box (donor_boxes i32 [n, 5]), blended with the edge ramp inv_ramp f32 [n, 2] and rounded to u8, in row
-    order.  ctrl f32 [n, M, 2], coef_a / coef_b f32 [n, M + 3, 2]: the halves of ONE warp_fit over the 2 n rows of morph_poses.  boxes,
-    links, max_box_pixels as warp_u8 takes them."""
+def _check_morph(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b,
+                 max_box_pixels, name):
+    """The argument checks morph_u8 and morph_colour_u8 share -> (n, M)."""
     if boxes.dim() != 2 or ctrl.dim() != 3:
         raise ValueError('boxes must be int32 [n, 5] and ctrl f32 [n, M, 2], got %s and %s' % (tuple(boxes.shape), tuple(ctrl.shape)))
     n, M = int(boxes.shape[0]), int(ctrl.shape[1])
@@ -909,7 +904,7 @@ def morph_u8(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor
     if _overlap(donor, dst):
         raise ValueError('the donor buffer is read only: it may be src, never dst')
     if n < 1 or n > 65535 or not 3 <= M <= WARP_MAX_POINTS:
-        raise ValueError('morph_u8 serves 1..65535 rows of 3 <= M <= %d control points, got n = %d, M = %d' % (WARP_MAX_POINTS, n, M))
+        raise ValueError('%s serves 1..65535 rows of 3 <= M <= %d control points, got n = %d, M = %d' % (name, WARP_MAX_POINTS, n, M))
     _check_tensors([('hw', hw, torch.int32, (None, 2)), ('donor_hw', donor_hw, torch.int32, (None, 2))])
     if hw.shape[0] < 1 or donor_hw.shape[0] < 1:
         raise ValueError('hw and donor_hw must hold at least one image, got %s and %s' % (tuple(hw.shape), tuple(donor_hw.shape)))
@@ -920,9 +915,77 @@ def morph_u8(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor
                     ('donor_offsets', donor_offsets, torch.int64, (donor_hw.shape[0],))])
     if int(max_box_pixels) < 1:
         raise ValueError('max_box_pixels must be positive, got %r' % (max_box_pixels,))
+    return n, M
+
+
+def morph_u8(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b,
+             max_box_pixels):
+    """The packed u8 photos dst (a copy of src) morphed in place (include/imm_morph.h: imm_morph_u8): every pixel of row b's box takes
+    the mix, by texture f32 [n], of the ORIGINAL photo's value (src, read only) at the place the row's spline coef_a sends it to and of
+    the donor photo's value (donor, a second packed buffer with donor_offsets / donor_hw, read only; it may be src) at the place coef_b
+    sends it to inside the donor box (donor_boxes i32 [n, 5]), blended with the edge ramp inv_ramp f32 [n, 2] and rounded to u8, in row
+    order.  ctrl f32 [n, M, 2], coef_a / coef_b f32 [n, M + 3, 2]: the halves of ONE warp_fit over the 2 n rows of morph_poses.  boxes,
+    links, max_box_pixels as warp_u8 takes them."""
+    n, M = _check_morph(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a,
+                        coef_b, max_box_pixels, 'morph_u8')
     call('imm_morph_u8', _p(src), _p(dst), _p(offsets), _p(hw), int(hw.shape[0]), _p(donor), _p(donor_offsets), _p(donor_hw),
          int(donor_hw.shape[0]), _p(boxes), _p(donor_boxes), _p(links), _p(inv_ramp), _p(texture), _p(ctrl), _p(coef_a), _p(coef_b), M, n,
          int(max_box_pixels), _s())
+
+
+COLOUR_MAX_AREA = 1 << 30     # H * W of a box whose pixels imm_colour_stats_u8 counts: the ellipse test stays inside 64 bits
+
+
+def colour_stats_u8(buf, offsets, hw, boxes, max_box_pixels, sums):
+    """The colour statistics of every row's region (include/imm_colour.h: imm_colour_stats_u8): buf u8 [bytes] with offsets i64 [images]
+    and hw i32 [images, 2] (a packed buffer, as morph_u8 reads it) and boxes i32 [n, 5] -> sums i64 [n, 7], read as unsigned: per row the
+    sums of v per channel, of v * v per channel and the pixel count over the pixels of the box that lie in the photo and in the ellipse
+    inscribed in the box.  sums is cleared on the stream first.  max_box_pixels sizes the grid only."""
+    if boxes.dim() != 2:
+        raise ValueError('boxes must be int32 [n, 5], got %s' % (tuple(boxes.shape),))
+    n = int(boxes.shape[0])
+    if n < 1 or n > 65535:
+        raise ValueError('colour_stats_u8 serves 1..65535 rows, got n = %d' % n)
+    _check_tensors([('buf', buf, torch.uint8, (None,)), ('hw', hw, torch.int32, (None, 2))])
+    if hw.shape[0] < 1:
+        raise ValueError('hw must hold at least one image, got %s' % (tuple(hw.shape),))
+    _check_tensors([('boxes', boxes, torch.int32, (n, 5)), ('offsets', offsets, torch.int64, (hw.shape[0],)), ('sums', sums, torch.int64, (n, 7))])
+    if int(max_box_pixels) < 1:
+        raise ValueError('max_box_pixels must be positive, got %r' % (max_box_pixels,))
+    call('imm_colour_stats_u8', _p(buf), _p(offsets), _p(hw), int(hw.shape[0]), _p(boxes), n, int(min(int(max_box_pixels), 2 ** 31 - 1)),
+         _p(sums), _s())
+
+
+def colour_gain(sums_a, sums_b, amount, max_gain, gain, flags):
+    """The gain and offset per row and channel (include/imm_colour.h: imm_colour_gain): sums_a, sums_b i64 [n, 7] (colour_stats_u8 of the
+    faces and of their donors) and amount f32 [n] -> gain f32 [n, 3, 2] ((G, O) per channel) and flags i32 [n] (bit 0: a region without
+    pixels or an amount that is not finite, the row got (1, 0)).  max_gain: finite, >= 1; the ratio of the spreads is clamped to
+    [1 / max_gain, max_gain]."""
+    if sums_a.dim() != 2:
+        raise ValueError('sums_a must be int64 [n, 7], got %s' % (tuple(sums_a.shape),))
+    n = int(sums_a.shape[0])
+    if n < 1 or n > 65535:
+        raise ValueError('colour_gain serves 1..65535 rows, got n = %d' % n)
+    _check_tensors([('sums_a', sums_a, torch.int64, (n, 7)), ('sums_b', sums_b, torch.int64, (n, 7)), ('amount', amount, torch.float32, (n,)),
+                    ('gain', gain, torch.float32, (n, 3, 2)), ('flags', flags, torch.int32, (n,))])
+    max_gain = float(max_gain)
+    if not (max_gain >= 1.0 and max_gain - max_gain == 0.0):
+        raise ValueError('max_gain must be finite and >= 1, got %r' % (max_gain,))
+    call('imm_colour_gain', _p(sums_a), _p(sums_b), _p(amount), max_gain, n, _p(gain), _p(flags), _s())
+
+
+def morph_colour_u8(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b,
+                    gain, max_box_pixels):
+    """morph_u8 with the donor's sample taken through gain f32 [n, 3, 2] (colour_gain's output for these rows) in front of the mix:
+    gB * G + O per channel (include/imm_colour.h: imm_morph_colour_u8).  Every other argument as morph_u8 takes it."""
+    n, M = _check_morph(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a,
+                        coef_b, max_box_pixels, 'morph_colour_u8')
+    _check_tensors([('gain', gain, torch.float32, (n, 3, 2))])
+    if _overlap(gain, dst):
+        raise ValueError('gain overlaps dst')
+    call('imm_morph_colour_u8', _p(src), _p(dst), _p(offsets), _p(hw), int(hw.shape[0]), _p(donor), _p(donor_offsets), _p(donor_hw),
+         int(donor_hw.shape[0]), _p(boxes), _p(donor_boxes), _p(links), _p(inv_ramp), _p(texture), _p(ctrl), _p(coef_a), _p(coef_b), _p(gain),
+         M, n, int(max_box_pixels), _s())
 
 
 def masked_sse_pool(a, b, batch, s, c, mask, S, partial, pool_a, pool_b):

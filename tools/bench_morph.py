@@ -15,7 +15,10 @@ there in numpy.  Writes the table to profiles/morph_bench.txt.
 All are timed with HIP events on the caller's stream, alternated window by window in the same run (median over the windows of the mean
 per-call time).  The photos and the donor photos are about 512 x 384 (sizes vary by a few pixels) with one box of about 250 x 250 each.
 An untrained model's landmarks sit in a small cloud, so lam = 1 keeps the systems regular; what the kernels cost does not depend on it.
-Usage: python tools/bench_morph.py [--batch 64] [--windows 7] [--reps 10] [--anchors 2]"""
+With --colour the same photos, sizes and protocol time colour matching instead: detector.morph at colour = 1 against colour = 0,
+alternated window by window after warm-up, and the new launches alone on one call's buffers (imm_colour_stats_u8 over the faces and
+over the donors, imm_colour_gain, imm_morph_colour_u8 next to imm_morph_u8); the table is APPENDED to profiles/morph_bench.txt.
+Usage: python tools/bench_morph.py [--batch 64] [--windows 7] [--reps 10] [--anchors 2] [--colour]"""
 import argparse
 import json
 import os
@@ -83,6 +86,11 @@ def main(args):
     coef2, ctrl2 = torch.empty(2 * B, M + 3, 2, device='cuda:0'), torch.empty(2 * B, M, 2, device='cuda:0')
     flags2 = torch.empty(2 * B, dtype=torch.int32, device='cuda:0')
     ops.morph_poses(pm.mu, pm.donor_mu, shape_d, poses2, mu2)
+    if args.colour:
+        return colour_leg(args, det, photos, donors, boxes, dboxes, rows, drows, pm, props, lambda gain: ops.morph_colour_u8(
+            src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, boxes_d, dboxes_d, links_d, ramp_d, texture_d, pm.ctrl, pm.coef_a, pm.coef_b, gain,
+            area), lambda: ops.morph_u8(src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, boxes_d, dboxes_d, links_d, ramp_d, texture_d, pm.ctrl,
+                                        pm.coef_a, pm.coef_b, area), (src, offs_d, hw_d, boxes_d), (don, doffs_d, dhw_d, dboxes_d), area)
     fns = {'morph': lambda: det.morph(photos, donors, boxes, dboxes, shape=0.5, anchors=m, lam=LAM), 'dissolve': dissolve,
            'pack': lambda: (pack_u8(photos, 'cuda:0', rows)[0].clone(), pack_u8(donors, 'cuda:0', drows)),
            'poses': lambda: ops.morph_poses(pm.mu, pm.donor_mu, shape_d, poses2, mu2),
@@ -123,6 +131,54 @@ def main(args):
                       'poses_ms': med['poses'], 'fit_ms': med['fit'], 'u8_ms': med['u8'], 'flagged': flagged}))
 
 
+def colour_leg(args, det, photos, donors, boxes, dboxes, rows, drows, pm, props, colour_u8, plain_u8, own, donor, area):
+    """--colour: morph at colour = 1 against colour = 0 on the same photos in the same run, and the new launches alone."""
+    import torch
+    from bench_detect import timed_ms
+    from imm_amd import ops
+    B, m = args.batch, args.anchors
+    darea = int(((drows[:, 3] - drows[:, 1]) * (drows[:, 4] - drows[:, 2])).max())
+    sums2 = torch.empty(2, B, 7, dtype=torch.int64, device='cuda:0')
+    gain, cflags = torch.empty(B, 3, 2, device='cuda:0'), torch.empty(B, dtype=torch.int32, device='cuda:0')
+    amount = ops.to_device_pinned(np.ones(B, np.float32), 'cuda:0')
+    fns = {'colour=0': lambda: det.morph(photos, donors, boxes, dboxes, shape=0.5, anchors=m, lam=LAM),
+           'colour=1': lambda: det.morph(photos, donors, boxes, dboxes, shape=0.5, anchors=m, lam=LAM, colour=1.0),
+           'stats_a': lambda: ops.colour_stats_u8(own[0], own[1], own[2], own[3], area, sums2[0]),
+           'stats_b': lambda: ops.colour_stats_u8(donor[0], donor[1], donor[2], donor[3], darea, sums2[1]),
+           'gain': lambda: ops.colour_gain(sums2[0], sums2[1], amount, 2.0, gain, cflags),
+           'u8': plain_u8, 'colour_u8': lambda: colour_u8(gain)}
+    ms = {k: [] for k in fns}
+    for k, fn in fns.items():
+        timed_ms(fn, 2, 1, args.warmup)
+    for _ in range(args.windows):                                   # alternated: one window of each, again and again
+        for k, fn in fns.items():
+            ms[k].append(timed_ms(fn, args.reps, 1, 0))
+    torch.cuda.synchronize()
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    spread = {k: (float(np.min(v)), float(np.max(v))) for k, v in ms.items()}
+    g = gain.cpu().numpy()
+    region = int(sums2[0, :, 6].sum()), int(sums2[1, :, 6].sum())
+    lines = ['==== colour matching (--colour) ====',
+             'device: %s (%s, %d CUs)' % (props.name, props.gcnArchName, props.multi_processor_count),
+             'the photos, donor photos, boxes and protocol of the tables above (B = %d, anchors = %d, lam = %g, bf16); ms per call: median '
+             '(min .. max) of %d alternated windows x %d calls; max_gain = 2' % (B, m, LAM, args.windows, args.reps),
+             'region pixels: %d of the faces, %d of the donors; gains %.3f .. %.3f, offsets %.1f .. %.1f; flagged rows: %d' % (
+                 region[0], region[1], g[..., 0].min(), g[..., 0].max(), g[..., 1].min(), g[..., 1].max(), int(cflags.sum())),
+             '%-10s %10s %22s %12s' % ('call', 'ms', '(min .. max)', 'faces/s')]
+    for k in fns:
+        lines.append('%-10s %10.3f %22s %12s' % (k, med[k], '(%.3f .. %.3f)' % spread[k], '%.0f' % (B / med[k] * 1e3) if '=' in k else '-'))
+    lines.append('colour=1 - colour=0: %+.3f ms per call (%+.2f %%); the three new launches alone: %.1f us; imm_colour_stats_u8: %.1f ps per '
+                 'region pixel of the faces' % (med['colour=1'] - med['colour=0'], 100 * (med['colour=1'] / med['colour=0'] - 1),
+                                                (med['stats_a'] + med['stats_b'] + med['gain']) * 1e3, med['stats_a'] * 1e9 / max(region[0], 1)))
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    if args.out:
+        with open(args.out, 'a') as f:
+            f.write('\n' + text)
+    print(json.dumps({'batch': B, 'anchors': m, 'colour0_ms': med['colour=0'], 'colour1_ms': med['colour=1'], 'stats_a_ms': med['stats_a'],
+                      'stats_b_ms': med['stats_b'], 'gain_ms': med['gain'], 'u8_ms': med['u8'], 'colour_u8_ms': med['colour_u8']}))
+
+
 if __name__ == '__main__':
     p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     p.add_argument('--batch', type=int, default=64)
@@ -130,5 +186,6 @@ if __name__ == '__main__':
     p.add_argument('--reps', type=int, default=10)
     p.add_argument('--warmup', type=int, default=3)
     p.add_argument('--anchors', type=int, default=2, help='anchor points per side of the box frame')
+    p.add_argument('--colour', action='store_true', help='time colour matching: morph at colour = 1 against colour = 0, and the new launches alone')
     p.add_argument('--out', type=str, default=OUT)
     main(p.parse_args())
