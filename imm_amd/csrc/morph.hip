@@ -18,6 +18,12 @@
 // imm_morph_colour_u8 (include/imm_colour.h) is the same kernel in a second, compile-time instantiation: the donor's sample takes
 // gB * G + O per channel in front of the mix, (G, O) = gain[b][ch] f32 [n, 3, 2].  The block's own row keeps its six floats in LDS, rows met
 // on a link walk read theirs through L2; gain reaches no address.  imm_morph_u8's instantiation carries none of it.
+// imm_morph_hull_u8 (include/imm_hull.h) is a third compile-time flag on the same kernel, with and without COLOUR: per pixel the row's K
+// lines (ny, nx, d) = edges[b][k] f32 [n, K, 3] (imm_hull_fit's) give dist = min_k (ny rr + nx cc) + d and w = clamp(dist * inv_soft[b], 0, 1);
+// a pixel with !(w > 0) is left alone BEFORE the spline is evaluated (it skips the M logf that bound the kernel), every other takes
+// paste_ramp(...) * w for its blend weight.  covers() stays the box test, so ownership, row order and links are what they were.  The
+// block's own row keeps its 3 K floats and its inv_soft in LDS (at most 964 bytes), rows met on a link walk read theirs through L2; edges
+// and inv_soft reach no address.  The two instantiations without HULL carry none of it.
 #include "paste_common.h"
 
 __global__ __launch_bounds__(256) void morph_poses_kernel(const float* __restrict__ mu_a, const float* __restrict__ mu_b,
@@ -47,22 +53,47 @@ struct MorphColourRow : MorphRow {
   const float* g;             // its gain [3][2]: (G, O) per channel
 };
 
-template <bool COLOUR>
+template <class Base>
+struct MorphHullRow : Base {
+  const float* e;             // its lines [K][3]: (ny, nx, d) per slot
+  const float* is;            // its inv_soft
+};
+
+// the hull weight of photo pixel (r, c) in a row's box: w = clamp(min_k ((ny_k rr + nx_k cc) + d_k) * inv_soft, 0, 1); a NaN s never
+// lowers the minimum, a NaN product becomes 0 in the first clamp
+__device__ __forceinline__ float hull_weight(const float* __restrict__ e, float inv_soft, int K, const PasteBox& box, int r, int c) {
+#pragma clang fp contract(off)
+  const float rr = (float)(r - box.y0), cc = (float)(c - box.x0);
+  float dist = __builtin_huge_valf();
+  for (int k = 0; k < K; ++k) {
+    const float a = e[3 * k] * rr, b = e[3 * k + 1] * cc;
+    const float s = (a + b) + e[3 * k + 2];
+    dist = fminf(dist, s);
+  }
+  return fminf(fmaxf(dist * inv_soft, 0.f), 1.f);
+}
+
+template <bool COLOUR, bool HULL = false>
 struct MorphPolicy {
-  typedef typename std::conditional<COLOUR, MorphColourRow, MorphRow>::type Row;
+  typedef typename std::conditional<COLOUR, MorphColourRow, MorphRow>::type BoxRow;
+  typedef typename std::conditional<HULL, MorphHullRow<BoxRow>, BoxRow>::type Row;
   const int32_t *boxes, *dboxes;
-  const float *inv_ramp, *texture, *ctrl, *coef_a, *coef_b, *gain;
+  const float *inv_ramp, *texture, *ctrl, *coef_a, *coef_b, *gain, *edges, *inv_soft;
   const uint8_t* sp;          // the row's photo in the ORIGINAL buffer
   const uint8_t* donor;
   const int64_t* doffs;
   const int32_t* dhw;
-  int sh, sw, n_donor, M;
+  int sh, sw, n_donor, M, K;
   Row own;
 
-  // row j with its arrays at ct, ca, cb (and its gain at g)
-  __device__ __forceinline__ Row row(int j, const float* ct, const float* ca, const float* cb, const float* g) const {
+  // row j with its arrays at ct, ca, cb (and its gain at g, its lines at e, its inv_soft at is)
+  __device__ __forceinline__ Row row(int j, const float* ct, const float* ca, const float* cb, const float* g, const float* e,
+                                     const float* is) const {
     Row q;
     if constexpr (COLOUR) q.g = g;
+    if constexpr (HULL) {
+      q.e = e; q.is = is;
+    }
     q.s = spline_row(boxes, inv_ramp, j, ct);
     q.ca = ca; q.cb = cb;
     q.tex = texture[j];
@@ -76,13 +107,18 @@ struct MorphPolicy {
   }
   __device__ __forceinline__ Row row(int j) const {
     return row(j, ctrl + (int64_t)j * 2 * M, coef_a + (int64_t)j * 2 * (M + 3), coef_b + (int64_t)j * 2 * (M + 3),
-               COLOUR ? gain + (int64_t)j * 6 : nullptr);
+               COLOUR ? gain + (int64_t)j * 6 : nullptr, HULL ? edges + (int64_t)j * 3 * K : nullptr, HULL ? inv_soft + j : nullptr);
   }
   __device__ __forceinline__ bool covers(const Row& q, int r, int c) const { return q.dimg >= 0 && paste_inside(q.s.box, r, c); }
   // the row's own photo sampled at (r, c) + (H/2, W/2) DA, the donor photo at the donor box's image of q + DB (COLOUR: times its gain,
-  // plus its offset), mixed by tex
+  // plus its offset), mixed by tex (HULL: only where the row's hull weight is > 0, and blended by the ramp times that weight)
   __device__ __forceinline__ void apply(const Row& q, int r, int c, float (&v)[3]) const {
 #pragma clang fp contract(off)
+    [[maybe_unused]] float w = 1.f;
+    if constexpr (HULL) {
+      w = hull_weight(q.e, *q.is, K, q.s.box, r, c);
+      if (!(w > 0.f)) return;                                      // outside the hull: no spline, no sample
+    }
     const float* const cf[2] = {q.ca, q.cb};
     float qy, qx, D[2][2], ga[3], gb[3], mix[3];
     spline_displace<2>(q.s, cf, M, r, c, qy, qx, D);
@@ -104,11 +140,16 @@ struct MorphPolicy {
       const float te = q.tex * e;
       mix[ch] = ga[ch] + te;
     }
-    paste_blend(v, mix, paste_ramp(q.s.box, r, c, q.s.iry, q.s.irx));
+    const float ramp = paste_ramp(q.s.box, r, c, q.s.iry, q.s.irx);
+    if constexpr (HULL) {
+      paste_blend(v, mix, ramp * w);
+    } else {
+      paste_blend(v, mix, ramp);
+    }
   }
 };
 
-template <bool COLOUR>
+template <bool COLOUR, bool HULL = false>
 __global__ __launch_bounds__(256) void morph_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                        const int64_t* __restrict__ offs, const int32_t* __restrict__ hw, int n_images,
                                                        const uint8_t* __restrict__ donor, const int64_t* __restrict__ doffs,
@@ -116,17 +157,19 @@ __global__ __launch_bounds__(256) void morph_u8_kernel(const uint8_t* __restrict
                                                        const int32_t* __restrict__ dboxes, const int32_t* __restrict__ links,
                                                        const float* __restrict__ inv_ramp, const float* __restrict__ texture,
                                                        const float* __restrict__ ctrl, const float* __restrict__ coef_a,
-                                                       const float* __restrict__ coef_b, const float* __restrict__ gain, int M, int n) {
+                                                       const float* __restrict__ coef_b, const float* __restrict__ gain, int M, int n,
+                                                       const float* __restrict__ edges, const float* __restrict__ inv_soft, int K) {
   __shared__ float ct_s[2 * SPLINE_MAX_M];
   __shared__ float ca_s[2 * SPLINE_MAX_N];
   __shared__ float cb_s[2 * SPLINE_MAX_N];
   __shared__ float g_s[COLOUR ? 6 : 1];                             // (without COLOUR: never referenced, takes no LDS)
+  __shared__ float e_s[HULL ? 3 * SPLINE_MAX_M + 1 : 1];            // its lines, then its inv_soft (without HULL: likewise)
   const int b = blockIdx.y;
   PastePhoto ph;
   if (!paste_photo(boxes, offs, hw, n_images, b, ph)) return;      // uniform over the block: no barrier is skipped by part of it
-  MorphPolicy<COLOUR> pol{boxes, dboxes, inv_ramp, texture, ctrl, coef_a, coef_b, gain, src + ph.off, donor, doffs, dhw, ph.sh, ph.sw, n_donor,
-                          M};
-  pol.own = pol.row(b, ct_s, ca_s, cb_s, g_s);
+  MorphPolicy<COLOUR, HULL> pol{boxes, dboxes, inv_ramp, texture, ctrl, coef_a, coef_b, gain, edges, inv_soft, src + ph.off, donor, doffs,
+                                dhw, ph.sh, ph.sw, n_donor, M, K};
+  pol.own = pol.row(b, ct_s, ca_s, cb_s, g_s, e_s, e_s + 3 * SPLINE_MAX_M);
   if (pol.own.dimg < 0) return;                                    // not active: uniform as well
   for (int i = threadIdx.x; i < 2 * M; i += 256) ct_s[i] = ctrl[(int64_t)b * 2 * M + i];
   for (int i = threadIdx.x; i < 2 * (M + 3); i += 256) {
@@ -135,6 +178,10 @@ __global__ __launch_bounds__(256) void morph_u8_kernel(const uint8_t* __restrict
   }
   if constexpr (COLOUR) {
     if (threadIdx.x < 6) g_s[threadIdx.x] = gain[(int64_t)b * 6 + threadIdx.x];
+  }
+  if constexpr (HULL) {
+    for (int i = threadIdx.x; i < 3 * K; i += 256) e_s[i] = edges[(int64_t)b * 3 * K + i];
+    if (threadIdx.x == 0) e_s[3 * SPLINE_MAX_M] = inv_soft[b];
   }
   __syncthreads();
   paste_rows(pol, pol.own.s.box, ph, dst + ph.off, boxes, links, n);
@@ -152,11 +199,13 @@ extern "C" int imm_morph_poses(const float* mu_a, const float* mu_b, const float
   return 0;
 }
 
-// the checks and the launch of imm_morph_u8 and imm_morph_colour_u8 (gain != nullptr: the COLOUR instantiation)
+// the checks and the launch of imm_morph_u8, imm_morph_colour_u8 and imm_morph_hull_u8 (gain != nullptr: the COLOUR instantiations;
+// edges != nullptr: the HULL ones)
 static int morph_launch(const char* name, const uint8_t* src, uint8_t* dst, const int64_t* offsets, const int32_t* hw, int n_images,
                         const uint8_t* donor, const int64_t* donor_offsets, const int32_t* donor_hw, int n_donor_images, const int32_t* boxes,
                         const int32_t* donor_boxes, const int32_t* links, const float* inv_ramp, const float* texture, const float* ctrl,
-                        const float* coef_a, const float* coef_b, const float* gain, int M, int n, int max_box_pixels, void* stream) {
+                        const float* coef_a, const float* coef_b, const float* gain, const float* edges, const float* inv_soft, int K, int M,
+                        int n, int max_box_pixels, void* stream) {
   IMM_REQUIRE(src && dst && offsets && hw && donor && donor_offsets && donor_hw && boxes && donor_boxes && links && inv_ramp && texture &&
                   ctrl && coef_a && coef_b, "%s: null pointer", name);
   IMM_REQUIRE(src != dst, "%s: dst must be a copy of src, not src itself (every row samples the original pixels)", name);
@@ -166,12 +215,20 @@ static int morph_launch(const char* name, const uint8_t* src, uint8_t* dst, cons
   IMM_REQUIRE(M >= 3 && M <= SPLINE_MAX_M, "%s: 3 <= M <= %d control points (got %d)", name, SPLINE_MAX_M, M);
   IMM_REQUIRE(max_box_pixels > 0, "%s: max_box_pixels > 0 (got %d)", name, max_box_pixels);
   const dim3 grid(paste_grid_x(max_box_pixels), n);
-  if (gain)
-    hipLaunchKernelGGL(morph_u8_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, offsets, hw, n_images, donor, donor_offsets,
-                       donor_hw, n_donor_images, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b, gain, M, n);
-  else
-    hipLaunchKernelGGL(morph_u8_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, offsets, hw, n_images, donor, donor_offsets,
-                       donor_hw, n_donor_images, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b, gain, M, n);
+#define MORPH_LAUNCH(kernel)                                                                                                             \
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, src, dst, offsets, hw, n_images, donor, donor_offsets, donor_hw,      \
+                     n_donor_images, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b, gain, M, n, edges, inv_soft, K)
+  if (edges) {
+    if (gain)
+      MORPH_LAUNCH((morph_u8_kernel<true, true>));
+    else
+      MORPH_LAUNCH((morph_u8_kernel<false, true>));
+  } else if (gain) {
+    MORPH_LAUNCH(morph_u8_kernel<true>);
+  } else {
+    MORPH_LAUNCH(morph_u8_kernel<false>);
+  }
+#undef MORPH_LAUNCH
   return 0;
 }
 
@@ -180,7 +237,7 @@ extern "C" int imm_morph_u8(const uint8_t* src, uint8_t* dst, const int64_t* off
                             const int32_t* donor_boxes, const int32_t* links, const float* inv_ramp, const float* texture, const float* ctrl,
                             const float* coef_a, const float* coef_b, int M, int n, int max_box_pixels, void* stream) {
   const int rc = morph_launch("morph_u8", src, dst, offsets, hw, n_images, donor, donor_offsets, donor_hw, n_donor_images, boxes, donor_boxes,
-                              links, inv_ramp, texture, ctrl, coef_a, coef_b, nullptr, M, n, max_box_pixels, stream);
+                              links, inv_ramp, texture, ctrl, coef_a, coef_b, nullptr, nullptr, nullptr, 0, M, n, max_box_pixels, stream);
   if (rc) return rc;
   IMM_CHECK_LAUNCH("imm_morph_u8");
   return 0;
@@ -193,8 +250,23 @@ extern "C" int imm_morph_colour_u8(const uint8_t* src, uint8_t* dst, const int64
                                    int n, int max_box_pixels, void* stream) {
   IMM_REQUIRE(gain, "morph_colour_u8: null pointer");
   const int rc = morph_launch("morph_colour_u8", src, dst, offsets, hw, n_images, donor, donor_offsets, donor_hw, n_donor_images, boxes,
-                              donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b, gain, M, n, max_box_pixels, stream);
+                              donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b, gain, nullptr, nullptr, 0, M, n, max_box_pixels, stream);
   if (rc) return rc;
   IMM_CHECK_LAUNCH("imm_morph_colour_u8");
+  return 0;
+}
+
+extern "C" int imm_morph_hull_u8(const uint8_t* src, uint8_t* dst, const int64_t* offsets, const int32_t* hw, int n_images,
+                                 const uint8_t* donor, const int64_t* donor_offsets, const int32_t* donor_hw, int n_donor_images,
+                                 const int32_t* boxes, const int32_t* donor_boxes, const int32_t* links, const float* inv_ramp,
+                                 const float* texture, const float* ctrl, const float* coef_a, const float* coef_b, const float* gain,
+                                 const float* edges, const float* inv_soft, int K, int M, int n, int max_box_pixels, void* stream) {
+  IMM_REQUIRE(edges && inv_soft, "morph_hull_u8: null pointer");
+  IMM_REQUIRE(K >= 1 && K <= SPLINE_MAX_M, "morph_hull_u8: 1 <= K <= %d landmarks (got %d)", SPLINE_MAX_M, K);
+  const int rc = morph_launch("morph_hull_u8", src, dst, offsets, hw, n_images, donor, donor_offsets, donor_hw, n_donor_images, boxes,
+                              donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b, gain, edges, inv_soft, K, M, n, max_box_pixels,
+                              stream);
+  if (rc) return rc;
+  IMM_CHECK_LAUNCH("imm_morph_hull_u8");
   return 0;
 }

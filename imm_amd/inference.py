@@ -826,7 +826,8 @@ class LandmarkDetector(BucketRunner):
         return out
 
     def morph(self, photos, donors, boxes=None, donor_boxes=None, shape=0.5, texture=None, feather=0.125, anchors=2, lam=0.0,
-              landmarks=None, donor_landmarks=None, return_transform=False, colour=0.0, max_gain=2.0):
+              landmarks=None, donor_landmarks=None, return_transform=False, colour=0.0, max_gain=2.0, mask=None, grow=1.25,
+              mask_feather=0.1):
         """The photos with every box's face blended with a donor's face, in shape and in texture, from the pixels of the two
         photographs: a list of u8 device tensors [h_i, w_i, 3], one per photo, views of one packed buffer (what warp returns); nothing
         is rendered.
@@ -851,16 +852,23 @@ class LandmarkDetector(BucketRunner):
         (max_gain finite, >= 1).  With any colour > 0, once per call in front of the buckets: imm_colour_stats_u8 over the faces' rows
         and over the donors' rows, imm_colour_gain; and per bucket imm_morph_colour_u8 in place of imm_morph_u8 (include/imm_colour.h
         states the rule).
+        mask: None (the default: every pixel of the box is blended, today's launches and bytes) or 'hull': only the face is pasted.
+        The convex hull of the row's blended landmarks, grown about their centroid by grow (a number or one per row in (0, 16]) and
+        softened inwards over mask_feather * min(H, W) pixels (a number or one per row in [0, 1]; at least one pixel), multiplies the
+        box's edge ramp, and pixels outside it skip the spline.  Per bucket imm_hull_fit runs behind imm_morph_poses, reading the blended
+        landmarks in place, and imm_morph_hull_u8 takes the place of imm_morph_u8 / imm_morph_colour_u8 (include/imm_hull.h states the
+        rule).
         return_transform=True: (photos, a morphing.PhotoMorph: coef_a, coef_b, ctrl, rows, donor_rows, mu, donor_mu, poses, flags,
-        to_source, to_donor, colour_gain, colour_flags)."""
+        to_source, to_donor, colour_gain, colour_flags, hull_edges, hull_flags, hull_weight)."""
         from . import morphing as MP
         from . import warping as WP
         from .generation import PasteSetup, box_areas
         K = self.K
-        photos, rows, donors, drows, drows_given, shape, texture, feather, m, lam, M, lm_a, lm_b, colour, max_gain = MP.plan_morph(
-            photos, donors, boxes, donor_boxes, shape, texture, feather, K, anchors, lam, landmarks, donor_landmarks, colour, max_gain)
+        plan = MP.plan_morph(photos, donors, boxes, donor_boxes, shape, texture, feather, K, anchors, lam, landmarks, donor_landmarks, colour,
+                             max_gain, mask, grow, mask_feather)
+        photos, rows, donors, drows, drows_given, shape, texture, feather, m, lam, M, lm_a, lm_b, colour, max_gain = plan
         n = len(rows)
-        matched = bool(colour.any())
+        matched, hull = bool(colour.any()), plan.mask == 'hull'
         lm_b = pose_landmarks(self, ('photos', donors, drows_given) if lm_b is None else ('landmarks', lm_b), n).contiguous()
         if lm_a is not None:
             lm_a = lm_a.to(device=self.dev, dtype=torch.float32).contiguous()
@@ -887,8 +895,13 @@ class LandmarkDetector(BucketRunner):
                 colour_d = ops.to_device_pinned(colour, self.dev)
                 sums2 = torch.empty(2, n, 7, dtype=torch.int64, device=self.dev)
                 gain, cflags = torch.empty(n, 3, 2, device=self.dev), torch.empty(n, dtype=torch.int32, device=self.dev)
+            grow_d = soft_d = edges = hflags = None
+            if hull:
+                grow_d, soft_d = ops.to_device_pinned(plan.grow, self.dev), ops.to_device_pinned(plan.inv_soft, self.dev)
+                edges, hflags = torch.empty(n, K, 3, device=self.dev), torch.empty(n, dtype=torch.int32, device=self.dev)
         with self._forked(*ps.tensors(), don, doffs_d, dhw_d, dboxes_d, shape_d, texture_d, anchors_d, lm_a, lm_b, coef_a, coef_b, ctrl,
-                          flags, poses, mu_out, poses2, mu2, coef2, ctrl2, flags2, colour_d, sums2, gain, cflags):
+                          flags, poses, mu_out, poses2, mu2, coef2, ctrl2, flags2, colour_d, sums2, gain, cflags, grow_d, soft_d, edges,
+                          hflags):
             if matched:                                                             # once per call, all rows
                 ops.colour_stats_u8(ps.src, ps.offs_d, ps.hw_d, ps.boxes_d, int(ps.area.max()), sums2[0])
                 ops.colour_stats_u8(don, doffs_d, dhw_d, dboxes_d, int(box_areas(drows).max()), sums2[1])
@@ -905,13 +918,19 @@ class LandmarkDetector(BucketRunner):
                 c2, t2 = coef2[:2 * count * (M + 3) * 2].view(2, count, M + 3, 2), ctrl2[:2 * count * M * 2].view(2, count, M, 2)
                 f2 = flags2[:2 * count].view(2, count)
                 ops.morph_poses(own, lm_b[part], shape_d[part], p2, m2)
+                if hull:                                                            # the blended landmarks, read in place
+                    ops.hull_fit(p2[0], ps.boxes_d[part], grow_d[part], edges[part], hflags[part])
                 ops.warp_fit(p2.view(2 * count, K, 2), m2.view(2 * count, K, 2), anchors_d, 1.0, lam, c2.view(2 * count, M + 3, 2),
                              t2.view(2 * count, M, 2), f2.view(2 * count))
                 coef_a[part].copy_(c2[0])
                 coef_b[part].copy_(c2[1])
                 ctrl[part].copy_(t2[0])
                 torch.bitwise_or(f2[0], f2[1], out=flags[part])
-                if matched:
+                if hull:
+                    ops.morph_hull_u8(ps.src, ps.canvas, ps.offs_d, ps.hw_d, don, doffs_d, dhw_d, ps.boxes_d[part], dboxes_d[part],
+                                      ps.links_d[part], ps.ramp_d[part], texture_d[part], t2[0], c2[0], c2[1],
+                                      gain[part] if matched else None, edges[part], soft_d[part], ps.max_pixels(part))
+                elif matched:
                     ops.morph_colour_u8(ps.src, ps.canvas, ps.offs_d, ps.hw_d, don, doffs_d, dhw_d, ps.boxes_d[part], dboxes_d[part],
                                         ps.links_d[part], ps.ramp_d[part], texture_d[part], t2[0], c2[0], c2[1], gain[part],
                                         ps.max_pixels(part))
@@ -925,7 +944,8 @@ class LandmarkDetector(BucketRunner):
         out = unpack_u8(ps.canvas, photos)
         if return_transform:
             return out, MP.PhotoMorph(coef_a, coef_b, ctrl, rows, drows, mu_out if lm_a is None else lm_a, lm_b, poses, flags, shape,
-                                      texture, lam, m, colour, max_gain, gain, cflags)
+                                      texture, lam, m, colour, max_gain, gain, cflags, plan.mask,
+                                      *((plan.grow, plan.mask_feather, plan.inv_soft, edges, hflags) if hull else ()))
         return out
 
     def colour_stats(self, photos, boxes=None):

@@ -14,6 +14,10 @@ morph(colour=...) adds colour matching (include/imm_colour.h states the rule): p
 pixels and of the donor's pixels, each over the ellipse inscribed in its box, give a gain and an offset that the donor's sample takes in
 front of the mix, so that a donor photographed in other light arrives in the face's tone.
 
+morph(mask='hull') pastes only the face (include/imm_hull.h states the rule): the convex hull of the row's blended landmarks, grown about
+their centroid by `grow` and softened inwards over mask_feather * min(H, W) pixels, multiplies the box's edge ramp, so the donor's
+background, hair and collar stay out of the photo; pixels outside the hull skip the spline altogether.
+
 Here: the pose blend in the kernel's f32 order, the argument checks of morph() and PhotoMorph, what morph(return_transform=True) returns.
 Nothing here needs a GPU."""
 import numpy as np
@@ -21,6 +25,8 @@ import numpy as np
 from .warping import _host, check_spline, displacement
 
 MAX_ROWS = 32767               # rows of one morph() call: imm_warp_fit takes 2 n <= 65535 rows
+MASKS = (None, 'hull')         # morph(mask=...)
+MAX_GROW = 16.0                # grow of morph(mask='hull') lies in (0, 16]
 COLOUR_MAX_AREA = 1 << 30      # H * W of a box whose colour statistics are taken: imm_colour_stats_u8's integer ellipse test stays in 64 bits
 
 
@@ -38,14 +44,20 @@ def blend_poses(mu_a, mu_b, shape):
         return ta + tb
 
 
-def _share(value, n, name):
-    """A scalar or [n] in [0, 1] -> f32 [n]."""
+def _share(value, n, name, bounds=None):
+    """A scalar or [n] in [0, 1] -> f32 [n].  bounds = (interval as text, test of the f64 values, what the number is): that interval
+    instead."""
     v = np.asarray(value, dtype=np.float64)
     if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != n):
         raise ValueError('%s must be a number or one per row [%d], got shape %s' % (name, n, v.shape))
     v = np.broadcast_to(v, (n,))
-    if not (np.isfinite(v).all() and (v >= 0.0).all() and (v <= 1.0).all()):
-        raise ValueError('%s must be finite and lie in [0, 1] (0: the face itself, 1: the donor), got %r' % (name, value))
+    if bounds is None:
+        if not (np.isfinite(v).all() and (v >= 0.0).all() and (v <= 1.0).all()):
+            raise ValueError('%s must be finite and lie in [0, 1] (0: the face itself, 1: the donor), got %r' % (name, value))
+    else:
+        interval, inside, what = bounds
+        if not (np.isfinite(v).all() and inside(v).all()):
+            raise ValueError('%s must be finite and lie in %s (%s), got %r' % (name, interval, what, value))
     return np.ascontiguousarray(v, dtype=np.float32)
 
 
@@ -73,8 +85,27 @@ def check_max_gain(max_gain):
     return g
 
 
+def hull_inv_soft(rows, mask_feather):
+    """inv_soft f32 [n] of morph(mask='hull'): (float)(1 / max(1, mask_feather * min(H, W))), formed in f64 from the f32 mask_feather
+    widened: the hull's weight is 0 on the grown hull's edge and 1 that many pixels (at least one) inside it."""
+    rows = np.asarray(rows)
+    side = np.minimum(rows[:, 3].astype(np.int64) - rows[:, 1], rows[:, 4].astype(np.int64) - rows[:, 2]).astype(np.float64)
+    soft = np.maximum(1.0, np.asarray(mask_feather, dtype=np.float32).astype(np.float64) * side)
+    return (1.0 / soft).astype(np.float32)
+
+
+class MorphPlan(tuple):
+    """What plan_morph returns: the fifteen values it has always returned, as a tuple, with the mask's as attributes: mask (None or
+    'hull'), grow f32 [n], mask_feather f32 [n] and inv_soft f32 [n] (hull_inv_soft of the rows)."""
+
+    def __new__(cls, values, mask, grow, mask_feather, inv_soft):
+        self = super(MorphPlan, cls).__new__(cls, values)
+        self.mask, self.grow, self.mask_feather, self.inv_soft = mask, grow, mask_feather, inv_soft
+        return self
+
+
 def plan_morph(photos, donors, boxes, donor_boxes, shape, texture, feather, K, anchors=2, lam=0.0, landmarks=None, donor_landmarks=None,
-               colour=0.0, max_gain=2.0):
+               colour=0.0, max_gain=2.0, mask=None, grow=1.25, mask_feather=0.1):
     """morph()'s arguments checked on the host, before anything reaches the device: (photos as decoded u8 arrays, box rows int32 [n, 5],
     donor photos as decoded u8 arrays, donor box rows int32 [n, 5] (ONE donor row is repeated for every face), the donor rows as given
     (what detector.landmarks(donors, .) is asked for), shape f32 [n], texture f32 [n], feather, m, lam, M, landmarks, donor_landmarks,
@@ -82,8 +113,12 @@ def plan_morph(photos, donors, boxes, donor_boxes, shape, texture, feather, K, a
     side is refused (imm_colour_stats_u8 would count nothing there).
     photos / boxes and donors / donor_boxes in generation.plan_repose's forms (lists of u8 arrays; box rows, by default one whole-photo
     box per photo).  texture=None: texture = shape.  landmarks / donor_landmarks: None or f32 [n, K, 2] tensors (donor_landmarks may have
-    one row when there is one donor row)."""
+    one row when there is one donor row).
+    mask: None or 'hull'; grow: a number or one per row in (0, 16]; mask_feather: likewise in [0, 1].  They are checked whatever mask is,
+    and returned as attributes of the result (a MorphPlan)."""
     from .generation import NEEDS_U8, check_feather
+    if mask not in MASKS:
+        raise ValueError("mask must be None or 'hull', got %r" % (mask,))
     from .inference import decode_u8
     from .keypoints import check_boxes
     m, lam, _strength, M = check_spline(anchors, lam, 1.0, K)
@@ -113,7 +148,12 @@ def plan_morph(photos, donors, boxes, donor_boxes, shape, texture, feather, K, a
             if (area > COLOUR_MAX_AREA).any():
                 raise ValueError('%s: row %d has %d pixels; colour matching serves boxes of at most 2^30' % (
                     name, int(np.argmax(area > COLOUR_MAX_AREA)), int(area.max())))
-    return photos, rows, donors, full, drows, shape, texture, feather, m, lam, M, landmarks, donor_landmarks, colour, max_gain
+    grow = _share(grow, n, 'grow', ('(0, %g]' % MAX_GROW, lambda v: (v > 0.0) & (v <= MAX_GROW),
+                                    'the factor by which the landmark hull is grown about its centroid'))
+    mask_feather = _share(mask_feather, n, 'mask_feather', ('[0, 1]', lambda v: (v >= 0.0) & (v <= 1.0),
+                                                            'the share of the box\'s shorter side over which the mask softens inwards'))
+    return MorphPlan((photos, rows, donors, full, drows, shape, texture, feather, m, lam, M, landmarks, donor_landmarks, colour, max_gain),
+                     mask, grow, mask_feather, hull_inv_soft(rows, mask_feather))
 
 
 def colour_moments(sums):
@@ -135,10 +175,15 @@ class PhotoMorph(object):
     alone), shape and texture f32 [n] (host), and the call's lam and anchors.  With colour matching (morph(colour > 0)): colour f32 [n]
     (host), max_gain, colour_gain f32 [n, 3, 2] (device: (gain, offset) per channel, what the donor's samples were taken through) and
     colour_flags int32 [n] (device; bit 0: a region without pixels, the row got (1, 0)); without it colour_gain and colour_flags are
+    None.  With the landmark-hull mask (morph(mask='hull')): mask 'hull', grow, mask_feather and inv_soft f32 [n] (host), hull_edges f32
+    [n, K, 3] (device: the lines (ny, nx, d) of every row's grown hull in box-relative pixels, imm_hull_fit's output) and hull_flags
+    int32 [n] (device; bit 0: an empty box, a pose or a grow that is not finite; bit 1: no hull with an inside; a flagged row wrote
+    nothing; OR-ed into nothing else), and hull_weight(i), the weight over row i's box; without it mask, hull_edges and hull_flags are
     None."""
 
     def __init__(self, coef_a, coef_b, ctrl, rows, donor_rows, mu, donor_mu, poses, flags, shape, texture, lam, anchors, colour=None,
-                 max_gain=None, colour_gain=None, colour_flags=None):
+                 max_gain=None, colour_gain=None, colour_flags=None, mask=None, grow=None, mask_feather=None, inv_soft=None,
+                 hull_edges=None, hull_flags=None):
         self.coef_a, self.coef_b, self.ctrl = coef_a, coef_b, ctrl
         self.rows, self.donor_rows = np.asarray(rows, dtype=np.int32), np.asarray(donor_rows, dtype=np.int32)
         self.mu, self.donor_mu, self.poses, self.flags = mu, donor_mu, poses, flags
@@ -147,6 +192,26 @@ class PhotoMorph(object):
         self.colour = np.zeros(len(self.rows), dtype=np.float32) if colour is None else np.asarray(colour, dtype=np.float32)
         self.max_gain = None if max_gain is None else float(max_gain)
         self.colour_gain, self.colour_flags = colour_gain, colour_flags
+        self.mask = mask
+        self.grow, self.mask_feather, self.inv_soft = (None if a is None else np.asarray(a, dtype=np.float32) for a in (grow, mask_feather, inv_soft))
+        self.hull_edges, self.hull_flags = hull_edges, hull_flags
+
+    def hull_weight(self, i):
+        """f32 [H_i, W_i]: the mask's weight at every pixel of row i's box, from the device's hull_edges in the rule's f32 order
+        (include/imm_hull.h): dist = min over the slots of (ny * rr + nx * cc) + d at rr = r - y0, cc = c - x0, w = clamp(dist *
+        inv_soft, 0, 1).  The kernel blends a pixel with w > 0 by the edge ramp times w and leaves every other alone."""
+        if self.hull_edges is None:
+            raise ValueError("hull_weight needs a morph with mask='hull'")
+        _img, y0, x0, y1, x1 = (int(v) for v in self.rows[i])
+        e = np.asarray(_host(self.hull_edges[i]), dtype=np.float32)
+        rr, cc = np.arange(max(y1 - y0, 0), dtype=np.float32)[:, None], np.arange(max(x1 - x0, 0), dtype=np.float32)[None, :]
+        dist = np.full((rr.shape[0], cc.shape[1]), np.inf, dtype=np.float32)
+        with np.errstate(all='ignore'):
+            for ny, nx, d in e:
+                dist = np.fmin(dist, (ny * rr + nx * cc) + d)
+            w = np.fmin(np.fmax(dist * self.inv_soft[i], np.float32(0)), np.float32(1))
+        assert w.dtype == np.float32
+        return w
 
     def _frame(self, points_px):
         pts = np.asarray(points_px, dtype=np.float64)

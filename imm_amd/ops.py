@@ -988,6 +988,43 @@ def morph_colour_u8(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes
          M, n, int(max_box_pixels), _s())
 
 
+def hull_fit(poses, boxes, grow, edges, flags):
+    """The supporting lines of every row's grown landmark hull (include/imm_hull.h: imm_hull_fit): poses f32 [n, K, 2] (the target
+    landmarks in the frame of the row's box; a contiguous view, e.g. the first half of morph_poses' poses2), boxes i32 [n, 5] and grow
+    f32 [n] -> edges f32 [n, K, 3] ((ny, nx, d) per slot) and flags i32 [n] (bit 0: an empty box, a pose or a grow that is not finite;
+    bit 1: no hull with an inside; a flagged row's lines give the weight 0 everywhere)."""
+    if poses.dim() != 3:
+        raise ValueError('poses must be f32 [n, K, 2], got %s' % (tuple(poses.shape),))
+    n, K = int(poses.shape[0]), int(poses.shape[1])
+    if n < 1 or n > 65535 or not 1 <= K <= WARP_MAX_POINTS:
+        raise ValueError('hull_fit serves 1..65535 rows of 1 <= K <= %d landmarks, got n = %d, K = %d' % (WARP_MAX_POINTS, n, K))
+    _check_tensors([('poses', poses, torch.float32, (n, K, 2)), ('boxes', boxes, torch.int32, (n, 5)), ('grow', grow, torch.float32, (n,)),
+                    ('edges', edges, torch.float32, (n, K, 3)), ('flags', flags, torch.int32, (n,))])
+    call('imm_hull_fit', _p(poses), _p(boxes), _p(grow), K, n, _p(edges), _p(flags), _s())
+
+
+def morph_hull_u8(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b,
+                  gain, edges, inv_soft, max_box_pixels):
+    """morph_u8 (gain None) or morph_colour_u8 (gain f32 [n, 3, 2]) with the landmark-hull mask (include/imm_hull.h:
+    imm_morph_hull_u8): edges f32 [n, K, 3] (hull_fit's output for these rows) and inv_soft f32 [n] give every pixel of a row's box the
+    weight w = clamp(min_k((ny rr + nx cc) + d) * inv_soft, 0, 1); a pixel with w = 0 is left alone, every other is blended with the edge
+    ramp times w.  Every other argument as morph_u8 takes it."""
+    n, M = _check_morph(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a,
+                        coef_b, max_box_pixels, 'morph_hull_u8')
+    if edges.dim() != 3 or not 1 <= int(edges.shape[1]) <= WARP_MAX_POINTS:
+        raise ValueError('edges must be f32 [n, K, 3] with 1 <= K <= %d, got %s' % (WARP_MAX_POINTS, tuple(edges.shape)))
+    K = int(edges.shape[1])
+    _check_tensors([('edges', edges, torch.float32, (n, K, 3)), ('inv_soft', inv_soft, torch.float32, (n,))])
+    if gain is not None:
+        _check_tensors([('gain', gain, torch.float32, (n, 3, 2))])
+    for name, t in (('gain', gain), ('edges', edges), ('inv_soft', inv_soft)):
+        if t is not None and _overlap(t, dst):
+            raise ValueError('%s overlaps dst' % name)
+    call('imm_morph_hull_u8', _p(src), _p(dst), _p(offsets), _p(hw), int(hw.shape[0]), _p(donor), _p(donor_offsets), _p(donor_hw),
+         int(donor_hw.shape[0]), _p(boxes), _p(donor_boxes), _p(links), _p(inv_ramp), _p(texture), _p(ctrl), _p(coef_a), _p(coef_b),
+         None if gain is None else _p(gain), _p(edges), _p(inv_soft), K, M, n, int(max_box_pixels), _s())
+
+
 def masked_sse_pool(a, b, batch, s, c, mask, S, partial, pool_a, pool_b):
     call('imm_masked_sse_pool', _p(a), _p(b), dtype_enum(a.dtype), batch, s, c, _p(mask), S, _p(partial), _p(pool_a), _p(pool_b), _s())
 

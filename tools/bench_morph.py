@@ -18,7 +18,12 @@ An untrained model's landmarks sit in a small cloud, so lam = 1 keeps the system
 With --colour the same photos, sizes and protocol time colour matching instead: detector.morph at colour = 1 against colour = 0,
 alternated window by window after warm-up, and the new launches alone on one call's buffers (imm_colour_stats_u8 over the faces and
 over the donors, imm_colour_gain, imm_morph_colour_u8 next to imm_morph_u8); the table is APPENDED to profiles/morph_bench.txt.
-Usage: python tools/bench_morph.py [--batch 64] [--windows 7] [--reps 10] [--anchors 2] [--colour]"""
+With --mask the same photos, sizes and protocol time the landmark-hull mask: detector.morph at mask = None against mask = 'hull', at
+colour 0 and 1, alternated window by window after warm-up, once with the model's own landmarks (the protocol of the tables above; an
+untrained model's landmarks sit in a small cloud, so its hull is small) and once with landmarks on a jittered grid over [-0.8, 0.8]^2
+given to both sides (a hull of the size a face's is), and the two new launches alone on one call's buffers (imm_hull_fit, and
+imm_morph_hull_u8 next to imm_morph_u8), with the share of the box pixels whose weight is > 0; the table is APPENDED as well.
+Usage: python tools/bench_morph.py [--batch 64] [--windows 7] [--reps 10] [--anchors 2] [--colour | --mask]"""
 import argparse
 import json
 import os
@@ -91,6 +96,11 @@ def main(args):
             src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, boxes_d, dboxes_d, links_d, ramp_d, texture_d, pm.ctrl, pm.coef_a, pm.coef_b, gain,
             area), lambda: ops.morph_u8(src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, boxes_d, dboxes_d, links_d, ramp_d, texture_d, pm.ctrl,
                                         pm.coef_a, pm.coef_b, area), (src, offs_d, hw_d, boxes_d), (don, doffs_d, dhw_d, dboxes_d), area)
+    if args.mask:
+        return mask_leg(args, det, photos, donors, boxes, dboxes, props, mid, poses2, lambda q, edges, soft: ops.morph_hull_u8(
+            src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, boxes_d, dboxes_d, links_d, ramp_d, texture_d, q.ctrl, q.coef_a, q.coef_b, None,
+            edges, soft, area), lambda q: ops.morph_u8(src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, boxes_d, dboxes_d, links_d, ramp_d,
+                                                       texture_d, q.ctrl, q.coef_a, q.coef_b, area), boxes_d)
     fns = {'morph': lambda: det.morph(photos, donors, boxes, dboxes, shape=0.5, anchors=m, lam=LAM), 'dissolve': dissolve,
            'pack': lambda: (pack_u8(photos, 'cuda:0', rows)[0].clone(), pack_u8(donors, 'cuda:0', drows)),
            'poses': lambda: ops.morph_poses(pm.mu, pm.donor_mu, shape_d, poses2, mu2),
@@ -179,6 +189,67 @@ def colour_leg(args, det, photos, donors, boxes, dboxes, rows, drows, pm, props,
                       'stats_b_ms': med['stats_b'], 'gain_ms': med['gain'], 'u8_ms': med['u8'], 'colour_u8_ms': med['colour_u8']}))
 
 
+def mask_leg(args, det, photos, donors, boxes, dboxes, props, grid, poses2, hull_u8, plain_u8, boxes_d):
+    """--mask: morph at mask = 'hull' against mask = None on the same photos in the same run, and the new launches alone."""
+    import torch
+    from bench_detect import timed_ms
+    from bench_warp import grid_poses
+    from imm_amd import ops
+    B, m = args.batch, args.anchors
+    common = dict(shape=0.5, anchors=m, lam=LAM)
+    given = dict(landmarks=grid, donor_landmarks=torch.from_numpy(grid_poses(B, seed=2)).cuda(), **common)
+    _out, own = det.morph(photos, donors, boxes, dboxes, mask='hull', return_transform=True, **common)
+    _out, grd = det.morph(photos, donors, boxes, dboxes, mask='hull', return_transform=True, **given)
+    torch.cuda.synchronize()
+    share = {}
+    for name, q in (('own', own), ('grid', grd)):
+        w = [q.hull_weight(i) for i in range(B)]
+        share[name] = (sum(int((x > 0).sum()) for x in w), sum(x.size for x in w), int((q.hull_flags != 0).sum()))
+    grow_d, soft_d = ops.to_device_pinned(own.grow, 'cuda:0'), ops.to_device_pinned(own.inv_soft, 'cuda:0')
+    edges, hflags = torch.empty(B, K, 3, device='cuda:0'), torch.empty(B, dtype=torch.int32, device='cuda:0')
+    fns = {'None c=0': lambda: det.morph(photos, donors, boxes, dboxes, **common),
+           'hull c=0': lambda: det.morph(photos, donors, boxes, dboxes, mask='hull', **common),
+           'None c=1': lambda: det.morph(photos, donors, boxes, dboxes, colour=1.0, **common),
+           'hull c=1': lambda: det.morph(photos, donors, boxes, dboxes, colour=1.0, mask='hull', **common),
+           'grid None': lambda: det.morph(photos, donors, boxes, dboxes, **given),
+           'grid hull': lambda: det.morph(photos, donors, boxes, dboxes, mask='hull', **given),
+           'hull_fit': lambda: ops.hull_fit(poses2[0], boxes_d, grow_d, edges, hflags),
+           'u8': lambda: plain_u8(own), 'hull_u8': lambda: hull_u8(own, own.hull_edges, soft_d),
+           'grid u8': lambda: plain_u8(grd), 'grid hull_u8': lambda: hull_u8(grd, grd.hull_edges, soft_d)}
+    ms = {k: [] for k in fns}
+    for k, fn in fns.items():
+        timed_ms(fn, 2, 1, args.warmup)
+    for _ in range(args.windows):                                   # alternated: one window of each, again and again
+        for k, fn in fns.items():
+            ms[k].append(timed_ms(fn, args.reps, 1, 0))
+    torch.cuda.synchronize()
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    spread = {k: (float(np.min(v)), float(np.max(v))) for k, v in ms.items()}
+    lines = ['==== landmark-hull mask (--mask) ====',
+             'device: %s (%s, %d CUs)' % (props.name, props.gcnArchName, props.multi_processor_count),
+             'the photos, donor photos, boxes and protocol of the tables above (B = %d, anchors = %d, lam = %g, bf16); ms per call: median '
+             '(min .. max) of %d alternated windows x %d calls; grow = 1.25, mask_feather = 0.1; "grid": landmarks on a jittered grid given to '
+             'both sides, otherwise the untrained model\'s own (a small cloud)' % (B, m, LAM, args.windows, args.reps),
+             'box pixels with w > 0: %d of %d (%.1f %%) with the model\'s landmarks, %d of %d (%.1f %%) with the grid\'s; rows with a hull '
+             'flag: %d and %d' % (share['own'][0], share['own'][1], 100.0 * share['own'][0] / share['own'][1], share['grid'][0],
+                                  share['grid'][1], 100.0 * share['grid'][0] / share['grid'][1], share['own'][2], share['grid'][2]),
+             '%-13s %10s %22s %12s' % ('call', 'ms', '(min .. max)', 'faces/s')]
+    for k in fns:
+        whole = k[:4] in ('None', 'hull', 'grid') and 'u8' not in k and k != 'hull_fit'
+        lines.append('%-13s %10.3f %22s %12s' % (k, med[k], '(%.3f .. %.3f)' % spread[k], '%.0f' % (B / med[k] * 1e3) if whole else '-'))
+    lines.append('hull - None: %+.3f ms per call at colour 0, %+.3f at colour 1, %+.3f with the grid\'s landmarks; imm_hull_fit %.1f us; '
+                 'imm_morph_hull_u8 against imm_morph_u8: %.1f against %.1f us with the model\'s landmarks, %.1f against %.1f us with the '
+                 'grid\'s' % (med['hull c=0'] - med['None c=0'], med['hull c=1'] - med['None c=1'], med['grid hull'] - med['grid None'],
+                              med['hull_fit'] * 1e3, med['hull_u8'] * 1e3, med['u8'] * 1e3, med['grid hull_u8'] * 1e3, med['grid u8'] * 1e3))
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    if args.out:
+        with open(args.out, 'a') as f:
+            f.write('\n' + text)
+    print(json.dumps(dict({'batch': B, 'anchors': m, 'share_own': share['own'][0] / share['own'][1],
+                           'share_grid': share['grid'][0] / share['grid'][1]}, **{k.replace(' ', '_') + '_ms': v for k, v in med.items()})))
+
+
 if __name__ == '__main__':
     p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     p.add_argument('--batch', type=int, default=64)
@@ -187,5 +258,7 @@ if __name__ == '__main__':
     p.add_argument('--warmup', type=int, default=3)
     p.add_argument('--anchors', type=int, default=2, help='anchor points per side of the box frame')
     p.add_argument('--colour', action='store_true', help='time colour matching: morph at colour = 1 against colour = 0, and the new launches alone')
+    p.add_argument('--mask', action='store_true',
+                   help="time the landmark-hull mask: morph at mask = 'hull' against mask = None at colour 0 and 1, and the new launches alone")
     p.add_argument('--out', type=str, default=OUT)
     main(p.parse_args())
