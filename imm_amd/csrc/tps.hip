@@ -28,7 +28,9 @@ struct TpsGeom {
 __global__ __launch_bounds__(256) void tps_warp_kernel(const float* __restrict__ src, int ld_src, int batch, int h, int w, int c, TpsGeom g,
                                                        const float* __restrict__ basis_t, int m3,
                                                        const float* __restrict__ w_tps, float* __restrict__ dst, int ld_dst,
-                                                       float* __restrict__ dst_c0, float* __restrict__ dst_rest, int ld_rest) {
+                                                       float* __restrict__ dst_c0, float* __restrict__ dst_rest, int ld_rest,
+                                                       int vec_src, int vec_dst) {
+  // vec_src / vec_dst: every pixel of src / dst is a 16-byte aligned group of 4 floats (decided by tps_launch)
   extern __shared__ float2 wsh[];                    // [m3][TPS_TB]: the parameters of this block's samples (zeros beyond nb)
   const int npix = g.gh * g.gw, nout = g.oh * g.ow, nsrc = h * w;
   const int po = blockIdx.x * 256 + threadIdx.x;       // output pixel
@@ -94,7 +96,7 @@ __global__ __launch_bounds__(256) void tps_warp_kernel(const float* __restrict__
         if ((unsigned)xi < (unsigned)pw && (unsigned)yi < (unsigned)ph) {
           const int xs = min(max(xi - g.pad_x, 0), w - 1), ys = min(max(yi - g.pad_y, 0), h - 1);
           const float* sp = sb + ((int64_t)ys * w + xs) * ld_src;
-          if (c == 4 && (ld_src & 3) == 0) {
+          if (vec_src) {
             const float4 v = *(const float4*)sp;
             acc[0] += wgt * v.x; acc[1] += wgt * v.y; acc[2] += wgt * v.z; acc[3] += wgt * v.w;
           } else {
@@ -106,7 +108,7 @@ __global__ __launch_bounds__(256) void tps_warp_kernel(const float* __restrict__
     const int64_t o = (int64_t)b * nout + po;
     if (dst) {
       float* dp = dst + o * ld_dst;
-      if (c == 4 && (ld_dst & 3) == 0) *(float4*)dp = make_float4(acc[0], acc[1], acc[2], acc[3]);
+      if (vec_dst) *(float4*)dp = make_float4(acc[0], acc[1], acc[2], acc[3]);
       else {
 #pragma unroll
         for (int ch = 0; ch < 8; ++ch) if (ch < c) dp[ch] = acc[ch];
@@ -134,8 +136,12 @@ static int tps_launch(const float* src, int ld_src, int batch, int h, int w, int
   IMM_REQUIRE((int64_t)batch * big * (int64_t)(ld_src > ld_dst ? ld_src : ld_dst) < (1LL << 40) && (int64_t)g.gh * g.gw < (1LL << 30), "tps_warp: size");
   const dim3 grid((g.oh * g.ow + 255) / 256, (batch + TPS_TB - 1) / TPS_TB);
   IMM_REQUIRE((size_t)m3 * TPS_TB * sizeof(float2) <= 60 * 1024, "tps_warp: too many control points (%d)", m3 - 3);
+  // the float4 paths: c == 4 at a leading dimension that is a multiple of 4 from a 16-byte aligned base, so that every pixel is
+  // aligned (a 4-channel view at a channel offset of a wider buffer has such an ld but not such a base: it takes the scalar path)
+  const int vec_src = c == 4 && (ld_src & 3) == 0 && ((uintptr_t)src & 15) == 0;
+  const int vec_dst = dst && c == 4 && (ld_dst & 3) == 0 && ((uintptr_t)dst & 15) == 0;
   hipLaunchKernelGGL(tps_warp_kernel, grid, dim3(256), (size_t)m3 * TPS_TB * sizeof(float2), (hipStream_t)stream, src, ld_src, batch, h, w, c, g,
-                     basis_t, m3, w_tps, dst, ld_dst, dst_c0, dst_rest, ld_rest);
+                     basis_t, m3, w_tps, dst, ld_dst, dst_c0, dst_rest, ld_rest, vec_src, vec_dst);
   IMM_CHECK_LAUNCH("imm_tps_warp");
   return 0;
 }

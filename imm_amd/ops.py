@@ -661,31 +661,73 @@ def debug_stamp(slots, index):
     call('imm_debug_stamp', _p(slots), int(index), _s())
 
 
-def tps_warp(src, basis_t, w_tps, dst=None, dst_c0=None, dst_rest=None):
-    """src [B,H,W,C] f32 NHWC; basis_t [M+3, H*W]; w_tps [B, M+3, 2]; outputs as in include/imm_hip.h (imm_tps_warp)."""
+def _check_pixels(name, t, shape, c_min, ld=None):
+    """t: an f32 NHWC tensor or view [shape..., >= c_min channels] whose pixels are dense at one stride: element (b, y, x, ch) at
+    ((b * h + y) * w + x) * ld + ch floats, which is how the kernels address it (ld: the stride the call passes, t.stride(2) when
+    None).  A ValueError that names the tensor otherwise; returns ld."""
+    b, h, w = shape
+    ld = t.stride(2) if ld is None and t.dim() == 4 else ld
+    if (t.dtype != torch.float32 or t.dim() != 4 or t.shape[0] != b or tuple(t.shape[1:3]) != (h, w) or t.shape[3] < c_min or
+            ld < t.shape[3] or any(n > 1 and st != want for n, st, want in zip(t.shape, t.stride(), (h * w * ld, w * ld, ld, 1)))):
+        raise ValueError('%s must be f32 [%d, %d, %d, >= %d] with dense pixels of one stride%s, got %s %s strides %s' % (
+            name, b, h, w, c_min, '' if ld is None else ' %d' % ld, t.dtype, tuple(t.shape), tuple(t.stride())))
+    return ld
+
+
+def _check_tps(src, basis_t, w_tps, grid_pixels):
+    """The operands both TPS warps share -> (b, h, w, c, ld_src, m3)."""
+    if src.dim() != 4:
+        raise ValueError('src must be f32 [B, H, W, C], got %s %s' % (src.dtype, tuple(src.shape)))
     b, h, w, c = src.shape
-    call('imm_tps_warp', _p(src), src.stride(2), b, h, w, c, _p(basis_t), basis_t.shape[0], _p(w_tps), _p(dst),
-         dst.stride(2) if dst is not None else 0, _p(dst_c0), _p(dst_rest), dst_rest.stride(2) if dst_rest is not None else 0, _s())
+    ld_src = _check_pixels('src', src, (b, h, w), c)
+    m3 = w_tps.shape[1] if w_tps.dim() == 3 else -1
+    _check_tensors([('w_tps', w_tps, torch.float32, (b, None, 2)), ('basis_t', basis_t, torch.float32, (m3, grid_pixels))])
+    return b, h, w, c, ld_src, m3
+
+
+def tps_warp(src, basis_t, w_tps, dst=None, dst_c0=None, dst_rest=None):
+    """src [B,H,W,C] f32 NHWC; basis_t [M+3, H*W]; w_tps [B, M+3, 2]; outputs as in include/imm_hip.h (imm_tps_warp): dst [B,H,W,>=C],
+    dst_c0 [B,H,W] (contiguous), dst_rest [B,H,W,>=C-1].  src, dst and dst_rest may be channel views of wider buffers (dense pixels of
+    one stride).  ValueError before the launch for a tensor of another type, shape or layout."""
+    b, h, w, c, ld_src, m3 = _check_tps(src, basis_t, w_tps, src.shape[1] * src.shape[2] if src.dim() == 4 else 0)
+    c_out = c if 1 <= c <= 8 else 0          # c out of range is the library's refusal
+    ld_dst = _check_pixels('dst', dst, (b, h, w), c_out) if dst is not None else 0
+    ld_rest = _check_pixels('dst_rest', dst_rest, (b, h, w), max(c_out - 1, 0)) if dst_rest is not None else 0
+    if dst_c0 is not None:
+        _check_tensors([('dst_c0', dst_c0, torch.float32, (b, h, w))])
+    call('imm_tps_warp', _p(src), ld_src, b, h, w, c, _p(basis_t), m3, _p(w_tps), _p(dst), ld_dst, _p(dst_c0), _p(dst_rest), ld_rest, _s())
 
 
 def tps_warp_pad(src, basis_t, w_tps, pad_yx, grid_hw, crop_yx, dst):
     """TPSRandomSampler(pad=True): src [B,H,W,C] f32 NHWC read as if replicate-padded by pad_yx, warped on a grid_hw grid
-    (basis_t [M+3, gh*gw]), window crop_yx + dst.shape[1:3] written to dst [B,oh,ow,C] (include/imm_hip.h: imm_tps_warp_pad)."""
-    b, h, w, c = src.shape
-    call('imm_tps_warp_pad', _p(src), src.stride(2), b, h, w, c, pad_yx[0], pad_yx[1], grid_hw[0], grid_hw[1], crop_yx[0], crop_yx[1],
-         dst.shape[1], dst.shape[2], _p(basis_t), basis_t.shape[0], _p(w_tps), _p(dst), dst.stride(2), _s())
+    (basis_t [M+3, gh*gw]), window crop_yx + dst.shape[1:3] written to dst [B,oh,ow,>=C] (include/imm_hip.h: imm_tps_warp_pad).
+    ValueError before the launch for a tensor of another type, shape or layout."""
+    b, h, w, c, ld_src, m3 = _check_tps(src, basis_t, w_tps, int(grid_hw[0]) * int(grid_hw[1]))
+    if dst.dim() != 4:
+        raise ValueError('dst must be f32 [B, oh, ow, >= C], got %s %s' % (dst.dtype, tuple(dst.shape)))
+    ld_dst = _check_pixels('dst', dst, (b, dst.shape[1], dst.shape[2]), c if 1 <= c <= 8 else 0)
+    call('imm_tps_warp_pad', _p(src), ld_src, b, h, w, c, pad_yx[0], pad_yx[1], grid_hw[0], grid_hw[1], crop_yx[0], crop_yx[1],
+         dst.shape[1], dst.shape[2], _p(basis_t), m3, _p(w_tps), _p(dst), ld_dst, _s())
 
 
 def resize_crop_u8(src_u8, offsets, hw, c, resize_hw, crop_yx, out_hw, dst, ld_dst=None, boxes=None):
-    """src_u8: flat u8 device buffer of packed HWC images; offsets i64 [B]; hw i32 [B,2]; dst f32 view whose element
-    (b,y,x,0) is dst.data_ptr() + ((b*oh+y)*ow+x)*ld_dst floats (include/imm_hip.h: imm_resize_crop_u8).
+    """src_u8: flat u8 device buffer of packed HWC images; offsets i64 [images]; hw i32 [images, 2]; dst f32 [>= batch, oh, ow, >= c],
+    a tensor or a channel view of a wider buffer, whose element (b,y,x,0) is dst.data_ptr() + ((b*oh+y)*ow+x)*ld_dst floats
+    (include/imm_hip.h: imm_resize_crop_u8; rows of dst beyond batch are left alone).
     boxes: None, or int32 [n, 5] device rows (image, y0, x0, y1, x1) checked on the host beforehand
-    (imm_amd.keypoints.check_boxes): output row b is box b cut from its image, zero-padded, then resized and cropped."""
+    (imm_amd.keypoints.check_boxes): output row b is box b cut from its image, zero-padded, then resized and cropped.
+    ValueError before the launch for a tensor of another type, shape or layout."""
     if boxes is not None and (boxes.dtype != torch.int32 or boxes.dim() != 2 or boxes.shape[1] != 5 or not boxes.is_contiguous()):
         raise ValueError('boxes must be contiguous int32 [n, 5], got %s %s' % (boxes.dtype, tuple(boxes.shape)))
+    _check_tensors([('src_u8', src_u8, torch.uint8, (None,)), ('hw', hw, torch.int32, (None, 2))])
+    _check_tensors([('offsets', offsets, torch.int64, (hw.shape[0],))])
     batch = hw.shape[0] if boxes is None else boxes.shape[0]
+    if dst.dim() != 4 or dst.shape[0] < batch:
+        raise ValueError('dst must be f32 [>= %d, %d, %d, >= c], got %s %s' % (batch, out_hw[0], out_hw[1], dst.dtype, tuple(dst.shape)))
+    # (c out of range is the library's refusal)
+    ld_dst = _check_pixels('dst', dst, (dst.shape[0], int(out_hw[0]), int(out_hw[1])), c if 1 <= c <= 4 else 0, ld_dst)
     call('imm_resize_crop_u8', _p(src_u8), _p(offsets), _p(hw), _p(boxes), batch, c, resize_hw[0], resize_hw[1], crop_yx[0],
-         crop_yx[1], out_hw[0], out_hw[1], _p(dst), dst.stride(2) if ld_dst is None else ld_dst, _s())
+         crop_yx[1], out_hw[0], out_hw[1], _p(dst), ld_dst, _s())
 
 
 MAX_ALIGN_M3 = 67             # basis functions of an alignment map: K <= 64 radial ones + 1, q_y, q_x

@@ -545,7 +545,9 @@ int64_t imm_masked_sse_workspace_bytes(int nfeat);                              
  * zero padding.  src f32 NHWC [B,h,w,ld_src] (first c <= 8 channels), basis_t f32 [m3][h*w] (TPSGridGen's L matrix
  * transposed, m3 = control points + 3), w_tps f32 [B][m3][2] ((x, y) columns).  Outputs (each may be NULL): dst = all c
  * channels [B,h,w,ld_dst]; dst_c0 = channel 0 only [B,h,w] (the mask plane); dst_rest = channels 1..c-1 [B,h,w,ld_rest]
- * (the image, e.g. straight into the training step's input buffer). */
+ * (the image, e.g. straight into the training step's input buffer).  src, dst and dst_rest need only 4-byte alignment, so any
+ * of them may be a channel view of a wider buffer: 16-byte accesses are used for c == 4 at a leading dimension that is a multiple
+ * of 4 only when that tensor's base pointer is 16-byte aligned. */
 int imm_tps_warp(const float* src, int ld_src, int batch, int h, int w, int c, const float* basis_t, int m3,
                  const float* w_tps, float* dst, int ld_dst, float* dst_c0, float* dst_rest, int ld_rest, void* stream);
 /* TPSRandomSampler(pad=True) (tps_sampler.py:24-29,89-92): the source is addressed as if replicate-padded by pad_y rows /
