@@ -169,8 +169,8 @@ struct SplineRow {
   const float* ct;                           // its control points [M][2]
 };
 
-__device__ __forceinline__ SplineRow spline_row(const int32_t* __restrict__ boxes, const float* __restrict__ inv_ramp, int j,
-                                                const float* ct) {
+// row j's box and scales, without its edge ramp (imm_seam_fit blends nothing)
+__device__ __forceinline__ SplineRow spline_box(const int32_t* __restrict__ boxes, int j, const float* ct) {
   SplineRow q;
   q.box = paste_box(boxes, j);
   const int ih = q.box.y1 - q.box.y0, iw = q.box.x1 - q.box.x0;
@@ -178,18 +178,23 @@ __device__ __forceinline__ SplineRow spline_row(const int32_t* __restrict__ boxe
   q.ry = ih > 0 ? (float)(2.0 / (double)ih) : 0.f;
   q.rx = iw > 0 ? (float)(2.0 / (double)iw) : 0.f;
   q.hy = 0.5f * (float)ih; q.hx = 0.5f * (float)iw;
-  q.iry = inv_ramp[2 * j]; q.irx = inv_ramp[2 * j + 1];
+  q.iry = q.irx = 0.f;
   q.ct = ct;
   return q;
 }
 
-// The frame coordinate (qy, qx) of photo pixel (r, c) in row q's box and, for each of NS coefficient sets cf[s] [M + 3][2] on the row's
-// control points, D[s] = sum_j w_j U(|q - ctrl_j|^2) + a_0 + a_1 q_y + a_2 q_x: one basis evaluation (one logf) feeds every set.
+__device__ __forceinline__ SplineRow spline_row(const int32_t* __restrict__ boxes, const float* __restrict__ inv_ramp, int j,
+                                                const float* ct) {
+  SplineRow q = spline_box(boxes, j, ct);
+  q.iry = inv_ramp[2 * j]; q.irx = inv_ramp[2 * j + 1];
+  return q;
+}
+
+// For each of NS coefficient sets cf[s] [M + 3][2] on row q's control points, D[s] = sum_j w_j U(|q - ctrl_j|^2) + a_0 + a_1 q_y + a_2 q_x at
+// the frame coordinate (qy, qx): one basis evaluation (one logf) feeds every set.
 template <int NS>
-__device__ __forceinline__ void spline_displace(const SplineRow& q, const float* const (&cf)[NS], int M, int r, int c, float& qy, float& qx,
-                                                float (&D)[NS][2]) {
+__device__ __forceinline__ void spline_sum(const SplineRow& q, const float* const (&cf)[NS], int M, float qy, float qx, float (&D)[NS][2]) {
 #pragma clang fp contract(off)
-  qy = (float)(r - q.box.y0) * q.ry - 1.f; qx = (float)(c - q.box.x0) * q.rx - 1.f;
 #pragma unroll
   for (int s = 0; s < NS; ++s) D[s][0] = D[s][1] = 0.f;
   for (int j = 0; j < M; ++j) {
@@ -207,4 +212,22 @@ __device__ __forceinline__ void spline_displace(const SplineRow& q, const float*
     D[s][0] = ((D[s][0] + cf[s][2 * M]) + cf[s][2 * M + 2] * qy) + cf[s][2 * M + 4] * qx;
     D[s][1] = ((D[s][1] + cf[s][2 * M + 1]) + cf[s][2 * M + 3] * qy) + cf[s][2 * M + 5] * qx;
   }
+}
+
+// The frame coordinate (qy, qx) of photo pixel (r, c) in row q's box and the displacements D[s] there.
+template <int NS>
+__device__ __forceinline__ void spline_displace(const SplineRow& q, const float* const (&cf)[NS], int M, int r, int c, float& qy, float& qx,
+                                                float (&D)[NS][2]) {
+#pragma clang fp contract(off)
+  qy = (float)(r - q.box.y0) * q.ry - 1.f; qx = (float)(c - q.box.x0) * q.rx - 1.f;
+  spline_sum<NS>(q, cf, M, qy, qx, D);
+}
+
+// The same at a fractional place (fy, fx) of the box, in box-relative pixels (the ring samples of imm_seam_fit).
+template <int NS>
+__device__ __forceinline__ void spline_displace_at(const SplineRow& q, const float* const (&cf)[NS], int M, float fy, float fx, float& qy,
+                                                   float& qx, float (&D)[NS][2]) {
+#pragma clang fp contract(off)
+  qy = fy * q.ry - 1.f; qx = fx * q.rx - 1.f;
+  spline_sum<NS>(q, cf, M, qy, qx, D);
 }

@@ -827,7 +827,7 @@ class LandmarkDetector(BucketRunner):
 
     def morph(self, photos, donors, boxes=None, donor_boxes=None, shape=0.5, texture=None, feather=0.125, anchors=2, lam=0.0,
               landmarks=None, donor_landmarks=None, return_transform=False, colour=0.0, max_gain=2.0, mask=None, grow=1.25,
-              mask_feather=0.1):
+              mask_feather=0.1, seamless=0.0, ring=128):
         """The photos with every box's face blended with a donor's face, in shape and in texture, from the pixels of the two
         photographs: a list of u8 device tensors [h_i, w_i, 3], one per photo, views of one packed buffer (what warp returns); nothing
         is rendered.
@@ -858,17 +858,23 @@ class LandmarkDetector(BucketRunner):
         box's edge ramp, and pixels outside it skip the spline.  Per bucket imm_hull_fit runs behind imm_morph_poses, reading the blended
         landmarks in place, and imm_morph_hull_u8 takes the place of imm_morph_u8 / imm_morph_colour_u8 (include/imm_hull.h states the
         rule).
+        seamless: a number or one per row in [0, 1] (0, the default: today's launches and bytes); any seamless > 0 needs mask='hull'.
+        The donor's pixels keep their detail and take a smooth correction that carries them onto the photo's own values on the outline
+        of the mask: at ring (an int in [16, 256], one for the call) samples of the outline the photo minus the morph's mix, and per
+        pixel the mean of those differences weighed by the pixel's mean-value coordinates, times seamless.  Per bucket imm_seam_fit runs
+        behind the spline fit and imm_morph_seam_u8 takes the place of imm_morph_hull_u8 (include/imm_seam.h states the rule).
         return_transform=True: (photos, a morphing.PhotoMorph: coef_a, coef_b, ctrl, rows, donor_rows, mu, donor_mu, poses, flags,
-        to_source, to_donor, colour_gain, colour_flags, hull_edges, hull_flags, hull_weight)."""
+        to_source, to_donor, colour_gain, colour_flags, hull_edges, hull_flags, hull_weight, seam_ring, seam_diff, seam_flags,
+        seam_field)."""
         from . import morphing as MP
         from . import warping as WP
         from .generation import PasteSetup, box_areas
         K = self.K
         plan = MP.plan_morph(photos, donors, boxes, donor_boxes, shape, texture, feather, K, anchors, lam, landmarks, donor_landmarks, colour,
-                             max_gain, mask, grow, mask_feather)
+                             max_gain, mask, grow, mask_feather, seamless, ring)
         photos, rows, donors, drows, drows_given, shape, texture, feather, m, lam, M, lm_a, lm_b, colour, max_gain = plan
         n = len(rows)
-        matched, hull = bool(colour.any()), plan.mask == 'hull'
+        matched, hull, seam = bool(colour.any()), plan.mask == 'hull', bool(plan.seamless.any())
         lm_b = pose_landmarks(self, ('photos', donors, drows_given) if lm_b is None else ('landmarks', lm_b), n).contiguous()
         if lm_a is not None:
             lm_a = lm_a.to(device=self.dev, dtype=torch.float32).contiguous()
@@ -899,9 +905,15 @@ class LandmarkDetector(BucketRunner):
             if hull:
                 grow_d, soft_d = ops.to_device_pinned(plan.grow, self.dev), ops.to_device_pinned(plan.inv_soft, self.dev)
                 edges, hflags = torch.empty(n, K, 3, device=self.dev), torch.empty(n, dtype=torch.int32, device=self.dev)
+            seam_d = dirs_d = sring = sdiff = sflags = None
+            if seam:
+                seam_d = ops.to_device_pinned(plan.seamless, self.dev)
+                dirs_d = ops.to_device_pinned(MP.seam_dirs(plan.ring), self.dev)
+                sring, sdiff = torch.empty(n, plan.ring, 2, device=self.dev), torch.empty(n, plan.ring, 3, device=self.dev)
+                sflags = torch.empty(n, dtype=torch.int32, device=self.dev)
         with self._forked(*ps.tensors(), don, doffs_d, dhw_d, dboxes_d, shape_d, texture_d, anchors_d, lm_a, lm_b, coef_a, coef_b, ctrl,
                           flags, poses, mu_out, poses2, mu2, coef2, ctrl2, flags2, colour_d, sums2, gain, cflags, grow_d, soft_d, edges,
-                          hflags):
+                          hflags, seam_d, dirs_d, sring, sdiff, sflags):
             if matched:                                                             # once per call, all rows
                 ops.colour_stats_u8(ps.src, ps.offs_d, ps.hw_d, ps.boxes_d, int(ps.area.max()), sums2[0])
                 ops.colour_stats_u8(don, doffs_d, dhw_d, dboxes_d, int(box_areas(drows).max()), sums2[1])
@@ -926,7 +938,15 @@ class LandmarkDetector(BucketRunner):
                 coef_b[part].copy_(c2[1])
                 ctrl[part].copy_(t2[0])
                 torch.bitwise_or(f2[0], f2[1], out=flags[part])
-                if hull:
+                if seam:
+                    ops.seam_fit(p2[0], ps.boxes_d[part], grow_d[part], edges[part], hflags[part], dirs_d, ps.src, ps.offs_d, ps.hw_d, don,
+                                 doffs_d, dhw_d, dboxes_d[part], texture_d[part], t2[0], c2[0], c2[1], gain[part] if matched else None,
+                                 sring[part], sdiff[part], sflags[part])
+                    ops.morph_seam_u8(ps.src, ps.canvas, ps.offs_d, ps.hw_d, don, doffs_d, dhw_d, ps.boxes_d[part], dboxes_d[part],
+                                      ps.links_d[part], ps.ramp_d[part], texture_d[part], t2[0], c2[0], c2[1],
+                                      gain[part] if matched else None, edges[part], soft_d[part], sring[part], sdiff[part], seam_d[part],
+                                      ps.max_pixels(part))
+                elif hull:
                     ops.morph_hull_u8(ps.src, ps.canvas, ps.offs_d, ps.hw_d, don, doffs_d, dhw_d, ps.boxes_d[part], dboxes_d[part],
                                       ps.links_d[part], ps.ramp_d[part], texture_d[part], t2[0], c2[0], c2[1],
                                       gain[part] if matched else None, edges[part], soft_d[part], ps.max_pixels(part))
@@ -945,7 +965,9 @@ class LandmarkDetector(BucketRunner):
         if return_transform:
             return out, MP.PhotoMorph(coef_a, coef_b, ctrl, rows, drows, mu_out if lm_a is None else lm_a, lm_b, poses, flags, shape,
                                       texture, lam, m, colour, max_gain, gain, cflags, plan.mask,
-                                      *((plan.grow, plan.mask_feather, plan.inv_soft, edges, hflags) if hull else ()))
+                                      *((plan.grow, plan.mask_feather, plan.inv_soft, edges, hflags) if hull else ()),
+                                      **(dict(seamless=plan.seamless, ring=plan.ring, seam_ring=sring, seam_diff=sdiff, seam_flags=sflags)
+                                         if seam else {}))
         return out
 
     def colour_stats(self, photos, boxes=None):

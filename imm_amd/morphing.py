@@ -18,6 +18,11 @@ morph(mask='hull') pastes only the face (include/imm_hull.h states the rule): th
 their centroid by `grow` and softened inwards over mask_feather * min(H, W) pixels, multiplies the box's edge ramp, so the donor's
 background, hair and collar stay out of the photo; pixels outside the hull skip the spline altogether.
 
+morph(mask='hull', seamless=...) hides the seam of the mask (include/imm_seam.h states the rule): the colour differences between the
+photo and the morph's mix at `ring` samples of the mask's outline are weighed, per pixel and in closed form, by the pixel's mean-value
+coordinates in that ring, and the share `seamless` of that smooth correction is added to the mix, so that the donor's pixels keep
+their detail and meet the photo's own values on the outline.
+
 Here: the pose blend in the kernel's f32 order, the argument checks of morph() and PhotoMorph, what morph(return_transform=True) returns.
 Nothing here needs a GPU."""
 import numpy as np
@@ -27,6 +32,7 @@ from .warping import _host, check_spline, displacement
 MAX_ROWS = 32767               # rows of one morph() call: imm_warp_fit takes 2 n <= 65535 rows
 MASKS = (None, 'hull')         # morph(mask=...)
 MAX_GROW = 16.0                # grow of morph(mask='hull') lies in (0, 16]
+MIN_RING, MAX_RING = 16, 256   # ring of morph(seamless=...): the samples on the outline of the mask
 COLOUR_MAX_AREA = 1 << 30      # H * W of a box whose colour statistics are taken: imm_colour_stats_u8's integer ellipse test stays in 64 bits
 
 
@@ -94,18 +100,64 @@ def hull_inv_soft(rows, mask_feather):
     return (1.0 / soft).astype(np.float32)
 
 
+def check_ring(ring):
+    """ring of morph(seamless=...): an int in [16, 256] -> int."""
+    if isinstance(ring, bool) or not isinstance(ring, (int, np.integer)) or not MIN_RING <= int(ring) <= MAX_RING:
+        raise ValueError('ring must be an int in [%d, %d] (the samples on the outline of the mask), got %r' % (MIN_RING, MAX_RING, ring))
+    return int(ring)
+
+
+def seam_dirs(ring):
+    """dirs f64 [ring, 2] of imm_seam_fit: (cos, sin) of 2 pi s / ring, the (y, x) direction of sample s, formed here so that no
+    transcendental function runs on the device."""
+    a = 2.0 * np.pi * np.arange(ring, dtype=np.float64) / np.float64(ring)
+    return np.ascontiguousarray(np.stack([np.cos(a), np.sin(a)], axis=1))
+
+
+def seam_field(ring, diff, H, W):
+    """The membrane of imm_morph_seam_u8 over a box of H x W pixels, f32 [H, W, 3], in the rule's f32 order (include/imm_seam.h): ring
+    f32 [B, 2] (box-relative pixels), diff f32 [B, 3].  Per pixel the mean of the diffs weighed by the pixel's mean-value coordinates in
+    the ring; the diff of the lowest sample the pixel lies on; 0 where the sum of the weights is not positive or a sum is not finite."""
+    f32 = np.float32
+    rg, df = np.asarray(ring, dtype=f32), np.asarray(diff, dtype=f32)
+    B = len(rg)
+    rr, cc = np.arange(max(H, 0), dtype=f32)[:, None], np.arange(max(W, 0), dtype=f32)[None, :]
+    with np.errstate(all='ignore'):
+        py, px = (rg[:, 0, None, None] - rr) + f32(0) * cc, (rg[:, 1, None, None] - cc) + f32(0) * rr      # [B, H, W]
+        ln = np.sqrt(py * py + px * px)
+        nxt = np.roll(np.arange(B), -1)
+        cr, dt = py * px[nxt] - px * py[nxt], py * py[nxt] + px * px[nxt]
+        th = cr / (ln * ln[nxt] + dt)
+        R, Ws = np.zeros(py.shape[1:] + (3,), f32), np.zeros(py.shape[1:], f32)
+        for k in range(B):
+            w = (th[k - 1] + th[k]) / ln[k]
+            R = R + w[..., None] * df[k]
+            Ws = Ws + w
+        ok = (Ws > 0) & np.isfinite(Ws) & np.isfinite(R).all(axis=-1)
+        out = np.where(ok[..., None], R / np.where(ok, Ws, f32(1))[..., None], f32(0)).astype(f32)
+    on = ln == 0
+    first = np.argmax(on, axis=0)
+    hit = on.any(axis=0)
+    out[hit] = df[first[hit]]
+    assert out.dtype == f32
+    return out
+
+
 class MorphPlan(tuple):
     """What plan_morph returns: the fifteen values it has always returned, as a tuple, with the mask's as attributes: mask (None or
-    'hull'), grow f32 [n], mask_feather f32 [n] and inv_soft f32 [n] (hull_inv_soft of the rows)."""
+    'hull'), grow f32 [n], mask_feather f32 [n] and inv_soft f32 [n] (hull_inv_soft of the rows), and the membrane's: seamless f32 [n]
+    and ring (an int)."""
 
-    def __new__(cls, values, mask, grow, mask_feather, inv_soft):
+    def __new__(cls, values, mask, grow, mask_feather, inv_soft, seamless=None, ring=128):
         self = super(MorphPlan, cls).__new__(cls, values)
         self.mask, self.grow, self.mask_feather, self.inv_soft = mask, grow, mask_feather, inv_soft
+        self.seamless = np.zeros(len(grow), dtype=np.float32) if seamless is None else seamless
+        self.ring = ring
         return self
 
 
 def plan_morph(photos, donors, boxes, donor_boxes, shape, texture, feather, K, anchors=2, lam=0.0, landmarks=None, donor_landmarks=None,
-               colour=0.0, max_gain=2.0, mask=None, grow=1.25, mask_feather=0.1):
+               colour=0.0, max_gain=2.0, mask=None, grow=1.25, mask_feather=0.1, seamless=0.0, ring=128):
     """morph()'s arguments checked on the host, before anything reaches the device: (photos as decoded u8 arrays, box rows int32 [n, 5],
     donor photos as decoded u8 arrays, donor box rows int32 [n, 5] (ONE donor row is repeated for every face), the donor rows as given
     (what detector.landmarks(donors, .) is asked for), shape f32 [n], texture f32 [n], feather, m, lam, M, landmarks, donor_landmarks,
@@ -115,7 +167,9 @@ def plan_morph(photos, donors, boxes, donor_boxes, shape, texture, feather, K, a
     box per photo).  texture=None: texture = shape.  landmarks / donor_landmarks: None or f32 [n, K, 2] tensors (donor_landmarks may have
     one row when there is one donor row).
     mask: None or 'hull'; grow: a number or one per row in (0, 16]; mask_feather: likewise in [0, 1].  They are checked whatever mask is,
-    and returned as attributes of the result (a MorphPlan)."""
+    and returned as attributes of the result (a MorphPlan).
+    seamless: a number or one per row in [0, 1], the share of the mean-value correction that is added; ring: an int in [16, 256].  Both
+    are checked whatever their value and returned as attributes; any seamless > 0 needs mask='hull'."""
     from .generation import NEEDS_U8, check_feather
     if mask not in MASKS:
         raise ValueError("mask must be None or 'hull', got %r" % (mask,))
@@ -152,8 +206,13 @@ def plan_morph(photos, donors, boxes, donor_boxes, shape, texture, feather, K, a
                                     'the factor by which the landmark hull is grown about its centroid'))
     mask_feather = _share(mask_feather, n, 'mask_feather', ('[0, 1]', lambda v: (v >= 0.0) & (v <= 1.0),
                                                             'the share of the box\'s shorter side over which the mask softens inwards'))
+    seamless = _share(seamless, n, 'seamless', ('[0, 1]', lambda v: (v >= 0.0) & (v <= 1.0),
+                                                'the share of the mean-value correction that is added to the donor\'s pixels'))
+    ring = check_ring(ring)
+    if seamless.any() and mask != 'hull':
+        raise ValueError("seamless > 0 needs mask='hull' (the correction is fitted to the outline of the mask), got mask=%r" % (mask,))
     return MorphPlan((photos, rows, donors, full, drows, shape, texture, feather, m, lam, M, landmarks, donor_landmarks, colour, max_gain),
-                     mask, grow, mask_feather, hull_inv_soft(rows, mask_feather))
+                     mask, grow, mask_feather, hull_inv_soft(rows, mask_feather), seamless, ring)
 
 
 def colour_moments(sums):
@@ -179,11 +238,15 @@ class PhotoMorph(object):
     [n, K, 3] (device: the lines (ny, nx, d) of every row's grown hull in box-relative pixels, imm_hull_fit's output) and hull_flags
     int32 [n] (device; bit 0: an empty box, a pose or a grow that is not finite; bit 1: no hull with an inside; a flagged row wrote
     nothing; OR-ed into nothing else), and hull_weight(i), the weight over row i's box; without it mask, hull_edges and hull_flags are
-    None."""
+    None.  With the membrane (morph(seamless > 0)): seamless f32 [n] (host), ring (the samples per row), seam_ring f32 [n, ring, 2]
+    (device: the samples of the mask's outline in box-relative pixels), seam_diff f32 [n, ring, 3] (device: the photo minus the morph's
+    mix at every sample), seam_flags int32 [n] (device; bit 0: the hull is flagged or the landmarks' centroid is not strictly inside
+    the mask cut with the box; bit 1: a ray without a positive finite length; a flagged row was pasted as the plain hull morph) and
+    seam_field(i), the correction over row i's box; without it all of these are None."""
 
     def __init__(self, coef_a, coef_b, ctrl, rows, donor_rows, mu, donor_mu, poses, flags, shape, texture, lam, anchors, colour=None,
                  max_gain=None, colour_gain=None, colour_flags=None, mask=None, grow=None, mask_feather=None, inv_soft=None,
-                 hull_edges=None, hull_flags=None):
+                 hull_edges=None, hull_flags=None, seamless=None, ring=None, seam_ring=None, seam_diff=None, seam_flags=None):
         self.coef_a, self.coef_b, self.ctrl = coef_a, coef_b, ctrl
         self.rows, self.donor_rows = np.asarray(rows, dtype=np.int32), np.asarray(donor_rows, dtype=np.int32)
         self.mu, self.donor_mu, self.poses, self.flags = mu, donor_mu, poses, flags
@@ -195,6 +258,17 @@ class PhotoMorph(object):
         self.mask = mask
         self.grow, self.mask_feather, self.inv_soft = (None if a is None else np.asarray(a, dtype=np.float32) for a in (grow, mask_feather, inv_soft))
         self.hull_edges, self.hull_flags = hull_edges, hull_flags
+        self.seamless = None if seamless is None else np.asarray(seamless, dtype=np.float32)
+        self.ring = None if ring is None else int(ring)
+        self.seam_ring, self.seam_diff, self.seam_flags = seam_ring, seam_diff, seam_flags
+
+    def seam_field(self, i):
+        """f32 [H_i, W_i, 3]: the correction r at every pixel of row i's box, from the device's seam_ring and seam_diff in the rule's f32
+        order (include/imm_seam.h).  The kernel adds seamless[i] * r to the mix of every pixel whose hull weight is > 0."""
+        if self.seam_ring is None:
+            raise ValueError('seam_field needs a morph with seamless > 0')
+        _img, y0, x0, y1, x1 = (int(v) for v in self.rows[i])
+        return seam_field(_host(self.seam_ring[i]), _host(self.seam_diff[i]), y1 - y0, x1 - x0)
 
     def hull_weight(self, i):
         """f32 [H_i, W_i]: the mask's weight at every pixel of row i's box, from the device's hull_edges in the rule's f32 order

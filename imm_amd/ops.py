@@ -1067,6 +1067,74 @@ def morph_hull_u8(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, 
          None if gain is None else _p(gain), _p(edges), _p(inv_soft), K, M, n, int(max_box_pixels), _s())
 
 
+SEAM_MIN_RING, SEAM_MAX_RING = 16, 256     # ring samples of a row (include/imm_seam.h)
+
+
+def _check_seam(ring, diff, n, name):
+    if ring.dim() != 3 or not SEAM_MIN_RING <= int(ring.shape[1]) <= SEAM_MAX_RING:
+        raise ValueError('%s: ring must be f32 [n, B, 2] with %d <= B <= %d, got %s' % (name, SEAM_MIN_RING, SEAM_MAX_RING, tuple(ring.shape)))
+    B = int(ring.shape[1])
+    _check_tensors([('ring', ring, torch.float32, (n, B, 2)), ('diff', diff, torch.float32, (n, B, 3))])
+    return B
+
+
+def seam_fit(poses, boxes, grow, edges, hull_flags, dirs, src, offsets, hw, donor, donor_offsets, donor_hw, donor_boxes, texture, ctrl,
+             coef_a, coef_b, gain, ring, diff, flags):
+    """The ring of a seamless morph (include/imm_seam.h: imm_seam_fit): per row B samples of the outline of its grown hull cut with its
+    box, ring f32 [n, B, 2] in box-relative pixels, where the rays from the landmarks' centroid along dirs f64 [B, 2] leave it, and at
+    every sample the own photo's value minus the morph's mix there, diff f32 [n, B, 3]; flags i32 [n] (bit 0: the hull is flagged or
+    the centroid is not strictly inside the region; bit 1: a ray without a positive finite length; a flagged row gets diff = 0 and
+    its centroid as every sample).  poses, boxes, grow, edges, hull_flags: hull_fit's inputs and outputs for these rows; the rest as
+    morph_hull_u8 takes it (gain None or f32 [n, 3, 2])."""
+    if poses.dim() != 3 or ctrl.dim() != 3:
+        raise ValueError('poses must be f32 [n, K, 2] and ctrl f32 [n, M, 2], got %s and %s' % (tuple(poses.shape), tuple(ctrl.shape)))
+    n, K, M = int(poses.shape[0]), int(poses.shape[1]), int(ctrl.shape[1])
+    if n < 1 or n > 65535 or not 1 <= K <= WARP_MAX_POINTS or not 3 <= M <= WARP_MAX_POINTS:
+        raise ValueError('seam_fit serves 1..65535 rows of 1 <= K <= %d landmarks and 3 <= M <= %d control points, got n = %d, K = %d, M = %d'
+                         % (WARP_MAX_POINTS, WARP_MAX_POINTS, n, K, M))
+    B = _check_seam(ring, diff, n, 'seam_fit')
+    _check_tensors([('src', src, torch.uint8, (None,)), ('donor', donor, torch.uint8, (None,)), ('hw', hw, torch.int32, (None, 2)),
+                    ('donor_hw', donor_hw, torch.int32, (None, 2))])
+    if hw.shape[0] < 1 or donor_hw.shape[0] < 1:
+        raise ValueError('hw and donor_hw must hold at least one image, got %s and %s' % (tuple(hw.shape), tuple(donor_hw.shape)))
+    _check_tensors([('poses', poses, torch.float32, (n, K, 2)), ('boxes', boxes, torch.int32, (n, 5)), ('grow', grow, torch.float32, (n,)),
+                    ('edges', edges, torch.float32, (n, K, 3)), ('hull_flags', hull_flags, torch.int32, (n,)),
+                    ('dirs', dirs, torch.float64, (B, 2)), ('offsets', offsets, torch.int64, (hw.shape[0],)),
+                    ('donor_offsets', donor_offsets, torch.int64, (donor_hw.shape[0],)), ('donor_boxes', donor_boxes, torch.int32, (n, 5)),
+                    ('texture', texture, torch.float32, (n,)), ('ctrl', ctrl, torch.float32, (n, M, 2)),
+                    ('coef_a', coef_a, torch.float32, (n, M + 3, 2)), ('coef_b', coef_b, torch.float32, (n, M + 3, 2)),
+                    ('flags', flags, torch.int32, (n,))])
+    if gain is not None:
+        _check_tensors([('gain', gain, torch.float32, (n, 3, 2))])
+    call('imm_seam_fit', _p(poses), _p(boxes), _p(grow), _p(edges), _p(hull_flags), _p(dirs), _p(src), _p(offsets), _p(hw), int(hw.shape[0]),
+         _p(donor), _p(donor_offsets), _p(donor_hw), int(donor_hw.shape[0]), _p(donor_boxes), _p(texture), _p(ctrl), _p(coef_a), _p(coef_b),
+         None if gain is None else _p(gain), K, M, B, n, _p(ring), _p(diff), _p(flags), _s())
+
+
+def morph_seam_u8(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b,
+                  gain, edges, inv_soft, ring, diff, seamless, max_box_pixels):
+    """morph_hull_u8 with the mean-value membrane (include/imm_seam.h: imm_morph_seam_u8): ring f32 [n, B, 2] and diff f32 [n, B, 3]
+    (seam_fit's output for these rows) give every pixel with a weight the correction r, the mean of the row's diffs weighed by the
+    pixel's mean-value coordinates in the ring, and the mix takes seamless[b] * r (seamless f32 [n]) in front of the blend.  Every other
+    argument as morph_hull_u8 takes it."""
+    n, M = _check_morph(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a,
+                        coef_b, max_box_pixels, 'morph_seam_u8')
+    if edges.dim() != 3 or not 1 <= int(edges.shape[1]) <= WARP_MAX_POINTS:
+        raise ValueError('edges must be f32 [n, K, 3] with 1 <= K <= %d, got %s' % (WARP_MAX_POINTS, tuple(edges.shape)))
+    K = int(edges.shape[1])
+    B = _check_seam(ring, diff, n, 'morph_seam_u8')
+    _check_tensors([('edges', edges, torch.float32, (n, K, 3)), ('inv_soft', inv_soft, torch.float32, (n,)),
+                    ('seamless', seamless, torch.float32, (n,))])
+    if gain is not None:
+        _check_tensors([('gain', gain, torch.float32, (n, 3, 2))])
+    for name, t in (('gain', gain), ('edges', edges), ('inv_soft', inv_soft), ('ring', ring), ('diff', diff), ('seamless', seamless)):
+        if t is not None and _overlap(t, dst):
+            raise ValueError('%s overlaps dst' % name)
+    call('imm_morph_seam_u8', _p(src), _p(dst), _p(offsets), _p(hw), int(hw.shape[0]), _p(donor), _p(donor_offsets), _p(donor_hw),
+         int(donor_hw.shape[0]), _p(boxes), _p(donor_boxes), _p(links), _p(inv_ramp), _p(texture), _p(ctrl), _p(coef_a), _p(coef_b),
+         None if gain is None else _p(gain), _p(edges), _p(inv_soft), _p(ring), _p(diff), _p(seamless), K, M, B, n, int(max_box_pixels), _s())
+
+
 def masked_sse_pool(a, b, batch, s, c, mask, S, partial, pool_a, pool_b):
     call('imm_masked_sse_pool', _p(a), _p(b), dtype_enum(a.dtype), batch, s, c, _p(mask), S, _p(partial), _p(pool_a), _p(pool_b), _s())
 

@@ -23,7 +23,11 @@ colour 0 and 1, alternated window by window after warm-up, once with the model's
 untrained model's landmarks sit in a small cloud, so its hull is small) and once with landmarks on a jittered grid over [-0.8, 0.8]^2
 given to both sides (a hull of the size a face's is), and the two new launches alone on one call's buffers (imm_hull_fit, and
 imm_morph_hull_u8 next to imm_morph_u8), with the share of the box pixels whose weight is > 0; the table is APPENDED as well.
-Usage: python tools/bench_morph.py [--batch 64] [--windows 7] [--reps 10] [--anchors 2] [--colour | --mask]"""
+With --seamless the same photos, sizes and protocol time the mean-value membrane: detector.morph at mask = 'hull' with seamless = 1
+against seamless = 0, alternated window by window after warm-up, with landmarks on the jittered grid given to both sides (a hull of the
+size a face's is), at ring = 128 and ring = 16, and the two new launches alone on one call's buffers (imm_seam_fit, and imm_morph_seam_u8
+next to imm_morph_hull_u8), with the ratios; the table is APPENDED as well.
+Usage: python tools/bench_morph.py [--batch 64] [--windows 7] [--reps 10] [--anchors 2] [--colour | --mask | --seamless]"""
 import argparse
 import json
 import os
@@ -101,6 +105,14 @@ def main(args):
             src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, boxes_d, dboxes_d, links_d, ramp_d, texture_d, q.ctrl, q.coef_a, q.coef_b, None,
             edges, soft, area), lambda q: ops.morph_u8(src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, boxes_d, dboxes_d, links_d, ramp_d,
                                                        texture_d, q.ctrl, q.coef_a, q.coef_b, area), boxes_d)
+    if args.seamless:
+        return seam_leg(args, det, photos, donors, boxes, dboxes, props, mid, lambda q, soft: ops.morph_hull_u8(
+            src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, boxes_d, dboxes_d, links_d, ramp_d, texture_d, q.ctrl, q.coef_a, q.coef_b, None,
+            q.hull_edges, soft, area), lambda q, soft, amount: ops.morph_seam_u8(
+            src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, boxes_d, dboxes_d, links_d, ramp_d, texture_d, q.ctrl, q.coef_a, q.coef_b, None,
+            q.hull_edges, soft, q.seam_ring, q.seam_diff, amount, area), lambda q, grow, dirs, ring, diff, flags: ops.seam_fit(
+            q.poses, boxes_d, grow, q.hull_edges, q.hull_flags, dirs, src, offs_d, hw_d, don, doffs_d, dhw_d, dboxes_d, texture_d, q.ctrl,
+            q.coef_a, q.coef_b, None, ring, diff, flags))
     fns = {'morph': lambda: det.morph(photos, donors, boxes, dboxes, shape=0.5, anchors=m, lam=LAM), 'dissolve': dissolve,
            'pack': lambda: (pack_u8(photos, 'cuda:0', rows)[0].clone(), pack_u8(donors, 'cuda:0', drows)),
            'poses': lambda: ops.morph_poses(pm.mu, pm.donor_mu, shape_d, poses2, mu2),
@@ -250,6 +262,65 @@ def mask_leg(args, det, photos, donors, boxes, dboxes, props, grid, poses2, hull
                            'share_grid': share['grid'][0] / share['grid'][1]}, **{k.replace(' ', '_') + '_ms': v for k, v in med.items()})))
 
 
+def seam_leg(args, det, photos, donors, boxes, dboxes, props, grid, hull_u8, seam_u8, seam_fit):
+    """--seamless: morph at seamless = 1 against seamless = 0 under the hull mask on the same photos in the same run, and the new
+    launches alone."""
+    import torch
+    from bench_detect import timed_ms
+    from bench_warp import grid_poses
+    from imm_amd import morphing as MP
+    from imm_amd import ops
+    B, m = args.batch, args.anchors
+    given = dict(shape=0.5, anchors=m, lam=LAM, landmarks=grid, donor_landmarks=torch.from_numpy(grid_poses(B, seed=2)).cuda(), mask='hull')
+    runs = {ring: det.morph(photos, donors, boxes, dboxes, seamless=1.0, ring=ring, return_transform=True, **given)[1] for ring in (128, 16)}
+    torch.cuda.synchronize()
+    q = runs[128]
+    w = [q.hull_weight(i) for i in range(B)]
+    share = (sum(int((x > 0).sum()) for x in w), sum(x.size for x in w))
+    flagged = {ring: int((r.seam_flags != 0).sum()) for ring, r in runs.items()}
+    grow_d, soft_d = ops.to_device_pinned(q.grow, 'cuda:0'), ops.to_device_pinned(q.inv_soft, 'cuda:0')
+    amount = ops.to_device_pinned(np.ones(B, np.float32), 'cuda:0')
+    fns = {'hull': lambda: det.morph(photos, donors, boxes, dboxes, **given), 'hull_u8': lambda: hull_u8(q, soft_d)}
+    for ring, r in runs.items():
+        dirs = ops.to_device_pinned(MP.seam_dirs(ring), 'cuda:0')
+        out = torch.empty(B, ring, 2, device='cuda:0'), torch.empty(B, ring, 3, device='cuda:0'), torch.empty(B, dtype=torch.int32, device='cuda:0')
+        fns['seamless %d' % ring] = lambda ring=ring: det.morph(photos, donors, boxes, dboxes, seamless=1.0, ring=ring, **given)
+        fns['seam_fit %d' % ring] = lambda r=r, dirs=dirs, out=out: seam_fit(r, grow_d, dirs, *out)
+        fns['seam_u8 %d' % ring] = lambda r=r: seam_u8(r, soft_d, amount)
+    ms = {k: [] for k in fns}
+    for k, fn in fns.items():
+        timed_ms(fn, 2, 1, args.warmup)
+    for _ in range(args.windows):                                   # alternated: one window of each, again and again
+        for k, fn in fns.items():
+            ms[k].append(timed_ms(fn, args.reps, 1, 0))
+    torch.cuda.synchronize()
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    spread = {k: (float(np.min(v)), float(np.max(v))) for k, v in ms.items()}
+    lines = ['==== mean-value membrane (--seamless) ====',
+             'device: %s (%s, %d CUs)' % (props.name, props.gcnArchName, props.multi_processor_count),
+             'the photos, donor photos, boxes and protocol of the tables above (B = %d, anchors = %d, lam = %g, bf16); ms per call: median '
+             '(min .. max) of %d alternated windows x %d calls; mask = hull, grow = 1.25, mask_feather = 0.1, landmarks on a jittered grid '
+             'given to both sides' % (B, m, LAM, args.windows, args.reps),
+             'box pixels with w > 0: %d of %d (%.1f %%); rows with a seam flag: %d at ring = 128, %d at ring = 16' % (
+                 share[0], share[1], 100.0 * share[0] / share[1], flagged[128], flagged[16]),
+             '%-13s %10s %22s %12s' % ('call', 'ms', '(min .. max)', 'faces/s')]
+    for k in fns:
+        whole = k == 'hull' or k.startswith('seamless')
+        lines.append('%-13s %10.3f %22s %12s' % (k, med[k], '(%.3f .. %.3f)' % spread[k], '%.0f' % (B / med[k] * 1e3) if whole else '-'))
+    for ring in runs:
+        lines.append('ring = %d: seamless / hull = %.2f per call (%.3f against %.3f ms); imm_morph_seam_u8 / imm_morph_hull_u8 = %.2f (%.1f '
+                     'against %.1f us, %.1f ps per pixel with w > 0 and ring sample); imm_seam_fit %.1f us' % (
+                         ring, med['seamless %d' % ring] / med['hull'], med['seamless %d' % ring], med['hull'],
+                         med['seam_u8 %d' % ring] / med['hull_u8'], med['seam_u8 %d' % ring] * 1e3, med['hull_u8'] * 1e3,
+                         (med['seam_u8 %d' % ring] - med['hull_u8']) * 1e9 / (share[0] * ring), med['seam_fit %d' % ring] * 1e3))
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    if args.out:
+        with open(args.out, 'a') as f:
+            f.write('\n' + text)
+    print(json.dumps(dict({'batch': B, 'anchors': m, 'share': share[0] / share[1]}, **{k.replace(' ', '_') + '_ms': v for k, v in med.items()})))
+
+
 if __name__ == '__main__':
     p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     p.add_argument('--batch', type=int, default=64)
@@ -260,5 +331,7 @@ if __name__ == '__main__':
     p.add_argument('--colour', action='store_true', help='time colour matching: morph at colour = 1 against colour = 0, and the new launches alone')
     p.add_argument('--mask', action='store_true',
                    help="time the landmark-hull mask: morph at mask = 'hull' against mask = None at colour 0 and 1, and the new launches alone")
+    p.add_argument('--seamless', action='store_true',
+                   help="time the mean-value membrane: morph at seamless = 1 against seamless = 0 under the hull mask, and the new launches alone")
     p.add_argument('--out', type=str, default=OUT)
     main(p.parse_args())
