@@ -356,6 +356,26 @@ def pose_landmarks(detector, pose, n, from_photos=None):
     return lm.expand(n, detector.K, 2) if lm.shape[0] != n else lm
 
 
+class _Held(list):
+    """The device tensors a call allocates on the caller's stream and uses on the object's: the record list of BucketRunner._forked,
+    complete because every such tensor is made through it.  keep(tensors...) takes tensors made elsewhere (pack_u8's, a PasteSetup's; None
+    is skipped), up(array) uploads one (ops.to_device_pinned), empty(*shape) allocates one; each returns what it holds."""
+
+    def __init__(self, device):
+        super(_Held, self).__init__()
+        self.device = device
+
+    def keep(self, *tensors):
+        self.extend(t for t in tensors if t is not None)
+        return tensors[0] if len(tensors) == 1 else tensors
+
+    def up(self, array):
+        return self.keep(ops.to_device_pinned(array, self.device))
+
+    def empty(self, *shape, **kw):
+        return self.keep(torch.empty(*shape, device=self.device, **kw))
+
+
 class _Launch(object):
     __slots__ = ('tag', 'name', 'family', 'fn')
 
@@ -801,16 +821,17 @@ class LandmarkDetector(BucketRunner):
         K = self.K
         photos, rows, pose, feather, m, lam, strength, M = WP.plan_warp(photos, poses, boxes, pose_boxes, feather, K, anchors, lam, strength)
         n = len(rows)
-        lm = pose_landmarks(self, pose, n).contiguous()
+        held = _Held(self.dev)
+        lm = held.keep(pose_landmarks(self, pose, n).contiguous())
         buckets = plan_buckets(n, self.max_batch)
         ps = PasteSetup(photos, rows, buckets, feather, self.dev)                   # all photos, once per call
+        held.keep(*ps.tensors())
         with torch.cuda.device(self.dev):
-            anchors_d = ops.to_device_pinned(WP.warp_anchors(m).astype(np.float32), self.dev) if m else None
-            coef = torch.empty(n, M + 3, 2, device=self.dev)
-            ctrl = torch.empty(n, M, 2, device=self.dev)
-            flags = torch.empty(n, dtype=torch.int32, device=self.dev)
-            mu_out = torch.empty(n, K, 2, device=self.dev) if return_transform else None
-        with self._forked(*ps.tensors(), anchors_d, lm, coef, ctrl, flags, mu_out):
+            anchors_d = held.up(WP.warp_anchors(m).astype(np.float32)) if m else None
+            coef, ctrl = held.empty(n, M + 3, 2), held.empty(n, M, 2)
+            flags = held.empty(n, dtype=torch.int32)
+            mu_out = held.empty(n, K, 2) if return_transform else None
+        with self._forked(*held):
             for start, count, bucket in buckets:
                 part = slice(start, start + count)
                 self._stage(count, bucket, packed=ps.packed(part))
@@ -872,54 +893,47 @@ class LandmarkDetector(BucketRunner):
         K = self.K
         plan = MP.plan_morph(photos, donors, boxes, donor_boxes, shape, texture, feather, K, anchors, lam, landmarks, donor_landmarks, colour,
                              max_gain, mask, grow, mask_feather, seamless, ring)
-        photos, rows, donors, drows, drows_given, shape, texture, feather, m, lam, M, lm_a, lm_b, colour, max_gain = plan
+        photos, rows, drows, m, lam, M = plan.photos, plan.rows, plan.donor_rows, plan.anchors, plan.lam, plan.M
         n = len(rows)
-        matched, hull, seam = bool(colour.any()), plan.mask == 'hull', bool(plan.seamless.any())
-        lm_b = pose_landmarks(self, ('photos', donors, drows_given) if lm_b is None else ('landmarks', lm_b), n).contiguous()
-        if lm_a is not None:
-            lm_a = lm_a.to(device=self.dev, dtype=torch.float32).contiguous()
+        matched, hull, seam = bool(plan.colour.any()), plan.mask == 'hull', bool(plan.seamless.any())
+        held = _Held(self.dev)                                                      # what _forked records: every tensor made below
+        lm_b = held.keep(pose_landmarks(self, ('photos', plan.donors, plan.donor_rows_given) if plan.donor_landmarks is None else
+                                        ('landmarks', plan.donor_landmarks), n).contiguous())
+        lm_a = None if plan.landmarks is None else held.keep(plan.landmarks.to(device=self.dev, dtype=torch.float32).contiguous())
         buckets = plan_buckets(n, self.max_batch)
-        ps = PasteSetup(photos, rows, buckets, feather, self.dev)                   # all photos, once per call
+        ps = PasteSetup(photos, rows, buckets, plan.feather, self.dev)              # all photos, once per call
+        held.keep(*ps.tensors())
+        extra = {}                                                                  # morph_paste's optional tensors, one row each
         with torch.cuda.device(self.dev):
-            don, doffs_d, dhw_d, dboxes_d = pack_u8(donors, self.dev, drows)        # all donor photos, once per call
-            shape_d = ops.to_device_pinned(shape, self.dev)
-            texture_d = ops.to_device_pinned(texture, self.dev)
-            anchors_d = ops.to_device_pinned(WP.warp_anchors(m).astype(np.float32), self.dev) if m else None
-            coef_a = torch.empty(n, M + 3, 2, device=self.dev)
-            coef_b = torch.empty(n, M + 3, 2, device=self.dev)
-            ctrl = torch.empty(n, M, 2, device=self.dev)
-            flags = torch.empty(n, dtype=torch.int32, device=self.dev)
-            poses = torch.empty(n, K, 2, device=self.dev) if return_transform else None
-            mu_out = torch.empty(n, K, 2, device=self.dev) if return_transform and lm_a is None else None
+            don, doffs_d, dhw_d, dboxes_d = held.keep(*pack_u8(plan.donors, self.dev, drows))      # all donor photos, once per call
+            shape_d, texture_d = held.up(plan.shape), held.up(plan.texture)
+            anchors_d = held.up(WP.warp_anchors(m).astype(np.float32)) if m else None
+            coef_a, coef_b, ctrl = held.empty(n, M + 3, 2), held.empty(n, M + 3, 2), held.empty(n, M, 2)
+            flags = held.empty(n, dtype=torch.int32)
+            poses = held.empty(n, K, 2) if return_transform else None
+            mu_out = held.empty(n, K, 2) if return_transform and lm_a is None else None
             # one bucket's scratch: the inputs and outputs of the fit over 2 * count rows
             B = max(count for _s, count, _b in buckets)
-            poses2, mu2 = torch.empty(2 * B * K * 2, device=self.dev), torch.empty(2 * B * K * 2, device=self.dev)
-            coef2, ctrl2 = torch.empty(2 * B * (M + 3) * 2, device=self.dev), torch.empty(2 * B * M * 2, device=self.dev)
-            flags2 = torch.empty(2 * B, dtype=torch.int32, device=self.dev)
-            gain = cflags = colour_d = sums2 = None
+            poses2, mu2 = held.empty(2 * B * K * 2), held.empty(2 * B * K * 2)
+            coef2, ctrl2 = held.empty(2 * B * (M + 3) * 2), held.empty(2 * B * M * 2)
+            flags2 = held.empty(2 * B, dtype=torch.int32)
+            cflags, hflags, sflags = (held.empty(n, dtype=torch.int32) if on else None for on in (matched, hull, seam))
             if matched:
-                colour_d = ops.to_device_pinned(colour, self.dev)
-                sums2 = torch.empty(2, n, 7, dtype=torch.int64, device=self.dev)
-                gain, cflags = torch.empty(n, 3, 2, device=self.dev), torch.empty(n, dtype=torch.int32, device=self.dev)
-            grow_d = soft_d = edges = hflags = None
+                colour_d, sums2 = held.up(plan.colour), held.empty(2, n, 7, dtype=torch.int64)
+                extra['gain'] = held.empty(n, 3, 2)
             if hull:
-                grow_d, soft_d = ops.to_device_pinned(plan.grow, self.dev), ops.to_device_pinned(plan.inv_soft, self.dev)
-                edges, hflags = torch.empty(n, K, 3, device=self.dev), torch.empty(n, dtype=torch.int32, device=self.dev)
-            seam_d = dirs_d = sring = sdiff = sflags = None
+                grow_d, extra['inv_soft'], extra['edges'] = held.up(plan.grow), held.up(plan.inv_soft), held.empty(n, K, 3)
             if seam:
-                seam_d = ops.to_device_pinned(plan.seamless, self.dev)
-                dirs_d = ops.to_device_pinned(MP.seam_dirs(plan.ring), self.dev)
-                sring, sdiff = torch.empty(n, plan.ring, 2, device=self.dev), torch.empty(n, plan.ring, 3, device=self.dev)
-                sflags = torch.empty(n, dtype=torch.int32, device=self.dev)
-        with self._forked(*ps.tensors(), don, doffs_d, dhw_d, dboxes_d, shape_d, texture_d, anchors_d, lm_a, lm_b, coef_a, coef_b, ctrl,
-                          flags, poses, mu_out, poses2, mu2, coef2, ctrl2, flags2, colour_d, sums2, gain, cflags, grow_d, soft_d, edges,
-                          hflags, seam_d, dirs_d, sring, sdiff, sflags):
+                extra['seamless'], dirs_d = held.up(plan.seamless), held.up(MP.seam_dirs(plan.ring))
+                extra['ring'], extra['diff'] = held.empty(n, plan.ring, 2), held.empty(n, plan.ring, 3)
+        with self._forked(*held):
             if matched:                                                             # once per call, all rows
                 ops.colour_stats_u8(ps.src, ps.offs_d, ps.hw_d, ps.boxes_d, int(ps.area.max()), sums2[0])
                 ops.colour_stats_u8(don, doffs_d, dhw_d, dboxes_d, int(box_areas(drows).max()), sums2[1])
-                ops.colour_gain(sums2[0], sums2[1], colour_d, max_gain, gain, cflags)
+                ops.colour_gain(sums2[0], sums2[1], colour_d, plan.max_gain, extra['gain'], cflags)
             for start, count, bucket in buckets:
                 part = slice(start, start + count)
+                opt = {k: t[part] for k, t in extra.items()}
                 if lm_a is None:
                     self._stage(count, bucket, packed=ps.packed(part))
                     self._run(bucket)
@@ -931,7 +945,7 @@ class LandmarkDetector(BucketRunner):
                 f2 = flags2[:2 * count].view(2, count)
                 ops.morph_poses(own, lm_b[part], shape_d[part], p2, m2)
                 if hull:                                                            # the blended landmarks, read in place
-                    ops.hull_fit(p2[0], ps.boxes_d[part], grow_d[part], edges[part], hflags[part])
+                    ops.hull_fit(p2[0], ps.boxes_d[part], grow_d[part], opt['edges'], hflags[part])
                 ops.warp_fit(p2.view(2 * count, K, 2), m2.view(2 * count, K, 2), anchors_d, 1.0, lam, c2.view(2 * count, M + 3, 2),
                              t2.view(2 * count, M, 2), f2.view(2 * count))
                 coef_a[part].copy_(c2[0])
@@ -939,35 +953,24 @@ class LandmarkDetector(BucketRunner):
                 ctrl[part].copy_(t2[0])
                 torch.bitwise_or(f2[0], f2[1], out=flags[part])
                 if seam:
-                    ops.seam_fit(p2[0], ps.boxes_d[part], grow_d[part], edges[part], hflags[part], dirs_d, ps.src, ps.offs_d, ps.hw_d, don,
-                                 doffs_d, dhw_d, dboxes_d[part], texture_d[part], t2[0], c2[0], c2[1], gain[part] if matched else None,
-                                 sring[part], sdiff[part], sflags[part])
-                    ops.morph_seam_u8(ps.src, ps.canvas, ps.offs_d, ps.hw_d, don, doffs_d, dhw_d, ps.boxes_d[part], dboxes_d[part],
-                                      ps.links_d[part], ps.ramp_d[part], texture_d[part], t2[0], c2[0], c2[1],
-                                      gain[part] if matched else None, edges[part], soft_d[part], sring[part], sdiff[part], seam_d[part],
-                                      ps.max_pixels(part))
-                elif hull:
-                    ops.morph_hull_u8(ps.src, ps.canvas, ps.offs_d, ps.hw_d, don, doffs_d, dhw_d, ps.boxes_d[part], dboxes_d[part],
-                                      ps.links_d[part], ps.ramp_d[part], texture_d[part], t2[0], c2[0], c2[1],
-                                      gain[part] if matched else None, edges[part], soft_d[part], ps.max_pixels(part))
-                elif matched:
-                    ops.morph_colour_u8(ps.src, ps.canvas, ps.offs_d, ps.hw_d, don, doffs_d, dhw_d, ps.boxes_d[part], dboxes_d[part],
-                                        ps.links_d[part], ps.ramp_d[part], texture_d[part], t2[0], c2[0], c2[1], gain[part],
-                                        ps.max_pixels(part))
-                else:
-                    ops.morph_u8(ps.src, ps.canvas, ps.offs_d, ps.hw_d, don, doffs_d, dhw_d, ps.boxes_d[part], dboxes_d[part],
-                                 ps.links_d[part], ps.ramp_d[part], texture_d[part], t2[0], c2[0], c2[1], ps.max_pixels(part))
+                    ops.seam_fit(p2[0], ps.boxes_d[part], grow_d[part], opt['edges'], hflags[part], dirs_d, ps.src, ps.offs_d, ps.hw_d, don,
+                                 doffs_d, dhw_d, dboxes_d[part], texture_d[part], t2[0], c2[0], c2[1], opt.get('gain'), opt['ring'],
+                                 opt['diff'], sflags[part])
+                ops.morph_paste(ps.src, ps.canvas, ps.offs_d, ps.hw_d, don, doffs_d, dhw_d, ps.boxes_d[part], dboxes_d[part], ps.links_d[part],
+                                ps.ramp_d[part], texture_d[part], t2[0], c2[0], c2[1], ps.max_pixels(part), **opt)
                 if return_transform:
                     poses[part].copy_(p2[0])
                     if mu_out is not None:
                         mu_out[part].copy_(own)
         out = unpack_u8(ps.canvas, photos)
         if return_transform:
-            return out, MP.PhotoMorph(coef_a, coef_b, ctrl, rows, drows, mu_out if lm_a is None else lm_a, lm_b, poses, flags, shape,
-                                      texture, lam, m, colour, max_gain, gain, cflags, plan.mask,
-                                      *((plan.grow, plan.mask_feather, plan.inv_soft, edges, hflags) if hull else ()),
-                                      **(dict(seamless=plan.seamless, ring=plan.ring, seam_ring=sring, seam_diff=sdiff, seam_flags=sflags)
-                                         if seam else {}))
+            return out, MP.PhotoMorph(
+                coef_a=coef_a, coef_b=coef_b, ctrl=ctrl, rows=rows, donor_rows=drows, mu=mu_out if lm_a is None else lm_a, donor_mu=lm_b,
+                poses=poses, flags=flags, shape=plan.shape, texture=plan.texture, lam=lam, anchors=m, colour=plan.colour,
+                max_gain=plan.max_gain, colour_gain=extra.get('gain'), colour_flags=cflags, mask=plan.mask,
+                grow=plan.grow if hull else None, mask_feather=plan.mask_feather if hull else None, inv_soft=plan.inv_soft if hull else None,
+                hull_edges=extra.get('edges'), hull_flags=hflags, seamless=plan.seamless if seam else None,
+                ring=plan.ring if seam else None, seam_ring=extra.get('ring'), seam_diff=extra.get('diff'), seam_flags=sflags)
         return out
 
     def colour_stats(self, photos, boxes=None):

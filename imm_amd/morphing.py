@@ -143,17 +143,18 @@ def seam_field(ring, diff, H, W):
     return out
 
 
-class MorphPlan(tuple):
-    """What plan_morph returns: the fifteen values it has always returned, as a tuple, with the mask's as attributes: mask (None or
-    'hull'), grow f32 [n], mask_feather f32 [n] and inv_soft f32 [n] (hull_inv_soft of the rows), and the membrane's: seamless f32 [n]
-    and ring (an int)."""
+class MorphPlan(object):
+    """What plan_morph returns, by name: photos and donors (decoded u8 arrays), rows and donor_rows int32 [n, 5] (ONE donor row is repeated
+    for every face), donor_rows_given (the donor rows as given: what detector.landmarks(donors, .) is asked for), shape and texture f32
+    [n], feather, anchors (per side), lam, M (control points), landmarks and donor_landmarks (None or f32 tensors), colour f32 [n] and
+    max_gain; the mask's: mask (None or 'hull'), grow f32 [n], mask_feather f32 [n] and inv_soft f32 [n] (hull_inv_soft of the rows); and
+    the membrane's: seamless f32 [n] and ring (an int)."""
+    FIELDS = ('photos', 'rows', 'donors', 'donor_rows', 'donor_rows_given', 'shape', 'texture', 'feather', 'anchors', 'lam', 'M', 'landmarks',
+              'donor_landmarks', 'colour', 'max_gain', 'mask', 'grow', 'mask_feather', 'inv_soft', 'seamless', 'ring')
 
-    def __new__(cls, values, mask, grow, mask_feather, inv_soft, seamless=None, ring=128):
-        self = super(MorphPlan, cls).__new__(cls, values)
-        self.mask, self.grow, self.mask_feather, self.inv_soft = mask, grow, mask_feather, inv_soft
-        self.seamless = np.zeros(len(grow), dtype=np.float32) if seamless is None else seamless
-        self.ring = ring
-        return self
+    def __init__(self, **fields):
+        assert set(fields) == set(self.FIELDS)
+        self.__dict__.update(fields)
 
 
 def plan_morph(photos, donors, boxes, donor_boxes, shape, texture, feather, K, anchors=2, lam=0.0, landmarks=None, donor_landmarks=None,
@@ -211,8 +212,10 @@ def plan_morph(photos, donors, boxes, donor_boxes, shape, texture, feather, K, a
     ring = check_ring(ring)
     if seamless.any() and mask != 'hull':
         raise ValueError("seamless > 0 needs mask='hull' (the correction is fitted to the outline of the mask), got mask=%r" % (mask,))
-    return MorphPlan((photos, rows, donors, full, drows, shape, texture, feather, m, lam, M, landmarks, donor_landmarks, colour, max_gain),
-                     mask, grow, mask_feather, hull_inv_soft(rows, mask_feather), seamless, ring)
+    return MorphPlan(photos=photos, rows=rows, donors=donors, donor_rows=full, donor_rows_given=drows, shape=shape, texture=texture,
+                     feather=feather, anchors=m, lam=lam, M=M, landmarks=landmarks, donor_landmarks=donor_landmarks, colour=colour,
+                     max_gain=max_gain, mask=mask, grow=grow, mask_feather=mask_feather, inv_soft=hull_inv_soft(rows, mask_feather),
+                     seamless=seamless, ring=ring)
 
 
 def colour_moments(sums):

@@ -934,30 +934,79 @@ def _overlap(a, b):
     return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
 
 
-def _check_morph(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b,
-                 max_box_pixels, name):
-    """The argument checks morph_u8 and morph_colour_u8 share -> (n, M)."""
+def _check_photos(src, offsets, hw, donor, donor_offsets, donor_hw):
+    """The packed photo and donor buffers as morph_paste and seam_fit read them: src and donor u8 [bytes], hw and donor_hw i32 [images, 2]
+    of at least one image each, offsets and donor_offsets i64, one per image."""
+    _check_tensors([('src', src, torch.uint8, (None,)), ('donor', donor, torch.uint8, (None,)), ('hw', hw, torch.int32, (None, 2)),
+                    ('donor_hw', donor_hw, torch.int32, (None, 2))])
+    if hw.shape[0] < 1 or donor_hw.shape[0] < 1:
+        raise ValueError('hw and donor_hw must hold at least one image, got %s and %s' % (tuple(hw.shape), tuple(donor_hw.shape)))
+    _check_tensors([('offsets', offsets, torch.int64, (hw.shape[0],)), ('donor_offsets', donor_offsets, torch.int64, (donor_hw.shape[0],))])
+
+
+def _need(name, **args):
+    """The arguments that define a named paste entry, as keywords of morph_paste: a ValueError names the first that is None."""
+    for k, t in args.items():
+        if t is None:
+            raise ValueError('%s needs %s, got None' % (name, k))
+    return args
+
+
+def morph_paste(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b,
+                max_box_pixels, gain=None, edges=None, inv_soft=None, ring=None, diff=None, seamless=None):
+    """The paste of LandmarkDetector.morph, every check made once and the entry point chosen by what is given, as morph_launch chooses
+    the kernel's instantiation: ring (with diff and seamless; needs edges) -> imm_morph_seam_u8, else edges (with inv_soft) ->
+    imm_morph_hull_u8, else gain -> imm_morph_colour_u8, else imm_morph_u8.  The sixteen leading arguments as morph_u8 takes them, the
+    optional ones as morph_colour_u8, morph_hull_u8 and morph_seam_u8 do; none of them may overlap dst."""
+    name = 'morph_seam_u8' if ring is not None else 'morph_hull_u8' if edges is not None else 'morph_colour_u8' if gain is not None else 'morph_u8'
     if boxes.dim() != 2 or ctrl.dim() != 3:
         raise ValueError('boxes must be int32 [n, 5] and ctrl f32 [n, M, 2], got %s and %s' % (tuple(boxes.shape), tuple(ctrl.shape)))
     n, M = int(boxes.shape[0]), int(ctrl.shape[1])
-    _check_tensors([('src', src, torch.uint8, (None,)), ('dst', dst, torch.uint8, (None,)), ('donor', donor, torch.uint8, (None,))])
+    _check_photos(src, offsets, hw, donor, donor_offsets, donor_hw)
+    _check_tensors([('dst', dst, torch.uint8, (None,))])
     if src.numel() != dst.numel() or _overlap(src, dst):
         raise ValueError('dst must be a copy of src (same size, another buffer): every row samples the original pixels')
     if _overlap(donor, dst):
         raise ValueError('the donor buffer is read only: it may be src, never dst')
     if n < 1 or n > 65535 or not 3 <= M <= WARP_MAX_POINTS:
         raise ValueError('%s serves 1..65535 rows of 3 <= M <= %d control points, got n = %d, M = %d' % (name, WARP_MAX_POINTS, n, M))
-    _check_tensors([('hw', hw, torch.int32, (None, 2)), ('donor_hw', donor_hw, torch.int32, (None, 2))])
-    if hw.shape[0] < 1 or donor_hw.shape[0] < 1:
-        raise ValueError('hw and donor_hw must hold at least one image, got %s and %s' % (tuple(hw.shape), tuple(donor_hw.shape)))
     _check_tensors([('boxes', boxes, torch.int32, (n, 5)), ('donor_boxes', donor_boxes, torch.int32, (n, 5)), ('links', links, torch.int32, (n, 2)),
                     ('inv_ramp', inv_ramp, torch.float32, (n, 2)), ('texture', texture, torch.float32, (n,)),
                     ('ctrl', ctrl, torch.float32, (n, M, 2)), ('coef_a', coef_a, torch.float32, (n, M + 3, 2)),
-                    ('coef_b', coef_b, torch.float32, (n, M + 3, 2)), ('offsets', offsets, torch.int64, (hw.shape[0],)),
-                    ('donor_offsets', donor_offsets, torch.int64, (donor_hw.shape[0],))])
+                    ('coef_b', coef_b, torch.float32, (n, M + 3, 2))])
     if int(max_box_pixels) < 1:
         raise ValueError('max_box_pixels must be positive, got %r' % (max_box_pixels,))
-    return n, M
+    extra = dict(gain=gain, edges=edges, inv_soft=inv_soft, ring=ring, diff=diff, seamless=seamless)
+    for group in (('edges', 'inv_soft'), ('ring', 'diff', 'seamless')):
+        absent = [k for k in group if extra[k] is None]
+        if absent and len(absent) < len(group):
+            raise ValueError('%s come together: %s is None' % (' and '.join(group), absent[0]))
+    if ring is not None and edges is None:
+        raise ValueError('ring, diff and seamless need the mask they are fitted to: edges is None')
+    # the 17 arguments every entry starts with, then what the chosen one adds: pointers, then sizes
+    args = [_p(src), _p(dst), _p(offsets), _p(hw), int(hw.shape[0]), _p(donor), _p(donor_offsets), _p(donor_hw), int(donor_hw.shape[0]),
+            _p(boxes), _p(donor_boxes), _p(links), _p(inv_ramp), _p(texture), _p(ctrl), _p(coef_a), _p(coef_b)]
+    sizes = [M]
+    if gain is not None:
+        _check_tensors([('gain', gain, torch.float32, (n, 3, 2))])
+    if name != 'morph_u8':
+        args.append(_p(gain))
+    if edges is not None:
+        if edges.dim() != 3 or not 1 <= int(edges.shape[1]) <= WARP_MAX_POINTS:
+            raise ValueError('edges must be f32 [n, K, 3] with 1 <= K <= %d, got %s' % (WARP_MAX_POINTS, tuple(edges.shape)))
+        K = int(edges.shape[1])
+        _check_tensors([('edges', edges, torch.float32, (n, K, 3)), ('inv_soft', inv_soft, torch.float32, (n,))])
+        args += [_p(edges), _p(inv_soft)]
+        sizes = [K, M]
+    if ring is not None:
+        B = _check_seam(ring, diff, n, name)
+        _check_tensors([('seamless', seamless, torch.float32, (n,))])
+        args += [_p(ring), _p(diff), _p(seamless)]
+        sizes = [K, M, B]
+    for k, t in extra.items():
+        if t is not None and _overlap(t, dst):
+            raise ValueError('%s overlaps dst' % k)
+    call('imm_' + name, *args, *sizes, n, int(max_box_pixels), _s())
 
 
 def morph_u8(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b,
@@ -968,11 +1017,8 @@ def morph_u8(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor
     sends it to inside the donor box (donor_boxes i32 [n, 5]), blended with the edge ramp inv_ramp f32 [n, 2] and rounded to u8, in row
     order.  ctrl f32 [n, M, 2], coef_a / coef_b f32 [n, M + 3, 2]: the halves of ONE warp_fit over the 2 n rows of morph_poses.  boxes,
     links, max_box_pixels as warp_u8 takes them."""
-    n, M = _check_morph(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a,
-                        coef_b, max_box_pixels, 'morph_u8')
-    call('imm_morph_u8', _p(src), _p(dst), _p(offsets), _p(hw), int(hw.shape[0]), _p(donor), _p(donor_offsets), _p(donor_hw),
-         int(donor_hw.shape[0]), _p(boxes), _p(donor_boxes), _p(links), _p(inv_ramp), _p(texture), _p(ctrl), _p(coef_a), _p(coef_b), M, n,
-         int(max_box_pixels), _s())
+    morph_paste(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b,
+                max_box_pixels)
 
 
 COLOUR_MAX_AREA = 1 << 30     # H * W of a box whose pixels imm_colour_stats_u8 counts: the ellipse test stays inside 64 bits
@@ -1020,14 +1066,8 @@ def morph_colour_u8(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes
                     gain, max_box_pixels):
     """morph_u8 with the donor's sample taken through gain f32 [n, 3, 2] (colour_gain's output for these rows) in front of the mix:
     gB * G + O per channel (include/imm_colour.h: imm_morph_colour_u8).  Every other argument as morph_u8 takes it."""
-    n, M = _check_morph(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a,
-                        coef_b, max_box_pixels, 'morph_colour_u8')
-    _check_tensors([('gain', gain, torch.float32, (n, 3, 2))])
-    if _overlap(gain, dst):
-        raise ValueError('gain overlaps dst')
-    call('imm_morph_colour_u8', _p(src), _p(dst), _p(offsets), _p(hw), int(hw.shape[0]), _p(donor), _p(donor_offsets), _p(donor_hw),
-         int(donor_hw.shape[0]), _p(boxes), _p(donor_boxes), _p(links), _p(inv_ramp), _p(texture), _p(ctrl), _p(coef_a), _p(coef_b), _p(gain),
-         M, n, int(max_box_pixels), _s())
+    morph_paste(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b,
+                max_box_pixels, **_need('morph_colour_u8', gain=gain))
 
 
 def hull_fit(poses, boxes, grow, edges, flags):
@@ -1051,20 +1091,8 @@ def morph_hull_u8(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, 
     imm_morph_hull_u8): edges f32 [n, K, 3] (hull_fit's output for these rows) and inv_soft f32 [n] give every pixel of a row's box the
     weight w = clamp(min_k((ny rr + nx cc) + d) * inv_soft, 0, 1); a pixel with w = 0 is left alone, every other is blended with the edge
     ramp times w.  Every other argument as morph_u8 takes it."""
-    n, M = _check_morph(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a,
-                        coef_b, max_box_pixels, 'morph_hull_u8')
-    if edges.dim() != 3 or not 1 <= int(edges.shape[1]) <= WARP_MAX_POINTS:
-        raise ValueError('edges must be f32 [n, K, 3] with 1 <= K <= %d, got %s' % (WARP_MAX_POINTS, tuple(edges.shape)))
-    K = int(edges.shape[1])
-    _check_tensors([('edges', edges, torch.float32, (n, K, 3)), ('inv_soft', inv_soft, torch.float32, (n,))])
-    if gain is not None:
-        _check_tensors([('gain', gain, torch.float32, (n, 3, 2))])
-    for name, t in (('gain', gain), ('edges', edges), ('inv_soft', inv_soft)):
-        if t is not None and _overlap(t, dst):
-            raise ValueError('%s overlaps dst' % name)
-    call('imm_morph_hull_u8', _p(src), _p(dst), _p(offsets), _p(hw), int(hw.shape[0]), _p(donor), _p(donor_offsets), _p(donor_hw),
-         int(donor_hw.shape[0]), _p(boxes), _p(donor_boxes), _p(links), _p(inv_ramp), _p(texture), _p(ctrl), _p(coef_a), _p(coef_b),
-         None if gain is None else _p(gain), _p(edges), _p(inv_soft), K, M, n, int(max_box_pixels), _s())
+    morph_paste(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b,
+                max_box_pixels, gain=gain, **_need('morph_hull_u8', edges=edges, inv_soft=inv_soft))
 
 
 SEAM_MIN_RING, SEAM_MAX_RING = 16, 256     # ring samples of a row (include/imm_seam.h)
@@ -1093,14 +1121,10 @@ def seam_fit(poses, boxes, grow, edges, hull_flags, dirs, src, offsets, hw, dono
         raise ValueError('seam_fit serves 1..65535 rows of 1 <= K <= %d landmarks and 3 <= M <= %d control points, got n = %d, K = %d, M = %d'
                          % (WARP_MAX_POINTS, WARP_MAX_POINTS, n, K, M))
     B = _check_seam(ring, diff, n, 'seam_fit')
-    _check_tensors([('src', src, torch.uint8, (None,)), ('donor', donor, torch.uint8, (None,)), ('hw', hw, torch.int32, (None, 2)),
-                    ('donor_hw', donor_hw, torch.int32, (None, 2))])
-    if hw.shape[0] < 1 or donor_hw.shape[0] < 1:
-        raise ValueError('hw and donor_hw must hold at least one image, got %s and %s' % (tuple(hw.shape), tuple(donor_hw.shape)))
+    _check_photos(src, offsets, hw, donor, donor_offsets, donor_hw)
     _check_tensors([('poses', poses, torch.float32, (n, K, 2)), ('boxes', boxes, torch.int32, (n, 5)), ('grow', grow, torch.float32, (n,)),
                     ('edges', edges, torch.float32, (n, K, 3)), ('hull_flags', hull_flags, torch.int32, (n,)),
-                    ('dirs', dirs, torch.float64, (B, 2)), ('offsets', offsets, torch.int64, (hw.shape[0],)),
-                    ('donor_offsets', donor_offsets, torch.int64, (donor_hw.shape[0],)), ('donor_boxes', donor_boxes, torch.int32, (n, 5)),
+                    ('dirs', dirs, torch.float64, (B, 2)), ('donor_boxes', donor_boxes, torch.int32, (n, 5)),
                     ('texture', texture, torch.float32, (n,)), ('ctrl', ctrl, torch.float32, (n, M, 2)),
                     ('coef_a', coef_a, torch.float32, (n, M + 3, 2)), ('coef_b', coef_b, torch.float32, (n, M + 3, 2)),
                     ('flags', flags, torch.int32, (n,))])
@@ -1117,22 +1141,9 @@ def morph_seam_u8(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, 
     (seam_fit's output for these rows) give every pixel with a weight the correction r, the mean of the row's diffs weighed by the
     pixel's mean-value coordinates in the ring, and the mix takes seamless[b] * r (seamless f32 [n]) in front of the blend.  Every other
     argument as morph_hull_u8 takes it."""
-    n, M = _check_morph(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a,
-                        coef_b, max_box_pixels, 'morph_seam_u8')
-    if edges.dim() != 3 or not 1 <= int(edges.shape[1]) <= WARP_MAX_POINTS:
-        raise ValueError('edges must be f32 [n, K, 3] with 1 <= K <= %d, got %s' % (WARP_MAX_POINTS, tuple(edges.shape)))
-    K = int(edges.shape[1])
-    B = _check_seam(ring, diff, n, 'morph_seam_u8')
-    _check_tensors([('edges', edges, torch.float32, (n, K, 3)), ('inv_soft', inv_soft, torch.float32, (n,)),
-                    ('seamless', seamless, torch.float32, (n,))])
-    if gain is not None:
-        _check_tensors([('gain', gain, torch.float32, (n, 3, 2))])
-    for name, t in (('gain', gain), ('edges', edges), ('inv_soft', inv_soft), ('ring', ring), ('diff', diff), ('seamless', seamless)):
-        if t is not None and _overlap(t, dst):
-            raise ValueError('%s overlaps dst' % name)
-    call('imm_morph_seam_u8', _p(src), _p(dst), _p(offsets), _p(hw), int(hw.shape[0]), _p(donor), _p(donor_offsets), _p(donor_hw),
-         int(donor_hw.shape[0]), _p(boxes), _p(donor_boxes), _p(links), _p(inv_ramp), _p(texture), _p(ctrl), _p(coef_a), _p(coef_b),
-         None if gain is None else _p(gain), _p(edges), _p(inv_soft), _p(ring), _p(diff), _p(seamless), K, M, B, n, int(max_box_pixels), _s())
+    morph_paste(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, donor_boxes, links, inv_ramp, texture, ctrl, coef_a, coef_b,
+                max_box_pixels, gain=gain,
+                **_need('morph_seam_u8', edges=edges, inv_soft=inv_soft, ring=ring, diff=diff, seamless=seamless))
 
 
 def masked_sse_pool(a, b, batch, s, c, mask, S, partial, pool_a, pool_b):

@@ -142,10 +142,10 @@ def test_plan_morph_checks_colour_and_max_gain():
     K = 10
     good = dict(photos=photos, donors=donors, boxes=None, donor_boxes=None, shape=0.5, texture=None, feather=0.125, K=K)
     plan = MP.plan_morph(**good)
-    assert len(plan) == 15 and plan[13].dtype == F32 and plan[13].tolist() == [0.0, 0.0] and plan[14] == 2.0
+    assert len(vars(plan)) == 21 and plan.colour.dtype == F32 and plan.colour.tolist() == [0.0, 0.0] and plan.max_gain == 2.0
     plan = MP.plan_morph(colour=[0.25, 1.0], max_gain=3, **good)
-    assert plan[13].tolist() == [0.25, 1.0] and plan[14] == 3.0 and isinstance(plan[14], float)
-    assert MP.plan_morph(colour=1, max_gain=1.0, **good)[13].tolist() == [1.0, 1.0]
+    assert plan.colour.tolist() == [0.25, 1.0] and plan.max_gain == 3.0 and isinstance(plan.max_gain, float)
+    assert MP.plan_morph(colour=1, max_gain=1.0, **good).colour.tolist() == [1.0, 1.0]
     huge = [(0, -40000, -40000, 40000, 40000), (1, 0, 0, 30, 30)]                      # 6.4e9 pixels
     for kw, match in ((dict(colour=1.5), 'colour'), (dict(colour=-0.1), 'colour'), (dict(colour=float('nan')), 'colour'),
                       (dict(colour=[0.1, 0.2, 0.3]), 'colour'), (dict(colour=[[0.1, 0.2]]), 'colour'), (dict(max_gain=0.5), 'max_gain'),
@@ -157,8 +157,8 @@ def test_plan_morph_checks_colour_and_max_gain():
         with pytest.raises(ValueError, match=match):
             MP.plan_morph(**args)
     # without colour matching such a box is what it was: accepted
-    assert MP.plan_morph(**dict(good, boxes=huge))[1].tolist() == [list(r) for r in huge]
-    assert MP.plan_morph(**dict(good, boxes=huge, colour=0.0, max_gain=4.0))[14] == 4.0
+    assert MP.plan_morph(**dict(good, boxes=huge)).rows.tolist() == [list(r) for r in huge]
+    assert MP.plan_morph(**dict(good, boxes=huge, colour=0.0, max_gain=4.0)).max_gain == 4.0
     # PhotoMorph: the fields, and their defaults for a caller of the earlier signature
     pm = MP.PhotoMorph(None, None, None, np.zeros((2, 5)), np.zeros((2, 5)), None, None, None, None, [0, 1], [1, 0], 0.0, 2)
     assert pm.colour.tolist() == [0.0, 0.0] and pm.colour_gain is None and pm.colour_flags is None and pm.max_gain is None

@@ -20,11 +20,10 @@ from alignment_reference import smooth_photo                                  # 
 from dataset_fixtures import make_celeba_tree                                 # noqa: E402
 from test_detector_gpu import _run_script, _write_config                      # noqa: E402
 from test_generator_gpu import make_model as make_generator_model             # noqa: E402
-from test_morph_gpu import DONOR_BOXES, DONOR_SIZES, device_fit, packed_mask, run_morph      # noqa: E402
+from test_morph_gpu import DONOR_BOXES, DONOR_SIZES, box_area, device_fit, packed_mask, run_morph      # noqa: E402
 from test_unalign_gpu import SURFACE_BOXES, SURFACE_SIZES                     # noqa: E402
 from test_warp_gpu import dev                                                 # noqa: E402
 
-from imm_amd import generation as G                                           # noqa: E402
 from imm_amd import morphing as MP                                            # noqa: E402
 from imm_amd.inference import plan_buckets                                    # noqa: E402
 
@@ -47,11 +46,6 @@ def ops():
 
 def _t(a):
     return torch.from_numpy(np.ascontiguousarray(a))
-
-
-def box_area(rows):
-    a = (rows[:, 3].astype(np.int64) - rows[:, 1]) * (rows[:, 4].astype(np.int64) - rows[:, 2])
-    return int(min(max(1, a.max()), 2 ** 31 - 1))
 
 
 def run_stats(ops, photos, rows, max_pixels=None, garbage=0x5A):
@@ -83,29 +77,8 @@ def run_gain(ops, sums_a, sums_b, amount, max_gain):
 def run_colour_morph(ops, photos, rows, donors, drows, ctrl, coef_a, coef_b, texture, feather, gain, launches=None, links=None,
                      donor_is_src=False, max_pixels=None):
     """test_morph_gpu.run_morph for imm_morph_colour_u8: gain f32 [n, 3, 2] in a guarded buffer as well."""
-    buf, offs, hw = CR.pack(photos)
-    dbuf, doffs, dhw = CR.pack(donors)
-    guarded.reset()
-    src = guarded.inp(_t(buf), DEV)
-    don = src if donor_is_src else guarded.inp(_t(dbuf), DEV)
-    canvas = guarded.out(buf.shape, torch.uint8, DEV, fill=_t(buf))
-    offs_d, hw_d, doffs_d, dhw_d = dev(ops, offs), dev(ops, hw), dev(ops, doffs), dev(ops, dhw)
-    ctrl_d, ca_d, cb_d, gain_d = (guarded.inp(_t(np.asarray(a, F32)), DEV) for a in (ctrl, coef_a, coef_b, gain))
-    tex_d = guarded.inp(_t(np.asarray(texture, F32)), DEV)
-    ramp = WR.inv_ramp(rows, feather)
-    for part in ([list(range(len(rows)))] if launches is None else launches):
-        assert part == list(range(part[0], part[-1] + 1))
-        sl = slice(part[0], part[-1] + 1)
-        sub = rows[sl]
-        area = box_area(sub) if max_pixels is None else max_pixels
-        lk = G.compose_links(sub) if links is None else links[sl]
-        ops.morph_colour_u8(src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, dev(ops, sub), dev(ops, drows[sl]), dev(ops, lk),
-                            dev(ops, ramp[sl]), tex_d[sl], ctrl_d[sl], ca_d[sl], cb_d[sl], gain_d[sl], area)
-    torch.cuda.synchronize()
-    guarded.check_guards()
-    assert np.array_equal(src.cpu().numpy(), buf), 'the source buffer is read only'
-    assert np.array_equal(don.cpu().numpy(), buf if donor_is_src else dbuf), 'the donor buffer is read only'
-    return canvas.cpu().numpy(), buf
+    return run_morph(ops, photos, rows, donors, drows, ctrl, coef_a, coef_b, texture, feather, launches, links, donor_is_src, max_pixels,
+                     gain=gain)
 
 
 # ----------------------------------------------------------------------------------------------------------------------------

@@ -130,13 +130,13 @@ def test_plan_morph_checks_the_mask():
     donors = [np.zeros((20, 25, 3), np.uint8), np.zeros((35, 30), np.uint8)]
     good = dict(photos=photos, donors=donors, boxes=None, donor_boxes=None, shape=0.5, texture=None, feather=0.125, K=10)
     plan = MP.plan_morph(**good)
-    assert len(plan) == 15 and plan.mask is None and plan.grow.tolist() == [1.25, 1.25] and plan.grow.dtype == F32
+    assert len(vars(plan)) == 21 and plan.mask is None and plan.grow.tolist() == [1.25, 1.25] and plan.grow.dtype == F32
     assert np.array_equal(plan.mask_feather, np.full(2, 0.1, F32))
     # mask=None: the fifteen values of a call without the keyword, whatever grow and mask_feather are
     for kw in (dict(mask=None), dict(mask=None, grow=3.0, mask_feather=0.5), dict(mask='hull'), dict(colour=0.0, mask=None)):
         other = MP.plan_morph(**dict(good, **kw))
-        assert len(other) == 15 and other.mask == kw.get('mask')
-        for x, y in zip(plan, other):
+        assert len(vars(other)) == 21 and other.mask == kw.get('mask')
+        for x, y in ((getattr(plan, k), getattr(other, k)) for k in MP.MorphPlan.FIELDS[:15]):
             if isinstance(x, list):                                          # the decoded photos
                 assert len(x) == len(y) and all(np.array_equal(a, b) for a, b in zip(x, y))
             else:
@@ -147,7 +147,7 @@ def test_plan_morph_checks_the_mask():
     assert plan.inv_soft.dtype == F32 and plan.inv_soft.tolist() == [1.0, F32(1.0 / 30.0)]
     assert MP.plan_morph(mask='hull', mask_feather=0.25, **good).inv_soft.tolist() == [F32(0.1), F32(1.0 / 7.5)]
     assert np.array_equal(MP.hull_inv_soft([(0, 0, 0, 3, 100)], [0.1]), [F32(1.0)]), 'at least one pixel'
-    assert np.array_equal(plan.inv_soft, HR.inv_soft(plan[1], [0.0, 1.0]))
+    assert np.array_equal(plan.inv_soft, HR.inv_soft(plan.rows, [0.0, 1.0]))
     for kw, match in ((dict(mask='ellipse'), 'mask'), (dict(mask='Hull'), 'mask'), (dict(mask=1), 'mask'), (dict(mask=True), 'mask'),
                       (dict(grow=0.0), 'grow'), (dict(grow=-1.0), 'grow'), (dict(grow=16.5), 'grow'), (dict(grow=float('nan')), 'grow'),
                       (dict(grow=float('inf')), 'grow'), (dict(grow=[1.0, 2.0, 3.0]), 'grow'), (dict(grow=[[1.0, 2.0]]), 'grow'),

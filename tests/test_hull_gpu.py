@@ -19,15 +19,13 @@ import unalign_reference as UR                                               # n
 import warp_reference as WR                                                  # noqa: E402
 from alignment_reference import smooth_photo                                  # noqa: E402
 from dataset_fixtures import make_celeba_tree                                 # noqa: E402
-from test_colour_gpu import _count_calls, box_area, run_colour_morph, wild_gains      # noqa: E402
+from test_colour_gpu import _count_calls, run_colour_morph, wild_gains      # noqa: E402
 from test_detector_gpu import _run_script, _write_config                      # noqa: E402
 from test_generator_gpu import make_model as make_generator_model             # noqa: E402
 from test_hull_cpu import flat_case                                           # noqa: E402
 from test_morph_gpu import DONOR_BOXES, DONOR_SIZES, device_fit, packed_mask, run_morph, same_values      # noqa: E402
 from test_unalign_gpu import SURFACE_BOXES, SURFACE_SIZES                     # noqa: E402
-from test_warp_gpu import dev                                                 # noqa: E402
 
-from imm_amd import generation as G                                           # noqa: E402
 from imm_amd.inference import plan_buckets                                    # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -66,30 +64,9 @@ def run_hull_fit(ops, poses, rows, grow, garbage=0x5A):
 
 def run_hull_morph(ops, photos, rows, donors, drows, ctrl, coef_a, coef_b, texture, feather, edges, soft, gain=None, launches=None,
                    links=None, max_pixels=None):
-    """test_morph_gpu.run_morph for imm_morph_hull_u8: edges f32 [n, K, 3], soft f32 [n] and (unless None) gain f32 [n, 3, 2] in guarded
-    buffers as well.  Returns (the whole canvas as a host array, the packed input)."""
-    buf, offs, hw = CR.pack(photos)
-    dbuf, doffs, dhw = CR.pack(donors)
-    guarded.reset()
-    src, don = guarded.inp(_t(buf), DEV), guarded.inp(_t(dbuf), DEV)
-    canvas = guarded.out(buf.shape, torch.uint8, DEV, fill=_t(buf))
-    offs_d, hw_d, doffs_d, dhw_d = dev(ops, offs), dev(ops, hw), dev(ops, doffs), dev(ops, dhw)
-    ctrl_d, ca_d, cb_d, edges_d, soft_d, tex_d = (guarded.inp(_t(np.asarray(a, F32)), DEV) for a in (ctrl, coef_a, coef_b, edges, soft, texture))
-    gain_d = None if gain is None else guarded.inp(_t(np.asarray(gain, F32)), DEV)
-    ramp = WR.inv_ramp(rows, feather)
-    for part in ([list(range(len(rows)))] if launches is None else launches):
-        assert part == list(range(part[0], part[-1] + 1))
-        sl = slice(part[0], part[-1] + 1)
-        sub = rows[sl]
-        area = box_area(sub) if max_pixels is None else max_pixels
-        lk = G.compose_links(sub) if links is None else links[sl]
-        ops.morph_hull_u8(src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, dev(ops, sub), dev(ops, drows[sl]), dev(ops, lk), dev(ops, ramp[sl]),
-                          tex_d[sl], ctrl_d[sl], ca_d[sl], cb_d[sl], None if gain is None else gain_d[sl], edges_d[sl], soft_d[sl], area)
-    torch.cuda.synchronize()
-    guarded.check_guards()
-    assert np.array_equal(src.cpu().numpy(), buf), 'the source buffer is read only'
-    assert np.array_equal(don.cpu().numpy(), dbuf), 'the donor buffer is read only'
-    return canvas.cpu().numpy(), buf
+    """test_morph_gpu.run_morph for imm_morph_hull_u8: edges f32 [n, K, 3], soft f32 [n] and (unless None) gain f32 [n, 3, 2]."""
+    return run_morph(ops, photos, rows, donors, drows, ctrl, coef_a, coef_b, texture, feather, launches, links, max_pixels=max_pixels,
+                     gain=gain, edges=edges, soft=soft)
 
 
 # ----------------------------------------------------------------------------------------------------------------------------

@@ -114,6 +114,53 @@ def test_wrapper_refusals_come_before_any_device_call():
             ops.morph_u8(**args)
 
 
+def test_morph_paste_checks_once_and_chooses_the_entry(monkeypatch):
+    """ops.morph_paste on host tensors (n = 2, M = 3, K = 1, B = 16, 64-byte buffers): what it refuses is refused before a launch, with
+    a ValueError that names the argument; the named wrappers refuse a None for the arguments that define them; and with the library
+    call recorded instead of made, what is given chooses the entry point, with as many arguments as _lib declares for it."""
+    from imm_amd import _lib as L
+    from imm_amd import ops
+    z = lambda *sh, **kw: torch.zeros(*sh, **kw)
+    n, M, K, B = 2, 3, 1, 16
+    pool = z(512, dtype=torch.uint8)                       # dst is its head: a tensor viewed on its head overlaps dst
+    over = lambda *sh: pool[:4 * int(np.prod(sh))].view(torch.float32).view(*sh)
+    boxes, coef = z(n, 5, dtype=torch.int32), z(n, M + 3, 2)
+    common = (z(64, dtype=torch.uint8), pool[:64], z(1, dtype=torch.int64), z(1, 2, dtype=torch.int32), z(64, dtype=torch.uint8),
+              z(1, dtype=torch.int64), z(1, 2, dtype=torch.int32), boxes, boxes, z(n, 2, dtype=torch.int32), z(n, 2), z(n), z(n, M, 2), coef, coef)
+    shapes = dict(gain=(n, 3, 2), edges=(n, K, 3), inv_soft=(n,), ring=(n, B, 2), diff=(n, B, 3), seamless=(n,))
+    opt = {k: z(*sh) for k, sh in shapes.items()}
+    pick = lambda *names, **kw: dict({k: opt[k] for k in names}, **kw)
+    refused = [(pick('inv_soft'), 'edges is None'), (pick('edges'), 'inv_soft is None'),
+               (pick('edges', 'inv_soft', 'ring', 'seamless'), 'diff is None'), (pick('edges', 'inv_soft', 'ring', 'diff'), 'seamless is None'),
+               (pick('ring', 'diff', 'seamless'), 'edges is None'), (pick('gain', 'ring', 'diff', 'seamless'), 'edges is None'),
+               (pick(gain=z(n, 3)), 'gain must be'), (pick('inv_soft', edges=z(n, 81, 3)), 'edges must be f32'),
+               (pick('edges', 'inv_soft', 'seamless', ring=z(n, 15, 2), diff=z(n, 15, 3)), 'morph_seam_u8: ring must be'),
+               (pick('edges', 'inv_soft', 'seamless', ring=z(n, 257, 2), diff=z(n, 257, 3)), 'morph_seam_u8: ring must be')]
+    refused += [(dict(opt, **{k: over(*sh)}), '%s overlaps dst' % k) for k, sh in shapes.items()]
+    for kw, match in refused:
+        with pytest.raises(ValueError, match=match):
+            ops.morph_paste(*common, 9, **kw)
+    g, e, s_, r, d, a = (opt[k] for k in ('gain', 'edges', 'inv_soft', 'ring', 'diff', 'seamless'))
+    for fn, args, match in ((ops.morph_colour_u8, (None,), 'gain'), (ops.morph_hull_u8, (g, None, s_), 'edges'),
+                            (ops.morph_hull_u8, (None, e, None), 'inv_soft'), (ops.morph_seam_u8, (g, None, s_, r, d, a), 'edges'),
+                            (ops.morph_seam_u8, (g, e, None, r, d, a), 'inv_soft'), (ops.morph_seam_u8, (None, e, s_, None, d, a), 'ring'),
+                            (ops.morph_seam_u8, (g, e, s_, r, None, a), 'diff'), (ops.morph_seam_u8, (g, e, s_, r, d, None), 'seamless')):
+        with pytest.raises(ValueError, match='%s needs %s' % (fn.__name__, match)):
+            fn(*common, *args, 9)
+    calls = []
+    monkeypatch.setattr(ops, 'call', lambda name, *args: calls.append((name, len(args))))
+    monkeypatch.setattr(ops, '_s', lambda: None)
+    sigs = dict(L._SIGS_MORPH, **dict(L._SIGS_COLOUR, **dict(L._SIGS_HULL, **L._SIGS_SEAM)))
+    for kw, entry in ((pick(), 'imm_morph_u8'), (pick('gain'), 'imm_morph_colour_u8'), (pick('edges', 'inv_soft'), 'imm_morph_hull_u8'),
+                      (pick('gain', 'edges', 'inv_soft'), 'imm_morph_hull_u8'), (opt, 'imm_morph_seam_u8'),
+                      (pick('edges', 'inv_soft', 'ring', 'diff', 'seamless'), 'imm_morph_seam_u8')):
+        ops.morph_paste(*common, 9, **kw)
+        assert calls[-1] == (entry, len(sigs[entry])), kw.keys()
+    ops.morph_u8(*common, 9), ops.morph_colour_u8(*common, g, 9), ops.morph_hull_u8(*common, None, e, s_, 9)
+    ops.morph_seam_u8(*common, g, e, s_, r, d, a, 9)
+    assert [c[0] for c in calls[-4:]] == ['imm_morph_u8', 'imm_morph_colour_u8', 'imm_morph_hull_u8', 'imm_morph_seam_u8']
+
+
 # ----------------------------------------------------------------------------------------------------------------------------
 # plan_morph and blend_poses
 # ----------------------------------------------------------------------------------------------------------------------------
@@ -123,15 +170,15 @@ def test_plan_morph_forms_and_refusals():
     K = 10
     lm_a, lm_b = R.landmarks(K, 2, np.random.RandomState(1))
     plan = MP.plan_morph(photos, donors, None, None, 0.5, None, 0.125, K)
-    assert plan[1].tolist() == [[0, 0, 0, 40, 50], [1, 0, 0, 30, 30]] and plan[3].tolist() == [[0, 0, 0, 20, 25], [1, 0, 0, 35, 30]]
-    assert plan[2][1].shape == (35, 30, 3) and plan[5].dtype == F32 and plan[5].tolist() == [0.5, 0.5] == plan[6].tolist()
-    assert plan[7:11] == (0.125, 2, 0.0, 18) and plan[11] is None and plan[12] is None
+    assert plan.rows.tolist() == [[0, 0, 0, 40, 50], [1, 0, 0, 30, 30]] and plan.donor_rows.tolist() == [[0, 0, 0, 20, 25], [1, 0, 0, 35, 30]]
+    assert plan.donors[1].shape == (35, 30, 3) and plan.shape.dtype == F32 and plan.shape.tolist() == [0.5, 0.5] == plan.texture.tolist()
+    assert (plan.feather, plan.anchors, plan.lam, plan.M) == (0.125, 2, 0.0, 18) and plan.landmarks is None and plan.donor_landmarks is None
     # one donor row for all faces; per-row shape and texture; given landmarks
     plan = MP.plan_morph(photos, donors[:1], [(1, 2, 2, 20, 20)] * 3, [(0, 1, 1, 11, 21)], [0.0, 0.25, 1.0], 1.0, 0.0, K, anchors=0,
                          landmarks=np.tile(lm_a[:1], (3, 1, 1)), donor_landmarks=lm_b[:1])
-    assert plan[3].tolist() == [[0, 1, 1, 11, 21]] * 3 and plan[4].tolist() == [[0, 1, 1, 11, 21]]
-    assert plan[5].tolist() == [0.0, 0.25, 1.0] and plan[6].tolist() == [1.0] * 3 and plan[10] == 10
-    assert tuple(plan[11].shape) == (3, K, 2) and tuple(plan[12].shape) == (1, K, 2) and plan[11].dtype == torch.float32
+    assert plan.donor_rows.tolist() == [[0, 1, 1, 11, 21]] * 3 and plan.donor_rows_given.tolist() == [[0, 1, 1, 11, 21]]
+    assert plan.shape.tolist() == [0.0, 0.25, 1.0] and plan.texture.tolist() == [1.0] * 3 and plan.M == 10
+    assert tuple(plan.landmarks.shape) == (3, K, 2) and tuple(plan.donor_landmarks.shape) == (1, K, 2) and plan.landmarks.dtype == torch.float32
     nan = lm_a.copy()
     nan[1, 2, 0] = np.nan
     good = dict(photos=photos, donors=donors, boxes=None, donor_boxes=None, shape=0.5, texture=None, feather=0.125, K=K)

@@ -79,11 +79,19 @@ def device_fit(ops, mu_a, mu_b, shape, m, lam):
     return poses2[0], coef[:n], coef[n:], ctrl[:n], flags[:n] | flags[n:]
 
 
+def box_area(rows):
+    a = (rows[:, 3].astype(np.int64) - rows[:, 1]) * (rows[:, 4].astype(np.int64) - rows[:, 2])
+    return int(min(max(1, a.max()), 2 ** 31 - 1))
+
+
 def run_morph(ops, photos, rows, donors, drows, ctrl, coef_a, coef_b, texture, feather, launches=None, links=None, donor_is_src=False,
-              max_pixels=None):
-    """imm_morph_u8 over the packed photos; source, donor and canvas in guarded buffers, the rows issued as the given launches (lists of
-    consecutive row indices, in order; default: one launch of all rows), the grid sized by max_pixels (default: the launch's largest box).
-    donor_is_src: the donor buffer IS the source buffer (donors must be the photos).  Returns (the whole canvas as a host array, the packed input)."""
+              max_pixels=None, gain=None, edges=None, soft=None, ring=None, diff=None, seamless=None):
+    """The paste over the packed photos, through the named wrapper of what is given: imm_morph_seam_u8 with ring f32 [n, B, 2], diff f32
+    [n, B, 3] and seamless f32 [n], else imm_morph_hull_u8 with edges f32 [n, K, 3] and soft f32 [n], else imm_morph_colour_u8 with gain
+    f32 [n, 3, 2] (the first two take a gain as well), else imm_morph_u8.  Source, donor, canvas and every array given in guarded buffers,
+    the rows issued as the given launches (lists of consecutive row indices, in order; default: one launch of all rows), the grid sized
+    by max_pixels (default: the launch's largest box).  donor_is_src: the donor buffer IS the source buffer (donors must be the photos).
+    Returns (the whole canvas as a host array, the packed input)."""
     buf, offs, hw = CR.pack(photos)
     dbuf, doffs, dhw = CR.pack(donors)
     guarded.reset()
@@ -91,18 +99,27 @@ def run_morph(ops, photos, rows, donors, drows, ctrl, coef_a, coef_b, texture, f
     don = src if donor_is_src else guarded.inp(_t(dbuf), DEV)
     canvas = guarded.out(buf.shape, torch.uint8, DEV, fill=_t(buf))
     offs_d, hw_d, doffs_d, dhw_d = dev(ops, offs), dev(ops, hw), dev(ops, doffs), dev(ops, dhw)
-    ctrl_d, ca_d, cb_d = (guarded.inp(_t(np.asarray(a, F32)), DEV) for a in (ctrl, coef_a, coef_b))
-    tex_d = guarded.inp(_t(np.asarray(texture, F32)), DEV)
+    ctrl_d, ca_d, cb_d, tex_d, gain_d, edges_d, soft_d, ring_d, diff_d, seam_d = (
+        None if a is None else guarded.inp(_t(np.asarray(a, F32)), DEV) for a in (ctrl, coef_a, coef_b, texture, gain, edges, soft, ring, diff, seamless))
     ramp = WR.inv_ramp(rows, feather)
     assert np.array_equal(ramp, G.compose_inv_ramp(rows, feather))
     for part in ([list(range(len(rows)))] if launches is None else launches):
         assert part == list(range(part[0], part[-1] + 1))
         sl = slice(part[0], part[-1] + 1)
         sub = rows[sl]
-        area = int(max(1, ((sub[:, 3] - sub[:, 1]) * (sub[:, 4] - sub[:, 2])).max())) if max_pixels is None else max_pixels
         lk = G.compose_links(sub) if links is None else links[sl]
-        ops.morph_u8(src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, dev(ops, sub), dev(ops, drows[sl]), dev(ops, lk), dev(ops, ramp[sl]),
-                     tex_d[sl], ctrl_d[sl], ca_d[sl], cb_d[sl], area)
+        common = (src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, dev(ops, sub), dev(ops, drows[sl]), dev(ops, lk), dev(ops, ramp[sl]), tex_d[sl],
+                  ctrl_d[sl], ca_d[sl], cb_d[sl])
+        area = box_area(sub) if max_pixels is None else max_pixels
+        g = None if gain is None else gain_d[sl]
+        if ring is not None:
+            ops.morph_seam_u8(*common, g, edges_d[sl], soft_d[sl], ring_d[sl], diff_d[sl], seam_d[sl], area)
+        elif edges is not None:
+            ops.morph_hull_u8(*common, g, edges_d[sl], soft_d[sl], area)
+        elif gain is not None:
+            ops.morph_colour_u8(*common, g, area)
+        else:
+            ops.morph_u8(*common, area)
     torch.cuda.synchronize()
     guarded.check_guards()
     assert np.array_equal(src.cpu().numpy(), buf), 'the source buffer is read only'
@@ -443,6 +460,47 @@ def test_detector_morph_with_its_own_landmarks(m128, scene):
         assert torch.equal(pw.coef, pm.coef_a) and torch.equal(pw.ctrl, pm.ctrl)
         assert all(torch.equal(x, y) for x, y in zip(out, want))
         assert not all(np.array_equal(o.cpu().numpy(), im) for o, im in zip(out, ims))
+
+
+def test_detector_morph_issues_the_parents_calls(ops, m128, scene):
+    """The library calls of one morph() call on the module's scene (seven rows, buckets of 4 and 3), by name and in order, against the lists
+    recorded from the commit in front of ops.morph_paste (landmarks given to both sides; in the last case the own side is staged and
+    runs its captured program), and the tensors handed to _join: everything on the device that the call returns, the PhotoMorph's
+    tensors and the photos' packed buffer, is among them, so the allocator cannot hand a result out again while the detector's stream
+    still works on it."""
+    from test_colour_gpu import _count_calls
+    cfg, model, eng, P, St = m128
+    ims, dons, lm_a, lm_b = scene
+    det = model.landmark_detector(S, max_batch=4)
+    n = len(SURFACE_BOXES)
+    assert [count for _s, count, _b in plan_buckets(n, 4)] == [4, 3]
+    base = dict(boxes=SURFACE_BOXES, donor_boxes=DONOR_BOXES, shape=np.linspace(0.0, 1.0, n).astype(F32), texture=0.8, donor_landmarks=lm_b,
+                return_transform=True)
+    hull, seam = dict(mask='hull'), dict(mask='hull', seamless=1.0, ring=16)
+    stats = ['imm_colour_stats_u8', 'imm_colour_stats_u8', 'imm_colour_gain']
+    cases = [
+        (dict(colour=0.0), ['imm_morph_poses', 'imm_warp_fit', 'imm_morph_u8'] * 2),
+        (dict(colour=0.0, **hull), ['imm_morph_poses', 'imm_hull_fit', 'imm_warp_fit', 'imm_morph_hull_u8'] * 2),
+        (dict(colour=0.0, **seam), ['imm_morph_poses', 'imm_hull_fit', 'imm_warp_fit', 'imm_seam_fit', 'imm_morph_seam_u8'] * 2),
+        (dict(colour=1.0), stats + ['imm_morph_poses', 'imm_warp_fit', 'imm_morph_colour_u8'] * 2),
+        (dict(colour=1.0, **hull), stats + ['imm_morph_poses', 'imm_hull_fit', 'imm_warp_fit', 'imm_morph_hull_u8'] * 2),
+        (dict(colour=1.0, **seam), stats + ['imm_morph_poses', 'imm_hull_fit', 'imm_warp_fit', 'imm_seam_fit', 'imm_morph_seam_u8'] * 2),
+        (dict(landmarks=None), ['imm_resize_crop_u8', 'imm_graph_launch', 'imm_morph_poses', 'imm_warp_fit', 'imm_morph_u8'] * 2)]
+    for kw, want in cases:
+        kw = dict(base, **dict(dict(landmarks=lm_a), **kw))
+        det.morph(ims, dons, **kw)                                             # (captures and allocations out of the way)
+        recorded, join0 = [], det._join
+        det._join = lambda cur, *record: (recorded.extend(t.data_ptr() for t in record if t is not None), join0(cur, *record))[1]
+        try:
+            (out, pm), calls = _count_calls(ops, lambda: det.morph(ims, dons, **kw))
+        finally:
+            del det._join
+        assert calls == want, kw
+        held = [getattr(pm, a) for a in ('coef_a', 'coef_b', 'ctrl', 'mu', 'donor_mu', 'poses', 'flags', 'colour_gain', 'colour_flags',
+                                         'hull_edges', 'hull_flags', 'seam_ring', 'seam_diff', 'seam_flags')]
+        assert sum(t is not None for t in held) == 7 + 2 * (kw.get('colour', 0.0) > 0) + 2 * ('mask' in kw) + 3 * ('ring' in kw)
+        assert all(t.is_cuda and t.data_ptr() in recorded for t in held if t is not None), kw
+        assert min(o.data_ptr() for o in out) in recorded, 'the packed buffer of the photos returned'
 
 
 def test_detector_morph_refusals(m128, scene):

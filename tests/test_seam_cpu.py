@@ -148,9 +148,9 @@ def test_plan_morph_checks_seamless_and_ring():
     donors = [np.zeros((20, 25, 3), np.uint8), np.zeros((35, 30), np.uint8)]
     good = dict(photos=photos, donors=donors, boxes=None, donor_boxes=None, shape=0.5, texture=None, feather=0.125, K=10)
     plan = MP.plan_morph(**good)
-    assert len(plan) == 15 and plan.seamless.tolist() == [0.0, 0.0] and plan.seamless.dtype == F32 and plan.ring == 128
+    assert len(vars(plan)) == 21 and plan.seamless.tolist() == [0.0, 0.0] and plan.seamless.dtype == F32 and plan.ring == 128
     plan = MP.plan_morph(mask='hull', seamless=[0.0, 1.0], ring=16, **good)
-    assert len(plan) == 15 and plan.seamless.tolist() == [0.0, 1.0] and plan.ring == 16 and plan.mask == 'hull'
+    assert len(vars(plan)) == 21 and plan.seamless.tolist() == [0.0, 1.0] and plan.ring == 16 and plan.mask == 'hull'
     assert MP.plan_morph(seamless=0.0, ring=256, **good).ring == 256, 'seamless = 0 needs no mask'
     for kw, match in ((dict(seamless=0.5), "needs mask='hull'"), (dict(seamless=[0.0, 0.01]), "needs mask='hull'"),
                       (dict(mask=None, seamless=1.0), "needs mask='hull'")):

@@ -19,15 +19,14 @@ import unalign_reference as UR                                               # n
 import warp_reference as WR                                                  # noqa: E402
 from alignment_reference import smooth_photo                                  # noqa: E402
 from dataset_fixtures import make_celeba_tree                                 # noqa: E402
-from test_colour_gpu import _count_calls, box_area                            # noqa: E402
+from test_colour_gpu import _count_calls                                      # noqa: E402
 from test_detector_gpu import _run_script, _write_config                      # noqa: E402
 from test_generator_gpu import make_model as make_generator_model             # noqa: E402
 from test_hull_gpu import run_hull_fit, run_hull_morph                        # noqa: E402
-from test_morph_gpu import DONOR_BOXES, DONOR_SIZES, device_fit, packed_mask, same_values      # noqa: E402
+from test_morph_gpu import DONOR_BOXES, DONOR_SIZES, device_fit, packed_mask, run_morph, same_values      # noqa: E402
 from test_unalign_gpu import SURFACE_BOXES, SURFACE_SIZES                     # noqa: E402
 from test_warp_gpu import dev                                                 # noqa: E402
 
-from imm_amd import generation as G                                           # noqa: E402
 from imm_amd.inference import plan_buckets                                    # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -71,32 +70,9 @@ def run_seam_fit(ops, photos, rows, donors, drows, poses, grow, edges, hflags, B
 
 def run_seam_morph(ops, photos, rows, donors, drows, ctrl, coef_a, coef_b, texture, feather, edges, soft, ring, diff, seamless, gain=None,
                    launches=None, links=None, max_pixels=None):
-    """test_hull_gpu.run_hull_morph for imm_morph_seam_u8: ring f32 [n, B, 2], diff f32 [n, B, 3] and seamless f32 [n] in guarded buffers
-    as well.  Returns (the whole canvas as a host array, the packed input)."""
-    buf, offs, hw = CR.pack(photos)
-    dbuf, doffs, dhw = CR.pack(donors)
-    guarded.reset()
-    src, don = guarded.inp(_t(buf), DEV), guarded.inp(_t(dbuf), DEV)
-    canvas = guarded.out(buf.shape, torch.uint8, DEV, fill=_t(buf))
-    offs_d, hw_d, doffs_d, dhw_d = dev(ops, offs), dev(ops, hw), dev(ops, doffs), dev(ops, dhw)
-    ctrl_d, ca_d, cb_d, edges_d, soft_d, tex_d, ring_d, diff_d, seam_d = (
-        guarded.inp(_t(np.asarray(a, F32)), DEV) for a in (ctrl, coef_a, coef_b, edges, soft, texture, ring, diff, seamless))
-    gain_d = None if gain is None else guarded.inp(_t(np.asarray(gain, F32)), DEV)
-    ramp = WR.inv_ramp(rows, feather)
-    for part in ([list(range(len(rows)))] if launches is None else launches):
-        assert part == list(range(part[0], part[-1] + 1))
-        sl = slice(part[0], part[-1] + 1)
-        sub = rows[sl]
-        area = box_area(sub) if max_pixels is None else max_pixels
-        lk = G.compose_links(sub) if links is None else links[sl]
-        ops.morph_seam_u8(src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, dev(ops, sub), dev(ops, drows[sl]), dev(ops, lk), dev(ops, ramp[sl]),
-                          tex_d[sl], ctrl_d[sl], ca_d[sl], cb_d[sl], None if gain is None else gain_d[sl], edges_d[sl], soft_d[sl],
-                          ring_d[sl], diff_d[sl], seam_d[sl], area)
-    torch.cuda.synchronize()
-    guarded.check_guards()
-    assert np.array_equal(src.cpu().numpy(), buf), 'the source buffer is read only'
-    assert np.array_equal(don.cpu().numpy(), dbuf), 'the donor buffer is read only'
-    return canvas.cpu().numpy(), buf
+    """test_morph_gpu.run_morph for imm_morph_seam_u8: ring f32 [n, B, 2], diff f32 [n, B, 3] and seamless f32 [n] as well."""
+    return run_morph(ops, photos, rows, donors, drows, ctrl, coef_a, coef_b, texture, feather, launches, links, max_pixels=max_pixels,
+                     gain=gain, edges=edges, soft=soft, ring=ring, diff=diff, seamless=seamless)
 
 
 def case_gains(n):

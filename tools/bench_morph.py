@@ -95,30 +95,25 @@ def main(args):
     coef2, ctrl2 = torch.empty(2 * B, M + 3, 2, device='cuda:0'), torch.empty(2 * B, M, 2, device='cuda:0')
     flags2 = torch.empty(2 * B, dtype=torch.int32, device='cuda:0')
     ops.morph_poses(pm.mu, pm.donor_mu, shape_d, poses2, mu2)
+
+    def paste_args(q):
+        """ops.morph_paste's sixteen leading arguments: the buffers above with the splines of the PhotoMorph q."""
+        return src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, boxes_d, dboxes_d, links_d, ramp_d, texture_d, q.ctrl, q.coef_a, q.coef_b, area
+
     if args.colour:
-        return colour_leg(args, det, photos, donors, boxes, dboxes, rows, drows, pm, props, lambda gain: ops.morph_colour_u8(
-            src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, boxes_d, dboxes_d, links_d, ramp_d, texture_d, pm.ctrl, pm.coef_a, pm.coef_b, gain,
-            area), lambda: ops.morph_u8(src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, boxes_d, dboxes_d, links_d, ramp_d, texture_d, pm.ctrl,
-                                        pm.coef_a, pm.coef_b, area), (src, offs_d, hw_d, boxes_d), (don, doffs_d, dhw_d, dboxes_d), area)
+        return colour_leg(args, det, photos, donors, boxes, dboxes, rows, drows, pm, props, paste_args, (src, offs_d, hw_d, boxes_d),
+                          (don, doffs_d, dhw_d, dboxes_d), area)
     if args.mask:
-        return mask_leg(args, det, photos, donors, boxes, dboxes, props, mid, poses2, lambda q, edges, soft: ops.morph_hull_u8(
-            src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, boxes_d, dboxes_d, links_d, ramp_d, texture_d, q.ctrl, q.coef_a, q.coef_b, None,
-            edges, soft, area), lambda q: ops.morph_u8(src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, boxes_d, dboxes_d, links_d, ramp_d,
-                                                       texture_d, q.ctrl, q.coef_a, q.coef_b, area), boxes_d)
+        return mask_leg(args, det, photos, donors, boxes, dboxes, props, mid, poses2, paste_args, boxes_d)
     if args.seamless:
-        return seam_leg(args, det, photos, donors, boxes, dboxes, props, mid, lambda q, soft: ops.morph_hull_u8(
-            src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, boxes_d, dboxes_d, links_d, ramp_d, texture_d, q.ctrl, q.coef_a, q.coef_b, None,
-            q.hull_edges, soft, area), lambda q, soft, amount: ops.morph_seam_u8(
-            src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, boxes_d, dboxes_d, links_d, ramp_d, texture_d, q.ctrl, q.coef_a, q.coef_b, None,
-            q.hull_edges, soft, q.seam_ring, q.seam_diff, amount, area), lambda q, grow, dirs, ring, diff, flags: ops.seam_fit(
+        return seam_leg(args, det, photos, donors, boxes, dboxes, props, mid, paste_args, lambda q, grow, dirs, ring, diff, flags: ops.seam_fit(
             q.poses, boxes_d, grow, q.hull_edges, q.hull_flags, dirs, src, offs_d, hw_d, don, doffs_d, dhw_d, dboxes_d, texture_d, q.ctrl,
             q.coef_a, q.coef_b, None, ring, diff, flags))
     fns = {'morph': lambda: det.morph(photos, donors, boxes, dboxes, shape=0.5, anchors=m, lam=LAM), 'dissolve': dissolve,
            'pack': lambda: (pack_u8(photos, 'cuda:0', rows)[0].clone(), pack_u8(donors, 'cuda:0', drows)),
            'poses': lambda: ops.morph_poses(pm.mu, pm.donor_mu, shape_d, poses2, mu2),
            'fit': lambda: ops.warp_fit(poses2.view(2 * B, K, 2), mu2.view(2 * B, K, 2), anchors_d, 1.0, LAM, coef2, ctrl2, flags2),
-           'u8': lambda: ops.morph_u8(src, canvas, offs_d, hw_d, don, doffs_d, dhw_d, boxes_d, dboxes_d, links_d, ramp_d, texture_d, pm.ctrl,
-                                      pm.coef_a, pm.coef_b, area)}
+           'u8': lambda: ops.morph_u8(*paste_args(pm))}
     ms = {k: [] for k in fns}
     for k, fn in fns.items():
         timed_ms(fn, 2, 1, args.warmup)
@@ -153,7 +148,7 @@ def main(args):
                       'poses_ms': med['poses'], 'fit_ms': med['fit'], 'u8_ms': med['u8'], 'flagged': flagged}))
 
 
-def colour_leg(args, det, photos, donors, boxes, dboxes, rows, drows, pm, props, colour_u8, plain_u8, own, donor, area):
+def colour_leg(args, det, photos, donors, boxes, dboxes, rows, drows, pm, props, paste_args, own, donor, area):
     """--colour: morph at colour = 1 against colour = 0 on the same photos in the same run, and the new launches alone."""
     import torch
     from bench_detect import timed_ms
@@ -168,7 +163,7 @@ def colour_leg(args, det, photos, donors, boxes, dboxes, rows, drows, pm, props,
            'stats_a': lambda: ops.colour_stats_u8(own[0], own[1], own[2], own[3], area, sums2[0]),
            'stats_b': lambda: ops.colour_stats_u8(donor[0], donor[1], donor[2], donor[3], darea, sums2[1]),
            'gain': lambda: ops.colour_gain(sums2[0], sums2[1], amount, 2.0, gain, cflags),
-           'u8': plain_u8, 'colour_u8': lambda: colour_u8(gain)}
+           'u8': lambda: ops.morph_u8(*paste_args(pm)), 'colour_u8': lambda: ops.morph_paste(*paste_args(pm), gain=gain)}
     ms = {k: [] for k in fns}
     for k, fn in fns.items():
         timed_ms(fn, 2, 1, args.warmup)
@@ -201,7 +196,7 @@ def colour_leg(args, det, photos, donors, boxes, dboxes, rows, drows, pm, props,
                       'stats_b_ms': med['stats_b'], 'gain_ms': med['gain'], 'u8_ms': med['u8'], 'colour_u8_ms': med['colour_u8']}))
 
 
-def mask_leg(args, det, photos, donors, boxes, dboxes, props, grid, poses2, hull_u8, plain_u8, boxes_d):
+def mask_leg(args, det, photos, donors, boxes, dboxes, props, grid, poses2, paste_args, boxes_d):
     """--mask: morph at mask = 'hull' against mask = None on the same photos in the same run, and the new launches alone."""
     import torch
     from bench_detect import timed_ms
@@ -226,8 +221,10 @@ def mask_leg(args, det, photos, donors, boxes, dboxes, props, grid, poses2, hull
            'grid None': lambda: det.morph(photos, donors, boxes, dboxes, **given),
            'grid hull': lambda: det.morph(photos, donors, boxes, dboxes, mask='hull', **given),
            'hull_fit': lambda: ops.hull_fit(poses2[0], boxes_d, grow_d, edges, hflags),
-           'u8': lambda: plain_u8(own), 'hull_u8': lambda: hull_u8(own, own.hull_edges, soft_d),
-           'grid u8': lambda: plain_u8(grd), 'grid hull_u8': lambda: hull_u8(grd, grd.hull_edges, soft_d)}
+           'u8': lambda: ops.morph_u8(*paste_args(own)),
+           'hull_u8': lambda: ops.morph_paste(*paste_args(own), edges=own.hull_edges, inv_soft=soft_d),
+           'grid u8': lambda: ops.morph_u8(*paste_args(grd)),
+           'grid hull_u8': lambda: ops.morph_paste(*paste_args(grd), edges=grd.hull_edges, inv_soft=soft_d)}
     ms = {k: [] for k in fns}
     for k, fn in fns.items():
         timed_ms(fn, 2, 1, args.warmup)
@@ -262,7 +259,7 @@ def mask_leg(args, det, photos, donors, boxes, dboxes, props, grid, poses2, hull
                            'share_grid': share['grid'][0] / share['grid'][1]}, **{k.replace(' ', '_') + '_ms': v for k, v in med.items()})))
 
 
-def seam_leg(args, det, photos, donors, boxes, dboxes, props, grid, hull_u8, seam_u8, seam_fit):
+def seam_leg(args, det, photos, donors, boxes, dboxes, props, grid, paste_args, seam_fit):
     """--seamless: morph at seamless = 1 against seamless = 0 under the hull mask on the same photos in the same run, and the new
     launches alone."""
     import torch
@@ -280,13 +277,15 @@ def seam_leg(args, det, photos, donors, boxes, dboxes, props, grid, hull_u8, sea
     flagged = {ring: int((r.seam_flags != 0).sum()) for ring, r in runs.items()}
     grow_d, soft_d = ops.to_device_pinned(q.grow, 'cuda:0'), ops.to_device_pinned(q.inv_soft, 'cuda:0')
     amount = ops.to_device_pinned(np.ones(B, np.float32), 'cuda:0')
-    fns = {'hull': lambda: det.morph(photos, donors, boxes, dboxes, **given), 'hull_u8': lambda: hull_u8(q, soft_d)}
+    fns = {'hull': lambda: det.morph(photos, donors, boxes, dboxes, **given),
+           'hull_u8': lambda: ops.morph_paste(*paste_args(q), edges=q.hull_edges, inv_soft=soft_d)}
     for ring, r in runs.items():
         dirs = ops.to_device_pinned(MP.seam_dirs(ring), 'cuda:0')
         out = torch.empty(B, ring, 2, device='cuda:0'), torch.empty(B, ring, 3, device='cuda:0'), torch.empty(B, dtype=torch.int32, device='cuda:0')
         fns['seamless %d' % ring] = lambda ring=ring: det.morph(photos, donors, boxes, dboxes, seamless=1.0, ring=ring, **given)
         fns['seam_fit %d' % ring] = lambda r=r, dirs=dirs, out=out: seam_fit(r, grow_d, dirs, *out)
-        fns['seam_u8 %d' % ring] = lambda r=r: seam_u8(r, soft_d, amount)
+        fns['seam_u8 %d' % ring] = lambda r=r: ops.morph_paste(*paste_args(r), edges=r.hull_edges, inv_soft=soft_d, ring=r.seam_ring,
+                                                               diff=r.seam_diff, seamless=amount)
     ms = {k: [] for k in fns}
     for k, fn in fns.items():
         timed_ms(fn, 2, 1, args.warmup)
