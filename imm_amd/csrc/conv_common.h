@@ -1,6 +1,7 @@
 // conv_common.h — argument block and epilogue shared by the implicit-GEMM convolution kernels.
 #pragma once
 #include "common.h"
+#include "gfx950.h"
 
 struct ConvArgs {
   const uint16_t* x;

@@ -27,8 +27,8 @@ struct ConvFirstArgs {
   int n_patches, patches_x, patches_y;
 };
 
-// chunk swizzle of 64-byte rows (4 chunks): a ds_read_b128 of 16 consecutive rows x 4 chunks is conflict-free (conv_halo.hip)
-__device__ __forceinline__ int cf_swz(int row) { return ((row >> 2) & 1) << 1; }
+// chunk swizzle of 64-byte rows (4 chunks): swz4 (gfx950.h) — a ds_read_b128 of 16 consecutive rows x 4 chunks is conflict-free
+// (conv_halo.hip)
 
 // FULL: co == 32 (every shipped configuration) — compile-time: every lane then issues exactly MT*NT output stores per patch, which is
 // what makes the counted s_waitcnt of the loop exact.
@@ -42,10 +42,9 @@ __device__ __forceinline__ int cf_swz(int row) { return ((row >> 2) & 1) << 1; }
 // that alternate, and the loop waits with a counted vmcnt: after the four loads of patch k come the stores of patch k-2 (4), the
 // loads of patch k+1 (4) and the stores of patch k-1 (4) -> vmcnt(12) (8 / 4 for the first two patches).  (A version with the
 // halo by 4-byte LDS-DMA pieces was slower, 37 us: that path wants 16-byte pieces.)
-typedef __attribute__((ext_vector_type(4))) unsigned int cf_u32x4_t;
 // asynchronous: `dst` is valid only after an s_waitcnt that covers this load AND a cf_arrived() on it (which stops the compiler from
 // reading the register any earlier)
-__device__ __forceinline__ void cf_load(float& dst, cf_u32x4_t rsrc, uint32_t voff) {
+__device__ __forceinline__ void cf_load(float& dst, u32x4_t rsrc, uint32_t voff) {
   asm volatile("buffer_load_dword %0, %1, %2, 0 offen" : "=v"(dst) : "v"(voff), "s"(rsrc) : "memory");
 }
 __device__ __forceinline__ void cf_arrived(float& v) { asm volatile("" : "+v"(v) :: "memory"); }
@@ -78,7 +77,7 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const ConvFirstArgs a) 
     const int tap = row / CF_BN, n = row - tap * CF_BN;
     uint4 v = make_uint4(0, 0, 0, 0);
     if (n < a.co) v = *(const uint4*)(a.wt + (int64_t)n * a.kpad + tap * 32 + q * 8);
-    Wl[row * 4 + (q ^ cf_swz(row))] = v;
+    Wl[row * 4 + (q ^ swz4(row))] = v;
   }
   for (int idx = tid; idx < T_U4; idx += 256) Tl[idx] = make_uint4(0, 0, 0, 0);     // (chunk 3 of every pixel stays zero)
   for (int idx = tid; idx < (CF_TR * SROW + 8) / 2; idx += 256) ((uint32_t*)Sl)[idx] = 0u;
@@ -95,8 +94,7 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const ConvFirstArgs a) 
     e_off[u] = (r * S * 3 + t) * 4;                   // byte offset relative to the f32 element of halo pixel (0, 0)
     e_lds[u] = e < N_ELEM ? r * SROW + t : CF_TR * SROW + (tid & 7);      // (beyond the halo: a dump slot nobody reads)
   }
-  const uint64_t ia = (uint64_t)a.img;
-  const cf_u32x4_t ir = {(uint32_t)ia, (uint32_t)(ia >> 32) & 0xffffu, (uint32_t)((int64_t)a.batch * S * S * 12), 0x00020000u};
+  const u32x4_t ir = buffer_rsrc(a.img, (uint32_t)((int64_t)a.batch * S * S * 12));
   float bufA[N_LD], bufB[N_LD];                      // the halos of the next two patches of this workgroup, in flight
   auto issue_halo = [&](int patch, float (&buf)[N_LD]) __attribute__((always_inline)) {
     const bool real = patch < a.n_patches;
@@ -106,7 +104,7 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const ConvFirstArgs a) 
 #pragma unroll
     for (int u = 0; u < N_LD; ++u) {
       const bool ok = real && (unsigned)(y0 + e_r[u]) < (unsigned)S && (unsigned)(x0 + e_px[u]) < (unsigned)S;
-      cf_load(buf[u], ir, ok ? (uint32_t)(pbase + e_off[u]) : 0x80000000u);
+      cf_load(buf[u], ir, ok ? (uint32_t)(pbase + e_off[u]) : BUFFER_OOB);
     }
   };
   // operand-tile builder: this thread's chunks are (pixel (tid >> 2) + 64 u, q = tid & 3), u = 0 .. 3 (pixel < 224); source = 8
@@ -125,7 +123,7 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const ConvFirstArgs a) 
       bv[j][r] = (f_bias && n < a.co) ? a.bias[n] : 0.f;
     }
   // everything loaded so far (filter image, bias) has ARRIVED before the loop: its waits must not land inside it
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
 #pragma unroll
   for (int j = 0; j < NT; ++j)
 #pragma unroll
@@ -139,15 +137,15 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const ConvFirstArgs a) 
   auto do_patch = [&](const int it, float (&buf)[N_LD]) __attribute__((always_inline)) {
     const int patch = blockIdx.x + it * G;
     // the four loads of this patch have arrived (see the header for the counts)
-    if (!FULL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // (co < 32: the store count per patch varies — drain)
-    else if (it == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_LD) : "memory");
-    else if (it == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_LD + MT * NT) : "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_LD + 2 * MT * NT) : "memory");
+    if (!FULL) wait_vmcnt<0>();                  // (co < 32: the store count per patch varies — drain)
+    else if (it == 0) wait_vmcnt<N_LD>();
+    else if (it == 1) wait_vmcnt<N_LD + MT * NT>();
+    else wait_vmcnt<N_LD + 2 * MT * NT>();
 #pragma unroll
     for (int u = 0; u < N_LD; ++u) cf_arrived(buf[u]);
 #pragma unroll
     for (int u = 0; u < N_LD; ++u) Sl[e_lds[u]] = ET::from_f32(buf[u]);         // 16-bit halo (outside the image: zeros)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkmcnt0();
     __builtin_amdgcn_s_barrier();            // halo complete; every wave is past the previous patch's reads of the operand tile
     if (t_q < 3) {
 #pragma unroll
@@ -158,11 +156,11 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const ConvFirstArgs a) 
           const uint32_t w0 = (uint32_t)src[0] | ((uint32_t)src[1] << 16), w1 = (uint32_t)src[2] | ((uint32_t)src[3] << 16);
           uint32_t w2 = (uint32_t)src[4] | ((uint32_t)src[5] << 16), w3 = (uint32_t)src[6] | ((uint32_t)src[7] << 16);
           if (t_q == 2) { w2 &= 0xffffu; w3 = 0u; }      // channels 21, 22, 23 do not exist
-          Tl[pix * 4 + (t_q ^ cf_swz(pix))] = make_uint4(w0, w1, w2, w3);
+          Tl[pix * 4 + (t_q ^ swz4(pix))] = make_uint4(w0, w1, w2, w3);
         }
       }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkmcnt0();
     __builtin_amdgcn_s_barrier();            // tile complete (also: the filter image, first patch)
     issue_halo(patch + 2 * G, buf);          // two patches ahead (out-of-range offsets beyond the last patch: the count stays exact)
 
@@ -177,12 +175,12 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const ConvFirstArgs a) 
 #pragma unroll
       for (int i = 0; i < MT; ++i) {
         const int hp = (wid * MT + i + ky) * CF_PW + frow;
-        af[i] = Tl[hp * 4 + (fchunk ^ cf_swz(hp))];
+        af[i] = Tl[hp * 4 + (fchunk ^ swz4(hp))];
       }
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
         const int row = ky * CF_BN + j * 16 + frow;
-        bf[j] = Wl[row * 4 + (fchunk ^ cf_swz(row))];
+        bf[j] = Wl[row * 4 + (fchunk ^ swz4(row))];
       }
 #pragma unroll
       for (int i = 0; i < MT; ++i)
@@ -223,7 +221,7 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const ConvFirstArgs a) 
     do_patch(it, bufA);
     if (it + 1 < n_mine) do_patch(it + 1, bufB);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the trailing look-ahead loads
+  wait_vmcnt<0>();       // the trailing look-ahead loads
 #pragma unroll
   for (int u = 0; u < N_LD; ++u) { cf_arrived(bufA[u]); cf_arrived(bufB[u]); }
 

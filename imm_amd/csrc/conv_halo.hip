@@ -16,28 +16,18 @@
 #include "conv_common.h"
 #include <stdlib.h>
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-
 #define HALO_PH 8                 // patch rows
 #define HALO_PW 16                // patch cols (= MFMA operand rows)
 #define HALO_HW (HALO_PW + 2)     // halo width 18
 #define HALO_HP 192               // halo pixels (10*18 = 180) padded to a whole number of DMA instructions
 
-__device__ __forceinline__ void halo_dma16(u32x4_t rsrc, uint32_t lds_addr, uint32_t voff, uint32_t soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :: "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
-
-// Chunk swizzle that keeps a ds_read_b128 of 16 CONSECUTIVE rows (any start offset: the nine taps shift the pixel
-// index by 0/1/2 and by the halo pitch) x 4 chunks conflict-free.  16-byte slot of (row r, stored chunk c') is
+// halo_swz<C8> (gfx950.h) is the chunk swizzle that keeps a ds_read_b128 of 16 CONSECUTIVE rows (any start offset: the nine taps
+// shift the pixel index by 0/1/2 and by the halo pitch) x 4 chunks conflict-free.  16-byte slot of (row r, stored chunk c') is
 // (r*C8 + c') mod 16; the instruction is served in 16-lane groups {rows 0-3,12-15 @ chunk c, rows 4-11 @ chunk c^1}.
 //   C8 = 8 (128-B rows): rows of equal parity share 8 slots; XOR bits 1-2 of the chunk with (r>>1)&3: the four
 //     rows {0,1,6,7}+q of one parity/chunk get 4 different values, bit 0 separates chunk c from c^1.
 //   C8 = 4 (64-B rows): rows equal mod 4 share 4 slots; XOR bit 1 with (r>>2)&1: the two rows (r, r+12) resp.
 //     (r+4, r+8) of a class differ, bit 0 again separates the two chunks.
-template <int C8>
-__device__ __forceinline__ int halo_swz(int row) { return C8 == 8 ? (((row >> 1) & 3) << 1) : (((row >> 2) & 1) << 1); }
 
 struct HaloArgs {
   ConvArgs c;
@@ -85,10 +75,7 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(const HaloArgs ha) {
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WGN, wn = wid % WGN;
-  constexpr uint32_t OOB = 0x80000000u;
-  const uint64_t xa = (uint64_t)a.x, wa = (uint64_t)a.wt;
-  const u32x4_t xr = {(uint32_t)xa, (uint32_t)(xa >> 32) & 0xffffu, a.x_bytes, 0x00020000u};
-  const u32x4_t wr = {(uint32_t)wa, (uint32_t)(wa >> 32) & 0xffffu, a.wt_bytes, 0x00020000u};
+  const u32x4_t xr = buffer_rsrc(a.x, a.x_bytes), wr = buffer_rsrc(a.wt, a.wt_bytes);
   const uint32_t lds_base = (uint32_t)(size_t)(lds_void_t*)smem;
 
   // ---- filter: all nine taps resident for the lifetime of the workgroup -----------------------------------
@@ -97,8 +84,8 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(const HaloArgs ha) {
     const int row = i * PIX_PER_DMA + lane / C8;          // tap*BN + n
     const int tap = row / BN, n = row - tap * BN;
     const int sc = (lane % C8) ^ halo_swz<C8>(row);
-    const uint32_t vo = (n < a.co) ? (uint32_t)((n * a.kpad + tap * CI) * 2 + sc * 16) : OOB;
-    halo_dma16(wr, __builtin_amdgcn_readfirstlane(lds_base + (uint32_t)(i * 1024)), vo, 0u);
+    const uint32_t vo = (n < a.co) ? (uint32_t)((n * a.kpad + tap * CI) * 2 + sc * 16) : BUFFER_OOB;
+    lds_dma16(wr, __builtin_amdgcn_readfirstlane(lds_base + (uint32_t)(i * 1024)), vo, 0u);
   }
 
   // ---- normalise on load: per-chunk coefficient table + this thread's halo pieces (DMA instruction wid + 4k, 16 bytes each) ----
@@ -151,8 +138,8 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(const HaloArgs ha) {
         ok = (hp < (HALO_PH + 2) * HALO_HW) && ((unsigned)iy < (unsigned)a.hi) && ((unsigned)ix < (unsigned)a.wi);
       }
       const int sc = (lane % C8) ^ halo_swz<C8>(hp);
-      const uint32_t vo = ok ? (uint32_t)((iy * a.wi + ix) * a.ldx * 2 + sc * 16) : OOB;
-      halo_dma16(xr, __builtin_amdgcn_readfirstlane(lds_base + (uint32_t)((W_U4 + stage * H_U4) * 16 + i * 1024)), vo, soff);
+      const uint32_t vo = ok ? (uint32_t)((iy * a.wi + ix) * a.ldx * 2 + sc * 16) : BUFFER_OOB;
+      lds_dma16(xr, __builtin_amdgcn_readfirstlane(lds_base + (uint32_t)((W_U4 + stage * H_U4) * 16 + i * 1024)), vo, soff);
     }
   };
 
@@ -182,10 +169,10 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(const HaloArgs ha) {
   constexpr int N_STORES = MT * NT * NCLS;                 // store instructions per wave and patch
   bool first = true;
   for (; patch < ha.n_patches; patch += gridDim.x) {
-    if (counted && !first) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_STORES) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's share of the filter / this patch's halo landed
+    if (counted && !first) wait_vmcnt<N_STORES>();
+    else wait_vmcnt<0>();  // this wave's share of the filter / this patch's halo landed
     first = false;
-    if constexpr (NOL) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (first patch: the coefficient table)
+    if constexpr (NOL) wait_lgkmcnt0();   // (first patch: the coefficient table)
     __builtin_amdgcn_s_barrier();                          // => everyone's share; everyone is done with the other stage
     if (patch + (int)gridDim.x < ha.n_patches && !(a.flags & IMM_DBG_NO_GLOAD)) issue_halo(patch + gridDim.x, stage ^ 1);
     const uint4* Hl = smem + W_U4 + stage * H_U4;
@@ -214,7 +201,7 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(const HaloArgs ha) {
           *slot = pack8<ET>(f);
         }
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      wait_lgkmcnt0();
       __builtin_amdgcn_s_barrier();                        // the normalised tile is complete
     }
 
@@ -343,7 +330,7 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(const HaloArgs ha) {
 
   if (f_stats) {
     // per-workgroup partial sums: 16 pixel lanes -> wave rows -> one row of stats per workgroup
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();
     float* red = (float*)(smem + W_U4);     // halo stages are free now: [WGM][2][BN]
 #pragma unroll

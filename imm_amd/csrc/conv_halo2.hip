@@ -23,14 +23,10 @@
 #include "conv_common.h"
 #include <stdlib.h>
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-
 #define H2_PH 8                 // patch rows
 #define H2_PW 16                // patch cols (= MFMA operand rows)
 #define H2_HW (H2_PW + 2)       // halo width 18
 #define H2_HP 192               // halo pixels (10*18 = 180) padded to a whole number of DMA instructions
-#define H2_OOB 0x80000000u      // buffer offset beyond every extent: loads return zero, stores are dropped
 
 struct Halo2Args {
   ConvArgs c;
@@ -39,24 +35,9 @@ struct Halo2Args {
   int lg_px, lg_pi;                       // log2(patches_x), log2(patches per image), or -1 when not powers of two
 };
 
-__device__ __forceinline__ void h2_dma16(u32x4_t rsrc, uint32_t lds_addr, uint32_t voff, uint32_t soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :: "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
-__device__ __forceinline__ void h2_store16(u32x4_t rsrc, u32x4_t data, uint32_t voff, uint32_t soff) {
-  // The trailing s_nop 1 is REQUIRED (round 5): a VMEM store of more than 64 bits reads its data registers over the cycles after
-  // issue, and hipcc — which does not know what is inside an asm statement — pads no wait states behind it; without them its next
-  // VALU instruction may overwrite v[data] before the store has read it (cdna_hip_programming.md §5.7 "Stores").  Seen as a
-  // 0.3 % rate of corrupted 16-byte outputs of the ci = 64 instantiations (358 registers, the data registers are reused at once)
-  // whenever a second process shared the GPU — the flaky two-rank test of rounds 3-5 (tools/det_graph.py reproduces it).
-  asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen\n\ts_nop 1" :: "v"(data), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
-
-// same chunk swizzle as conv_halo.hip: a ds_read_b128 of 16 consecutive halo pixels (any start) is conflict-free
-template <int C8>
-__device__ __forceinline__ int h2_swz(int row) { return C8 == 8 ? (((row >> 1) & 3) << 1) : (((row >> 2) & 1) << 1); }
-
-template <int V> struct H2Int { static constexpr int value = V; };
+// Loop VMEM ops: lds_dma16 and store16 (gfx950.h; store16 carries the round-5 wait-state fix found in this kernel).
+// Chunk swizzle: halo_swz<C8> (gfx950.h), the same as conv_halo.hip: a ds_read_b128 of 16 consecutive halo pixels (any start)
+// is conflict-free.
 
 // halo pixel slots of one LDS stage: (8 + kh - 1) x (16 + kw - 1) pixels, rounded up so that the tile is a whole number
 // of 1-KB DMA instructions per wave (4 waves)
@@ -65,11 +46,7 @@ __host__ __device__ constexpr int h2_halo_slots(int ci, int kh, int kw) {
   return ((H2_PH + kh - 1) * (H2_PW + kw - 1) + per_round - 1) / per_round * per_round;
 }
 
-// sched_group_barrier masks (LLVM AMDGPU): the MFMA loop of a halo row is laid out as "1 MFMA + up to 3 other issues"
-#define H2_SG_VALU 0x002
-#define H2_SG_SALU 0x004
-#define H2_SG_MFMA 0x008
-#define H2_SG_DSREAD 0x100
+// sched_group_barrier (masks SG_*: gfx950.h): the MFMA loop of a halo row is laid out as "1 MFMA + up to 3 other issues"
 
 template <typename ET, int CI, int BN, bool MASK, bool STATS, int NS, int KH = 3, int KW = 3>
 __global__ __launch_bounds__(256) void conv_halo2_kernel(const Halo2Args ha) {
@@ -99,10 +76,7 @@ __global__ __launch_bounds__(256) void conv_halo2_kernel(const Halo2Args ha) {
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);      // scalar: LDS-DMA destinations are wave-uniform
   const int wm = wid / WGN, wn = wid % WGN;
   const int frow = lane & 15, q = lane >> 4;
-  const uint64_t xa = (uint64_t)a.x, ya = (uint64_t)a.y, ma = (uint64_t)a.mask;
-  const u32x4_t xr = {(uint32_t)xa, (uint32_t)(xa >> 32) & 0xffffu, a.x_bytes, 0x00020000u};
-  const u32x4_t yr = {(uint32_t)ya, (uint32_t)(ya >> 32) & 0xffffu, ha.y_bytes, 0x00020000u};
-  const u32x4_t mr = {(uint32_t)ma, (uint32_t)(ma >> 32) & 0xffffu, ha.mask_bytes, 0x00020000u};
+  const u32x4_t xr = buffer_rsrc(a.x, a.x_bytes), yr = buffer_rsrc(a.y, ha.y_bytes), mr = buffer_rsrc(a.mask, ha.mask_bytes);
   const uint32_t lds_base = (uint32_t)(size_t)(lds_void_t*)smem;
   const int G = gridDim.x, per_img = ha.patches_x * ha.patches_y;
   // Patch order.  Workgroups are dealt round-robin to the 8 XCDs (private L2 each): give every XCD one contiguous
@@ -176,7 +150,7 @@ __global__ __launch_bounds__(256) void conv_halo2_kernel(const Halo2Args ha) {
   for (int k = 0; k < DH; ++k) {
     const int hp = (wid + 4 * k) * PIX_PER_DMA + lane / C8;        // halo slot 0..191
     const int hy = hp / HW, hx = hp - hy * HW;
-    const int sc = (lane % C8) ^ h2_swz<C8>(hx);
+    const int sc = (lane % C8) ^ halo_swz<C8>(hx);
     hyx[k] = ((hp < HROWS * HW ? hy : 0x4000) << 16) | hx;
     hrel[k] = (uint32_t)((hy * a.wi + hx) * a.ldx * 2 + sc * 16);
   }
@@ -189,11 +163,11 @@ __global__ __launch_bounds__(256) void conv_halo2_kernel(const Halo2Args ha) {
     uint32_t in_range = base + hrel[k];
     asm volatile("" : "+v"(in_range));        // keep the add unconditional: a select, not an exec-masked block
 #ifdef H2_ABLATE   // diagnosis builds only (tools/ablate_build.sh): bit 0 = no halo bytes move, bit 1 = no output bytes move
-    const uint32_t vo = (H2_ABLATE & 1) ? H2_OOB : (ok ? in_range : H2_OOB);
+    const uint32_t vo = (H2_ABLATE & 1) ? BUFFER_OOB : (ok ? in_range : BUFFER_OOB);
 #else
-    const uint32_t vo = ok ? in_range : H2_OOB;
+    const uint32_t vo = ok ? in_range : BUFFER_OOB;
 #endif
-    h2_dma16(xr, lds_base + (uint32_t)((stage * H_U4) * 16 + (wid + 4 * k) * 1024), vo, soff);
+    lds_dma16(xr, lds_base + (uint32_t)((stage * H_U4) * 16 + (wid + 4 * k) * 1024), vo, soff);
   };
   uint32_t mrel[DM > 0 ? DM : 1];
   if constexpr (MASK) {
@@ -208,8 +182,8 @@ __global__ __launch_bounds__(256) void conv_halo2_kernel(const Halo2Args ha) {
   auto mask_piece = [&](const Pd& d, int stage, int k) {
     if constexpr (MASK) {
       const uint32_t soff = (uint32_t)(d.img * a.ho * a.wo) * (uint32_t)(a.ldmask * 2);
-      const uint32_t vo = d.y0 < 0x4000 ? (uint32_t)((d.y0 * a.wo + d.x0) * a.ldmask * 2) + mrel[k] : H2_OOB;
-      h2_dma16(mr, lds_base + (uint32_t)((NS * H_U4 + stage * M_U4) * 16 + (wid + 4 * k) * 1024), vo, soff);
+      const uint32_t vo = d.y0 < 0x4000 ? (uint32_t)((d.y0 * a.wo + d.x0) * a.ldmask * 2) + mrel[k] : BUFFER_OOB;
+      lds_dma16(mr, lds_base + (uint32_t)((NS * H_U4 + stage * M_U4) * 16 + (wid + 4 * k) * 1024), vo, soff);
     }
   };
 
@@ -217,7 +191,7 @@ __global__ __launch_bounds__(256) void conv_halo2_kernel(const Halo2Args ha) {
   // halo row rr = + rr * ROWB, an immediate of the ds_read)
   int lrel[KW];
 #pragma unroll
-  for (int kx = 0; kx < KW; ++kx) lrel[kx] = wm * MT * ROWB + (frow + kx) * PIXB + (q ^ h2_swz<C8>(frow + kx)) * 16;
+  for (int kx = 0; kx < KW; ++kx) lrel[kx] = wm * MT * ROWB + (frow + kx) * PIXB + (q ^ halo_swz<C8>(frow + kx)) * 16;
   const int moff = frow * O8 + ((wn * 4 + q) ^ (frow & (O8 - 1)));   // + patch row * 16 * O8
   const uint32_t ovoff = (uint32_t)((frow * a.ldy + wn * 32 + q * 8) * 2);   // lane part of the output address
 
@@ -234,7 +208,7 @@ __global__ __launch_bounds__(256) void conv_halo2_kernel(const Halo2Args ha) {
 #pragma unroll
     for (int k = 0; k < DM; ++k) mask_piece(s >= 1 ? dq[s - 1] : none, s >= 1 ? s - 1 : NS - 1, k);
 #pragma unroll
-    for (int i = 0; i < MT; ++i) h2_store16(yr, zero4, H2_OOB, 0u);
+    for (int i = 0; i < MT; ++i) store16(yr, zero4, BUFFER_OOB, 0u);
   }
 
   f32x4_t acc[2][MT][NT];
@@ -243,7 +217,7 @@ __global__ __launch_bounds__(256) void conv_halo2_kernel(const Halo2Args ha) {
 #pragma unroll
     for (int j = 0; j < NT; ++j) acc[1][i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   int it = 0, hs = 0;                        // sequence index of this workgroup's patch, its halo stage (it % NS)
-  uint32_t prev_voff = H2_OOB, prev_soff = 0u;
+  uint32_t prev_voff = BUFFER_OOB, prev_soff = 0u;
   float prev_w = 0.f;                        // 1 when the previous patch exists (BN partial sums)
 
   // One patch: MFMA loop of patch `it` into acc[PH] with the epilogue of patch it-1 (acc[PH^1]) interleaved.
@@ -252,7 +226,7 @@ __global__ __launch_bounds__(256) void conv_halo2_kernel(const Halo2Args ha) {
     constexpr int PH = decltype(phase)::value;
     constexpr bool MMA = decltype(mma)::value;
     __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WAITN) : "memory");   // this wave's share of halo(it) and mask(it-1) landed
+    wait_vmcnt<WAITN>();   // this wave's share of halo(it) and mask(it-1) landed
     __builtin_amdgcn_s_barrier();                                  // => everyone's; stage it-1 is free for reuse
     __builtin_amdgcn_sched_barrier(0);
     const int hprev = hs == 0 ? NS - 1 : hs - 1;                   // (it-1) % NS
@@ -339,9 +313,9 @@ __global__ __launch_bounds__(256) void conv_halo2_kernel(const Halo2Args ha) {
         const uint4 o = pack8<ET>(v);
         const u32x4_t od = {o.x, o.y, o.z, o.w};
 #ifdef H2_ABLATE
-        h2_store16(yr, od, (H2_ABLATE & 2) ? H2_OOB : prev_voff + (uint32_t)((wm * MT + i) * a.wo * a.ldy * 2), prev_soff);
+        store16(yr, od, (H2_ABLATE & 2) ? BUFFER_OOB : prev_voff + (uint32_t)((wm * MT + i) * a.wo * a.ldy * 2), prev_soff);
 #else
-        h2_store16(yr, od, prev_voff + (uint32_t)((wm * MT + i) * a.wo * a.ldy * 2), prev_soff);
+        store16(yr, od, prev_voff + (uint32_t)((wm * MT + i) * a.wo * a.ldy * 2), prev_soff);
 #endif
       }
       if (rr == NR - 1) {
@@ -356,12 +330,12 @@ __global__ __launch_bounds__(256) void conv_halo2_kernel(const Halo2Args ha) {
         }
       }
       if constexpr (MMA) {
-        __builtin_amdgcn_sched_group_barrier(H2_SG_DSREAD, KW * KS, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_DSREAD, KW * KS, 0);
 #pragma unroll
         for (int m = 0; m < 36; ++m) {
           if (m < n_mfma) {
-            __builtin_amdgcn_sched_group_barrier(H2_SG_MFMA, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(H2_SG_VALU | H2_SG_SALU, 3, 0);
+            __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(SG_VALU | SG_SALU, 3, 0);
           }
         }
       }
@@ -372,13 +346,13 @@ __global__ __launch_bounds__(256) void conv_halo2_kernel(const Halo2Args ha) {
   };
   // patches p0 .. p_last (every workgroup has at least one), then one more pass that only stores p_last
   for (;;) {
-    step(H2Int<0>(), H2Int<1>());
-    if (dq[0].y0 >= 0x4000) { step(H2Int<1>(), H2Int<0>()); break; }
-    step(H2Int<1>(), H2Int<1>());
-    if (dq[0].y0 >= 0x4000) { step(H2Int<0>(), H2Int<0>()); break; }
+    step(Int<0>(), Int<1>());
+    if (dq[0].y0 >= 0x4000) { step(Int<1>(), Int<0>()); break; }
+    step(Int<1>(), Int<1>());
+    if (dq[0].y0 >= 0x4000) { step(Int<0>(), Int<0>()); break; }
   }
 
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // no LDS-DMA may outlive the workgroup
+  wait_vmcnt<0>();     // no LDS-DMA may outlive the workgroup
   if constexpr (STATS) {
     __syncthreads();
     float* red = (float*)smem;                         // [WGM][2][BN]
@@ -475,10 +449,7 @@ __global__ __launch_bounds__(256) void conv_halo2x_kernel(const Halo2Args ha) {
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid >> 1, wn = wid & 1;
   const int px = lane & 15, half = (lane >> 4) & 1, h5 = lane >> 5;
-  const uint64_t xa = (uint64_t)a.x, ya = (uint64_t)a.y, ma = (uint64_t)a.mask;
-  const u32x4_t xr = {(uint32_t)xa, (uint32_t)(xa >> 32) & 0xffffu, a.x_bytes, 0x00020000u};
-  const u32x4_t yr = {(uint32_t)ya, (uint32_t)(ya >> 32) & 0xffffu, ha.y_bytes, 0x00020000u};
-  const u32x4_t mr = {(uint32_t)ma, (uint32_t)(ma >> 32) & 0xffffu, ha.mask_bytes, 0x00020000u};
+  const u32x4_t xr = buffer_rsrc(a.x, a.x_bytes), yr = buffer_rsrc(a.y, ha.y_bytes), mr = buffer_rsrc(a.mask, ha.mask_bytes);
   const uint32_t lds_base = (uint32_t)(size_t)(lds_void_t*)smem;
   const int G = gridDim.x, per_img = ha.patches_x * ha.patches_y;
   const bool xcd_mode = (G & 7) == 0;
@@ -546,8 +517,8 @@ __global__ __launch_bounds__(256) void conv_halo2x_kernel(const Halo2Args ha) {
     const bool ok = ((unsigned)iy < (unsigned)a.hi) & ((unsigned)ix < (unsigned)a.wi);
     uint32_t in_range = base + hrel[k];
     asm volatile("" : "+v"(in_range));
-    const uint32_t vo = (H2X_ABLATE & 1) ? H2_OOB : (ok ? in_range : H2_OOB);
-    h2_dma16(xr, lds_base + (uint32_t)((stage * H_U4) * 16 + (wid + 4 * k) * 1024), vo, soff);
+    const uint32_t vo = (H2X_ABLATE & 1) ? BUFFER_OOB : (ok ? in_range : BUFFER_OOB);
+    lds_dma16(xr, lds_base + (uint32_t)((stage * H_U4) * 16 + (wid + 4 * k) * 1024), vo, soff);
   };
   uint32_t mrel[DM > 0 ? DM : 1];
   if constexpr (MASK) {
@@ -562,8 +533,8 @@ __global__ __launch_bounds__(256) void conv_halo2x_kernel(const Halo2Args ha) {
   auto mask_piece = [&](const Pd& d, int stage, int k) {
     if constexpr (MASK) {
       const uint32_t soff = (uint32_t)(d.img * a.ho * a.wo) * (uint32_t)(a.ldmask * 2);
-      const uint32_t vo = d.y0 < 0x4000 ? (uint32_t)((d.y0 * a.wo + d.x0) * a.ldmask * 2) + mrel[k] : H2_OOB;
-      h2_dma16(mr, lds_base + (uint32_t)((NS * H_U4 + stage * M_U4) * 16 + (wid + 4 * k) * 1024), vo, soff);
+      const uint32_t vo = d.y0 < 0x4000 ? (uint32_t)((d.y0 * a.wo + d.x0) * a.ldmask * 2) + mrel[k] : BUFFER_OOB;
+      lds_dma16(mr, lds_base + (uint32_t)((NS * H_U4 + stage * M_U4) * 16 + (wid + 4 * k) * 1024), vo, soff);
     }
   };
 
@@ -589,7 +560,7 @@ __global__ __launch_bounds__(256) void conv_halo2x_kernel(const Halo2Args ha) {
 #pragma unroll
     for (int k = 0; k < DM; ++k) mask_piece(s >= 1 ? dq[s - 1] : none, s >= 1 ? s - 1 : NS - 1, k);
 #pragma unroll
-    for (int i = 0; i < MT; ++i) h2_store16(yr, zero4, H2_OOB, 0u);
+    for (int i = 0; i < MT; ++i) store16(yr, zero4, BUFFER_OOB, 0u);
   }
 
   f32x16_t acc[2][2];                          // [accumulator set][tile]
@@ -598,13 +569,13 @@ __global__ __launch_bounds__(256) void conv_halo2x_kernel(const Halo2Args ha) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[1][t][r] = 0.f;
   int it = 0, hs = 0;
-  uint32_t prev_voff = H2_OOB, prev_soff = 0u;
+  uint32_t prev_voff = BUFFER_OOB, prev_soff = 0u;
 
   auto step = [&](auto phase, auto mma) {
     constexpr int PH = decltype(phase)::value;
     constexpr bool MMA = decltype(mma)::value;
     __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WAITN) : "memory");
+    wait_vmcnt<WAITN>();
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     const int hprev = hs == 0 ? NS - 1 : hs - 1;
@@ -671,7 +642,7 @@ __global__ __launch_bounds__(256) void conv_halo2x_kernel(const Halo2Args ha) {
         }
         const uint4 o = pack8<ET>(v);
         const u32x4_t od = {o.x, o.y, o.z, o.w};
-        h2_store16(yr, od, (H2X_ABLATE & 2) ? H2_OOB : prev_voff + (uint32_t)((wm * MT + t) * a.wo * a.ldy * 2 + ch * 16), prev_soff);
+        store16(yr, od, (H2X_ABLATE & 2) ? BUFFER_OOB : prev_voff + (uint32_t)((wm * MT + t) * a.wo * a.ldy * 2 + ch * 16), prev_soff);
       }
       if (u == NU - 1) {
         if constexpr (MMA) {
@@ -686,9 +657,9 @@ __global__ __launch_bounds__(256) void conv_halo2x_kernel(const Halo2Args ha) {
 #pragma unroll
         for (int m = 0; m < 2 * KS; ++m) {
           if (m < n_mfma) {
-            __builtin_amdgcn_sched_group_barrier(H2_SG_MFMA, 1, 0);
-            if (m < KS) __builtin_amdgcn_sched_group_barrier(H2_SG_DSREAD, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(H2_SG_VALU | H2_SG_SALU, 4, 0);
+            __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+            if (m < KS) __builtin_amdgcn_sched_group_barrier(SG_DSREAD, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(SG_VALU | SG_SALU, 4, 0);
           }
         }
       }
@@ -698,12 +669,12 @@ __global__ __launch_bounds__(256) void conv_halo2x_kernel(const Halo2Args ha) {
     ++it;
   };
   for (;;) {
-    step(H2Int<0>(), H2Int<1>());
-    if (dq[0].y0 >= 0x4000) { step(H2Int<1>(), H2Int<0>()); break; }
-    step(H2Int<1>(), H2Int<1>());
-    if (dq[0].y0 >= 0x4000) { step(H2Int<0>(), H2Int<0>()); break; }
+    step(Int<0>(), Int<1>());
+    if (dq[0].y0 >= 0x4000) { step(Int<1>(), Int<0>()); break; }
+    step(Int<1>(), Int<1>());
+    if (dq[0].y0 >= 0x4000) { step(Int<0>(), Int<0>()); break; }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // no LDS-DMA may outlive the workgroup
+  wait_vmcnt<0>();     // no LDS-DMA may outlive the workgroup
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -785,29 +756,29 @@ static void h2_dispatch(const imm_conv_desc* d, F&& f) {
   const bool mask = d->flags & IMM_CONV_MASK, stats = d->flags & IMM_CONV_STATS;
   const int ns = h2_ns(mask);
   if (d->kh == 7) {   // 7x1 first layer: 32 -> 32 channels
-    if (stats) f(H2Int<32>(), H2Int<32>(), H2Int<0>(), H2Int<1>(), H2Int<4>(), H2Int<7>(), H2Int<1>());
-    else f(H2Int<32>(), H2Int<32>(), H2Int<0>(), H2Int<0>(), H2Int<4>(), H2Int<7>(), H2Int<1>());
+    if (stats) f(Int<32>(), Int<32>(), Int<0>(), Int<1>(), Int<4>(), Int<7>(), Int<1>());
+    else f(Int<32>(), Int<32>(), Int<0>(), Int<0>(), Int<4>(), Int<7>(), Int<1>());
     return;
   }
   auto with_ns = [&](auto c, auto b, auto st) {
-    if (ns == 3) f(c, b, H2Int<0>(), st, H2Int<3>(), H2Int<3>(), H2Int<3>());
-    else f(c, b, H2Int<0>(), st, H2Int<4>(), H2Int<3>(), H2Int<3>());
+    if (ns == 3) f(c, b, Int<0>(), st, Int<3>(), Int<3>(), Int<3>());
+    else f(c, b, Int<0>(), st, Int<4>(), Int<3>(), Int<3>());
   };
   auto with_stats = [&](auto c, auto b) {
-    if (stats) with_ns(c, b, H2Int<1>()); else with_ns(c, b, H2Int<0>());
+    if (stats) with_ns(c, b, Int<1>()); else with_ns(c, b, Int<0>());
   };
   if (mask) {      // ci == co in {32, 64}: ReLU-backward mask (VGG conv1_2) and, with stats, the batch-norm backward sums
     auto with_mask = [&](auto c, auto st) {
-      if (ns == 3) f(c, c, H2Int<1>(), st, H2Int<3>(), H2Int<3>(), H2Int<3>());
-      else f(c, c, H2Int<1>(), st, H2Int<4>(), H2Int<3>(), H2Int<3>());
+      if (ns == 3) f(c, c, Int<1>(), st, Int<3>(), Int<3>(), Int<3>());
+      else f(c, c, Int<1>(), st, Int<4>(), Int<3>(), Int<3>());
     };
-    if (ci == 64) { if (stats) with_mask(H2Int<64>(), H2Int<1>()); else with_mask(H2Int<64>(), H2Int<0>()); }
-    else { if (stats) with_mask(H2Int<32>(), H2Int<1>()); else with_mask(H2Int<32>(), H2Int<0>()); }
+    if (ci == 64) { if (stats) with_mask(Int<64>(), Int<1>()); else with_mask(Int<64>(), Int<0>()); }
+    else { if (stats) with_mask(Int<32>(), Int<1>()); else with_mask(Int<32>(), Int<0>()); }
   }
-  else if (ci == 64 && co == 64) with_stats(H2Int<64>(), H2Int<64>());
-  else if (ci == 64) with_stats(H2Int<64>(), H2Int<32>());
-  else if (co == 64) with_stats(H2Int<32>(), H2Int<64>());
-  else with_stats(H2Int<32>(), H2Int<32>());
+  else if (ci == 64 && co == 64) with_stats(Int<64>(), Int<64>());
+  else if (ci == 64) with_stats(Int<64>(), Int<32>());
+  else if (co == 64) with_stats(Int<32>(), Int<64>());
+  else with_stats(Int<32>(), Int<32>());
 }
 
 // number of persistent workgroups (= rows of BN partial sums).  Queried on the bf16 instantiation: both element types

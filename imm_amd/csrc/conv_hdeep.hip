@@ -17,9 +17,6 @@
 #include <stdlib.h>
 #include <stdio.h>
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-
 #define HD_PW 16                         // patch width (= MFMA operand rows)
 #define HD_HW (HD_PW + 2)                // halo width 18
 // patch height PH = 16 (8 waves, 512 threads) or 8 (4 waves, 256 threads: half the tile, for grids that would
@@ -28,7 +25,6 @@ typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 #define HD_SLOTS(PH) (((PH) + 2) * HD_HW)            // halo pixels: 324 / 180
 #define HD_HINSTR(PH) ((HD_SLOTS(PH) + 7) / 8)       // DMA instructions (8 pixels x 128 B each): 41 / 23
 #define HD_HSTAGE(PH) (HD_HINSTR(PH) * 64)           // uint4 per halo stage
-#define HD_OOB 0x80000000u
 
 struct HdArgs {
   ConvArgs c;
@@ -38,12 +34,7 @@ struct HdArgs {
   unsigned long long* prof;              // IMM_HDEEP_PROF=1: wall-clock stamps of workgroup 0 / wave 0 (diagnosis only)
 };
 
-__device__ __forceinline__ void hd_dma16(u32x4_t rsrc, uint32_t lds_addr, uint32_t voff, uint32_t soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :: "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
-// halo pixel -> chunk swizzle (same as conv_halo2.hip): a ds_read_b128 of 16 consecutive pixels is conflict-free
-__device__ __forceinline__ int hd_swz(int hx) { return ((hx >> 1) & 3) << 1; }
+// halo pixel -> chunk swizzle: swz8 (gfx950.h; same as conv_halo2.hip): a ds_read_b128 of 16 consecutive pixels is conflict-free
 // Filter stage in LDS: row = output channel of the BN block (128 B = 8 chunks), chunk XOR-swizzled by hd_bswz.  The MFMA
 // B-operand row rho of tile j is NOT channel 16j + rho but channel (rho>>2)*4NT + 4j + (rho&3) of the wave's TN = 16 NT
 // channels: then a lane (which holds D rows 4q..4q+3 of every tile) owns 4NT CONSECUTIVE channels of its pixel — 16-byte
@@ -53,20 +44,6 @@ template <int NT>
 __device__ __forceinline__ int hd_bswz(int row) { return ((row >> 1) & 1) | (((row >> (NT == 4 ? 4 : 3)) & 3) << 1); }
 template <int NT>
 __device__ __forceinline__ int hd_bidx(int row, int chunk) { return row * 8 + (chunk ^ hd_bswz<NT>(row)); }
-
-template <int V> struct HdInt { static constexpr int value = V; };
-
-// total over each row of 16 lanes, in every lane: x += row_ror(x, 8), 4, 2, 1 — the rotation rides on the add (one VALU
-// instruction per step; s_nop 1 = the two wait states a DPP read needs after the VALU write of its source)
-__device__ __forceinline__ float hd_row_sum16(float x) {
-  float y;
-  asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
-               "s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
-               "s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_ror:2 row_mask:0xf bank_mask:0xf\n\t"
-               "s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_ror:1 row_mask:0xf bank_mask:0xf\n\ts_nop 1"
-               : "=&v"(y) : "v"(x));
-  return y;
-}
 
 // MAP8: the maps are 8x8 (VGG conv5 at 128x128 inputs): a workgroup tile is TWO whole images (each with its own 10x10
 // zero-padded halo), wave wm owns image wm, and an MFMA operand row of 16 pixels is two image rows of 8.
@@ -131,9 +108,7 @@ __global__ __launch_bounds__(NW * 64) void conv_hdeep_kernel(const HdArgs ha) {
   const int wm = wid >> 1, wn = wid & 1;
   const int frow = lane & 15, q = lane >> 4;
   const int per_img = ha.patches_x * ha.patches_y;
-  const uint64_t xa = (uint64_t)a.x, wa = (uint64_t)a.wt;
-  const u32x4_t xr = {(uint32_t)xa, (uint32_t)(xa >> 32) & 0xffffu, a.x_bytes, 0x00020000u};
-  const u32x4_t wr = {(uint32_t)wa, (uint32_t)(wa >> 32) & 0xffffu, a.wt_bytes, 0x00020000u};
+  const u32x4_t xr = buffer_rsrc(a.x, a.x_bytes), wr = buffer_rsrc(a.wt, a.wt_bytes);
   const uint32_t lds_base = (uint32_t)(size_t)(lds_void_t*)smem;
 
   // ---- tile state ----------------------------------------------------------------------------------------------------
@@ -166,7 +141,7 @@ __global__ __launch_bounds__(NW * 64) void conv_hdeep_kernel(const HdArgs ha) {
       else { hy = hp / HD_HW; hx = hp - hy * HD_HW; }
       const int iy = y0 - 1 + hy, ix = x0 - 1 + hx;
       const bool ok = hp < SLOTS && (unsigned)iy < (unsigned)a.hi && (unsigned)ix < (unsigned)a.wi && (!MAP8 || img + il < ha.n_img);
-      h_voff[k] = ok ? (uint32_t)(((il * a.hi + iy) * a.wi + ix) * a.ldx * 2 + (((lane & 7) ^ hd_swz(hx)) * 16)) : HD_OOB;
+      h_voff[k] = ok ? (uint32_t)(((il * a.hi + iy) * a.wi + ix) * a.ldx * 2 + (((lane & 7) ^ swz8(hx)) * 16)) : BUFFER_OOB;
     }
     h_soff = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(img * a.hi * a.wi) * (uint32_t)(a.ldx * 2)));
   };
@@ -174,7 +149,7 @@ __global__ __launch_bounds__(NW * 64) void conv_hdeep_kernel(const HdArgs ha) {
 #pragma unroll
     for (int j = 0; j < B_I; ++j) {
       const int r = (wid * B_I + j) * 8 + (lane >> 3);
-      bv[j] = (n0 + r < a.co) ? (uint32_t)((n0 + r) * a.kpad * 2 + (((lane & 7) ^ hd_bswz<NT>(r)) * 16)) : HD_OOB;
+      bv[j] = (n0 + r < a.co) ? (uint32_t)((n0 + r) * a.kpad * 2 + (((lane & 7) ^ hd_bswz<NT>(r)) * 16)) : BUFFER_OOB;
     }
   };
   const int ncc = a.ci8 >> 3;                          // 64-channel slices
@@ -186,14 +161,14 @@ __global__ __launch_bounds__(NW * 64) void conv_hdeep_kernel(const HdArgs ha) {
     const uint32_t soff = (uint32_t)((tp * (a.ci8 << 3) + cc * 64) * 2);
 #pragma unroll
     for (int j = 0; j < B_I; ++j)
-      hd_dma16(wr, lds_base + (uint32_t)((BRING_U4 + stage * B_U4 + (wid * B_I + j) * 64) * 16), real ? b_voff[j] : HD_OOB, soff);
+      lds_dma16(wr, lds_base + (uint32_t)((BRING_U4 + stage * B_U4 + (wid * B_I + j) * 64) * 16), real ? b_voff[j] : BUFFER_OOB, soff);
   };
   // halo piece k of slice cc of the loader's tile -> halo stage hs
   auto issue_halo_piece = [&](int cc, int hs, int k, bool real) {
     const int i = wid + NW * k;
     const bool exists = real && i < HINSTR;
     const uint32_t dst = exists ? (uint32_t)((hs * HSTAGE + i * 64) * 16) : (uint32_t)(DUMP_U4 * 16);
-    hd_dma16(xr, lds_base + dst, exists ? h_voff[k < NPIECE ? k : 0] : HD_OOB, h_soff + (uint32_t)(cc * 128));
+    lds_dma16(xr, lds_base + dst, exists ? h_voff[k < NPIECE ? k : 0] : BUFFER_OOB, h_soff + (uint32_t)(cc * 128));
   };
 
   const int G = PERSIST ? (int)gridDim.x : 1;
@@ -233,8 +208,8 @@ __global__ __launch_bounds__(NW * 64) void conv_hdeep_kernel(const HdArgs ha) {
   auto frag_offsets = [&]() {
 #pragma unroll
     for (int kx = 0; kx < 3; ++kx) {
-      if (MAP8) aoff[kx] = (wm * 100 + (frow >> 3) * 10 + (frow & 7) + kx) * 8 + (q ^ hd_swz((frow & 7) + kx));
-      else aoff[kx] = (wm * 4 * HD_HW + frow + kx) * 8 + (q ^ hd_swz(frow + kx));
+      if (MAP8) aoff[kx] = (wm * 100 + (frow >> 3) * 10 + (frow & 7) + kx) * 8 + (q ^ swz8((frow & 7) + kx));
+      else aoff[kx] = (wm * 4 * HD_HW + frow + kx) * 8 + (q ^ swz8(frow + kx));
     }
 #pragma unroll
     for (int j = 0; j < NT; ++j)
@@ -274,7 +249,7 @@ __global__ __launch_bounds__(NW * 64) void conv_hdeep_kernel(const HdArgs ha) {
 #pragma unroll
     for (int j = 0; j < NT; ++j) bf[ks][j] = Bs[boff[j][ks]];
   };
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"((ROW3 ? 6 : HD_NSB - 1) * B_I) : "memory");   // halo(0) and filter tap 0 (ROW3: row 0)
+  wait_vmcnt<(ROW3 ? 6 : HD_NSB - 1) * B_I>();   // halo(0) and filter tap 0 (ROW3: row 0)
   __builtin_amdgcn_s_barrier();
   read_frags(0, smem, smem + BRING_U4, 0, 0);
 
@@ -302,7 +277,7 @@ __global__ __launch_bounds__(NW * 64) void conv_hdeep_kernel(const HdArgs ha) {
         for (int j = 0; j < 6; ++j) {                  // k-step j of the row: tap (ky, kx = j / 2), channels 32 (j & 1) ..
           const int cur = j & 1;                      // tap (ky, j >> 1), channel half j & 1 = fragment buffer
           __builtin_amdgcn_sched_barrier(0);
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // fragments of k-step j are in registers
+          wait_lgkmcnt0();       // fragments of k-step j are in registers
           __builtin_amdgcn_sched_barrier(0);
           // (COL: the outer index `ky` of this loop nest is the filter COLUMN kx and (j >> 1) the row; stage = 3 outer + inner either way)
           if (j < 5) {
@@ -312,8 +287,8 @@ __global__ __launch_bounds__(NW * 64) void conv_hdeep_kernel(const HdArgs ha) {
           } else {
             // every fragment of this row has been read: its three stages are free; the next row's taps (requested one
             // slice = three rows ago) and, before the last row, the next slice's halo (requested after the first) must be in
-            if (ky == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * B_I + NPIECE) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * B_I) : "memory");
+            if (ky == 1) wait_vmcnt<3 * B_I + NPIECE>();
+            else wait_vmcnt<3 * B_I>();
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -335,9 +310,9 @@ __global__ __launch_bounds__(NW * 64) void conv_hdeep_kernel(const HdArgs ha) {
             for (int jj = 0; jj < NT; ++jj) acc[cls][i][jj] = ET::mfma(bf[cur][jj], af[cur][i + arow], acc[cls][i][jj]);
 #pragma unroll
           for (int m = 0; m < MT * NT; ++m) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x006, 2, 0);
+            __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(SG_DSREAD, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(SG_VALU | SG_SALU, 2, 0);
           }
         }
       }
@@ -365,7 +340,7 @@ __global__ __launch_bounds__(NW * 64) void conv_hdeep_kernel(const HdArgs ha) {
       const uint4* Bn = smem + BRING_U4 + nbs * B_U4;
 
       __builtin_amdgcn_sched_barrier(0);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      wait_lgkmcnt0();
       __builtin_amdgcn_sched_barrier(0);
       read_frags(1, Hc, Bc, ky, kx);
       const int cls = S2D ? ((ky & 1) * 2 + (kx & 1)) : 0;                                 // parity class of this tap
@@ -376,18 +351,18 @@ __global__ __launch_bounds__(NW * 64) void conv_hdeep_kernel(const HdArgs ha) {
       // issue order inside the region: 1 MFMA, 1 ds_read, <= 2 address ops, ... (non-MFMA issues ride in the pipe's shadow)
 #pragma unroll
       for (int m = 0; m < MT * NT; ++m) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x006, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_DSREAD, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_VALU | SG_SALU, 2, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      wait_lgkmcnt0();
       // first tile only: the prologue issued its filter taps back to back (no halo pieces in between)
-      if (it == 0 && t == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((HD_NSB - 2) * B_I) : "memory");          // taps 2.. in flight
-      else if (it == 0 && t == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((HD_NSB - 2) * B_I + 1) : "memory");
+      if (it == 0 && t == 0) wait_vmcnt<(HD_NSB - 2) * B_I>();          // taps 2.. in flight
+      else if (it == 0 && t == 1) wait_vmcnt<(HD_NSB - 2) * B_I + 1>();
       else if (it > 0 && t < HD_NSB - 1) { /* taps 1 .. NSB-1 landed before the previous tile's epilogue (drain below): no wait, so
                                               that its output stores get NSB-1 taps to be acknowledged before a counted wait sees them */ }
-      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WN_STEADY) : "memory");
+      else wait_vmcnt<WN_STEADY>();
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
       HD_STAMP(3);
@@ -416,9 +391,9 @@ __global__ __launch_bounds__(NW * 64) void conv_hdeep_kernel(const HdArgs ha) {
       for (int m = 2 * QM; m < MT * NT; ++m) acc[cls][m % MT][m / MT] = ET::mfma(bf[1][m / MT], af[1][m % MT], acc[cls][m % MT][m / MT]);
 #pragma unroll
       for (int m = 0; m < 2 * QM; ++m) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x006, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_DSREAD, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_VALU | SG_SALU, 2, 0);
       }
       bs = nbs;
       ++t;
@@ -426,13 +401,13 @@ __global__ __launch_bounds__(NW * 64) void conv_hdeep_kernel(const HdArgs ha) {
   }
   HD_STAMP(4);
   if (!have_next) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // trailing no-op pieces: no LDS-DMA may outlive the workgroup
+    wait_lgkmcnt0();
+    wait_vmcnt<0>();   // trailing no-op pieces: no LDS-DMA may outlive the workgroup
     __syncthreads();
   } else {
     // the next tile's halo and first NSB filter taps (issued 0.5 .. NSB-0.5 taps ago) have landed: from here on only this
     // tile's output stores are outstanding, and the next tile's first NSB-1 taps need no counted wait
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
   }
   HD_STAMP(5);
   const int img = e_img, y0 = e_y0, x0 = e_x0, n0 = e_n0, patch = e_patch;
@@ -592,7 +567,7 @@ __global__ __launch_bounds__(NW * 64) void conv_hdeep_kernel(const HdArgs ha) {
 #pragma unroll
     for (int j = 0; j < NT; ++j)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) { s1[j][r] = hd_row_sum16(s1[j][r]); s2[j][r] = hd_row_sum16(s2[j][r]); }
+      for (int r = 0; r < 4; ++r) { s1[j][r] = row_sum16(s1[j][r]); s2[j][r] = row_sum16(s2[j][r]); }
     if (frow == 0) {
 #pragma unroll
       for (int j = 0; j < NT; ++j)
@@ -603,7 +578,7 @@ __global__ __launch_bounds__(NW * 64) void conv_hdeep_kernel(const HdArgs ha) {
           red[(wm * 2 + 1) * BN + nl] = s2[j][r];
         }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // LDS only: a __syncthreads would also drain the next tile's DMA
+    wait_lgkmcnt0();   // LDS only: a __syncthreads would also drain the next tile's DMA
     __builtin_amdgcn_s_barrier();
     if (tid < BN) {
       float t1 = 0.f, t2 = 0.f;

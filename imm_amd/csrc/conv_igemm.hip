@@ -92,12 +92,10 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int blo
   }
   uint4 ra[A_PASSES], rb[B_PASSES];
   const uint4 zero4 = make_uint4(0, 0, 0, 0);
-  typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 
   // ---- generic cursor (ci = 8 or 16): k8 = kt*4 + chunk -> (tap=(ky,kx), c8), per lane ----------------
   int c8 = chunk, tap = 0, ky = 0, kx = 0;
   // ---- fast path state --------------------------------------------------------------------------------
-  constexpr uint32_t OOB = 0x80000000u;
   uint32_t a_voff[A_PASSES], b_voff[B_PASSES];
   int cs = 0;                               // channel slice of the current tap (uniform)
   const int ncs = a.ci8 >> 2;
@@ -109,21 +107,21 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int blo
       bool ok = true;
       if (a.updiv == 2) { ok = (((iy | ix) & 1) == 0); iy >>= 1; ix >>= 1; }
       ok = ok && ((unsigned)iy < (unsigned)a.hi) && ((unsigned)ix < (unsigned)a.wi);
-      a_voff[i] = ok ? (uint32_t)((((int)pbase[i] + iy * a.wi + ix) * a.ldx + chunk * 8) * 2) : OOB;
+      a_voff[i] = ok ? (uint32_t)((((int)pbase[i] + iy * a.wi + ix) * a.ldx + chunk * 8) * 2) : BUFFER_OOB;
     }
   };
   if constexpr (FAST) {
-    xr = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
-    wr = __builtin_amdgcn_make_buffer_rsrc((void*)a.wt, 0, a.wt_bytes, 0x00020000);
+    xr = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, BUFFER_RSRC_FLAGS);
+    wr = __builtin_amdgcn_make_buffer_rsrc((void*)a.wt, 0, a.wt_bytes, BUFFER_RSRC_FLAGS);
 #pragma unroll
     for (int j = 0; j < B_PASSES; ++j) {
       const int cidx = j * 256 + tid;
       const int n = n0 + (cidx >> 2);
-      b_voff[j] = (cidx < B_CHUNKS && n < a.co) ? (uint32_t)((n * a.kpad + chunk * 8) * 2) : OOB;
+      b_voff[j] = (cidx < B_CHUNKS && n < a.co) ? (uint32_t)((n * a.kpad + chunk * 8) * 2) : BUFFER_OOB;
     }
     if (a.flags & IMM_DBG_NO_GLOAD) {
 #pragma unroll
-      for (int j = 0; j < B_PASSES; ++j) b_voff[j] = OOB;
+      for (int j = 0; j < B_PASSES; ++j) b_voff[j] = BUFFER_OOB;
     }
     tap_offsets();
   } else {
@@ -135,7 +133,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int blo
       const int a_soff = cs * 64, b_soff = kt * 64;
 #pragma unroll
       for (int i = 0; i < A_PASSES; ++i) {
-        const uint32_t vo = (a.flags & IMM_DBG_NO_GLOAD) ? OOB : a_voff[i];
+        const uint32_t vo = (a.flags & IMM_DBG_NO_GLOAD) ? BUFFER_OOB : a_voff[i];
         const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(xr, vo, a_soff, 0);
         ra[i] = make_uint4(v.x, v.y, v.z, v.w);
       }

@@ -11,23 +11,9 @@
 #include "conv_common.h"
 #include <stdlib.h>
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-
 __device__ __forceinline__ int lds64_idx(int row, int chunk) { return row * 8 + (chunk ^ ((row >> 1) & 7)); }
 
-// One LDS-DMA instruction: 64 lanes x 16 B from buffer `rsrc` (+ per-lane voff + scalar soff; out-of-range lanes
-// deliver zeros) to LDS bytes [lds_addr, lds_addr + 1024).  Inline asm on purpose: hipcc models the builtin form
-// as an LDS write and drains vmcnt(0) in front of the next ds_read, which serialises the ring; an asm statement is
-// invisible to that bookkeeping, so the counted s_waitcnt below is the only wait.  M0 (LDS base of the DMA) is
-// written in the same statement that uses it (the compiler does not preserve M0 across statements).
-__device__ __forceinline__ void lds_dma16(u32x4_t rsrc, uint32_t lds_addr, uint32_t voff, uint32_t soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :: "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
-
-// NS-stage LDS ring: tile kt+NS-1 is DMA'd while tile kt feeds the MFMAs.  Ordering per K step (raw
+// NS-stage LDS ring: tile kt+NS-1 is DMA'd (lds_dma16, gfx950.h) while tile kt feeds the MFMAs.  Ordering per K step (raw
 // s_barrier, counted vmcnt -- a __syncthreads() would drain the DMA queue to zero):
 //   s_waitcnt vmcnt((NS-2)*LPT)   this wave's share of tile kt has landed (LPT = DMA instructions per tile per wave)
 //   s_barrier                     => every wave's share has landed, and every wave finished reading tile kt-1
@@ -55,10 +41,7 @@ __device__ __forceinline__ void conv_igemm64_body(const ConvArgs& a, int bid_in)
   const int nblk = bid % a.n_nblk, mblk = bid / a.n_nblk;
   const int m0 = mblk * BM, n0 = nblk * BN;
 
-  constexpr uint32_t OOB = 0x80000000u;
-  const uint64_t xa = (uint64_t)a.x, wa = (uint64_t)a.wt;
-  const u32x4_t xr = {(uint32_t)xa, (uint32_t)(xa >> 32) & 0xffffu, a.x_bytes, 0x00020000u};
-  const u32x4_t wr = {(uint32_t)wa, (uint32_t)(wa >> 32) & 0xffffu, a.wt_bytes, 0x00020000u};
+  const u32x4_t xr = buffer_rsrc(a.x, a.x_bytes), wr = buffer_rsrc(a.wt, a.wt_bytes);
   const uint32_t lds_base = (uint32_t)(size_t)(lds_void_t*)smem;
 
   // ---- loader state: this lane's rows and source chunk --------------------------------------------------
@@ -85,7 +68,7 @@ __device__ __forceinline__ void conv_igemm64_body(const ConvArgs& a, int bid_in)
   for (int j = 0; j < B_INSTR; ++j) {
     const int r = (wid * B_INSTR + j) * 8 + lrow;
     const int n = n0 + r;
-    b_voff[j] = (n < a.co) ? (uint32_t)(n * a.kpad * 2 + (lchunk ^ ((r >> 1) & 7)) * 16) : OOB;
+    b_voff[j] = (n < a.co) ? (uint32_t)(n * a.kpad * 2 + (lchunk ^ ((r >> 1) & 7)) * 16) : BUFFER_OOB;
   }
   int ky = 0, kx = 0, cs = 0;           // wave-uniform tap walk; cs = 64-channel slice
   const int ncs = a.ci8 >> 3;
@@ -96,7 +79,7 @@ __device__ __forceinline__ void conv_igemm64_body(const ConvArgs& a, int bid_in)
       bool ok = true;
       if (a.updiv == 2) { ok = (((iy | ix) & 1) == 0); iy >>= 1; ix >>= 1; }
       ok = ok && ((unsigned)iy < (unsigned)a.hi) && ((unsigned)ix < (unsigned)a.wi);
-      a_voff[i] = ok ? (uint32_t)((pbase[i] + iy * a.wi + ix) * a.ldx * 2 + a_coff[i]) : OOB;
+      a_voff[i] = ok ? (uint32_t)((pbase[i] + iy * a.wi + ix) * a.ldx * 2 + a_coff[i]) : BUFFER_OOB;
     }
   };
   tap_offsets();
@@ -130,8 +113,8 @@ __device__ __forceinline__ void conv_igemm64_body(const ConvArgs& a, int bid_in)
   int stage = 0;
   for (int kt = 0; kt < a.KT; ++kt) {
     // tiles kt .. min(kt+NS-2, KT-1) are in flight; tile kt must have landed
-    if (kt + NS - 2 < a.KT) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * LPT) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (kt + NS - 2 < a.KT) wait_vmcnt<(NS - 2) * LPT>();
+    else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     {
       const int nt = kt + NS - 1;

@@ -23,10 +23,6 @@
 // for the landmark detector whose batch norm is folded into W and b, the ReLU.
 #include "conv_common.h"
 #include <stdlib.h>
-#include <type_traits>
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 
 #define S2_PH 8
 #define S2_PW 16
@@ -36,40 +32,15 @@ typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 #define S2_HINSTR 37                            // DMA instructions per halo stage (16 slots x 64 B each)
 #define S2_HSTAGE (S2_HINSTR * 1024)            // 37 888 B
 #define S2_RUNB (S2_RP * 64)                    // bytes per (row, parity) run: 1 088
-#define S2_OOB 0x80000000u
 
 struct S2fArgs {
   ConvArgs c;
   int n_patches, patches_x, patches_y, n_wg;
 };
 
-template <int I, int N, typename F>
-__device__ __forceinline__ void s2_static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    s2_static_for<I + 1, N>(f);
-  }
-}
-
-__device__ __forceinline__ void s2_dma16(u32x4_t rsrc, uint32_t lds_addr, uint32_t voff, uint32_t soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :: "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
-// 64-byte LDS rows: chunk ^= 2 * bit 2 of the slot's column (halo) / 2 * bit 4 of the filter row — a ds_read_b128 lane group
-// ({0-3, 12-15, 20-27}, ...; MI355X_MICROARCH.md) then hits 16 distinct 16-byte slots mod 256 B (checked by enumeration)
-__device__ __forceinline__ int s2_aswz(int j) { return ((j >> 2) & 1) << 1; }
+// 64-byte LDS rows: chunk ^= 2 * bit 2 of the slot's column (halo: swz4, gfx950.h) / 2 * bit 4 of the filter row — a ds_read_b128
+// lane group ({0-3, 12-15, 20-27}, ...; MI355X_MICROARCH.md) then hits 16 distinct 16-byte slots mod 256 B (checked by enumeration)
 __device__ __forceinline__ int s2_bswz(int r) { return ((r >> 4) & 1) << 1; }
-
-// total over each row of 16 lanes, in every lane (DPP row rotations; conv_hdeep.hip)
-__device__ __forceinline__ float s2_row_sum16(float x) {
-  float y;
-  asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
-               "s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
-               "s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_ror:2 row_mask:0xf bank_mask:0xf\n\t"
-               "s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_ror:1 row_mask:0xf bank_mask:0xf\n\ts_nop 1"
-               : "=&v"(y) : "v"(x));
-  return y;
-}
 
 template <typename ET, int BN>
 __global__ __launch_bounds__(BN * 4) void conv_s2f_kernel(const S2fArgs ha) {
@@ -87,9 +58,7 @@ __global__ __launch_bounds__(BN * 4) void conv_s2f_kernel(const S2fArgs ha) {
   __builtin_assume(wid >= 0 && wid < NW);
   const int wm = wid & 1, wn = wid >> 1;
   const int frow = lane & 15, q = lane >> 4;
-  const uint64_t xa = (uint64_t)a.x, wa = (uint64_t)a.wt;
-  const u32x4_t xr = {(uint32_t)xa, (uint32_t)(xa >> 32) & 0xffffu, a.x_bytes, 0x00020000u};
-  const u32x4_t wr = {(uint32_t)wa, (uint32_t)(wa >> 32) & 0xffffu, a.wt_bytes, 0x00020000u};
+  const u32x4_t xr = buffer_rsrc(a.x, a.x_bytes), wr = buffer_rsrc(a.wt, a.wt_bytes);
   const uint32_t lds_base = (uint32_t)(size_t)(lds_void_t*)smem;
   const int ci = a.ci8 << 3;
   const int nsl = ci >> 5;                             // 32-channel slices
@@ -116,22 +85,22 @@ __global__ __launch_bounds__(BN * 4) void conv_s2f_kernel(const S2fArgs ha) {
     const int r = rp >> 1, p = rp & 1;
     const int iy = 2 * y0 + r, ix = 2 * x0 + 2 * j + p;
     const bool ok = s < S2_SLOTS && (p == 0 || j < 16) && iy < a.hi && ix < a.wi;
-    h_voff[k] = ok ? (uint32_t)((iy * a.wi + ix) * a.ldx * 2 + (((lane & 3) ^ s2_aswz(j)) * 16)) : S2_OOB;
+    h_voff[k] = ok ? (uint32_t)((iy * a.wi + ix) * a.ldx * 2 + (((lane & 3) ^ swz4(j)) * 16)) : BUFFER_OOB;
   }
   const uint32_t h_soff = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(img * a.hi * a.wi) * (uint32_t)(a.ldx * 2)));
   uint32_t b_voff;
   {
     const int r = wid * 16 + (lane >> 2);              // filter row of the BN block: one DMA instruction per wave and stage
-    b_voff = (n0 + r < a.co) ? (uint32_t)((n0 + r) * a.kpad * 2 + (((lane & 3) ^ s2_bswz(r)) * 16)) : S2_OOB;
+    b_voff = (n0 + r < a.co) ? (uint32_t)((n0 + r) * a.kpad * 2 + (((lane & 3) ^ s2_bswz(r)) * 16)) : BUFFER_OOB;
   }
   auto dma_b = [&](int sl, int tp, bool real) {        // filter tap tp of slice sl -> stage tp
     const uint32_t soff = (uint32_t)((tp * ci + sl * 32) * 2);
-    s2_dma16(wr, lds_base + (uint32_t)(real ? RING + tp * BSTAGE + wid * 1024 : DUMP), real ? b_voff : S2_OOB, soff);
+    lds_dma16(wr, lds_base + (uint32_t)(real ? RING + tp * BSTAGE + wid * 1024 : DUMP), real ? b_voff : BUFFER_OOB, soff);
   };
   auto dma_h = [&](int sl, int hs, int k, bool real) {   // halo piece k of slice sl -> halo stage hs
     const int i = wid + NW * k;
     const bool ex = real && i < S2_HINSTR;
-    s2_dma16(xr, lds_base + (uint32_t)(ex ? hs * S2_HSTAGE + i * 1024 : DUMP), ex ? h_voff[k] : S2_OOB, h_soff + (uint32_t)(sl * 64));
+    lds_dma16(xr, lds_base + (uint32_t)(ex ? hs * S2_HSTAGE + i * 1024 : DUMP), ex ? h_voff[k] : BUFFER_OOB, h_soff + (uint32_t)(sl * 64));
   };
 
   // ---- prologue: bias (inline asm, ahead of the DMA: see conv_hdeep6.hip), halo of slice 0, the nine taps of slice 0 ------------
@@ -154,7 +123,7 @@ __global__ __launch_bounds__(BN * 4) void conv_s2f_kernel(const S2fArgs ha) {
   uint32_t aoff[2], boff;
 #pragma unroll
   for (int sh = 0; sh < 2; ++sh)
-    aoff[sh] = (uint32_t)(((16 * wm * S2_RP + frow + sh) * 4 + (q ^ s2_aswz(frow + sh))) * 16);
+    aoff[sh] = (uint32_t)(((16 * wm * S2_RP + frow + sh) * 4 + (q ^ swz4(frow + sh))) * 16);
   {
     const int r = wn * 32 + (frow >> 2) * 8 + (frow & 3);
     boff = (uint32_t)(RING + (r * 4 + (q ^ s2_bswz(r))) * 16);
@@ -188,7 +157,7 @@ __global__ __launch_bounds__(BN * 4) void conv_s2f_kernel(const S2fArgs ha) {
   const int nss = nsl >> 1;
   for (int ss = 0; ss < nss; ++ss) {
     const bool more_pairs = ss + 1 < nss;
-    s2_static_for<0, 18>([&](auto uc) __attribute__((always_inline)) {
+    static_for<0, 18>([&](auto uc) __attribute__((always_inline)) {
       constexpr int u = decltype(uc)::value;
       constexpr int h = u / 9, t = u % 9, ky = t / 3, kx = t % 3, cur = u & 1;
       const int sl = 2 * ss + h;                                   // this k-step's slice; its halo sits in stage h
@@ -199,7 +168,7 @@ __global__ __launch_bounds__(BN * 4) void conv_s2f_kernel(const S2fArgs ha) {
       constexpr int wslot = kx == 2 ? 0 : kx + 1;
       constexpr int wrow = kx == 2 ? ky : (ky + 2) % 3;            // the row the window's barrier freed
       S2_FENCE();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // fragments of this tap are in registers
+      wait_lgkmcnt0();          // fragments of this tap are in registers
       S2_FENCE();
       if constexpr (kx < 2) {
         read_frags(cur ^ 1, h, ky, kx + 1);
@@ -208,7 +177,7 @@ __global__ __launch_bounds__(BN * 4) void conv_s2f_kernel(const S2fArgs ha) {
         // issued since are outstanding: 3 filter stages, plus the next slice's whole halo in the window of a slice's FIRST barrier
         // (it — and the refilled row 0 — must be in at the slice's LAST barrier: the next slice starts right behind it)
         constexpr int allow = ky == 1 ? 3 + NPIECE : 3;
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(allow) : "memory");
+        wait_vmcnt<allow>();
         __builtin_amdgcn_s_barrier();
         S2_FENCE();
         if constexpr (ky == 2) {
@@ -220,8 +189,8 @@ __global__ __launch_bounds__(BN * 4) void conv_s2f_kernel(const S2fArgs ha) {
       S2_MFMA(cur, 0, 4);
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_DSREAD, 2, 0);
       }
       S2_FENCE();
       // the window's pieces of this slot.  Windows opened in this slice load slice sl + 1; the window of the previous slice's last
@@ -251,7 +220,7 @@ __global__ __launch_bounds__(BN * 4) void conv_s2f_kernel(const S2fArgs ha) {
   }
 #undef S2_MFMA
 #undef S2_FENCE
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // trailing dummy pieces: no LDS-DMA may outlive the workgroup
+  wait_vmcnt<0>();     // trailing dummy pieces: no LDS-DMA may outlive the workgroup
   __syncthreads();
 
   // ---- epilogue: lane = pixel (row 4 wm + i, col frow), 8 consecutive channels; bias is in the accumulators ----------------------
@@ -285,7 +254,7 @@ __global__ __launch_bounds__(BN * 4) void conv_s2f_kernel(const S2fArgs ha) {
 #pragma unroll
     for (int j = 0; j < NT; ++j)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) { s1[j][r] = s2_row_sum16(s1[j][r]); s2[j][r] = s2_row_sum16(s2[j][r]); }
+      for (int r = 0; r < 4; ++r) { s1[j][r] = row_sum16(s1[j][r]); s2[j][r] = row_sum16(s2[j][r]); }
     if (frow == 0) {
 #pragma unroll
       for (int j = 0; j < NT; ++j)

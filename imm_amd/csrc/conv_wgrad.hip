@@ -11,6 +11,7 @@
 // The pixel range is split over `nsplit` blocks per tile; each writes its f32 partial tile to
 // slab[split][kpad][co]; imm_conv2d_wgrad_reduce sums slabs in a fixed order (deterministic).
 #include "common.h"
+#include "gfx950.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -81,8 +82,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
   const bool b_ok = (g < BN / 8) && (n0 + g * 8 < a.lddy);   // dY channel group inside the row
   uint4 ra[PSUB][2], rb[PSUB][2];
   const uint4 zero4 = make_uint4(0, 0, 0, 0);
-  typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-  constexpr uint32_t OOB = 0x80000000u;
 
   // ---- generic pixel cursor (per lane) ---------------------------------------------------------------
   int pcur = p_begin + 2 * pp;
@@ -102,8 +101,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
     const int rem0 = p_begin - s_img * hw;
     s_y0 = rem0 / a.wo;
     s_x0 = rem0 - s_y0 * a.wo;
-    xr = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
-    dr = __builtin_amdgcn_make_buffer_rsrc((void*)a.dy, 0, a.dy_bytes, 0x00020000);
+    xr = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, BUFFER_RSRC_FLAGS);
+    dr = __builtin_amdgcn_make_buffer_rsrc((void*)a.dy, 0, a.dy_bytes, BUFFER_RSRC_FLAGS);
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int j = 2 * pp + q;
@@ -111,7 +110,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
       const int jx = (a.wo >= 32) ? j : j - jy * a.wo;
       cy[q] = jy * a.stride - a.pad_t + a_ky;
       cx[q] = jx * a.stride - a.pad_l + a_kx;
-      b_voff[q] = b_ok ? (uint32_t)((j * a.lddy + n0 + g * 8) * 2) : OOB;
+      b_voff[q] = b_ok ? (uint32_t)((j * a.lddy + n0 + g * 8) * 2) : BUFFER_OOB;
     }
   }
 
@@ -124,7 +123,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
       for (int q = 0; q < 2; ++q) {
         const int iy = ys + cy[q], ix = xs + cx[q];
         const bool ok = a_ok && ((unsigned)iy < (unsigned)a.hi) && ((unsigned)ix < (unsigned)a.wi);
-        const uint32_t vo = ok ? (uint32_t)(((iy * a.wi + ix) * a.ldx + a_c8 * 8) * 2) : OOB;
+        const uint32_t vo = ok ? (uint32_t)(((iy * a.wi + ix) * a.ldx + a_c8 * 8) * 2) : BUFFER_OOB;
         const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(xr, vo, a_soff, 0);
         ra[u][q] = make_uint4(v.x, v.y, v.z, v.w);
         const u32x4_t w = __builtin_amdgcn_raw_buffer_load_b128(dr, b_voff[q], b_soff, 0);

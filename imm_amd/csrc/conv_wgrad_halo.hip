@@ -22,8 +22,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
 typedef __attribute__((address_space(3))) s16x4_t lds_s16x4_t;
 
@@ -49,10 +47,6 @@ typedef __attribute__((address_space(3))) s16x4_t lds_s16x4_t;
 #define WH_S2_PP 160
 #define WH_S2_HP 640
 
-__device__ __forceinline__ void wh_dma16(u32x4_t rsrc, uint32_t lds_addr, uint32_t voff, uint32_t soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :: "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
 // Chunk swizzle of an LDS image [pixel][C8 chunks of 16 B], for the 8-byte transpose reads.  A 32-lane half of such a read takes
 // EIGHT pixels of one image row — x..x+3 and x+8..x+11 — times 32 bytes (16 channels), and the LDS serves 256 B = its 64 banks
 // per pass: the eight 32-byte windows must differ modulo 256 B.  Pixel stride 128 B (64 channels): even and odd pixels already
@@ -105,10 +99,7 @@ __device__ __forceinline__ void conv_wgrad_halo_body(const WgradHaloArgs& a, con
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wc = wid % WC, wn = wid / WC;
   const int ci0 = by * CI, co0 = bz * CO;     // channel slice of this workgroup
-  constexpr uint32_t OOB = 0x80000000u;
-  const uint64_t xa = (uint64_t)a.x, ya = (uint64_t)a.dy;
-  const u32x4_t xr = {(uint32_t)xa, (uint32_t)(xa >> 32) & 0xffffu, a.x_bytes, 0x00020000u};
-  const u32x4_t yr = {(uint32_t)ya, (uint32_t)(ya >> 32) & 0xffffu, a.dy_bytes, 0x00020000u};
+  const u32x4_t xr = buffer_rsrc(a.x, a.x_bytes), yr = buffer_rsrc(a.dy, a.dy_bytes);
   const uint32_t lds_base = (uint32_t)(size_t)(lds_void_t*)smem;
   const int per_img = a.patches_x * a.patches_y;
 
@@ -166,12 +157,12 @@ __device__ __forceinline__ void conv_wgrad_halo_body(const WgradHaloArgs& a, con
 #pragma unroll
     for (int u = 0; u < XU; ++u) {
       const bool ok = ((unsigned)(py + x_iy[u]) < (unsigned)h_in) && ((unsigned)(px + x_ix[u]) < (unsigned)w_in);
-      const uint32_t vo = ok ? (uint32_t)(x_rel[u] + poff) : OOB;
-      wh_dma16(xr, __builtin_amdgcn_readfirstlane(lds_stage + (uint32_t)(u * 4096)), vo, xs);
+      const uint32_t vo = ok ? (uint32_t)(x_rel[u] + poff) : BUFFER_OOB;
+      lds_dma16(xr, __builtin_amdgcn_readfirstlane(lds_stage + (uint32_t)(u * 4096)), vo, xs);
     }
 #pragma unroll
     for (int u = 0; u < YU; ++u)
-      wh_dma16(yr, __builtin_amdgcn_readfirstlane(lds_stage + (uint32_t)(X_BYTES + u * 4096)), y_rel[u], ys);
+      lds_dma16(yr, __builtin_amdgcn_readfirstlane(lds_stage + (uint32_t)(X_BYTES + u * 4096)), y_rel[u], ys);
   };
 
   f32x4_t acc[NTAP][TNT];
@@ -211,9 +202,9 @@ __device__ __forceinline__ void conv_wgrad_halo_body(const WgradHaloArgs& a, con
     // patches it .. min(it+NS-2, n_mine-1) are in flight; patch `it` must have landed (this wave's share, then everyone's)
     constexpr int ABL = IMM_WH_ABLATE;
     if (!(ABL & 16) || it == 0) {
-      if (it + NS - 2 < n_mine) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * LPP) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (nol) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (first patch: the coefficient table)
+      if (it + NS - 2 < n_mine) wait_vmcnt<(NS - 2) * LPP>();
+      else wait_vmcnt<0>();
+      if (nol) wait_lgkmcnt0();      // (first patch: the coefficient table)
       __builtin_amdgcn_s_barrier();
     }
     if (it + NS - 1 < n_mine && !(ABL & 1)) {      // into the stage patch it-1 occupied: every wave is past its reads (the barrier above)
@@ -247,7 +238,7 @@ __device__ __forceinline__ void conv_wgrad_halo_body(const WgradHaloArgs& a, con
           *slot = pack8<ET>(f);
         }
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      wait_lgkmcnt0();
       __builtin_amdgcn_s_barrier();
     }
 

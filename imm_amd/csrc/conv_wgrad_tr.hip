@@ -12,11 +12,10 @@
 // tools/probes/tr_read_probe.hip).  No VGPR staging, no ds_write, no packing.
 // Requires the wave-uniform pixel walk (ho*wo % 32 == 0, wo | 32 or 32 | wo) and ci % 8 == 0.
 #include "common.h"
+#include "gfx950.h"
 #include <stdlib.h>
 #include <string.h>
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
 typedef __attribute__((address_space(3))) s16x4_t lds_s16x4_t;
 
@@ -27,11 +26,6 @@ struct WgradTrArgs {
   int n_kblk, n_nblk, nsplit, p_per_split;
   uint32_t x_bytes, dy_bytes;
 };
-
-__device__ __forceinline__ void wt_dma16(u32x4_t rsrc, uint32_t lds_addr, uint32_t voff, uint32_t soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :: "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
 
 // chunk swizzle by pixel row for an LDS image with CB 16-byte chunks per row: the 8 pixels x 32 bytes that one
 // 32-lane half of a transpose read touches must fall into 8 different 32-byte bank windows of the 256-byte bank row
@@ -75,10 +69,7 @@ __device__ __forceinline__ void conv_wgrad_tr_body(const WgradTrArgs& a, int bid
   const int p_end = min(a.P, p_begin + a.p_per_split);
   const int nsteps = (p_end - p_begin) / 32;                 // P and p_per_split are multiples of 32
 
-  constexpr uint32_t OOB = 0x80000000u;
-  const uint64_t xa = (uint64_t)a.x, ya = (uint64_t)a.dy;
-  const u32x4_t xr = {(uint32_t)xa, (uint32_t)(xa >> 32) & 0xffffu, a.x_bytes, 0x00020000u};
-  const u32x4_t yr = {(uint32_t)ya, (uint32_t)(ya >> 32) & 0xffffu, a.dy_bytes, 0x00020000u};
+  const u32x4_t xr = buffer_rsrc(a.x, a.x_bytes), yr = buffer_rsrc(a.dy, a.dy_bytes);
   const uint32_t lds_base = (uint32_t)(size_t)(lds_void_t*)smem;
   const uint32_t dummy_lds = lds_base + (uint32_t)(NS * STAGE);
 
@@ -111,7 +102,7 @@ __device__ __forceinline__ void conv_wgrad_tr_body(const WgradTrArgs& a, int bid
     const int p = q * B_PPI + lane / CB;
     const int c = (lane % CB) ^ wt_swz<CB>(p);
     const int n = n0 + c * 8;
-    b_voff[i] = (b_real[i] && n < a.lddy) ? (uint32_t)((p * a.lddy + n) * 2) : OOB;
+    b_voff[i] = (b_real[i] && n < a.lddy) ? (uint32_t)((p * a.lddy + n) * 2) : BUFFER_OOB;
   }
   // wave-uniform walk of the 32-pixel step origin
   int s_img, s_y0, s_x0, s_p0 = p_begin;
@@ -132,14 +123,14 @@ __device__ __forceinline__ void conv_wgrad_tr_body(const WgradTrArgs& a, int bid
     for (int i = 0; i < A_PER_WAVE; ++i) {
       const int iy = ys + a_cy[i], ix = xs + a_cx[i];
       const bool ok = a_ok[i] && ((unsigned)iy < (unsigned)a.hi) && ((unsigned)ix < (unsigned)a.wi);
-      const uint32_t vo = ok ? (uint32_t)((iy * a.wi + ix) * a.ldx * 2 + a_coff[i]) : OOB;
-      wt_dma16(xr, __builtin_amdgcn_readfirstlane(st + (uint32_t)((wid * A_PER_WAVE + i) * 1024)), vo, a_soff);
+      const uint32_t vo = ok ? (uint32_t)((iy * a.wi + ix) * a.ldx * 2 + a_coff[i]) : BUFFER_OOB;
+      lds_dma16(xr, __builtin_amdgcn_readfirstlane(st + (uint32_t)((wid * A_PER_WAVE + i) * 1024)), vo, a_soff);
     }
 #pragma unroll
     for (int i = 0; i < B_PER_WAVE; ++i) {
       const uint32_t vo = b_voff[i];
       const uint32_t dst = b_real[i] ? st + (uint32_t)(A_BYTES + (wid * B_PER_WAVE + i) * 1024) : dummy_lds;
-      wt_dma16(yr, __builtin_amdgcn_readfirstlane(dst), vo, b_soff);
+      lds_dma16(yr, __builtin_amdgcn_readfirstlane(dst), vo, b_soff);
     }
     s_p0 += 32;
     if (a.wo >= 32) { s_x0 += 32; if (s_x0 == a.wo) { s_x0 = 0; ++s_y0; } }
@@ -167,8 +158,8 @@ __device__ __forceinline__ void conv_wgrad_tr_body(const WgradTrArgs& a, int bid
   // help either: NS = 6 / 8 instead of 4: 3.555 -> 3.655 ms, 38.7 -> 54 us on that layer.)
   int stage = 0;
   for (int st = 0; st < nsteps; ++st) {
-    if (st + NS - 2 < nsteps) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * LPT) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (st + NS - 2 < nsteps) wait_vmcnt<(NS - 2) * LPT>();
+    else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     {
       int ns = stage + NS - 1; if (ns >= NS) ns -= NS;

@@ -22,13 +22,9 @@
 #include "conv_common.h"
 #include <stdlib.h>
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-
 #define VH_PH 8
 #define VH_PW 16
 #define VH_HW 18
-#define VH_OOB 0x80000000u
 #define VH_GROW 24                  // gray patch row: image columns x0-4 .. x0+19 (16-byte aligned pieces)
 #define VH_GSTAGE_U4 256            // one gray stage: 4 waves x 1 KB (72 pieces of 16 B used)
 #define VH_HSTAGE_U4 (192 * 8)      // one halo stage: 192 pixel slots x 128 B
@@ -45,22 +41,8 @@ struct VhArgs {
   uint32_t gray_bytes, act_bytes;
 };
 
-__device__ __forceinline__ void vh_dma16(u32x4_t rsrc, uint32_t lds_addr, uint32_t voff, uint32_t soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :: "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
-// (the trailing s_nop 1: conv_halo2.hip h2_store16 — a > 64-bit store reads its data registers after issue)
-__device__ __forceinline__ void vh_store16(u32x4_t rsrc, u32x4_t data, uint32_t voff, uint32_t soff) {
-  asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen\n\ts_nop 1" :: "v"(data), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
-__device__ __forceinline__ int vh_swz(int hx) { return ((hx >> 1) & 3) << 1; }
-
-template <int V> struct VhInt { static constexpr int value = V; };
-
-#define VH_SG_VALU 0x002
-#define VH_SG_SALU 0x004
-#define VH_SG_MFMA 0x008
-#define VH_SG_DSREAD 0x100
+// Loop VMEM ops: lds_dma16 and store16 of gfx950.h (store16's trailing s_nop 1: a > 64-bit store reads its data registers after
+// issue); halo chunk swizzle: swz8, as in conv_halo2.hip.
 
 // normalised gray image as (hi, lo) pairs of the activation type (the VALU expression of vgg_conv1_1_fwd_kernel, bit for bit)
 template <typename ET>
@@ -95,10 +77,7 @@ __global__ __launch_bounds__(256) void conv_halo2_vgg_head_kernel(const VhArgs h
   const int wm = wid >> 1, wn = wid & 1;
   const int frow = lane & 15, q = lane >> 4;
   const int S = ha.s;
-  const uint64_t ga = (uint64_t)ha.gray, ya = (uint64_t)ha.y12, aa = (uint64_t)ha.a11;
-  const u32x4_t gr = {(uint32_t)ga, (uint32_t)(ga >> 32) & 0xffffu, ha.gray_bytes, 0x00020000u};
-  const u32x4_t yr = {(uint32_t)ya, (uint32_t)(ya >> 32) & 0xffffu, ha.act_bytes, 0x00020000u};
-  const u32x4_t ar = {(uint32_t)aa, (uint32_t)(aa >> 32) & 0xffffu, ha.act_bytes, 0x00020000u};
+  const u32x4_t gr = buffer_rsrc(ha.gray, ha.gray_bytes), yr = buffer_rsrc(ha.y12, ha.act_bytes), ar = buffer_rsrc(ha.a11, ha.act_bytes);
   const uint32_t lds_base = (uint32_t)(size_t)(lds_void_t*)smem;
   const int G = gridDim.x, per_img = ha.patches_x * ha.patches_y;
   // patch order: conv_halo2.hip (one contiguous band of patches per XCD, walked side by side by its workgroups)
@@ -195,7 +174,7 @@ __global__ __launch_bounds__(256) void conv_halo2_vgg_head_kernel(const VhArgs h
     const int hy = hp / VH_HW, hx = hp - hy * VH_HW;
     p_hyx[k] = ((hp < (VH_PH + 2) * VH_HW ? hy : 0x40) << 8) | hx;
     p_gb[k] = hy * VH_GROW + hx + 2;
-    p_hw[k] = hp * PIXB + ((q ^ vh_swz(hx)) << 4);
+    p_hw[k] = hp * PIXB + ((q ^ swz8(hx)) << 4);
     p_ar[k] = ((hy - 1) * S + (hx - 1)) * (CI * 2) + q * 16;
   }
 #pragma unroll
@@ -211,8 +190,8 @@ __global__ __launch_bounds__(256) void conv_halo2_vgg_head_kernel(const VhArgs h
     const bool ok = (g_piece < 72) & ((unsigned)iy < (unsigned)S) & ((unsigned)ix < (unsigned)S);
     uint32_t in_range = (uint32_t)((iy * S + ix) * 4);
     asm volatile("" : "+v"(in_range));
-    const uint32_t vo = ok ? in_range : VH_OOB;
-    vh_dma16(gr, lds_base + (uint32_t)((2 * H_U4 + slot * VH_GSTAGE_U4) * 16 + wid * 1024), vo, (uint32_t)(d.img * S * S) * 4u);
+    const uint32_t vo = ok ? in_range : BUFFER_OOB;
+    lds_dma16(gr, lds_base + (uint32_t)((2 * H_U4 + slot * VH_GSTAGE_U4) * 16 + wid * 1024), vo, (uint32_t)(d.img * S * S) * 4u);
   };
   // producer, group k, in three pieces that the row loop spreads over consecutive rows (each piece's inputs are then a row old: no
   // exposed latency, and the VALU part rides in the shadow of the 3x3 loop's MFMAs like the epilogue does):
@@ -240,7 +219,7 @@ __global__ __launch_bounds__(256) void conv_halo2_vgg_head_kernel(const VhArgs h
     const float cap = valid ? __builtin_huge_valf() : 0.f;
     uint32_t a_in = (uint32_t)((d.y0 * S + d.x0) * (CI * 2) + p_ar[k]);
     asm volatile("" : "+v"(a_in));
-    const uint32_t a_vo = interior ? a_in : VH_OOB;
+    const uint32_t a_vo = interior ? a_in : BUFFER_OOB;
     const uint32_t a_soff = (uint32_t)(d.img * S * S) * (uint32_t)(CI * 2);
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
@@ -251,10 +230,10 @@ __global__ __launch_bounds__(256) void conv_halo2_vgg_head_kernel(const VhArgs h
 #ifdef VH_ABLATE      // diagnosis builds only (tools/ablate_build.sh): 2 = no conv1_1 stores, 4 = no halo writes either
       if (!(VH_ABLATE & 4)) *(uint4*)(Hs + (p_hw[k] ^ (p << 6))) = pk;
       else if (pk.x == 0x12345678u) *(uint4*)(Hs + (p_hw[k] ^ (p << 6))) = pk;
-      if (!(VH_ABLATE & 6)) vh_store16(ar, u32x4_t{pk.x, pk.y, pk.z, pk.w}, interior ? a_vo + (uint32_t)(p << 6) : VH_OOB, a_soff);
+      if (!(VH_ABLATE & 6)) store16(ar, u32x4_t{pk.x, pk.y, pk.z, pk.w}, interior ? a_vo + (uint32_t)(p << 6) : BUFFER_OOB, a_soff);
 #else
       *(uint4*)(Hs + (p_hw[k] ^ (p << 6))) = pk;
-      vh_store16(ar, u32x4_t{pk.x, pk.y, pk.z, pk.w}, interior ? a_vo + (uint32_t)(p << 6) : VH_OOB, a_soff);
+      store16(ar, u32x4_t{pk.x, pk.y, pk.z, pk.w}, interior ? a_vo + (uint32_t)(p << 6) : BUFFER_OOB, a_soff);
 #endif
     }
   };
@@ -262,7 +241,7 @@ __global__ __launch_bounds__(256) void conv_halo2_vgg_head_kernel(const VhArgs h
   // per-lane byte offset of the A fragments inside a halo stage (conv_halo2.hip)
   int lrel[KW];
 #pragma unroll
-  for (int kx = 0; kx < KW; ++kx) lrel[kx] = wm * MT * ROWB + (frow + kx) * PIXB + ((q ^ vh_swz(frow + kx)) << 4);
+  for (int kx = 0; kx < KW; ++kx) lrel[kx] = wm * MT * ROWB + (frow + kx) * PIXB + ((q ^ swz8(frow + kx)) << 4);
   const uint32_t ovoff = (uint32_t)((frow * 64 + wn * 32 + q * 8) * 2);
 
   // ---- prologue ------------------------------------------------------------------------------------------------------------------
@@ -270,7 +249,7 @@ __global__ __launch_bounds__(256) void conv_halo2_vgg_head_kernel(const VhArgs h
 #pragma unroll
   for (int s_ = 0; s_ < 4; ++s_) dq[s_] = decode(seq_patch(s_));
   gray_dma(dq[0], 0); gray_dma(dq[1], 1); gray_dma(dq[2], 2);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -285,7 +264,7 @@ __global__ __launch_bounds__(256) void conv_halo2_vgg_head_kernel(const VhArgs h
     for (int j = 0; j < NT; ++j) acc[1][i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   int it = 0;
   int gs1 = 1;                                 // gray slot of patch it+1 = (it + 1) % 3
-  uint32_t prev_voff = VH_OOB, prev_soff = 0u;
+  uint32_t prev_voff = BUFFER_OOB, prev_soff = 0u;
 
   auto step = [&](auto phase, auto mma) {
     constexpr int PH = decltype(phase)::value;
@@ -355,7 +334,7 @@ __global__ __launch_bounds__(256) void conv_halo2_vgg_head_kernel(const VhArgs h
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[j * 4 + r] = fmaxf(acc[PH ^ 1][i][j][r] + bv[j][r], 0.f);
         const uint4 o = pack8<ET>(v);
-        vh_store16(yr, u32x4_t{o.x, o.y, o.z, o.w}, prev_voff == VH_OOB ? VH_OOB : prev_voff + (uint32_t)((wm * MT + i) * S * 64 * 2), prev_soff);
+        store16(yr, u32x4_t{o.x, o.y, o.z, o.w}, prev_voff == BUFFER_OOB ? BUFFER_OOB : prev_voff + (uint32_t)((wm * MT + i) * S * 64 * 2), prev_soff);
       }
       // ---- the conv1_1 halo of patch it+1: three 16-slot groups per wave, software-pipelined over rows 0 .. 3 ---------------------
       if constexpr (MMA) {
@@ -365,19 +344,19 @@ __global__ __launch_bounds__(256) void conv_halo2_vgg_head_kernel(const VhArgs h
         if (rr == 3) { ppost(dq[1], hs ^ 1, 2, paA); }
       }
       if constexpr (MMA) {
-        __builtin_amdgcn_sched_group_barrier(VH_SG_DSREAD, KW * KS, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_DSREAD, KW * KS, 0);
 #pragma unroll
         for (int m = 0; m < 44; ++m) {
           if (m < n_mfma) {
-            __builtin_amdgcn_sched_group_barrier(VH_SG_MFMA, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(VH_SG_VALU | VH_SG_SALU, 3, 0);
+            __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(SG_VALU | SG_SALU, 3, 0);
           }
         }
       }
       __builtin_amdgcn_sched_barrier(0);
     }
     if constexpr (MMA) {
-      prev_voff = dq[0].y0 < 0x4000 ? (uint32_t)((dq[0].y0 * S + dq[0].x0) * 64 * 2) + ovoff : VH_OOB;
+      prev_voff = dq[0].y0 < 0x4000 ? (uint32_t)((dq[0].y0 * S + dq[0].x0) * 64 * 2) + ovoff : BUFFER_OOB;
       prev_soff = (uint32_t)(dq[0].img * S * S) * (uint32_t)(64 * 2);
       dq[0] = dq[1]; dq[1] = dq[2]; dq[2] = dq[3];
       dq[3] = decode(seq_patch(it + 4));
@@ -386,12 +365,12 @@ __global__ __launch_bounds__(256) void conv_halo2_vgg_head_kernel(const VhArgs h
     ++it;
   };
   for (;;) {
-    step(VhInt<0>(), VhInt<1>());
-    if (dq[0].y0 >= 0x4000) { step(VhInt<1>(), VhInt<0>()); break; }
-    step(VhInt<1>(), VhInt<1>());
-    if (dq[0].y0 >= 0x4000) { step(VhInt<0>(), VhInt<0>()); break; }
+    step(Int<0>(), Int<1>());
+    if (dq[0].y0 >= 0x4000) { step(Int<1>(), Int<0>()); break; }
+    step(Int<1>(), Int<1>());
+    if (dq[0].y0 >= 0x4000) { step(Int<0>(), Int<0>()); break; }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // no LDS-DMA may outlive the workgroup
+  wait_vmcnt<0>();     // no LDS-DMA may outlive the workgroup
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------

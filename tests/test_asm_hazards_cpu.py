@@ -78,6 +78,15 @@ def test_checker_follows_an_asm_load_to_its_wait():
     assert [f for f in findings(LOAD.replace('\ts_waitcnt vmcnt(0)', '\ts_nop 0') % '\ts_endpgm') if 'never waited' in f]
 
 
+def test_lds_dma_and_wide_store_are_defined_once():
+    """The two statements whose wait states the audit's M and S rules check exist ONCE in imm_amd/csrc/ (gfx950.h): a private copy
+    in a kernel is a copy a later fix can miss.  Text only, comments included; no compiler."""
+    csrc = os.path.join(ROOT, 'imm_amd', 'csrc')
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if os.path.isfile(os.path.join(csrc, f))}
+    for statement in ('offen lds', 'buffer_store_dwordx4'):
+        assert {f: t.count(statement) for f, t in text.items() if statement in t} == {'gfx950.h': 1}, statement
+
+
 @pytest.mark.timeout(900)
 def test_shipped_sources_have_no_inline_asm_hazard():
     if not os.path.exists(os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')):

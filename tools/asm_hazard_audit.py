@@ -4,7 +4,8 @@
 hipcc treats an `asm volatile` statement as one opaque instruction: it neither counts its memory operations nor pads the
 hazards of the instructions inside (cdna_hip_programming.md §5.7).  Round 5 found one such hazard the hard way (a 16-byte
 `buffer_store` without trailing wait states in conv_halo2.hip: 0.3 % corrupted stores whenever a second process shared the GPU).
-This tool compiles every source that contains inline asm to gfx950 assembly (`hipcc --cuda-device-only -S`, no GPU needed)
+This tool compiles every source that contains inline asm — its own, or the shared statements of imm_amd/csrc/gfx950.h, where the
+LDS-DMA load, the 16-byte store and the DPP row sum are defined once — to gfx950 assembly (`hipcc --cuda-device-only -S`, no GPU needed)
 and checks, on the instruction stream the compiler actually emitted around each `;;#ASMSTART … ;;#ASMEND` block:
 
   S  a VMEM store of more than 64 bits inside an asm block is followed, inside the block, by `s_nop 1` or more;
@@ -183,10 +184,16 @@ def audit(name, text):
     return found, n_asm, n_vmem
 
 
+def audited_sources():
+    """The sources with inline asm: an `asm volatile("…` literal of their own, or the shared primitives of gfx950.h (LDS-DMA, 16-byte
+    store, DPP row sum), included directly or through conv_common.h."""
+    wanted = re.compile(r'asm volatile\("[^"]|#include "(?:gfx950|conv_common)\.h"')
+    return [p for p in sorted(glob.glob(os.path.join(ROOT, 'imm_amd', 'csrc', '*.hip'))) if wanted.search(open(p).read())]
+
+
 def compile_all(outdir):
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    srcs = [p for p in sorted(glob.glob(os.path.join(ROOT, 'imm_amd', 'csrc', '*.hip')))
-            if re.search(r'asm volatile\("[^"]', open(p).read())]
+    srcs = audited_sources()
     procs, outs = [], []
     for src in srcs:
         out = os.path.join(outdir, os.path.basename(src)[:-4] + '.s')
