@@ -20,7 +20,7 @@ CONV_BIAS, CONV_RELU, CONV_STATS, CONV_MASK, CONV_OUT_F32 = 1, 2, 4, 8, 16
 SSE_BLOCKS = 512
 OPTIMIZERS = {'adam': 0, 'adadelta': 1, 'adagrad': 2}      # IMM_OPT_* (scripts/train.py:97-104)
 GAUSS_MODES = {'rot': 0, 'flat': 1, 'ankush': 2}     # IMM_GAUSS_* (config key gauss_mode, imm_model.py:48-72)
-ABI_VERSION = 34     # 34: imm_seam_fit / imm_morph_seam_u8 (include/imm_seam.h).  33: imm_hull_fit / imm_morph_hull_u8 (include/imm_hull.h).  32: imm_colour_stats_u8 / imm_colour_gain / imm_morph_colour_u8 (include/imm_colour.h).  31: imm_morph_poses / imm_morph_u8 (include/imm_morph.h).  30: imm_warp_fit / imm_warp_u8 (include/imm_warp.h).  29: imm_retarget (include/imm_retarget.h).  28: imm_track_step (include/imm_track.h).  27: imm_unalign_maps / imm_unalign_u8 (include/imm_unalign.h).  26: imm_compose_u8 (include/imm_compose.h).  25: imm_align_coeffs / imm_align_warp_u8 (include/imm_align.h).  24: box-crop mode of imm_resize_crop_u8, keypoint epilogue of imm_pose_head_fwd.  23: render-only mode of imm_softargmax_gauss_fwd (heat NULL).  22: s2f / conv_first accept IMM_CONV_RELU
+ABI_VERSION = 35     # 35: imm_clip_rows / imm_clip_ema (include/imm_clip.h).  34: imm_seam_fit / imm_morph_seam_u8 (include/imm_seam.h).  33: imm_hull_fit / imm_morph_hull_u8 (include/imm_hull.h).  32: imm_colour_stats_u8 / imm_colour_gain / imm_morph_colour_u8 (include/imm_colour.h).  31: imm_morph_poses / imm_morph_u8 (include/imm_morph.h).  30: imm_warp_fit / imm_warp_u8 (include/imm_warp.h).  29: imm_retarget (include/imm_retarget.h).  28: imm_track_step (include/imm_track.h).  27: imm_unalign_maps / imm_unalign_u8 (include/imm_unalign.h).  26: imm_compose_u8 (include/imm_compose.h).  25: imm_align_coeffs / imm_align_warp_u8 (include/imm_align.h).  24: box-crop mode of imm_resize_crop_u8, keypoint epilogue of imm_pose_head_fwd.  23: render-only mode of imm_softargmax_gauss_fwd (heat NULL).  22: s2f / conv_first accept IMM_CONV_RELU
 
 
 class ImmHipError(RuntimeError):
@@ -201,6 +201,12 @@ _SIGS_SEAM = {
     'imm_morph_seam_u8': [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
 }
 
+# the clip-morph entry points (include/imm_clip.h, ABI 35)
+_SIGS_CLIP = {
+    'imm_clip_rows': [_P, _P, _P, _P, _I, _I, _I, _D, _P, _P, _P, _P, _P],
+    'imm_clip_ema': [_P, _P, _P, _P, _P, _I, _I, _F, _P],
+}
+
 # byte-size twins of the row-count queries (int64 result; < 0 = unsupported)
 _SIGS64 = {
     'imm_conv2d_workspace_bytes': [C.POINTER(ConvDesc)],
@@ -272,6 +278,11 @@ def seam_symbols():
     return sorted(_SIGS_SEAM)
 
 
+def clip_symbols():
+    """The entry points include/imm_clip.h declares."""
+    return sorted(_SIGS_CLIP)
+
+
 def load():
     """Load (once) and return the ctypes handle; raises ImmHipError if the library is absent."""
     global _lib
@@ -294,7 +305,7 @@ def load():
     for name in ('imm_last_error', 'imm_source_digest'):
         getattr(lib, name).restype = C.c_char_p
         getattr(lib, name).argtypes = []
-    for name, args in list(_SIGS.items()) + list(_SIGS_ALIGN.items()) + list(_SIGS_COMPOSE.items()) + list(_SIGS_UNALIGN.items()) + list(_SIGS_TRACK.items()) + list(_SIGS_RETARGET.items()) + list(_SIGS_WARP.items()) + list(_SIGS_MORPH.items()) + list(_SIGS_COLOUR.items()) + list(_SIGS_HULL.items()) + list(_SIGS_SEAM.items()):
+    for name, args in list(_SIGS.items()) + list(_SIGS_ALIGN.items()) + list(_SIGS_COMPOSE.items()) + list(_SIGS_UNALIGN.items()) + list(_SIGS_TRACK.items()) + list(_SIGS_RETARGET.items()) + list(_SIGS_WARP.items()) + list(_SIGS_MORPH.items()) + list(_SIGS_COLOUR.items()) + list(_SIGS_HULL.items()) + list(_SIGS_SEAM.items()) + list(_SIGS_CLIP.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int

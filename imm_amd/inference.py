@@ -973,6 +973,30 @@ class LandmarkDetector(BucketRunner):
                 ring=plan.ring if seam else None, seam_ring=extra.get('ring'), seam_diff=extra.get('diff'), seam_flags=sflags)
         return out
 
+    def morph_clip(self, frames, boxes, donors, donor_boxes=None, shape=0.0, texture=1.0, feather=0.125, anchors=2, lam=0.0,
+                   donor_landmarks=None, colour=0.0, max_gain=2.0, mask=None, grow=1.25, mask_feather=0.1, seamless=0.0, ring=128,
+                   smooth=True, colour_smooth=0.25, seam_smooth=0.25, box_smooth=0.5, one_euro=OneEuro(), fps=25.0, chunk_frames=32):
+        """A donor's face follows a tracked face through a clip: track() and morph() joined on the device, a clip.ClipMorph (frames,
+        track, own, fit_flags, colour_gain, colour_flags, hull_flags, seam_diff, seam_flags).
+        frames, boxes, box_smooth, one_euro, fps, chunk_frames: exactly as track takes them; boxes are the F faces of frames[0], at most
+        max_batch of them.  donors, donor_boxes, donor_landmarks: one donor row per face, or ONE for all, in morph's forms.  shape,
+        texture, feather, anchors, lam, colour, max_gain, mask, grow, mask_feather, seamless, ring: as morph takes them, a number or
+        one per face, with morph's refusals; the defaults shape = 0, texture = 1 swap the donor's face in, in place.
+        smooth=True: the faces' own landmarks are the tracker's One-Euro points (Track.points_smooth) brought back into the frame of
+        each frame's box; False: the pose head's mu.  colour_smooth and seam_smooth in (0, 1]: the weight of a frame's colour gain and
+        of its membrane differences in a first-order filter, s <- s + a (x - s), box_smooth's convention; 1 means no filter, and the
+        filter's launch is then not issued.  The defaults of 0.25 are by analogy with box_smooth: nobody has tuned them on footage.
+        A face the tracker lost on a frame (Track.lost) is not pasted on that frame: the frame keeps its pixels there.
+        Once per call the donors are packed and uploaded, their landmarks detected (unless given) and their colour sums taken; per chunk
+        the frames are uploaded and copied into a canvas on the device; per frame the tracker's launches, imm_clip_rows
+        (include/imm_clip.h) and morph's chain run on the detector's stream with the box rows the frame before left in device memory.
+        Between the first and the last frame's launches nothing is copied to the host and the stream is not synchronised."""
+        from . import clip as CL
+        plan = CL.plan_clip(frames, boxes, donors, donor_boxes, shape, texture, feather, self.K, anchors, lam, donor_landmarks, colour, max_gain,
+                            mask, grow, mask_feather, seamless, ring, smooth, colour_smooth, seam_smooth, box_smooth, one_euro, fps,
+                            chunk_frames, self.max_batch)
+        return CL.run(self, plan)
+
     def colour_stats(self, photos, boxes=None):
         """The statistics colour matching works from, per box row and channel: (count int64 [n], mean f64 [n, 3], standard deviation f64
         [n, 3]) on the host.  photos, boxes: as morph takes them (a list of u8 arrays; box rows, by default one whole-photo box per

@@ -1146,6 +1146,63 @@ def morph_seam_u8(src, dst, offsets, hw, donor, donor_offsets, donor_hw, boxes, 
                 **_need('morph_seam_u8', edges=edges, inv_soft=inv_soft, ring=ring, diff=diff, seamless=seamless))
 
 
+CLIP_MAX_WIDTH = 768          # values of a row imm_clip_ema filters: 3 * SEAM_MAX_RING
+
+
+def clip_rows(boxes, track_flags, mu, points, image_size, feather, mask_feather, own, inv_ramp, inv_soft):
+    """One frame's rows of a clip morph (include/imm_clip.h: imm_clip_rows): boxes i32 [F, 5] (the rows this frame was cut with),
+    track_flags i32 [F] (track_step's flags of the frame), mu f32 [F, K, 2] and points f32 [F, K, 2] or None (track_step's points or
+    points_smooth), feather (a float in [0, 0.5]) and mask_feather f32 [F] or None -> own f32 [F, K, 2] (the landmarks in the frame of
+    the box: mu's bits without points, NaN for a lost face), inv_ramp f32 [F, 2] (generation.compose_inv_ramp's bits) and inv_soft f32
+    [F] (morphing.hull_inv_soft's bits; None exactly when mask_feather is)."""
+    if mu.dim() != 3 or mu.shape[2] != 2:
+        raise ValueError('mu must be f32 [F, K, 2], got %s' % (tuple(mu.shape),))
+    F, K = int(mu.shape[0]), int(mu.shape[1])
+    if F < 1 or F > 65535 or K < 1 or K > WARP_MAX_POINTS:
+        raise ValueError('clip_rows serves 1..65535 faces of 1..%d landmarks, got F = %d, K = %d' % (WARP_MAX_POINTS, F, K))
+    if (mask_feather is None) != (inv_soft is None):
+        raise ValueError('inv_soft is given exactly when mask_feather is')
+    specs = [('boxes', boxes, torch.int32, (F, 5)), ('track_flags', track_flags, torch.int32, (F,)), ('mu', mu, torch.float32, (F, K, 2)),
+             ('own', own, torch.float32, (F, K, 2)), ('inv_ramp', inv_ramp, torch.float32, (F, 2))]
+    if points is not None:
+        specs.append(('points', points, torch.float32, (F, K, 2)))
+    if mask_feather is not None:
+        specs += [('mask_feather', mask_feather, torch.float32, (F,)), ('inv_soft', inv_soft, torch.float32, (F,))]
+    _check_tensors(specs)
+    for name, t in (('mu', mu), ('points', points)):
+        if t is not None and _overlap(t, own):
+            raise ValueError('%s overlaps own: the output is written while the inputs are read' % name)
+    feather, S = float(feather), int(image_size)
+    if not 0.0 <= feather <= 0.5:
+        raise ValueError('feather must lie in [0, 0.5], got %r' % (feather,))
+    if not 0 < S <= 8192:
+        raise ValueError('image_size must lie in (0, 8192], got %r' % (image_size,))
+    call('imm_clip_rows', _p(boxes), _p(track_flags), _p(mu), None if points is None else _p(points), K, S, F, feather,
+         None if mask_feather is None else _p(mask_feather), _p(own), _p(inv_ramp), None if inv_soft is None else _p(inv_soft), _s())
+
+
+def clip_ema(x, state, seen, skip, lost, alpha):
+    """The filter of a clip morph (include/imm_clip.h: imm_clip_ema): x f32 [n, width] is filtered in place against state f32 [n, width],
+    state = state + alpha * (x - state), the first value a row sees (seen i32 [n] == 0) passing through; a row with skip i32 [n] != 0 or
+    bit 0 of lost i32 [n] (or None) set leaves its x, state and seen alone.  alpha in (0, 1]."""
+    if x.dim() != 2:
+        raise ValueError('x must be f32 [n, width], got %s' % (tuple(x.shape),))
+    n, width = int(x.shape[0]), int(x.shape[1])
+    if n < 1 or n > 65535 or width < 1 or width > CLIP_MAX_WIDTH:
+        raise ValueError('clip_ema serves 1..65535 rows of 1..%d values, got n = %d, width = %d' % (CLIP_MAX_WIDTH, n, width))
+    specs = [('x', x, torch.float32, (n, width)), ('state', state, torch.float32, (n, width)), ('seen', seen, torch.int32, (n,)),
+             ('skip', skip, torch.int32, (n,))]
+    if lost is not None:
+        specs.append(('lost', lost, torch.int32, (n,)))
+    _check_tensors(specs)
+    if _overlap(x, state):
+        raise ValueError('x overlaps state')
+    alpha = float(alpha)
+    if not 0.0 < alpha <= 1.0:
+        raise ValueError('alpha must lie in (0, 1], got %r' % (alpha,))
+    call('imm_clip_ema', _p(x), _p(state), _p(seen), _p(skip), None if lost is None else _p(lost), n, width, alpha, _s())
+
+
 def masked_sse_pool(a, b, batch, s, c, mask, S, partial, pool_a, pool_b):
     call('imm_masked_sse_pool', _p(a), _p(b), dtype_enum(a.dtype), batch, s, c, _p(mask), S, _p(partial), _p(pool_a), _p(pool_b), _s())
 

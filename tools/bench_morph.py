@@ -27,7 +27,14 @@ With --seamless the same photos, sizes and protocol time the mean-value membrane
 against seamless = 0, alternated window by window after warm-up, with landmarks on the jittered grid given to both sides (a hull of the
 size a face's is), at ring = 128 and ring = 16, and the two new launches alone on one call's buffers (imm_seam_fit, and imm_morph_seam_u8
 next to imm_morph_hull_u8), with the ratios; the table is APPENDED as well.
-Usage: python tools/bench_morph.py [--batch 64] [--windows 7] [--reps 10] [--anchors 2] [--colour | --mask | --seamless]"""
+With --clip the clip morph is timed instead: LandmarkDetector.morph_clip over a synthetic clip of 64 frames of 1280 x 720 with two faces
+of about 250 x 250 and two donor photos, against the loop over public calls it replaces (track(), .cpu(), then per frame the landmarks
+brought back into the frame's box on the host and morph([frame], donors, boxes, landmarks, donor_landmarks)), for the four pastes (plain;
+colour = 1; mask = 'hull'; mask = 'hull', seamless = 1, colour = 0.5).  Both sides are wall-clock times of the whole clip, from the call
+to a final synchronisation (the loop synchronises every frame by construction), alternated window by window after warm-up clips; the
+loop runs calls that this tool's commit shares unchanged with its parent.  The library calls per frame are counted on the host (the
+difference between a whole and a half clip).  Writes profiles/clip_morph_bench.txt.
+Usage: python tools/bench_morph.py [--batch 64] [--windows 7] [--reps 10] [--anchors 2] [--colour | --mask | --seamless | --clip]"""
 import argparse
 import json
 import os
@@ -40,8 +47,107 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
 
 OUT = os.path.join(ROOT, 'profiles', 'morph_bench.txt')
+CLIP_OUT = os.path.join(ROOT, 'profiles', 'clip_morph_bench.txt')
 S, K = 128, 10
 LAM = 1.0
+
+
+def clip_leg(args):
+    """--clip: morph_clip against the loop over public calls, ms per frame, and the library calls per frame."""
+    import time
+    import torch
+    from bench_repose import make_generator, scene
+    from imm_amd import ops
+    from imm_amd.tracking import OneEuro
+    T, F, H, W = args.frames, 2, 720, 1280
+    rng = np.random.RandomState(0)
+    base = rng.randint(0, 256, size=(H + T, W + T, 3)).astype(np.uint8)
+    frames = [np.ascontiguousarray(base[t:t + H, t:t + W]) for t in range(T)]          # the scene moves a pixel a frame
+    faces = [(0, 120, 200, 370, 450), (0, 300, 800, 556, 1044)]
+    donors, dboxes, _lm = scene(F, seed=1)
+    _model, gen = make_generator(F)
+    det = gen.detector
+    props = torch.cuda.get_device_properties(0)
+    dl = det.landmarks(donors, dboxes).clone()
+    track_kw = dict(box_smooth=0.5, one_euro=OneEuro(), fps=25.0)
+    common = dict(donor_boxes=dboxes, donor_landmarks=dl, shape=0.0, texture=1.0, anchors=args.anchors, lam=LAM)
+    pastes = [('plain', dict()), ('colour', dict(colour=1.0)), ('hull', dict(mask='hull')), ('seamless', dict(mask='hull', seamless=1.0, colour=0.5))]
+
+    def loop(paste):
+        tr = det.track(frames, faces, **track_kw).cpu()
+        boxes, pts = tr.boxes.numpy().astype(np.float64), tr.points_smooth.numpy().astype(np.float64)
+        out = []
+        for t in range(T):
+            side = boxes[t, :, 2:] - boxes[t, :, :2]
+            scale = (side.astype(np.float32) / np.float32(S)).astype(np.float64)
+            own = np.clip((pts[t] - boxes[t, :, None, :2]) / scale[:, None] / S * 2.0 - 1.0, -1.0, 1.0).astype(np.float32)
+            rows = [(0,) + tuple(int(v) for v in b) for b in tr.boxes[t].tolist()]
+            out.append(det.morph([frames[t]], donors, boxes=rows, landmarks=torch.from_numpy(own), **dict(common, **paste))[0])
+        return out
+
+    def clip(paste, n=T):
+        return det.morph_clip(frames[:n], faces, donors, colour_smooth=0.25, seam_smooth=0.25, **dict(common, **dict(track_kw, **paste)))
+
+    def wall_ms(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    def calls_per_frame(paste):
+        count, real = [0], ops.call
+
+        def counting(name, *a):
+            count[0] += 1
+            return real(name, *a)
+        ops.call = counting
+        try:
+            clip(paste, T)
+            whole = count[0]
+            count[0] = 0
+            clip(paste, T // 2)
+            half = count[0]
+        finally:
+            ops.call = real
+        return (whole - half) / float(T - T // 2)
+
+    lines = ['==== clip morph (--clip) ====',
+             'device: %s (%s, %d CUs)' % (props.name, props.gcnArchName, props.multi_processor_count),
+             'S = %d, K = %d, anchors = %d, lam = %g, bf16; a synthetic clip of %d u8 frames of %d x %d, %d faces of about 250 x 250, %d donor '
+             'photos of about 512 x 384; box_smooth 0.5, OneEuro(), 25 fps, chunk_frames 32, smooth = True, colour_smooth = seam_smooth = 0.25'
+             % (S, K, args.anchors, LAM, T, W, H, F, F),
+             'wall-clock ms per frame (the clip\'s time over its frames), the two sides alternating, median (min .. max) of %d windows after %d '
+             'warm-up clips each' % (args.windows, args.warmup),
+             'loop = track(), .cpu(), then per frame the landmarks brought back on the host and morph([frame], donors, ...): calls that this '
+             'commit shares unchanged with its parent',
+             'clip = LandmarkDetector.morph_clip(frames, faces, donors, ...); calls = library calls per frame of it, counted on the host (the '
+             'captured pose program is one; the copy of the landmarks and the OR of the fit flags are two torch launches more)',
+             '%-9s %28s %28s %8s %7s' % ('paste', 'loop ms/frame', 'clip ms/frame', 'ratio', 'calls')]
+    rows = []
+    for name, paste in pastes:
+        for _ in range(args.warmup):
+            loop(paste)
+            clip(paste)
+        t_loop, t_clip = [], []
+        for _ in range(args.windows):
+            t_loop.append(wall_ms(lambda: loop(paste)) / T)
+            t_clip.append(wall_ms(lambda: clip(paste)) / T)
+        ml, mc = float(np.median(t_loop)), float(np.median(t_clip))
+        calls = calls_per_frame(paste)
+        fmt = lambda v: '%7.3f (%7.3f .. %7.3f)' % (float(np.median(v)), min(v), max(v))
+        lines.append('%-9s %28s %28s %8.2f %7.1f' % (name, fmt(t_loop), fmt(t_clip), ml / mc, calls))
+        print(lines[-1], flush=True)
+        rows.append({'paste': name, 'loop_ms_per_frame': ml, 'clip_ms_per_frame': mc, 'loop_over_clip': ml / mc, 'calls_per_frame': calls})
+    slower = [r['paste'] for r in rows if r['loop_over_clip'] <= 1.0]
+    lines.append('morph_clip is faster than the loop for every paste' if not slower else
+                 'morph_clip is NOT faster than the loop for: %s' % ', '.join(slower))
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write(text)
+    print(json.dumps({'frames': T, 'faces': F, 'rows': rows}))
 
 
 def main(args):
@@ -332,5 +438,14 @@ if __name__ == '__main__':
                    help="time the landmark-hull mask: morph at mask = 'hull' against mask = None at colour 0 and 1, and the new launches alone")
     p.add_argument('--seamless', action='store_true',
                    help="time the mean-value membrane: morph at seamless = 1 against seamless = 0 under the hull mask, and the new launches alone")
-    p.add_argument('--out', type=str, default=OUT)
-    main(p.parse_args())
+    p.add_argument('--clip', action='store_true',
+                   help='time the clip morph: morph_clip against the loop over public calls it replaces, ms per frame, for the four pastes')
+    p.add_argument('--frames', type=int, default=64, help='with --clip: the frames of the synthetic clip')
+    p.add_argument('--out', type=str, default=None, help='default: profiles/morph_bench.txt, with --clip profiles/clip_morph_bench.txt')
+    a = p.parse_args()
+    if a.out is None:
+        a.out = CLIP_OUT if a.clip else OUT
+    if a.clip:
+        clip_leg(a)
+    else:
+        main(a)
