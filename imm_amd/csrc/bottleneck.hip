@@ -389,13 +389,10 @@ __global__ void gauss_render_f32_kernel(const float* __restrict__ mu, int K, flo
 
 static const size_t kMaxDynLds = 160 * 1024 - 1024;
 
+// (the LDS size follows the heat-map's, call by call: the opt-in is made for each size, not latched as in imm_launch)
 template <typename K_>
 static int set_dyn_lds(K_ kernel, size_t bytes) {
-  if (bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return imm_fail(IMM_E_HIP, "hipFuncSetAttribute(dyn LDS %zu): %s", bytes, hipGetErrorString(e));
-  }
-  return 0;
+  return (bytes > 64 * 1024 && !imm_dyn_lds_opt_in((const void*)kernel, bytes)) ? IMM_E_HIP : 0;
 }
 
 extern "C" int imm_softargmax_gauss_fwd(const float* heat, int ldh, int batch, int h, int w, int k, float inv_std, int s,

@@ -11,6 +11,7 @@
 //   y[m][n] = epilogue( sum_k gather(x)[m][k] * wt[n][k] ),  k = (ky * kw + kx) * ci + c
 //   slab[s][k][n] = sum_{m in split s} gather(x)[m][k] * dy[m][n]
 #include "common.h"
+#include "conv_dispatch.h"
 
 namespace {
 constexpr int F_BM = 64, F_BN = 64, F_BK = 16, F_THREADS = 256;

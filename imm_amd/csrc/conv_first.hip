@@ -262,20 +262,9 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const ConvFirstArgs a) 
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static int cf_num_cu() {
-  static int n = 0;
-  if (n == 0) {
-    hipDeviceProp_t p; int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-    else (void)hipGetLastError();
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
 static int cf_grid(int batch, int s) {
   const int n_patches = batch * (s / CF_PH) * (s / CF_PW);
-  const int grid = 4 * cf_num_cu();                 // ~31 KB of LDS and 4 waves per workgroup: four per CU keep enough patches in flight
+  const int grid = 4 * imm_device_cus();                // ~31 KB of LDS and 4 waves per workgroup: four per CU keep enough patches in flight
   return n_patches < grid ? n_patches : grid;
 }
 

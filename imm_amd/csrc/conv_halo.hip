@@ -14,6 +14,7 @@
 // Epilogue = bias / ReLU / ReLU-backward mask / 16-bit or f32 NHWC store; BN partial sums are accumulated in
 // registers over all patches of the workgroup and written once (one partial row per workgroup).
 #include "conv_common.h"
+#include "conv_dispatch.h"
 #include <stdlib.h>
 
 #define HALO_PH 8                 // patch rows
@@ -367,16 +368,6 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(const HaloArgs ha) {
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static int g_halo_cu = 0;
-static int halo_num_cu() {
-  if (g_halo_cu == 0) {
-    hipDeviceProp_t p; int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) g_halo_cu = p.multiProcessorCount;
-    if (g_halo_cu <= 0) g_halo_cu = 256;
-  }
-  return imm_limit_cus(g_halo_cu);
-}
-
 static bool halo_is_s2(const imm_conv_desc* d) {
   return d->kh == 3 && d->kw == 3 && d->stride == 2 && d->updiv == 1 && d->pad_t == 0 && d->pad_l == 0 && d->ci == 32 &&
          d->co > 32 && d->co <= 64 && d->hi == 2 * d->ho && d->wi == 2 * d->wo && d->ho % HALO_PH == 0 && d->wo % HALO_PW == 0 &&
@@ -412,19 +403,16 @@ int imm_halo_grid(const imm_conv_desc* d) {
   int per_cu = (int)((160 * 1024) / lds);
   if (per_cu > 4) per_cu = 4;
   if (per_cu < 1) per_cu = 1;
-  const int grid = halo_num_cu() * per_cu;
+  const int grid = imm_launch_cus() * per_cu;
   return n_patches < grid ? n_patches : grid;
 }
 
+// imm_conv2d_variant: 3 * 100000 + stride 2 * 10000 + input channels * 100 + channel block
+int imm_halo_variant(const imm_conv_desc* d) { return 300000 + (d->stride == 2 ? 10000 : 0) + d->ci * 100 + halo_bn(d->co); }
+
 template <typename ET, int CI, int BN, bool S2 = false, bool NOL = false, bool S2D = false>
 static void halo_launch_cfg(const HaloArgs& ha, int grid, hipStream_t s) {
-  const size_t lds = halo_lds(CI, BN, S2, NOL);
-  static bool attr_set = false;
-  if (!attr_set && lds > 64 * 1024) {
-    (void)hipFuncSetAttribute((const void*)conv_halo_kernel<ET, CI, BN, S2, NOL, S2D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((conv_halo_kernel<ET, CI, BN, S2, NOL, S2D>), dim3(grid), dim3(256), lds, s, ha);
+  imm_launch<conv_halo_kernel<ET, CI, BN, S2, NOL, S2D>>(dim3(grid), dim3(256), halo_lds(CI, BN, S2, NOL), s, ha);
 }
 
 template <typename ET>
@@ -498,7 +486,7 @@ void imm_conv_halo_s2d_launch(int dtype, const imm_conv_desc* d, const ConvArgs&
   ha.n_patches = d->batch * ha.patches_x * ha.patches_y;
   ha.c.x_bytes = (uint32_t)((int64_t)d->batch * d->hi * d->wi * d->ldx * 2);
   ha.c.wt_bytes = (uint32_t)((int64_t)d->co * d->kpad * 2);
-  const int cus = halo_num_cu();                       // 84 KB of LDS: one persistent workgroup per CU
+  const int cus = imm_launch_cus();                    // 84 KB of LDS: one persistent workgroup per CU
   const int grid = ha.n_patches < cus ? ha.n_patches : cus;
   if (dtype == IMM_BF16) halo_launch_cfg<BF16, 64, 32, false, false, true>(ha, grid, s);
   else halo_launch_cfg<F16, 64, 32, false, false, true>(ha, grid, s);

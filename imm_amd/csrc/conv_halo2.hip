@@ -21,6 +21,7 @@
 // consecutive channels of its pixel: one 16-byte store (and one 16-byte mask read) per pixel and tile row.
 // Results are bit-identical to v1 except for the order of the BN partial sums (deterministic either way).
 #include "conv_common.h"
+#include "conv_dispatch.h"
 #include <stdlib.h>
 
 #define H2_PH 8                 // patch rows
@@ -682,23 +683,7 @@ __global__ __launch_bounds__(256) void conv_halo2x_kernel(const Halo2Args ha) {
 // ---------------------------------------------------------------------------------------------
 // Halo ring depth (prefetch distance NS-1 patches): bytes in flight per CU, not arithmetic, set the speed of these
 // layers (one workgroup per CU at ci = 64).  ci = 64: 24 KB per stage, +16 KB for the mask stage.
-static int h2_ns(bool mask) {
-  static int v[2] = {0, 0};
-  if (v[mask] == 0) {
-    v[mask] = mask ? 3 : 4;
-  }
-  return v[mask];
-}
-
-static int h2_num_cu() {
-  static int cu = 0;
-  if (cu == 0) {
-    hipDeviceProp_t p; int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cu = p.multiProcessorCount;
-    if (cu <= 0) cu = 256;
-  }
-  return imm_limit_cus(cu);
-}
+static int h2_ns(bool mask) { return mask ? 3 : 4; }
 
 bool imm_halo2_applicable(const imm_conv_desc* d) {
   static const bool off = imm_conv_disabled("halo2") || imm_conv_disabled("halo");
@@ -722,9 +707,14 @@ bool imm_halo2_applicable(const imm_conv_desc* d) {
 
 // IMM_HALO2X=1: the 64 -> 64 launches without batch-norm partial sums take conv_halo2x_kernel (32x32x16 tiles).  OFF by default:
 // measured 79-81 us against 75-78 for VGG conv1_2 (profiles/r06_halo2x_ablation.txt)
-bool imm_halo2_x32(const imm_conv_desc* d) {
-  static const bool on = getenv("IMM_HALO2X") && getenv("IMM_HALO2X")[0] == '1';
-  return on && imm_halo2_applicable(d) && d->ci == 64 && d->co == 64 && d->kh == 3 && d->kw == 3 && !(d->flags & IMM_CONV_STATS);
+static bool h2_x32(const imm_conv_desc* d) {
+  return imm_env_flag(IMM_ENV_HALO2X) && imm_halo2_applicable(d) && d->ci == 64 && d->co == 64 && d->kh == 3 && d->kw == 3 &&
+         !(d->flags & IMM_CONV_STATS);
+}
+
+// imm_conv2d_variant: 4 * 100000 + the 32x32x16 form * 20000 + the 7x1 filter * 10000 + input channels * 100 + channel block
+int imm_halo2_variant(const imm_conv_desc* d) {
+  return 400000 + (d->kw == 1 ? 10000 : 0) + (h2_x32(d) ? 20000 : 0) + d->ci * 100 + (d->co > 32 ? 64 : 32);
 }
 
 static size_t h2_lds(int ci, int bn, bool mask, int ns, int kh = 3, int kw = 3) {
@@ -736,11 +726,9 @@ static int h2_occupancy() {
   static int occ = 0;
   if (occ == 0) {
     const size_t lds = h2_lds(CI, BN, MASK, NS, KH, KW);
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)conv_halo2_kernel<ET, CI, BN, MASK, STATS, NS, KH, KW>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_halo2_kernel<ET, CI, BN, MASK, STATS, NS, KH, KW>, 256, lds) != hipSuccess || n < 1) {
+    if (!imm_dyn_lds<conv_halo2_kernel<ET, CI, BN, MASK, STATS, NS, KH, KW>>(lds) ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_halo2_kernel<ET, CI, BN, MASK, STATS, NS, KH, KW>, 256, lds) != hipSuccess || n < 1) {
       (void)hipGetLastError();
       n = 1;
     }
@@ -790,7 +778,7 @@ int imm_halo2_grid(const imm_conv_desc* d) {
     occ = h2_occupancy<BF16, decltype(ci)::value, decltype(bn)::value, (bool)decltype(mk)::value, (bool)decltype(st)::value,
                        decltype(ns)::value, decltype(kh)::value, decltype(kw)::value>();
   });
-  const int grid = h2_num_cu() * occ;
+  const int grid = imm_launch_cus() * occ;
   return n_patches < grid ? n_patches : grid;
 }
 
@@ -811,26 +799,18 @@ static void h2_launch(const imm_conv_desc* d, const ConvArgs& a, hipStream_t s) 
     ha.lg_px = __builtin_ctz(ha.patches_x); ha.lg_pi = __builtin_ctz(per_img);
   }
   const int grid = imm_halo2_grid(d);
-  if (imm_halo2_x32(d)) {     // 64 -> 64 channels without batch-norm sums: the 32x32x16 form (one workgroup per CU either way)
+  if (h2_x32(d)) {     // 64 -> 64 channels without batch-norm sums: the 32x32x16 form (one workgroup per CU either way)
     const bool mask = d->flags & IMM_CONV_MASK;
     const size_t lds = h2_lds(64, 64, mask, h2_ns(mask));
-    static bool attr_set[2] = {false, false};       // (per element type: this function is a template)
-    if (!attr_set[mask]) {
-      if (mask) (void)hipFuncSetAttribute((const void*)conv_halo2x_kernel<ET, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      else (void)hipFuncSetAttribute((const void*)conv_halo2x_kernel<ET, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set[mask] = true;
-    }
-    if (mask) hipLaunchKernelGGL((conv_halo2x_kernel<ET, true, 3>), dim3(grid), dim3(256), lds, s, ha);
-    else hipLaunchKernelGGL((conv_halo2x_kernel<ET, false, 4>), dim3(grid), dim3(256), lds, s, ha);
+    if (mask) imm_launch<conv_halo2x_kernel<ET, true, 3>>(dim3(grid), dim3(256), lds, s, ha);
+    else imm_launch<conv_halo2x_kernel<ET, false, 4>>(dim3(grid), dim3(256), lds, s, ha);
     return;
   }
   h2_dispatch(d, [&](auto ci, auto bn, auto mk, auto st, auto ns, auto kh, auto kw) {
     constexpr int CI = decltype(ci)::value, BN = decltype(bn)::value, NS = decltype(ns)::value;
     constexpr int KH = decltype(kh)::value, KW = decltype(kw)::value;
     constexpr bool MASK = decltype(mk)::value, STATS = decltype(st)::value;
-    (void)h2_occupancy<ET, CI, BN, MASK, STATS, NS, KH, KW>();  // sets the dynamic-LDS attribute on first use
-    hipLaunchKernelGGL((conv_halo2_kernel<ET, CI, BN, MASK, STATS, NS, KH, KW>), dim3(grid), dim3(256),
-                       h2_lds(CI, BN, MASK, NS, KH, KW), s, ha);
+    imm_launch<conv_halo2_kernel<ET, CI, BN, MASK, STATS, NS, KH, KW>>(dim3(grid), dim3(256), h2_lds(CI, BN, MASK, NS, KH, KW), s, ha);
   });
 }
 

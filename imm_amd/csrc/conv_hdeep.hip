@@ -14,6 +14,7 @@
 // issued from inline asm with exactly (BN/64 + 1) instructions per wave and tap (halo pieces of the next slice ride on
 // taps 0-5, the rest are no-op pieces into a dump slot), so one counted s_waitcnt vmcnt per tap is exact.
 #include "conv_common.h"
+#include "conv_dispatch.h"
 #include <stdlib.h>
 #include <stdio.h>
 
@@ -608,32 +609,19 @@ __global__ __launch_bounds__(NW * 64) void conv_hdeep_kernel(const HdArgs ha) {
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static int hd_num_cu() {
-  static int cu = 0;
-  if (cu == 0) {
-    hipDeviceProp_t p; int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cu = p.multiProcessorCount;
-    else (void)hipGetLastError();
-    if (cu <= 0) cu = 256;
-  }
-  return imm_limit_cus(cu);
-}
-
 // Tile plan of a layer: patch height (16 = 8-wave kernel, 8 = 4-wave kernel) and channel-block width.
 //   16 x 16 patch x 128 channels when that still gives every CU a workgroup;
 //   16 x 16 x 64 when THAT does;
 //   else 8 x 16 x 64 (4 waves, two workgroups per CU) when the map height allows — the small-grid layers (16x16 maps of
 //   a 32-image batch: 32 patches) otherwise leave half the chip idle.
-struct HdPlan { int ph, bn, n_patches, n_wg; bool map8, persist, row3; };
+struct HdPlan { int ph, bn, n_patches, n_wg, cus; bool map8, persist, row3; };   // cus: the CU count the plan was made for
 
 static HdPlan hd_plan(const imm_conv_desc* d) {
-  constexpr bool no_small = false;
-  const int cus = hd_num_cu();
+  const int cus = imm_launch_cus();
   constexpr int small_below = 2;   // x CUs (round 3: 4 -> 2.  128 -> 64 channels at 64x64 maps, batch 32 — renderer conv_5, VGG conv2_1's data
                                    // gradient — as 512 tiles of 16x16x64 (8 waves) instead of 1024 of 8x16x64: -12 us per step, same box)
-  constexpr bool no_big = false;
   HdPlan p;
-  p.map8 = false; p.persist = false; p.row3 = false;
+  p.cus = cus; p.map8 = false; p.persist = false; p.row3 = false;
   if (d->ho == 8 && d->wo == 8) {                      // two whole 8x8 images per (4-wave) workgroup
     p.ph = 8; p.bn = 64; p.map8 = true;
     p.n_patches = (d->batch + 1) / 2;
@@ -641,21 +629,17 @@ static HdPlan hd_plan(const imm_conv_desc* d) {
     return p;
   }
   const int np16 = (d->ho % 16 == 0) ? d->batch * (d->ho / 16) * (d->wo / HD_PW) : 0;
-  if (!no_big && np16 > 0 && d->co % 128 == 0 && np16 * (d->co / 128) >= cus) { p.ph = 16; p.bn = 128; p.n_patches = np16; }
-  else if (np16 > 0 && (np16 * (d->co / 64) >= small_below * cus || no_small)) { p.ph = 16; p.bn = 64; p.n_patches = np16; }
-  else if (!no_small) { p.ph = 8; p.bn = 64; p.n_patches = d->batch * (d->ho / 8) * (d->wo / HD_PW); }
-  else { p.ph = 16; p.bn = 64; p.n_patches = np16; }
+  if (np16 > 0 && d->co % 128 == 0 && np16 * (d->co / 128) >= cus) { p.ph = 16; p.bn = 128; p.n_patches = np16; }
+  else if (np16 > 0 && np16 * (d->co / 64) >= small_below * cus) { p.ph = 16; p.bn = 64; p.n_patches = np16; }
+  else { p.ph = 8; p.bn = 64; p.n_patches = d->batch * (d->ho / 8) * (d->wo / HD_PW); }
   p.n_wg = p.n_patches * (d->co / p.bn);
   // 8x16 tiles that would be two rounds of 4-wave workgroups (e.g. 32x32 maps, 128 channels: 512) as ONE round of 8-wave
   // 16x16x64 workgroups with the row-at-a-time schedule
-  constexpr bool row3_big = true;
-  if (row3_big && !no_small && p.ph == 8 && p.bn == 64 && p.n_wg > cus && np16 > 0 && np16 * (d->co / 64) <= cus &&
-      np16 * (d->co / 64) >= cus / 2) {
+  if (p.ph == 8 && p.n_wg > cus && np16 > 0 && np16 * (d->co / 64) <= cus && np16 * (d->co / 64) >= cus / 2) {
     p.ph = 16; p.n_patches = np16; p.n_wg = np16 * (d->co / 64); p.row3 = true;
   }
   // more tiles than CUs: one persistent workgroup per CU walks them
-  constexpr bool persist = true;
-  p.persist = persist && p.ph == 16 && p.n_wg > cus && (cus % 8) == 0 && !(d->flags & IMM_CONV_STATS);
+  p.persist = p.ph == 16 && p.n_wg > cus && (cus % 8) == 0 && !(d->flags & IMM_CONV_STATS);
   return p;
 }
 
@@ -677,46 +661,57 @@ bool imm_hdeep_applicable(const imm_conv_desc* d) {
 
 int imm_hdeep_stats_blocks(const imm_conv_desc* d) { return hd_plan(d).n_patches; }
 
-static bool hd_takes_hdeep6(const imm_conv_desc* d, const HdPlan& p);
-// imm_conv2d_variant: 6 * 100000 + persist for the six-k-steps-per-barrier kernel (conv_hdeep6.hip), else
+// One instantiation of conv_hdeep_kernel, and the code imm_conv2d_variant reports for it:
 // 5 * 100000 + map8 * 40000 + row-at-a-time * 20000 + persistent * 10000 + channel block * 10 + waves
+template <int BN_, int NW_, int PH_, bool MAP8_ = false, int NSB_ = 0, bool PERSIST_ = false, bool ROW3_ = false>
+struct HdKernel {
+  static constexpr int BN = BN_, NW = NW_, PH = PH_, NSB = NSB_;
+  static constexpr bool MAP8 = MAP8_, PERSIST = PERSIST_, ROW3 = ROW3_;
+  static constexpr int variant = 500000 + (MAP8 ? 40000 : 0) + (ROW3 ? 20000 : 0) + (PERSIST ? 10000 : 0) + BN * 10 + NW;
+};
+
+// The kernel a plan runs with: f(HdKernel<...>()) of the ONE instantiation chosen here; the launch and the variant code both
+// go through it.  Row-at-a-time (one barrier per filter row, DESIGN item 27) takes 119 KB of LDS, one workgroup per CU — only
+// where the grid leaves it at one per CU anyway; with more tiles than CUs the 78 KB tap-at-a-time form keeps two co-resident
+// (32x32 128->128, 512 tiles: 14.2 vs 17.1 us).
+template <typename F>
+static auto hd_kernel(const HdPlan& p, F&& f) {
+  const bool one_wave = p.n_wg <= p.cus;
+  if (p.ph == 8 && one_wave) return p.map8 ? f(HdKernel<64, 4, 8, true, 9, false, true>()) : f(HdKernel<64, 4, 8, false, 9, false, true>());
+  if (p.map8) return f(HdKernel<64, 4, 8, true>());
+  if (p.ph == 16 && p.bn == 128) return p.persist ? f(HdKernel<128, 8, 16, false, 0, true>()) : f(HdKernel<128, 8, 16>());
+  if (p.ph == 16 && p.row3) return f(HdKernel<64, 8, 16, false, 9, false, true>());
+  if (p.ph == 16) return p.persist ? f(HdKernel<64, 8, 16, false, 0, true>()) : f(HdKernel<64, 8, 16>());
+  return f(HdKernel<64, 4, 8>());
+}
+
+// the 16x16x128 tile without batch-norm partial sums runs the six-k-steps-per-barrier form (conv_hdeep6.hip)
+static bool hd_takes_hdeep6(const imm_conv_desc* d, const HdPlan& p) {
+  return p.ph == 16 && p.bn == 128 && !p.map8 && !(d->flags & IMM_CONV_STATS) && imm_hdeep6_enabled();
+}
+
+// imm_conv2d_variant: 6 * 100000 + persist for conv_hdeep6.hip, else the chosen HdKernel's code
 int imm_hdeep_variant(const imm_conv_desc* d) {
   const HdPlan p = hd_plan(d);
   if (hd_takes_hdeep6(d, p)) return 600000 + (p.persist ? 1 : 0);
-  const bool one_wave = p.n_wg <= hd_num_cu();
-  const bool row3 = (p.map8 && one_wave) || (p.ph == 8 && p.bn == 64 && !p.map8 && one_wave) || (p.ph == 16 && p.bn == 64 && p.row3);
-  const bool persist = !row3 && !p.map8 && p.ph == 16 && p.persist;
-  return 500000 + (p.map8 ? 40000 : 0) + (row3 ? 20000 : 0) + (persist ? 10000 : 0) + p.bn * 10 + (p.ph == 16 ? 8 : 4);
+  return hd_kernel(p, [](auto k) { return decltype(k)::variant; });
 }
 
 template <typename ET, int BN, int NW, int PH, bool MAP8 = false, int NSB_ = 0, bool PERSIST = false, bool ROW3 = false, bool S2D = false>
 static void hd_launch_cfg(const HdArgs& ha, hipStream_t s) {
   constexpr int hstage = MAP8 ? 25 * 64 : HD_HSTAGE(PH), nsb = NSB_ ? NSB_ : MAP8 ? 3 : 4;
   constexpr int lds = (2 * hstage + 64 + nsb * BN * 8) * 16 + (PERSIST ? NW * BN * 4 : 0);   // + [NW/2][2][BN] f32 stats scratch
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)conv_hdeep_kernel<ET, BN, NW, PH, MAP8, NSB_, PERSIST, ROW3, S2D>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
-  const int grid = PERSIST ? (ha.n_wg < hd_num_cu() ? ha.n_wg : hd_num_cu()) : ha.n_wg;
-  hipLaunchKernelGGL((conv_hdeep_kernel<ET, BN, NW, PH, MAP8, NSB_, PERSIST, ROW3, S2D>), dim3(grid), dim3(NW * 64), lds, s, ha);
+  const int cus = imm_launch_cus();
+  const int grid = PERSIST ? (ha.n_wg < cus ? ha.n_wg : cus) : ha.n_wg;
+  imm_launch<conv_hdeep_kernel<ET, BN, NW, PH, MAP8, NSB_, PERSIST, ROW3, S2D>>(dim3(grid), dim3(NW * 64), lds, s, ha);
 }
 
 template <typename ET>
 static void hd_launch(const HdPlan& p, const HdArgs& ha, hipStream_t s) {
-  constexpr bool row3 = true;   // one barrier per filter row (DESIGN item 27)
-  // (119 KB of LDS: one workgroup per CU — only where the grid leaves it at one per CU anyway; with more tiles than CUs the
-  // 78 KB tap-at-a-time form keeps two co-resident: 32x32 128->128, 512 tiles, 14.2 vs 17.1 us)
-  const bool one_wave = p.n_wg <= hd_num_cu();
-  if (p.map8 && row3 && one_wave) hd_launch_cfg<ET, 64, 4, 8, true, 9, false, true>(ha, s);
-  else if (p.ph == 8 && p.bn == 64 && !p.map8 && row3 && one_wave) hd_launch_cfg<ET, 64, 4, 8, false, 9, false, true>(ha, s);
-  else if (p.map8) hd_launch_cfg<ET, 64, 4, 8, true>(ha, s);
-  else if (p.ph == 16 && p.bn == 128 && p.persist) hd_launch_cfg<ET, 128, 8, 16, false, 0, true>(ha, s);
-  else if (p.ph == 16 && p.bn == 128) hd_launch_cfg<ET, 128, 8, 16>(ha, s);
-  else if (p.ph == 16 && p.bn == 64 && p.row3) hd_launch_cfg<ET, 64, 8, 16, false, 9, false, true>(ha, s);
-  else if (p.ph == 16 && p.persist) hd_launch_cfg<ET, 64, 8, 16, false, 0, true>(ha, s);
-  else if (p.ph == 16) hd_launch_cfg<ET, 64, 8, 16>(ha, s);
-  else hd_launch_cfg<ET, 64, 4, 8>(ha, s);
+  hd_kernel(p, [&](auto k) {
+    using K = decltype(k);
+    hd_launch_cfg<ET, K::BN, K::NW, K::PH, K::MAP8, K::NSB, K::PERSIST, K::ROW3>(ha, s);
+  });
 }
 
 // IMM_HDEEP_PROF=1: workgroup 0 / wave 0 of every hdeep launch stamps the device wall clock (100 MHz) at its tile / tap
@@ -733,18 +728,10 @@ static void hd_prof_dump() {
             i > 1 ? (double)((host[i] & mask) - (host[i - 1] & mask)) / 100.0 : 0.0);
 }
 
-bool imm_hdeep6_enabled();                                                           // conv_hdeep6.hip
-void imm_conv_hdeep6_launch(int dtype, const ConvArgs& a, int n_patches, int patches_x, int patches_y, int n_wg, bool persist, int cus,
-                            hipStream_t s);
-// the 16x16x128 tile without batch-norm partial sums runs the six-k-steps-per-barrier form (conv_hdeep6.hip)
-static bool hd_takes_hdeep6(const imm_conv_desc* d, const HdPlan& p) {
-  return p.ph == 16 && p.bn == 128 && !p.map8 && !(d->flags & IMM_CONV_STATS) && imm_hdeep6_enabled();
-}
-
 void imm_conv_hdeep_launch(int dtype, const imm_conv_desc* d, const ConvArgs& a, hipStream_t s) {
   HdArgs ha;
   ha.c = a;
-  static const bool prof = getenv("IMM_HDEEP_PROF") != nullptr;
+  const bool prof = imm_env_flag(IMM_ENV_HDEEP_PROF);
   if (prof && !hd_prof_buf && hipMalloc((void**)&hd_prof_buf, 4000 * sizeof(unsigned long long)) == hipSuccess) {
     (void)hipMemset(hd_prof_buf, 0, 4000 * sizeof(unsigned long long));
     atexit(hd_prof_dump);
@@ -759,7 +746,7 @@ void imm_conv_hdeep_launch(int dtype, const imm_conv_desc* d, const ConvArgs& a,
   ha.c.x_bytes = (uint32_t)((int64_t)d->batch * d->hi * d->wi * d->ldx * 2);
   ha.c.wt_bytes = (uint32_t)((int64_t)d->co * d->kpad * 2);
   if (hd_takes_hdeep6(d, p)) {
-    imm_conv_hdeep6_launch(dtype, ha.c, ha.n_patches, ha.patches_x, ha.patches_y, ha.n_wg, p.persist, hd_num_cu(), s);
+    imm_conv_hdeep6_launch(dtype, ha.c, ha.n_patches, ha.patches_x, ha.patches_y, ha.n_wg, p.persist, p.cus, s);
     return;
   }
   if (dtype == IMM_BF16) hd_launch<BF16>(p, ha, s); else hd_launch<F16>(p, ha, s);
@@ -796,7 +783,7 @@ void imm_conv_hdeep_s2d_launch(int dtype, const imm_conv_desc* d, const ConvArgs
   ha.c.wt_bytes = (uint32_t)((int64_t)d->co * d->kpad * 2);
   // one round of workgroups or less: the row-at-a-time schedule (119 KB of LDS, one workgroup per CU anyway); larger grids keep
   // the 78 KB tap-at-a-time form
-  const bool row3 = ha.n_wg <= hd_num_cu();
+  const bool row3 = ha.n_wg <= imm_launch_cus();
   if (dtype == IMM_BF16) {
     if (row3) hd_launch_cfg<BF16, 64, 4, 8, false, 9, false, true, true>(ha, s);
     else hd_launch_cfg<BF16, 64, 4, 8, false, 0, false, false, true>(ha, s);

@@ -21,6 +21,7 @@
 // slot are issued 3 right after the barrier and 3 + 3 inside the first two k-steps of the following interval, between MFMA
 // quarters.  Persistent workgroups (more tiles than CUs) simply let the loader run on into the next tile.
 #include "conv_common.h"
+#include "conv_dispatch.h"
 #include <stdlib.h>
 
 #define H6_PW 16
@@ -447,13 +448,8 @@ bool imm_hdeep6_enabled() {
 
 template <typename ET, bool PERSIST>
 static void h6_launch_cfg(const H6Args& ha, int cus, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)conv_hdeep6_kernel<ET, PERSIST>, hipFuncAttributeMaxDynamicSharedMemorySize, H6_LDS);
-    attr_set = true;
-  }
   const int grid = PERSIST ? (ha.n_wg < cus ? ha.n_wg : cus) : ha.n_wg;
-  hipLaunchKernelGGL((conv_hdeep6_kernel<ET, PERSIST>), dim3(grid), dim3(512), H6_LDS, s, ha);
+  imm_launch<conv_hdeep6_kernel<ET, PERSIST>>(dim3(grid), dim3(512), H6_LDS, s, ha);
 }
 
 void imm_conv_hdeep6_launch(int dtype, const ConvArgs& a, int n_patches, int patches_x, int patches_y, int n_wg, bool persist, int cus,

@@ -13,30 +13,8 @@
 // CONSECUTIVE channels of one pixel -> 8-byte (16-bit out) / 16-byte (f32 out) NHWC stores.
 // Epilogue: bias, ReLU, ReLU-backward mask, and deterministic per-M-block batch-norm partial sums.
 #include "conv_common.h"
+#include "conv_dispatch.h"
 #include <stdlib.h>
-
-bool imm_halo_applicable(const imm_conv_desc* d);                                  // conv_halo.hip
-int imm_halo_grid(const imm_conv_desc* d);
-void imm_conv_halo_launch(int dtype, const imm_conv_desc* d, const ConvArgs& a, hipStream_t s);
-bool imm_hdeep_applicable(const imm_conv_desc* d);                                 // conv_hdeep.hip
-int imm_hdeep_stats_blocks(const imm_conv_desc* d);
-int imm_hdeep_variant(const imm_conv_desc* d);
-void imm_conv_hdeep_launch(int dtype, const imm_conv_desc* d, const ConvArgs& a, hipStream_t s);
-bool imm_halo_nol_applicable(const imm_conv_desc* d);
-void imm_conv_halo_nol_launch(int dtype, const imm_conv_desc* d, const ConvArgs& a, const float* scale, const float* shift, int relu,
-                              hipStream_t s);
-bool imm_halo_s2d_applicable(const imm_conv_desc* d);
-void imm_conv_halo_s2d_launch(int dtype, const imm_conv_desc* d, const ConvArgs& a, hipStream_t s);
-bool imm_s2f_applicable(const imm_conv_desc* d);                                   // conv_s2f.hip
-int imm_s2f_stats_blocks(const imm_conv_desc* d);
-int imm_s2f_variant(const imm_conv_desc* d);
-void imm_conv_s2f_launch(int dtype, const imm_conv_desc* d, const ConvArgs& a, hipStream_t s);
-bool imm_hdeep_s2d_applicable(const imm_conv_desc* d);
-void imm_conv_hdeep_s2d_launch(int dtype, const imm_conv_desc* d, const ConvArgs& a, hipStream_t s);
-bool imm_halo2_applicable(const imm_conv_desc* d);                                 // conv_halo2.hip
-int imm_halo2_grid(const imm_conv_desc* d);
-bool imm_halo2_x32(const imm_conv_desc* d);
-void imm_conv_halo2_launch(int dtype, const imm_conv_desc* d, const ConvArgs& a, hipStream_t s);
 
 __device__ __forceinline__ int lds_chunk_idx(int row, int chunk) {
   // 64-byte rows; swizzle so the four 16-lane service groups of ds_read_b128 hit 16 distinct slots
@@ -239,18 +217,6 @@ __global__ __launch_bounds__(256) void conv_igemm_group_kernel(const ConvArgsGro
 // ---------------------------------------------------------------------------------------------
 struct TileCfg { int bm, bn; };
 
-static int g_num_cu = 0;
-static int num_cu() {
-  if (g_num_cu == 0) {
-    hipDeviceProp_t p;
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess)
-      g_num_cu = p.multiProcessorCount;
-    if (g_num_cu <= 0) g_num_cu = 256;
-  }
-  return g_num_cu;
-}
-
 static TileCfg pick_tile(int64_t M, int co) {
   // candidates in order of preference (largest tile first); take the first that fills the chip
   TileCfg cands[3];
@@ -259,7 +225,7 @@ static TileCfg pick_tile(int64_t M, int co) {
   else if (co > 32) { cands[nc++] = {128, 64}; cands[nc++] = {64, 64}; }
   else if (co > 16) { cands[nc++] = {128, 32}; }
   else { cands[nc++] = {128, 16}; }
-  const int64_t want = 2LL * num_cu();
+  const int64_t want = 2LL * imm_device_cus();
   for (int i = 0; i < nc; ++i) {
     const int64_t blocks = ((M + cands[i].bm - 1) / cands[i].bm) * ((co + cands[i].bn - 1) / cands[i].bn);
     if (blocks >= want) return cands[i];
@@ -284,15 +250,44 @@ static int validate_desc(const imm_conv_desc* d) {
   return 0;
 }
 
+// The kernel imm_conv2d runs for a (valid) descriptor.  The dispatch order is the order of the tests in conv_plan and is written
+// nowhere else: the launch, imm_conv2d_variant, imm_conv_stats_blocks, imm_conv2d_tap_supported and group_plan all read the plan.
+// Families (= variant / 100000): 1 conv_igemm (BK = 32, register-staged), 2 conv_igemm64 (BK = 64, LDS-DMA ring), 3 conv_halo
+// (filter in LDS), 4 conv_halo2 (filter in registers), 5 conv_hdeep (LDS halo, tap / row at a time), 6 conv_hdeep6 (chosen
+// inside conv_hdeep.hip), 7 conv_s2f (stride-2 forward through a parity-de-interleaved LDS halo).
+enum { FAM_IGEMM = 1, FAM_IGEMM64 = 2, FAM_HALO = 3, FAM_HALO2 = 4, FAM_HDEEP = 5, FAM_HDEEP6 = 6, FAM_S2F = 7 };
+struct ConvPlan {
+  int family, variant, stats_rows;      // variant: imm_conv2d_variant's code; stats_rows: rows of batch-norm partial sums
+  // the im2col kernels' choice (families 1 and 2; filled for every descriptor: group_plan asks what a member WOULD take)
+  TileCfg tile;
+  bool fast, deep;                      // one tap x 32 channels per K tile through buffer loads; the BK = 64 kernel
+  uint32_t x_bytes, wt_bytes;           // buffer extents of the fast path, else 0
+};
+
+static ConvPlan conv_plan(const imm_conv_desc* d) {
+  ConvPlan p;
+  const int64_t M = (int64_t)d->batch * d->ho * d->wo;
+  p.tile = pick_tile(M, d->co);
+  const int64_t xb = (int64_t)d->batch * d->hi * d->wi * d->ldx * 2, wb = (int64_t)d->co * d->kpad * 2;
+  p.fast = (d->ci % 32 == 0) && xb < (1LL << 31) && wb < (1LL << 31);
+  p.deep = p.fast && (d->ci % 64 == 0) && p.tile.bn >= 64 && !(d->flags & 0xf00) && !imm_conv_disabled("deepk");
+  p.x_bytes = (uint32_t)(p.fast ? xb : 0);
+  p.wt_bytes = (uint32_t)(p.fast ? wb : 0);
+  if (imm_halo2_applicable(d)) { p.variant = imm_halo2_variant(d); p.stats_rows = imm_halo2_grid(d); }
+  else if (imm_halo_applicable(d)) { p.variant = imm_halo_variant(d); p.stats_rows = imm_halo_grid(d); }
+  else if (imm_hdeep_applicable(d)) { p.variant = imm_hdeep_variant(d); p.stats_rows = imm_hdeep_stats_blocks(d); }
+  else if (imm_s2f_applicable(d)) { p.variant = imm_s2f_variant(d); p.stats_rows = imm_s2f_stats_blocks(d); }
+  else {
+    p.variant = (p.deep ? FAM_IGEMM64 : FAM_IGEMM) * 100000 + (p.fast ? 10000 : 0) + (p.tile.bm / 16) * 100 + p.tile.bn / 16;
+    p.stats_rows = (int)((M + p.tile.bm - 1) / p.tile.bm);
+  }
+  p.family = p.variant / 100000;
+  return p;
+}
+
 extern "C" int imm_conv_stats_blocks(const imm_conv_desc* d) {
   if (validate_desc(d)) return IMM_E_INVALID;
-  if (imm_halo2_applicable(d)) return imm_halo2_grid(d);
-  if (imm_halo_applicable(d)) return imm_halo_grid(d);
-  if (imm_hdeep_applicable(d)) return imm_hdeep_stats_blocks(d);
-  if (imm_s2f_applicable(d)) return imm_s2f_stats_blocks(d);
-  const int64_t M = (int64_t)d->batch * d->ho * d->wo;
-  const TileCfg t = pick_tile(M, d->co);
-  return (int)((M + t.bm - 1) / t.bm);
+  return conv_plan(d).stats_rows;
 }
 
 template <typename ET, int BM, int BN, int WGM, int WGN>
@@ -302,9 +297,6 @@ static void launch_cfg(ConvArgs& a, bool fast, hipStream_t s) {
   if (fast) hipLaunchKernelGGL((conv_igemm_kernel<ET, BM, BN, WGM, WGN, true>), dim3(a.n_blocks), dim3(256), 0, s, a);
   else hipLaunchKernelGGL((conv_igemm_kernel<ET, BM, BN, WGM, WGN, false>), dim3(a.n_blocks), dim3(256), 0, s, a);
 }
-
-void imm_conv64_launch(int dtype, ConvArgs& a, int bm, int bn, hipStream_t s);   // conv_igemm64.hip
-bool imm_conv64_group_launch(int dtype, ConvArgs* args, int n, int bm, int bn, hipStream_t s);
 
 static void fill_args(ConvArgs& a, const imm_conv_desc* d, const void* x, const void* wt, const float* bias, void* y,
                       float* stats, const void* mask) {
@@ -325,64 +317,35 @@ static int conv_launch(const imm_conv_desc* d, const void* x, const void* wt, co
                        float* stats, const void* mask, hipStream_t s) {
   ConvArgs a;
   fill_args(a, d, x, wt, bias, y, stats, mask);
-  if (imm_halo2_applicable(d)) {
-    imm_conv_halo2_launch(ET::kEnum, d, a, s);
-    IMM_CHECK_LAUNCH("imm_conv2d(halo2)");
-    return 0;
+  const ConvPlan p = conv_plan(d);
+  switch (p.family) {
+    case FAM_HALO2: imm_conv_halo2_launch(ET::kEnum, d, a, s); IMM_CHECK_LAUNCH("imm_conv2d(halo2)"); return 0;
+    case FAM_HALO: imm_conv_halo_launch(ET::kEnum, d, a, s); IMM_CHECK_LAUNCH("imm_conv2d(halo)"); return 0;
+    case FAM_HDEEP:
+    case FAM_HDEEP6: imm_conv_hdeep_launch(ET::kEnum, d, a, s); IMM_CHECK_LAUNCH("imm_conv2d(hdeep)"); return 0;
+    case FAM_S2F: imm_conv_s2f_launch(ET::kEnum, d, a, s); IMM_CHECK_LAUNCH("imm_conv2d(s2f)"); return 0;
   }
-  if (imm_halo_applicable(d)) {
-    imm_conv_halo_launch(ET::kEnum, d, a, s);
-    IMM_CHECK_LAUNCH("imm_conv2d(halo)");
-    return 0;
-  }
-  if (imm_hdeep_applicable(d)) {
-    imm_conv_hdeep_launch(ET::kEnum, d, a, s);
-    IMM_CHECK_LAUNCH("imm_conv2d(hdeep)");
-    return 0;
-  }
-  if (imm_s2f_applicable(d)) {
-    imm_conv_s2f_launch(ET::kEnum, d, a, s);
-    IMM_CHECK_LAUNCH("imm_conv2d(s2f)");
-    return 0;
-  }
-  const TileCfg t = pick_tile(a.M, a.co);
+  const TileCfg t = p.tile;
   a.n_nblk = (a.co + t.bn - 1) / t.bn;
-  const int64_t xb = (int64_t)d->batch * d->hi * d->wi * d->ldx * 2, wb = (int64_t)d->co * d->kpad * 2;
-  const bool fast = (d->ci % 32 == 0) && xb < (1LL << 31) && wb < (1LL << 31);
-  a.x_bytes = (uint32_t)(fast ? xb : 0);
-  a.wt_bytes = (uint32_t)(fast ? wb : 0);
-  const bool deep = fast && (d->ci % 64 == 0) && t.bn >= 64 && !(d->flags & 0xf00) && !imm_conv_disabled("deepk");
-  if (deep) imm_conv64_launch(ET::kEnum, a, t.bm, t.bn, s);
-  else if (t.bm == 128 && t.bn == 128) launch_cfg<ET, 128, 128, 2, 2>(a, fast, s);
-  else if (t.bm == 128 && t.bn == 64) launch_cfg<ET, 128, 64, 2, 2>(a, fast, s);
-  else if (t.bm == 64 && t.bn == 64) launch_cfg<ET, 64, 64, 2, 2>(a, fast, s);
-  else if (t.bm == 128 && t.bn == 32) launch_cfg<ET, 128, 32, 4, 1>(a, fast, s);
-  else launch_cfg<ET, 128, 16, 4, 1>(a, fast, s);
+  a.x_bytes = p.x_bytes;
+  a.wt_bytes = p.wt_bytes;
+  if (p.deep) imm_conv64_launch(ET::kEnum, a, t.bm, t.bn, s);
+  else if (t.bm == 128 && t.bn == 128) launch_cfg<ET, 128, 128, 2, 2>(a, p.fast, s);
+  else if (t.bm == 128 && t.bn == 64) launch_cfg<ET, 128, 64, 2, 2>(a, p.fast, s);
+  else if (t.bm == 64 && t.bn == 64) launch_cfg<ET, 64, 64, 2, 2>(a, p.fast, s);
+  else if (t.bm == 128 && t.bn == 32) launch_cfg<ET, 128, 32, 4, 1>(a, p.fast, s);
+  else launch_cfg<ET, 128, 16, 4, 1>(a, p.fast, s);
   IMM_CHECK_LAUNCH("imm_conv2d");
   return 0;
 }
 
-// Which kernel imm_conv2d runs for a descriptor (the twin of imm_conv2d_wgrad_variant): family * 100000 + tile variant, following
-// conv_launch's order exactly.  Families: 1 conv_igemm (BK = 32, register-staged), 2 conv_igemm64 (BK = 64, LDS-DMA ring),
-// 3 conv_halo (filter in LDS), 4 conv_halo2 (filter in registers), 5 conv_hdeep (LDS halo, tap / row at a time), 6 conv_hdeep6,
-// 7 conv_s2f (stride-2 forward through a parity-de-interleaved LDS halo).
+// Which kernel imm_conv2d runs for a descriptor (the twin of imm_conv2d_wgrad_variant): conv_plan's variant code.
 extern "C" int imm_conv2d_variant(const imm_conv_desc* d, int dtype) {
   if (validate_desc(d)) return IMM_E_INVALID;
   if (dtype == IMM_F32) return 800000;                 // family 8: the plain f32 kernels of the witness engine (conv_f32.hip)
   IMM_REQUIRE(dtype == IMM_BF16 || dtype == IMM_F16, "unknown dtype %d", dtype);
-  if (imm_halo2_applicable(d)) return 400000 + (d->kw == 1 ? 10000 : 0) + (imm_halo2_x32(d) ? 20000 : 0) + d->ci * 100 + (d->co > 32 ? 64 : 32);   // + 20000: the 32x32x16 form
-  if (imm_halo_applicable(d)) return 300000 + (d->stride == 2 ? 10000 : 0) + d->ci * 100 + (d->co > 32 ? 64 : d->co > 16 ? 32 : 16);
-  if (imm_hdeep_applicable(d)) return imm_hdeep_variant(d);
-  if (imm_s2f_applicable(d)) return imm_s2f_variant(d);
-  const TileCfg t = pick_tile((int64_t)d->batch * d->ho * d->wo, d->co);
-  const int64_t xb = (int64_t)d->batch * d->hi * d->wi * d->ldx * 2, wb = (int64_t)d->co * d->kpad * 2;
-  const bool fast = (d->ci % 32 == 0) && xb < (1LL << 31) && wb < (1LL << 31);
-  const bool deep = fast && (d->ci % 64 == 0) && t.bn >= 64 && !(d->flags & 0xf00) && !imm_conv_disabled("deepk");
-  return (deep ? 200000 : 100000) + (fast ? 10000 : 0) + (t.bm / 16) * 100 + t.bn / 16;
+  return conv_plan(d).variant;
 }
-
-int imm_conv_f32(const imm_conv_desc* d, const void* x, const void* wt, const float* bias, void* y, float* stats_partial,
-                 const void* mask_ref, hipStream_t s);                                  // conv_f32.hip
 
 extern "C" int imm_conv2d(const imm_conv_desc* d, int dtype, const void* x, const void* wt, const float* bias,
                           void* y, float* stats_partial, const void* mask_ref, void* stream) {
@@ -403,8 +366,8 @@ extern "C" int imm_conv2d(const imm_conv_desc* d, int dtype, const void* x, cons
 extern "C" int imm_conv2d_tap_supported(const imm_conv_desc* d) {
   if (!d || validate_desc(d)) return 0;
   if (d->flags & (IMM_CONV_BIAS | IMM_CONV_RELU | IMM_CONV_STATS | IMM_CONV_MASK | IMM_CONV_OUT_F32 | 0xfe0)) return 0;
-  if (imm_halo2_applicable(d) || imm_halo_applicable(d)) return 0;
-  return imm_hdeep_applicable(d) && d->co % 8 == 0 ? 1 : 0;
+  const int family = conv_plan(d).family;
+  return (family == FAM_HDEEP || family == FAM_HDEEP6) && d->co % 8 == 0 ? 1 : 0;
 }
 
 extern "C" int imm_conv2d_tap(const imm_conv_desc* d, int dtype, const void* x, const void* wt, void* y, const void* a_pred,
@@ -502,27 +465,28 @@ struct GroupPlan { bool grouped, grouped32; int bm, bn; int rows[4]; int total_r
 static int group_plan(const imm_conv_desc* descs, int n, GroupPlan* gp) {
   static const bool off = imm_conv_disabled("group");
   gp->grouped = !off; gp->grouped32 = !off && !imm_conv_disabled("group32"); gp->bm = gp->bn = 0; gp->total_rows = 0;
+  int own_rows[4];                     // a member launched on its own (imm_conv2d) writes its own plan's rows
   for (int i = 0; i < n; ++i) {
     const imm_conv_desc* d = descs + i;
     if (validate_desc(d)) return IMM_E_INVALID;
     IMM_REQUIRE(!(d->flags & IMM_CONV_BIAS), "conv_group: members carry no bias");
-    if (imm_halo2_applicable(d) || imm_halo_applicable(d) || imm_hdeep_applicable(d)) gp->grouped = gp->grouped32 = false;
-    const int64_t M = (int64_t)d->batch * d->ho * d->wo;
-    const TileCfg t = pick_tile(M, d->co);
-    const int64_t xb = (int64_t)d->batch * d->hi * d->wi * d->ldx * 2, wb = (int64_t)d->co * d->kpad * 2;
-    const bool deep = (d->ci % 64 == 0) && xb < (1LL << 31) && wb < (1LL << 31) && t.bn >= 64 && !(d->flags & 0xf00) &&
-                      !imm_conv_disabled("deepk");
-    if (!deep || (i > 0 && (t.bm != gp->bm || t.bn != gp->bn))) gp->grouped = false;
+    const ConvPlan p = conv_plan(d);
+    const TileCfg t = p.tile;
+    // a member that takes a halo kernel (halo2, halo, hdeep / hdeep6) keeps it.  conv_s2f is not in this list: it cannot take a
+    // parity class of ops.dgrad_s2_class_descs (stride 1, out_scale 2), but imm_conv2d_group accepts any member, and one that
+    // conv_s2f would take alone has always been grouped on its im2col tile
+    if (p.family >= FAM_HALO && p.family != FAM_S2F) gp->grouped = gp->grouped32 = false;
+    if (!p.deep || (i > 0 && (t.bm != gp->bm || t.bn != gp->bn))) gp->grouped = false;
     // the general kernel's 128x32 tile, one tap x 32 channels per K tile (ci % 32 == 0)
-    const bool fast32 = (d->ci % 32 == 0) && xb < (1LL << 31) && wb < (1LL << 31) && t.bm == 128 && t.bn == 32 && !(d->flags & 0xf00);
-    if (!fast32) gp->grouped32 = false;
+    if (!(p.fast && t.bm == 128 && t.bn == 32 && !(d->flags & 0xf00))) gp->grouped32 = false;
     gp->bm = t.bm; gp->bn = t.bn;
+    own_rows[i] = p.stats_rows;
   }
   if (gp->grouped) gp->grouped32 = false;
   if (gp->grouped && !(gp->bm == 64 && gp->bn == 64)) gp->grouped = false;   // the grouped kernel exists for the 64x64 tile only
   for (int i = 0; i < n; ++i) {
     const int64_t M = (int64_t)descs[i].batch * descs[i].ho * descs[i].wo;
-    gp->rows[i] = gp->grouped ? (int)((M + 63) / 64) : gp->grouped32 ? (int)((M + 127) / 128) : imm_conv_stats_blocks(descs + i);
+    gp->rows[i] = gp->grouped ? (int)((M + 63) / 64) : gp->grouped32 ? (int)((M + 127) / 128) : own_rows[i];
     gp->total_rows += gp->rows[i];
   }
   return 0;

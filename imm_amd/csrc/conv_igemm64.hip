@@ -9,6 +9,7 @@
 // covers row (l>>3) of an 8-row group and fetches source chunk (l&7) ^ swz(row).  Out-of-image taps and
 // rows beyond M / channels beyond co use an out-of-range buffer offset, for which the DMA writes zeros.
 #include "conv_common.h"
+#include "conv_dispatch.h"
 #include <stdlib.h>
 
 __device__ __forceinline__ int lds64_idx(int row, int chunk) { return row * 8 + (chunk ^ ((row >> 1) & 7)); }
@@ -162,12 +163,7 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm64_group_kernel(const ConvA
 template <typename ET, int BM, int BN, int NS, int NW = 4>
 static void launch64_cfg(const ConvArgs& a, hipStream_t s) {
   constexpr int lds = NS * (BM + BN) * 128;
-  static bool attr_set = false;   // per instantiation; > 64 KB of dynamic LDS needs the opt-in once
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)conv_igemm64_kernel<ET, BM, BN, NS, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((conv_igemm64_kernel<ET, BM, BN, NS, NW>), dim3(a.n_blocks), dim3(NW * 64), lds, s, a);
+  imm_launch<conv_igemm64_kernel<ET, BM, BN, NS, NW>>(dim3(a.n_blocks), dim3(NW * 64), lds, s, a);
 }
 
 template <typename ET>
@@ -186,11 +182,6 @@ template <typename ET>
 static bool launch64_group(ConvArgs* args, int n, int bm, int bn, hipStream_t s) {
   if (!(bm == 64 && bn == 64) || n < 1 || n > IMM_CONV_GROUP_MAX) return false;
   constexpr int NS = 4, lds = NS * (64 + 64) * 128;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)conv_igemm64_group_kernel<ET, 64, 64, NS, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
   ConvArgsGroup g;
   g.n = n;
   int total = 0;
@@ -202,7 +193,7 @@ static bool launch64_group(ConvArgs* args, int n, int bm, int bn, hipStream_t s)
     total += args[i].n_blocks;
   }
   for (int i = n; i <= IMM_CONV_GROUP_MAX; ++i) g.first[i] = total;
-  hipLaunchKernelGGL((conv_igemm64_group_kernel<ET, 64, 64, NS, 4>), dim3(total), dim3(256), lds, s, g);
+  imm_launch<conv_igemm64_group_kernel<ET, 64, 64, NS, 4>>(dim3(total), dim3(256), lds, s, g);
   return true;
 }
 

@@ -22,6 +22,7 @@
 // the batch-norm partial sums (one row per patch) — the stride-2 layers are conv + BN + ReLU blocks (imm_model.py:182-217) — and,
 // for the landmark detector whose batch norm is folded into W and b, the ReLU.
 #include "conv_common.h"
+#include "conv_dispatch.h"
 #include <stdlib.h>
 
 #define S2_PH 8
@@ -276,21 +277,10 @@ __global__ __launch_bounds__(BN * 4) void conv_s2f_kernel(const S2fArgs ha) {
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static int s2f_num_cu() {
-  static int cu = 0;
-  if (cu == 0) {
-    hipDeviceProp_t p; int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cu = p.multiProcessorCount;
-    else (void)hipGetLastError();
-    if (cu <= 0) cu = 256;
-  }
-  return cu;
-}
-
 // channel-block width: 128 (8 waves) when that still gives every CU a workgroup, else 64 (4 waves)
 static int s2f_bn(const imm_conv_desc* d) {
   const int np = d->batch * (d->ho / S2_PH) * (d->wo / S2_PW);
-  return (d->co % 128 == 0 && np * (d->co / 128) >= s2f_num_cu()) ? 128 : 64;
+  return (d->co % 128 == 0 && np * (d->co / 128) >= imm_device_cus()) ? 128 : 64;
 }
 
 bool imm_s2f_applicable(const imm_conv_desc* d) {
@@ -312,12 +302,7 @@ int imm_s2f_variant(const imm_conv_desc* d) { return 700000 + s2f_bn(d); }
 template <typename ET, int BN>
 static void s2f_launch_cfg(const S2fArgs& ha, hipStream_t s) {
   constexpr int lds = 2 * S2_HSTAGE + 1024 + 9 * BN * 64;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)conv_s2f_kernel<ET, BN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((conv_s2f_kernel<ET, BN>), dim3(ha.n_wg), dim3(BN * 4), lds, s, ha);
+  imm_launch<conv_s2f_kernel<ET, BN>>(dim3(ha.n_wg), dim3(BN * 4), lds, s, ha);
 }
 
 void imm_conv_s2f_launch(int dtype, const imm_conv_desc* d, const ConvArgs& a, hipStream_t s) {

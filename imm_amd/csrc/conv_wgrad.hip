@@ -11,6 +11,7 @@
 // The pixel range is split over `nsplit` blocks per tile; each writes its f32 partial tile to
 // slab[split][kpad][co]; imm_conv2d_wgrad_reduce sums slabs in a fixed order (deterministic).
 #include "common.h"
+#include "conv_dispatch.h"
 #include "gfx950.h"
 #include <stdlib.h>
 #include <string.h>
@@ -242,14 +243,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
 template <typename ET, int BK, int BN, int WGK, int WGN, bool FAST, int PSUB>
 static void wg_launch_one(const WgradArgs& a, hipStream_t s) {
   constexpr int lds = 2 * (BK + BN) * 64 * PSUB;
-  static bool attr_set = false;
-  if (!attr_set && lds > 64 * 1024) {
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_kernel<ET, BK, BN, WGK, WGN, FAST, PSUB>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((conv_wgrad_kernel<ET, BK, BN, WGK, WGN, FAST, PSUB>), dim3(a.n_kblk * a.n_nblk * a.nsplit),
-                     dim3(256), lds, s, a);
+  imm_launch<conv_wgrad_kernel<ET, BK, BN, WGK, WGN, FAST, PSUB>>(dim3(a.n_kblk * a.n_nblk * a.nsplit), dim3(256), lds, s, a);
 }
 
 template <typename ET, int BK, int BN, int WGK, int WGN>
@@ -294,19 +288,20 @@ static int wgrad_launch(const imm_conv_desc* d, const void* x, const void* dy, i
   return 0;
 }
 
-bool imm_wgrad_tr_applicable(const imm_conv_desc* d, int lddy);            // conv_wgrad_tr.hip
-void imm_wgrad_tr_launch(int dtype, const imm_conv_desc* d, const void* x, const void* dy, int lddy, float* slab, int nsplit,
-                         hipStream_t s);
-bool imm_wgrad_halo_applicable(const imm_conv_desc* d, int lddy);          // conv_wgrad_halo.hip
-int imm_wgrad_halo_splits(const imm_conv_desc* d, int lddy);
-void imm_wgrad_halo_launch(int dtype, const imm_conv_desc* d, const void* x, const void* dy, int lddy, float* slab,
-                           int nsplit, hipStream_t s, const float* nol_scale, const float* nol_shift, int nol_relu);
-
-int imm_conv_f32_wgrad(const imm_conv_desc* d, const void* x, const void* dy, int lddy, float* slab, int nsplit, hipStream_t s);   // conv_f32.hip
-
 extern "C" int imm_conv2d_wgrad_splits(const imm_conv_desc* d, int lddy) {
   if (!d) return IMM_E_INVALID;
   return imm_wgrad_halo_applicable(d, lddy) ? imm_wgrad_halo_splits(d, lddy) : 0;
+}
+
+// Kernel family + variant of a filter gradient: the LDS-halo kernels (halo_ok: the multi-problem launch gives them any split
+// count, imm_conv2d_wgrad only the forced one), the transpose-read kernels, else the generic kernel of this file.
+enum { WGM_SINGLE = 0, WGM_TR = 1, WGM_HALO = 2 };
+static void wgm_classify(const imm_conv_desc* d, int lddy, int dtype, bool halo_ok, int* kind, int* variant) {
+  const bool fast_dt = dtype == IMM_BF16 || dtype == IMM_F16;
+  const int hv = fast_dt && halo_ok ? imm_wgrad_halo_variant(d, lddy) : 0;
+  if (hv) { *kind = WGM_HALO; *variant = hv; return; }
+  if (fast_dt && imm_wgrad_tr_applicable(d, lddy)) { *kind = WGM_TR; *variant = imm_wgrad_tr_variant(d); return; }
+  *kind = WGM_SINGLE; *variant = 0;
 }
 
 extern "C" int imm_conv2d_wgrad(const imm_conv_desc* d, int dtype, const void* x, const void* dy, int lddy,
@@ -320,12 +315,14 @@ extern "C" int imm_conv2d_wgrad(const imm_conv_desc* d, int dtype, const void* x
   IMM_REQUIRE(d->wo % 2 == 0, "wgrad: output width must be even (pixel pairs)");
   IMM_REQUIRE(((uintptr_t)x % 16 == 0) && ((uintptr_t)dy % 16 == 0) && ((uintptr_t)slab % 16 == 0), "wgrad: alignment");
   if (dtype == IMM_F32) return imm_conv_f32_wgrad(d, x, dy, lddy, slab, nsplit, (hipStream_t)stream);     // the f32 witness (conv_f32.hip)
-  if (imm_wgrad_halo_applicable(d, lddy) && nsplit == imm_wgrad_halo_splits(d, lddy) && (dtype == IMM_BF16 || dtype == IMM_F16)) {
+  int kind, variant;
+  wgm_classify(d, lddy, dtype, /*halo_ok=*/nsplit == imm_conv2d_wgrad_splits(d, lddy), &kind, &variant);   // halo: at the forced split count only
+  if (kind == WGM_HALO) {
     imm_wgrad_halo_launch(dtype, d, x, dy, lddy, slab, nsplit, (hipStream_t)stream, nullptr, nullptr, 0);
     IMM_CHECK_LAUNCH("imm_conv2d_wgrad(halo)");
     return 0;
   }
-  if (imm_wgrad_tr_applicable(d, lddy) && (dtype == IMM_BF16 || dtype == IMM_F16)) {
+  if (kind == WGM_TR) {
     imm_wgrad_tr_launch(dtype, d, x, dy, lddy, slab, nsplit, (hipStream_t)stream);
     IMM_CHECK_LAUNCH("imm_conv2d_wgrad(tr)");
     return 0;
@@ -341,35 +338,13 @@ extern "C" int imm_conv2d_wgrad(const imm_conv_desc* d, int dtype, const void* x
 // leave the serial BN-backward -> data-gradient chain, a grouped launch has thousands of workgroups to balance, and — since
 // the chip no longer has to be filled by ONE layer — each layer needs far fewer pixel splits (slab traffic = nsplit x |dW|).
 // ---------------------------------------------------------------------------------------------------------------------
-int imm_wgrad_tr_variant(const imm_conv_desc* d);
-int imm_wgrad_tr_args_bytes();
-int imm_wgrad_tr_fill(const imm_conv_desc* d, const void* x, const void* dy, int lddy, float* slab, int nsplit, void* out, int* steps);
-void imm_wgrad_tr_launch_multi(int dtype, int bn, const void* tab_dev, const int* first_dev, int n, int blocks, hipStream_t s);
-int imm_wgrad_halo_variant(const imm_conv_desc* d, int lddy);
-int imm_wgrad_halo_blocks(const imm_conv_desc* d, int lddy, int* n_patches);
-int imm_wgrad_halo_args_bytes();
-int imm_wgrad_halo_per_cu(int variant);
-int imm_wgrad_halo_fill(const imm_conv_desc* d, const void* x, const void* dy, int lddy, float* slab, int nsplit, void* out, int* steps,
-                        const float* nol_scale, const float* nol_shift, int nol_relu);
-void imm_wgrad_halo_launch_multi(int dtype, int variant, const void* tab_dev, const int* first_dev, int n, int blocks, hipStream_t s);
-
 namespace {
 constexpr uint32_t WGM_MAGIC = 0x57474d31u;   // "WGM1"
 constexpr int WGM_MAX_LAUNCH = 16, WGM_MAX_JOBS = 64, WGM_ARG_STRIDE = 192, WGM_HEADER = 1024;
-enum { WGM_SINGLE = 0, WGM_TR = 1, WGM_HALO = 2 };
 struct WgmLaunch { int32_t kind, variant, n, arg_off, first_off, blocks, job0, pad; };
 struct WgmHeader { uint32_t magic; int32_t dtype, n_jobs, n_launch; WgmLaunch launch[WGM_MAX_LAUNCH]; };
 static_assert(sizeof(WgmHeader) <= WGM_HEADER, "header");
 
-// kernel family + variant a job runs with (the same choice imm_conv2d_wgrad makes, except that the halo kernel takes any
-// split count here)
-void wgm_classify(const imm_wgrad_job* j, int dtype, int* kind, int* variant) {
-  const bool fast_dt = dtype == IMM_BF16 || dtype == IMM_F16;
-  const int hv = fast_dt ? imm_wgrad_halo_variant(&j->desc, j->lddy) : 0;
-  if (hv) { *kind = WGM_HALO; *variant = hv; return; }
-  if (fast_dt && imm_wgrad_tr_applicable(&j->desc, j->lddy)) { *kind = WGM_TR; *variant = imm_wgrad_tr_variant(&j->desc); return; }
-  *kind = WGM_SINGLE; *variant = 0;
-}
 int wgm_check_job(const imm_wgrad_job* j) {
   const imm_conv_desc* d = &j->desc;
   IMM_REQUIRE(j->x && j->dy && j->slab, "wgrad_multi: null");
@@ -390,16 +365,14 @@ extern "C" int64_t imm_conv2d_wgrad_multi_table_bytes(int n) {
 
 extern "C" int imm_conv2d_wgrad_variant(const imm_conv_desc* d, int lddy, int dtype, int* wg_per_split, int* units, int* wg_per_cu) {
   IMM_REQUIRE(d && lddy >= d->co, "wgrad_variant: args");
-  imm_wgrad_job j; j.desc = *d; j.lddy = lddy; j.nsplit = 1; j.x = j.dy = nullptr; j.slab = nullptr;
-  j.x_scale = j.x_shift = nullptr; j.x_relu = 0;
   int kind, variant;
-  wgm_classify(&j, dtype, &kind, &variant);
+  wgm_classify(d, lddy, dtype, true, &kind, &variant);
   int wps = 1, un = 1, pcu = 2;                                // transpose-read / generic kernels: 65 KB of LDS, two per CU
   if (kind == WGM_HALO) {
     wps = imm_wgrad_halo_blocks(d, lddy, &un);                 // units: 8x16-pixel patches
     pcu = imm_wgrad_halo_per_cu(variant);
   } else {
-    const int bn = d->co > 64 ? 128 : d->co > 32 ? 64 : d->co > 16 ? 32 : 16;
+    const int bn = wgrad_bn(d->co);
     wps = ((d->kpad + 127) / 128) * ((d->co + bn - 1) / bn);
     un = (d->batch * d->ho * d->wo + 31) / 32;                 // units: 32-pixel steps
   }
@@ -420,7 +393,7 @@ extern "C" int imm_conv2d_wgrad_multi_plan(const imm_wgrad_job* jobs, int n, int
   bool done[WGM_MAX_JOBS];
   for (int i = 0; i < n; ++i) {
     if (wgm_check_job(&jobs[i])) return IMM_E_INVALID;
-    wgm_classify(&jobs[i], dtype, &kind[i], &variant[i]);
+    wgm_classify(&jobs[i].desc, jobs[i].lddy, dtype, true, &kind[i], &variant[i]);
     IMM_REQUIRE((jobs[i].x_scale == nullptr) == (jobs[i].x_shift == nullptr), "wgrad_multi_plan: job %d: x_scale / x_shift come together", i);
     IMM_REQUIRE(jobs[i].x_scale == nullptr || kind[i] == WGM_HALO,
                 "wgrad_multi_plan: job %d: normalise-on-load (x_scale) is served by the LDS-halo filter-gradient kernels only "

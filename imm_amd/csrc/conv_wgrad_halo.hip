@@ -19,6 +19,7 @@
 // contraction is consistent.  All 9*ci*co accumulators of the workgroup stay in registers over its patches and
 // are written once as one f32 slab per workgroup (summed by imm_wgrad_reduce_multi, fixed order).
 #include "conv_common.h"
+#include "conv_dispatch.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -324,16 +325,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_halo_multi_kernel(const WgradH
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static int wh_num_cu() {
-  static int n = 0;
-  if (n == 0) {
-    hipDeviceProp_t p; int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
 // Slice plan of a layer: channel slice widths, number of slices and pixel splits.
 struct WhPlan { int cs, ns, nci, nco, nsplit; bool k71, s2; };
 
@@ -352,7 +343,7 @@ static bool wh_plan(const imm_conv_desc* d, int lddy, WhPlan* pl) {
     if (xb2 >= (1LL << 31) || yb2 >= (1LL << 31)) return false;
     pl->cs = 32; pl->ns = 64; pl->nci = 1; pl->nco = 1;
     const int n_patches2 = d->batch * (d->ho / WH_PH) * (d->wo / WH_PW);
-    int ns2 = wh_num_cu();
+    int ns2 = imm_device_cus();
     if (ns2 > n_patches2 / 4) ns2 = n_patches2 / 4;
     pl->nsplit = ns2 < 1 ? 1 : ns2;
     return true;
@@ -390,8 +381,8 @@ static bool wh_plan(const imm_conv_desc* d, int lddy, WhPlan* pl) {
   // one workgroup per CU: two per CU (round 1) run the launches no faster and double the slab traffic of the whole-filter
   // layers (64->64 at 64x64: 75 MB of slabs each); measured 3.83 -> 3.80 ms per step (round 2, same box)
   constexpr int per_cu = 1;
-  int grid = per_cu * wh_num_cu();
-  if (blocks > 1) grid = wh_num_cu();                  // sliced layers: slab bytes = nsplit x |dW|, keep nsplit small
+  int grid = per_cu * imm_device_cus();
+  if (blocks > 1) grid = imm_device_cus();                  // sliced layers: slab bytes = nsplit x |dW|, keep nsplit small
   int nsplit = (grid + blocks - 1) / blocks;
   const int min_patches = blocks > 1 ? 2 : 4;          // patches per workgroup that amortise its slab write
   if (nsplit > n_patches / min_patches) nsplit = n_patches / min_patches;
@@ -430,12 +421,7 @@ static void wh_launch_cfg(const WgradHaloArgs& a, dim3 grid, hipStream_t s) {
   constexpr int stage = WhRing<CI, CO, KH, KW, ST>::stage;
   constexpr int NS = WhRing<CI, CO, KH, KW, ST>::NS;
   constexpr int lds = NS * stage + CI * 8;             // + the normalise-on-load coefficient table
-  static bool attr_set = false;
-  if (!attr_set && lds > 64 * 1024) {
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_halo_kernel<ET, CI, CO, NS, KH, KW, ST>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((conv_wgrad_halo_kernel<ET, CI, CO, NS, KH, KW, ST>), grid, dim3(256), lds, s, a);
+  imm_launch<conv_wgrad_halo_kernel<ET, CI, CO, NS, KH, KW, ST>>(grid, dim3(256), lds, s, a);
 }
 
 static WgradHaloArgs wh_fill(const imm_conv_desc* d, const void* x, const void* dy, int lddy, float* slab, int nsplit,
@@ -504,12 +490,7 @@ static void wh_launch_multi_cfg(const WgradHaloArgs* tab, const int* first, int 
   constexpr int stage = WhRing<CI, CO, KH, KW, ST>::stage;
   constexpr int NS = WhRing<CI, CO, KH, KW, ST>::NS;
   constexpr int lds = NS * stage + CI * 8;             // + the normalise-on-load coefficient table
-  static bool attr_set = false;
-  if (!attr_set && lds > 64 * 1024) {
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_halo_multi_kernel<ET, CI, CO, NS, KH, KW, ST>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((conv_wgrad_halo_multi_kernel<ET, CI, CO, NS, KH, KW, ST>), dim3(blocks), dim3(256), lds, s, tab, first, n);
+  imm_launch<conv_wgrad_halo_multi_kernel<ET, CI, CO, NS, KH, KW, ST>>(dim3(blocks), dim3(256), lds, s, tab, first, n);
 }
 
 void imm_wgrad_halo_launch_multi(int dtype, int variant, const void* tab_dev, const int* first_dev, int n, int blocks,

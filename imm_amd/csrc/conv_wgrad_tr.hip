@@ -12,6 +12,7 @@
 // tools/probes/tr_read_probe.hip).  No VGPR staging, no ds_write, no packing.
 // Requires the wave-uniform pixel walk (ho*wo % 32 == 0, wo | 32 or 32 | wo) and ci % 8 == 0.
 #include "common.h"
+#include "conv_dispatch.h"
 #include "gfx950.h"
 #include <stdlib.h>
 #include <string.h>
@@ -232,23 +233,13 @@ __global__ __launch_bounds__(256) void conv_wgrad_tr_multi_kernel(const WgradTrA
 template <typename ET, int BN, int WGK, int WGN, int NS>
 static void wt_launch_multi_cfg(const WgradTrArgs* tab, const int* first, int n, int blocks, hipStream_t s) {
   constexpr int lds = NS * (32 * 128 * 2 + 32 * BN * 2) + 1024;
-  static bool attr_set = false;
-  if (!attr_set && lds > 64 * 1024) {
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_tr_multi_kernel<ET, BN, WGK, WGN, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((conv_wgrad_tr_multi_kernel<ET, BN, WGK, WGN, NS>), dim3(blocks), dim3(256), lds, s, tab, first, n);
+  imm_launch<conv_wgrad_tr_multi_kernel<ET, BN, WGK, WGN, NS>>(dim3(blocks), dim3(256), lds, s, tab, first, n);
 }
 
 template <typename ET, int BN, int WGK, int WGN, int NS>
 static void wt_launch_cfg(const WgradTrArgs& a, hipStream_t s) {
   constexpr int lds = NS * (32 * 128 * 2 + 32 * BN * 2) + 1024;
-  static bool attr_set = false;
-  if (!attr_set && lds > 64 * 1024) {
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_tr_kernel<ET, BN, WGK, WGN, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((conv_wgrad_tr_kernel<ET, BN, WGK, WGN, NS>), dim3(a.n_kblk * a.n_nblk * a.nsplit), dim3(256), lds, s, a);
+  imm_launch<conv_wgrad_tr_kernel<ET, BN, WGK, WGN, NS>>(dim3(a.n_kblk * a.n_nblk * a.nsplit), dim3(256), lds, s, a);
 }
 
 template <typename ET>
@@ -290,7 +281,6 @@ static WgradTrArgs wt_fill(const imm_conv_desc* d, const void* x, const void* dy
   return a;
 }
 
-// called from conv_wgrad.hip
 void imm_wgrad_tr_launch(int dtype, const imm_conv_desc* d, const void* x, const void* dy, int lddy, float* slab, int nsplit,
                          hipStream_t s) {
   const WgradTrArgs a = wt_fill(d, x, dy, lddy, slab, nsplit);

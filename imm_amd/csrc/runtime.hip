@@ -29,7 +29,31 @@ bool imm_conv_disabled(const char* name) {
   }
   return false;
 }
+bool imm_env_flag(ImmEnvFlag which) {
+  if (which == IMM_ENV_HALO2X) {
+    static const bool on = getenv("IMM_HALO2X") && getenv("IMM_HALO2X")[0] == '1';
+    return on;
+  }
+  static const bool prof = getenv("IMM_HDEEP_PROF") != nullptr;
+  return prof;
+}
 extern "C" const char* imm_last_error(void) { return imm_err_buf; }
+
+int imm_device_cus() {
+  static int cus = 0;
+  if (cus == 0) {
+    hipDeviceProp_t p; int dev = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cus = p.multiProcessorCount;
+    else (void)hipGetLastError();       // no device (the CPU-only queries): not an error of the caller's next launch
+    if (cus <= 0) cus = 256;
+  }
+  return cus;
+}
+bool imm_dyn_lds_opt_in(const void* kernel, size_t bytes) {
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e != hipSuccess) imm_fail(IMM_E_HIP, "hipFuncSetAttribute(dyn LDS %zu): %s", bytes, hipGetErrorString(e));
+  return e == hipSuccess;
+}
 
 static thread_local int imm_cu_limit_tl = 0;
 int imm_limit_cus(int device_cus) { return (imm_cu_limit_tl > 0 && imm_cu_limit_tl < device_cus) ? imm_cu_limit_tl : device_cus; }
@@ -172,13 +196,6 @@ extern "C" int imm_crc32c(const void* data, uint64_t n, uint32_t* crc_inout) {
 // ---------------------------------------------------------------------------------------------
 // workspace sizes (bytes) of the caller-allocated scratch buffers: thin twins of the row-count queries
 // ---------------------------------------------------------------------------------------------
-extern "C" int imm_conv_stats_blocks(const imm_conv_desc* d);
-extern "C" int imm_conv2d_group_stats_blocks(const imm_conv_desc* descs, int n);
-extern "C" int imm_conv2d_wgrad_splits(const imm_conv_desc* d, int lddy);
-extern "C" int imm_colsum_blocks(int64_t npix, int c);
-extern "C" int imm_bn_bwd_blocks(int64_t npix, int c);
-extern "C" int imm_upsample2x_bwd_bn_blocks(int batch, int h, int w, int c);
-
 extern "C" int64_t imm_conv2d_workspace_bytes(const imm_conv_desc* d) {
   if (!d) return IMM_E_INVALID;
   if (!(d->flags & IMM_CONV_STATS)) return 0;

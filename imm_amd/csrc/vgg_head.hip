@@ -374,16 +374,6 @@ __global__ __launch_bounds__(256) void conv_halo2_vgg_head_kernel(const VhArgs h
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-static int vh_num_cu() {
-  static int cu = 0;
-  if (cu == 0) {
-    hipDeviceProp_t p; int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cu = p.multiProcessorCount;
-    if (cu <= 0) cu = 256;
-  }
-  return imm_limit_cus(cu);
-}
-
 extern "C" int imm_vgg_head_supported(int batch, int s, int dtype) {
   static const bool off = imm_conv_disabled("vgg_head");
   if (off || (dtype != IMM_BF16 && dtype != IMM_F16)) return 0;
@@ -422,15 +412,9 @@ extern "C" int imm_vgg_head_fwd(const float* gt, const float* pred, int ldp, int
   ha.gray_bytes = (uint32_t)(npix * 4);
   ha.act_bytes = (uint32_t)(npix * 128);
   const size_t lds = (size_t)(2 * VH_HSTAGE_U4 + VH_NG * VH_GSTAGE_U4) * 16;
-  static bool attr[2] = {false, false};
-  const int grid = ha.n_patches < vh_num_cu() ? ha.n_patches : vh_num_cu();
-  IMM_DISPATCH_DTYPE(dtype, {
-    if (!attr[dtype == IMM_F16]) {
-      (void)hipFuncSetAttribute((const void*)conv_halo2_vgg_head_kernel<ET>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr[dtype == IMM_F16] = true;
-    }
-    hipLaunchKernelGGL((conv_halo2_vgg_head_kernel<ET>), dim3(grid), dim3(256), lds, st, ha);
-  });
+  const int cus = imm_launch_cus();
+  const int grid = ha.n_patches < cus ? ha.n_patches : cus;
+  IMM_DISPATCH_DTYPE(dtype, imm_launch<conv_halo2_vgg_head_kernel<ET>>(dim3(grid), dim3(256), lds, st, ha));
   IMM_CHECK_LAUNCH("imm_vgg_head_fwd");
   return 0;
 }

@@ -269,3 +269,38 @@ def test_pinned_stager_host_side():
     assert torch.equal(dst, torch.arange(35.).reshape(7, 5).t())
     t = ops.to_device_pinned(np.arange(6, dtype=np.float64), 'cpu', torch.float32)
     assert t.dtype == torch.float32 and torch.equal(t, torch.arange(6.))
+
+
+def test_convolution_host_side_has_one_definition_of_each_fact():
+    """The private interface between the .hip files lives in csrc/conv_dispatch.h (no file declares an internal imm_* function it
+    does not define; every file that defines or calls one of the header's functions includes it), and device properties,
+    environment variables and the dynamic-LDS opt-in are each touched in runtime.hip only."""
+    csrc = os.path.join(ROOT, 'imm_amd', 'csrc')
+    text = {fn: open(os.path.join(csrc, fn)).read() for fn in sorted(os.listdir(csrc)) if fn.endswith(('.hip', '.h'))}
+    hips = [fn for fn in text if fn.endswith('.hip')]
+    assert 'conv_dispatch.h' in text and len(hips) > 30
+    head = re.compile(r'^(?:extern "C" )?(?:static )?(?:inline )?(?:const )?\w+[\w \*&]*?[ \*&](imm_\w+)\(', re.M)
+
+    def functions(src):
+        """name -> set of 'decl' / 'def' for every imm_* function head at the start of a line"""
+        seen = {}
+        for m in head.finditer(src):
+            i, depth = m.end(), 1
+            while depth:
+                depth += {'(': 1, ')': -1}.get(src[i], 0)
+                i += 1
+            seen.setdefault(m.group(1), set()).add('decl' if src[i:].lstrip()[:1] == ';' else 'def')
+        return seen
+
+    assert functions('int imm_a(int (*f)(int));\nextern "C" int imm_b(void) {\n') == {'imm_a': {'decl'}, 'imm_b': {'def'}}
+    foreign = ['%s: %s' % (fn, name) for fn in hips for name, kinds in functions(text[fn]).items() if kinds == {'decl'}]
+    assert not foreign, 'prototypes of functions defined elsewhere (declare them in conv_dispatch.h / common.h):\n' + '\n'.join(foreign)
+    for word, home in (('hipGetDeviceProperties', ['runtime.hip']), ('getenv', ['runtime.hip']), ('hipFuncSetAttribute', ['runtime.hip'])):
+        assert [fn for fn in text if word in text[fn]] == home, word
+    shared = sorted(functions(text['conv_dispatch.h']))
+    assert len(shared) > 40, shared
+    uses = re.compile(r'\b(?:%s)\(' % '|'.join(shared))
+    missing = [fn for fn in hips if uses.search(text[fn]) and '#include "conv_dispatch.h"' not in text[fn]]
+    assert not missing, missing
+    defined = {name for fn in hips for name, kinds in functions(text[fn]).items() if 'def' in kinds}
+    assert not set(shared) - defined, sorted(set(shared) - defined)
