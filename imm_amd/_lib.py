@@ -20,7 +20,7 @@ CONV_BIAS, CONV_RELU, CONV_STATS, CONV_MASK, CONV_OUT_F32 = 1, 2, 4, 8, 16
 SSE_BLOCKS = 512
 OPTIMIZERS = {'adam': 0, 'adadelta': 1, 'adagrad': 2}      # IMM_OPT_* (scripts/train.py:97-104)
 GAUSS_MODES = {'rot': 0, 'flat': 1, 'ankush': 2}     # IMM_GAUSS_* (config key gauss_mode, imm_model.py:48-72)
-ABI_VERSION = 35     # the history stands next to IMM_ABI_VERSION in include/imm_hip.h
+ABI_VERSION = 36     # the history stands next to IMM_ABI_VERSION in include/imm_hip.h
 
 
 class ImmHipError(RuntimeError):
@@ -217,6 +217,10 @@ _header('imm_seam.h', {  # the seamless-morph entry points (ABI 34)
 _header('imm_clip.h', {  # the clip-morph entry points (ABI 35)
     'imm_clip_rows': [_P, _P, _P, _P, _I, _I, _I, _D, _P, _P, _P, _P, _P],
     'imm_clip_ema': [_P, _P, _P, _P, _P, _I, _I, _F, _P],
+})
+
+_header('imm_score.h', {  # the landmark-quality entry point (ABI 36)
+    'imm_landmark_scores': [_P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _D, _D, _I, _P, _P, _P, _P, _P],
 })
 
 _lib = None

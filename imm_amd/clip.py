@@ -54,7 +54,7 @@ def check_smooth(value, name):
 class ClipPlan(object):
     """morph_clip()'s checked arguments: frames (decoded u8 arrays), rows int32 [F, 5], morph (the morphing.MorphPlan of the first
     frame's rows and the donors: every setting of the morph), smooth, colour_smooth, seam_smooth, box_smooth, one_euro, fps,
-    chunk_frames."""
+    chunk_frames, gate (a quality.QualityGate handed to the tracker, or None)."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -62,16 +62,17 @@ class ClipPlan(object):
 
 def plan_clip(frames, boxes, donors, donor_boxes=None, shape=0.0, texture=1.0, feather=0.125, K=10, anchors=2, lam=0.0,
               donor_landmarks=None, colour=0.0, max_gain=2.0, mask=None, grow=1.25, mask_feather=0.1, seamless=0.0, ring=128, smooth=True,
-              colour_smooth=0.25, seam_smooth=0.25, box_smooth=0.5, one_euro=TR.OneEuro(), fps=25.0, chunk_frames=32, max_batch=256):
+              colour_smooth=0.25, seam_smooth=0.25, box_smooth=0.5, one_euro=TR.OneEuro(), fps=25.0, chunk_frames=32, max_batch=256,
+              gate=None):
     """morph_clip()'s arguments checked on the host, before anything reaches the device: a ClipPlan.  frames, boxes, box_smooth, one_euro,
     fps and chunk_frames go through tracking.plan_track, the donors and the morph's settings through morphing.plan_morph with the first
     frame as the one photo (its checks and refusals are the morph's own); colour_smooth and seam_smooth must lie in (0, 1]."""
     colour_smooth, seam_smooth = check_smooth(colour_smooth, 'colour_smooth'), check_smooth(seam_smooth, 'seam_smooth')
-    frames, rows, beta, _consts, chunk = TR.plan_track(frames, boxes, max_batch, box_smooth, one_euro, fps, chunk_frames)
+    frames, rows, beta, _consts, chunk = TR.plan_track(frames, boxes, max_batch, box_smooth, one_euro, fps, chunk_frames, gate)
     morph = MP.plan_morph(frames[:1], donors, rows.tolist(), donor_boxes, shape, texture, feather, K, anchors, lam, None, donor_landmarks,
                           colour, max_gain, mask, grow, mask_feather, seamless, ring)
     return ClipPlan(frames=frames, rows=rows, morph=morph, smooth=bool(smooth), colour_smooth=colour_smooth, seam_smooth=seam_smooth,
-                    box_smooth=beta, one_euro=one_euro, fps=float(fps), chunk_frames=chunk)
+                    box_smooth=beta, one_euro=one_euro, fps=float(fps), chunk_frames=chunk, gate=gate)
 
 
 class ClipMorph(object):
@@ -144,7 +145,7 @@ def run(det, plan):
         if matched:                                            # once per call: the donors' sums
             with torch.cuda.stream(det.stream):
                 ops.colour_stats_u8(don, doffs_d, dhw_d, dboxes_d, int(box_areas(mp.donor_rows).max()), sums_b)
-    tracker = TR.FaceTracker(det, None, plan.box_smooth, plan.one_euro, plan.fps, capacity=T)
+    tracker = TR.FaceTracker(det, None, plan.box_smooth, plan.one_euro, plan.fps, capacity=T, gate=plan.gate)
     tracker._begin(rows)
     tracker._cur = det._fork()
     out = []

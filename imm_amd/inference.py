@@ -737,6 +737,39 @@ class LandmarkDetector(BucketRunner):
                 mu_out[start:start + count].copy_(self._mu[:count])
         return mu_out
 
+    def quality(self, images, boxes=None, template=None, gate=None):
+        """How far every row's landmarks deserve trust: a quality.LandmarkQuality (mu f32 [n, K, 2], spread f32 [n, K], score f32 [n, 2] =
+        (mean spread, shape residual), flags int32 [n], and the soft-argmax marginals py, px f32 [n, S/8, K]) on the detector's device,
+        one row per box (per image without boxes).  images, boxes: as keypoints() takes them.  template: an alignment.LandmarkTemplate
+        of this detector's K and S, the reference shape of the residual (taken on the landmarks themselves: the template lives in the
+        S x S frame); without one the residual is 0.  gate: a quality.QualityGate whose thresholds set the flags; without one only a
+        NaN score sets a flag.  Stills are scored, never blanked: mu is detect()'s.
+        Per bucket: detect()'s program, then imm_landmark_scores (include/imm_score.h) on the buffers it left, then device copies.
+        Nobody has measured how well these scores tell a face from a non-face: see quality.py."""
+        from . import quality as QL
+        QL.check_gate(gate, self.K, self.S)
+        if template is not None:
+            template.check(self.K, self.S)
+        images, _u8, rows, geom = photo_rows(images, boxes, self.S)
+        N, K, He = len(geom), self.K, self.He
+        held = _Held(self.dev)
+        with torch.cuda.device(self.dev):
+            ref = None if template is None else held.up(np.ascontiguousarray(template.points, dtype=np.float64))
+            mu, spread, score, flags = held.empty(N, K, 2), held.empty(N, K), held.empty(N, 2), held.empty(N, dtype=torch.int32)
+            py, px = held.empty(N, He, K), held.empty(N, He, K)
+        with self._forked(*held):
+            for start, count, bucket in plan_buckets(N, self.max_batch):
+                self._stage_rows(images, rows, start, count, bucket)
+                self._run(bucket)
+                sl = slice(start, start + count)
+                ops.landmark_scores(self._py[:count], self._px[:count], self._mu[:count], None, ref, 0, self.S,
+                                    None if gate is None else gate.max_spread, None if gate is None else gate.max_residual, 0,
+                                    spread[sl], score[sl], flags[sl], None)
+                mu[sl].copy_(self._mu[:count])
+                py[sl].copy_(self._py[:count])
+                px[sl].copy_(self._px[:count])
+        return QL.LandmarkQuality(mu, spread, score, flags, py, px, self.S)
+
     def track(self, frames, boxes, regressor=None, box_smooth=0.5, one_euro=OneEuro(), fps=25.0, chunk_frames=32):
         """The faces of a clip followed from its first frame: a tracking.Track (mu, points, points_smooth [T, F, K, 2], boxes int32
         [T, F, 4], flags [T, F], keypoints [T, F, M, 2] with a regressor) on the detector's device.
@@ -744,6 +777,7 @@ class LandmarkDetector(BucketRunner):
         as keypoints.check_boxes takes them; at most max_batch of them.  box_smooth in (0, 1]: the weight of a frame's measurement in
         the box filter.  one_euro: a tracking.OneEuro (the default: OneEuro()), or None for points_smooth == points.  fps: the clip's
         frame rate (the filter's time step).  chunk_frames: frames packed and uploaded at a time.
+        With a quality gate the same clip is tracked by tracker(..., gate=gate).track(frames, boxes, chunk_frames).
         Per frame, on the detector's stream: imm_resize_crop_u8 with the box rows the frame before left in device memory, the bucket's
         captured program (with the keypoint epilogue, given a regressor), imm_track_step (include/imm_track.h) and a device copy of the
         landmarks.  Between the first and the last frame's launches nothing is copied to the host and the stream is not synchronised."""
@@ -751,11 +785,14 @@ class LandmarkDetector(BucketRunner):
         frames, rows, beta, _consts, chunk = TR.plan_track(frames, boxes, self.max_batch, box_smooth, one_euro, fps, chunk_frames)
         return TR.FaceTracker(self, regressor, beta, one_euro, fps, capacity=len(frames)).run(frames, rows, chunk)
 
-    def tracker(self, regressor=None, box_smooth=0.5, one_euro=OneEuro(), fps=25.0):
+    def tracker(self, regressor=None, box_smooth=0.5, one_euro=OneEuro(), fps=25.0, gate=None):
         """A tracking.FaceTracker for live input: .start(frame, boxes), .step(frame), .result() -> the Track of the frames seen so far.
-        The launches of track(), with one-frame uploads."""
+        The launches of track(), with one-frame uploads; .track(frames, boxes, chunk_frames) runs a whole clip as track() does.
+        gate: a quality.QualityGate, or None.  With one, every frame's faces are scored (Track.spread, .score, .qflags) and a face that
+        fails the gate's thresholds on a frame after the first is lost on that frame (Track.unsure, Track.lost): its box and filters
+        stay, its points are NaN.  No default thresholds exist: a gate is fitted on faces known to be good (quality.QualityGate.fit)."""
         from . import tracking as TR
-        return TR.FaceTracker(self, regressor, box_smooth, one_euro, fps)
+        return TR.FaceTracker(self, regressor, box_smooth, one_euro, fps, gate=gate)
 
     def align(self, images, template, boxes=None, model='similarity', lam=0.0, out_size=None, return_transform=False, _packed=None):
         """Every face warped so that its landmarks land on the template: f32 [n, So, So, 3] in [0, 255] on the detector's device, one
@@ -975,7 +1012,8 @@ class LandmarkDetector(BucketRunner):
 
     def morph_clip(self, frames, boxes, donors, donor_boxes=None, shape=0.0, texture=1.0, feather=0.125, anchors=2, lam=0.0,
                    donor_landmarks=None, colour=0.0, max_gain=2.0, mask=None, grow=1.25, mask_feather=0.1, seamless=0.0, ring=128,
-                   smooth=True, colour_smooth=0.25, seam_smooth=0.25, box_smooth=0.5, one_euro=OneEuro(), fps=25.0, chunk_frames=32):
+                   smooth=True, colour_smooth=0.25, seam_smooth=0.25, box_smooth=0.5, one_euro=OneEuro(), fps=25.0, chunk_frames=32,
+                   gate=None):
         """A donor's face follows a tracked face through a clip: track() and morph() joined on the device, a clip.ClipMorph (frames,
         track, own, fit_flags, colour_gain, colour_flags, hull_flags, seam_diff, seam_flags).
         frames, boxes, box_smooth, one_euro, fps, chunk_frames: exactly as track takes them; boxes are the F faces of frames[0], at most
@@ -986,7 +1024,8 @@ class LandmarkDetector(BucketRunner):
         each frame's box; False: the pose head's mu.  colour_smooth and seam_smooth in (0, 1]: the weight of a frame's colour gain and
         of its membrane differences in a first-order filter, s <- s + a (x - s), box_smooth's convention; 1 means no filter, and the
         filter's launch is then not issued.  The defaults of 0.25 are by analogy with box_smooth: nobody has tuned them on footage.
-        A face the tracker lost on a frame (Track.lost) is not pasted on that frame: the frame keeps its pixels there.
+        A face the tracker lost on a frame (Track.lost) is not pasted on that frame: the frame keeps its pixels there.  gate: a
+        quality.QualityGate handed to the tracker, or None: a face that fails it on a frame is lost there (ClipMorph.track.unsure).
         Once per call the donors are packed and uploaded, their landmarks detected (unless given) and their colour sums taken; per chunk
         the frames are uploaded and copied into a canvas on the device; per frame the tracker's launches, imm_clip_rows
         (include/imm_clip.h) and morph's chain run on the detector's stream with the box rows the frame before left in device memory.
@@ -994,7 +1033,7 @@ class LandmarkDetector(BucketRunner):
         from . import clip as CL
         plan = CL.plan_clip(frames, boxes, donors, donor_boxes, shape, texture, feather, self.K, anchors, lam, donor_landmarks, colour, max_gain,
                             mask, grow, mask_feather, seamless, ring, smooth, colour_smooth, seam_smooth, box_smooth, one_euro, fps,
-                            chunk_frames, self.max_batch)
+                            chunk_frames, self.max_batch, gate)
         return CL.run(self, plan)
 
     def colour_stats(self, photos, boxes=None):

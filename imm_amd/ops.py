@@ -844,6 +844,38 @@ def track_step(mu, boxes, hw, state, image_size, next_image, init, box_smooth, m
          _p(points), _p(points_smooth), _p(boxes_next), _p(geom_next), _p(flags), _s())
 
 
+def landmark_scores(py, px, mu, boxes, ref, ref_stride, image_size, max_spread, max_residual, blank, spread, score, qflags, mu_out):
+    """The quality scores of F faces (include/imm_score.h: imm_landmark_scores): the soft-argmax marginals py f32 [F, h, K], px f32
+    [F, w, K] and the landmarks mu f32 [F, K, 2] -> spread f32 [F, K], score f32 [F, 2] = (mean spread, shape residual), qflags i32 [F]
+    (bit 0: the spread fails max_spread, bit 1: the residual fails max_residual; None or +inf: not applied) and mu_out f32 [F, K, 2] (mu's
+    bits, NaN for a flagged face with blank; None allowed without blank).  boxes i32 [F, 5] or None: the rows the faces were cut with
+    (the residual is then taken in source pixels).  ref: a contiguous f64 tensor holding the reference shape [K, 2] of face f at element
+    f * ref_stride (ref_stride 0: one shape for all), or None (residual 0)."""
+    if mu.dim() != 3 or py.dim() != 3 or px.dim() != 3:
+        raise ValueError('py [F, h, K], px [F, w, K], mu [F, K, 2], got %s, %s, %s' % (tuple(py.shape), tuple(px.shape), tuple(mu.shape)))
+    F, K, h, w = int(mu.shape[0]), int(mu.shape[1]), int(py.shape[1]), int(px.shape[1])
+    specs = [('py', py, torch.float32, (F, h, K)), ('px', px, torch.float32, (F, w, K)), ('mu', mu, torch.float32, (F, K, 2)),
+             ('spread', spread, torch.float32, (F, K)), ('score', score, torch.float32, (F, 2)), ('qflags', qflags, torch.int32, (F,))]
+    if boxes is not None:
+        specs.append(('boxes', boxes, torch.int32, (F, 5)))
+    if mu_out is not None:
+        specs.append(('mu_out', mu_out, torch.float32, (F, K, 2)))
+    if ref is not None:
+        specs.append(('ref', ref, torch.float64, tuple(None for _ in ref.shape)))
+    _check_tensors(specs)
+    ref_stride = int(ref_stride) if ref is not None else 0
+    if ref is not None and not (ref_stride == 0 or ref_stride >= 2 * K) or (
+            ref is not None and ref.numel() < (F - 1) * ref_stride + 2 * K):
+        raise ValueError('ref must hold 2 K doubles per face at a stride of 0 or >= 2 K, got %d values at stride %d for F = %d, K = %d' % (
+            ref.numel(), ref_stride, F, K))
+    if mu_out is not None and _overlap(mu, mu_out):
+        raise ValueError('mu overlaps mu_out: the output is written while the input is read')
+    inf = float('inf')
+    call('imm_landmark_scores', _p(py), _p(px), _p(mu), _p(boxes), _p(ref), ref_stride, K, h, w, int(image_size), F,
+         inf if max_spread is None else float(max_spread), inf if max_residual is None else float(max_residual), int(blank),
+         _p(spread), _p(score), _p(qflags), _p(mu_out), _s())
+
+
 def retarget(q, anchor, driver_flags, m, prev, init, relative, rigid, gain, out, flags):
     """One frame of re-enactment (include/imm_retarget.h: imm_retarget): the driver's points q f32 [K, 2] of this frame, the anchor f64
     [K, 2] (set to q with init) and the driver's track_step flags i32 [1] -> the poses out f32 [n, K, 2] of the source faces with the

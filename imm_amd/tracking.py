@@ -5,12 +5,18 @@ box of every later frame comes from the landmarks of the frame before it, on the
 
     tr = det.track(frames, boxes)                       # frames: T u8 HWC arrays, boxes: the faces of frames[0]
     tr.points, tr.points_smooth                         # f32 [T, F, K, 2] source pixels (y, x); tr.boxes int32 [T, F, 4]; tr.lost
+    tr = det.tracker(gate=gate).track(frames, boxes)    # a quality.QualityGate: a face that fails it on a frame is lost there (tr.unsure)
     live = det.tracker(); live.start(frame0, boxes); live.step(frame1); ...; live.result()
 
 Per frame, on the detector's stream: imm_resize_crop_u8 with the box rows in device memory, the captured pose program of the bucket,
 imm_track_step (include/imm_track.h states the rule once: landmarks -> source pixels -> similarity fit of the first frame's shape ->
 box filter -> the next frame's box row and geometry -> One-Euro filter of the points), and a device copy of the landmarks into the
 result.  Nothing comes back to the host between a clip's first and last launch.
+
+With a gate (imm_amd/quality.py) one launch stands between the pose program and imm_track_step: imm_landmark_scores (include/imm_score.h)
+scores the frame's faces from the soft-argmax marginals and from the first frame's shape in the tracker's state, and hands imm_track_step
+NaN landmarks for a face that fails the gate's thresholds.  The lost rule of imm_track.h does the rest: the face keeps its state, box and
+filter pairs, its points are NaN and FLAG_LOST is set.  Without a gate the launches, arguments and buffers are those of before.
 
 This module holds the host side: OneEuro (the filter's constants), plan_track (every argument checked before anything reaches the
 device), the state layout, Track (the result) and FaceTracker (the launches).  It imports without a GPU."""
@@ -90,10 +96,13 @@ def check_first_boxes(boxes, what='frame 0'):
         raise
 
 
-def plan_track(frames, boxes, n_faces_max, box_smooth=0.5, one_euro=OneEuro(), fps=25.0, chunk_frames=32):
+def plan_track(frames, boxes, n_faces_max, box_smooth=0.5, one_euro=OneEuro(), fps=25.0, chunk_frames=32, gate=None):
     """track()'s arguments checked on the host, before anything reaches the device: (frames as decoded u8 arrays, box rows int32
-    [F, 5], box_smooth, filter constants (filter_constants), chunk_frames).  n_faces_max: the detector's max_batch."""
+    [F, 5], box_smooth, filter constants (filter_constants), chunk_frames).  n_faces_max: the detector's max_batch.  gate: None or a
+    quality.QualityGate (ValueError otherwise)."""
     from .inference import decode_u8
+    from .quality import check_gate
+    check_gate(gate)
     if not isinstance(frames, (list, tuple)):
         raise ValueError('track needs the frames as a list of u8 HWC arrays (a tensor batch holds no photo to cut boxes from)')
     if len(frames) == 0:
@@ -115,10 +124,13 @@ class Track(object):
     """What tracking returns, T frames by F faces, tensors on the detector's device (or the host after .cpu()):
     mu f32 [T, F, K, 2] the landmarks (y, x) in [-1, 1] of each frame's box; points f32 [T, F, K, 2] the same in source pixels;
     points_smooth f32 [T, F, K, 2] after the One-Euro filter; boxes int32 [T, F, 4] the box (y0, x0, y1, x1) each frame was cut
-    with; flags int32 [T, F] (bit 0 lost, bit 1 the next box left the photo); keypoints f32 [T, F, M, 2] with a regressor, else None."""
+    with; flags int32 [T, F] (bit 0 lost, bit 1 the next box left the photo); keypoints f32 [T, F, M, 2] with a regressor, else None.
+    Tracked with a gate (quality.QualityGate), also spread f32 [T, F, K], score f32 [T, F, 2] = (mean spread, shape residual against the
+    first frame's shape; 0 on frame 0) and qflags int32 [T, F] (bit 0: the spread failed the gate, bit 1: the residual did); else None."""
 
-    def __init__(self, mu, points, points_smooth, boxes, flags, keypoints=None):
+    def __init__(self, mu, points, points_smooth, boxes, flags, keypoints=None, spread=None, score=None, qflags=None):
         self.mu, self.points, self.points_smooth, self.boxes, self.flags, self.keypoints = mu, points, points_smooth, boxes, flags, keypoints
+        self.spread, self.score, self.qflags = spread, score, qflags
 
     def __len__(self):
         return int(self.mu.shape[0])
@@ -133,10 +145,17 @@ class Track(object):
         """bool [T, F]: the box made from that frame does not intersect the photo the frame was cut from."""
         return (self.flags & FLAG_OUTSIDE) != 0
 
+    @property
+    def unsure(self):
+        """bool [T, F]: a quality score of that frame failed the gate (all False when tracked without a gate).  On every frame but the
+        first such a face is also lost; on the first frame it is scored but kept: the caller vouches for the first boxes."""
+        return (self.flags & 0) != 0 if self.qflags is None else self.qflags != 0
+
     def cpu(self):
         from . import ops
         get = lambda t: None if t is None else ops.download(t.contiguous())
-        return Track(get(self.mu), get(self.points), get(self.points_smooth), get(self.boxes), get(self.flags), get(self.keypoints))
+        return Track(get(self.mu), get(self.points), get(self.points_smooth), get(self.boxes), get(self.flags), get(self.keypoints),
+                     spread=get(self.spread), score=get(self.score), qflags=get(self.qflags))
 
 
 class FaceTracker(object):
@@ -146,9 +165,13 @@ class FaceTracker(object):
     Every frame is issued on the detector's stream without a device -> host copy and without synchronising that stream; the host
     waits only for its own uploads, on a side stream.  With a regressor the geometry rows of the detector (the keypoint epilogue's
     input) are written by each frame for the next one: keypoints() or align() calls on the same detector between two steps of such a
-    tracker overwrite them."""
+    tracker overwrite them.
+    gate: a quality.QualityGate (its thresholds possibly both None: the frames are then scored and nothing is blanked), or None: no
+    scores, and exactly the launches of a tracker without this argument."""
 
-    def __init__(self, detector, regressor=None, box_smooth=0.5, one_euro=OneEuro(), fps=25.0, capacity=64):
+    def __init__(self, detector, regressor=None, box_smooth=0.5, one_euro=OneEuro(), fps=25.0, capacity=64, gate=None):
+        from .quality import check_gate
+        self.gate = check_gate(gate, detector.K, detector.S)
         self.det = detector
         self.reg = regressor
         if regressor is not None:
@@ -169,6 +192,9 @@ class FaceTracker(object):
                 'boxes': torch.zeros(cap + 1, F, 5, dtype=torch.int32, device=dev)}
         if self.reg is not None:
             bufs['kp'] = torch.empty(cap, F, self.reg.M, 2, device=dev)
+        if self.gate is not None:
+            bufs.update(spread=torch.empty(cap, F, K, device=dev), score=torch.empty(cap, F, 2, device=dev),
+                        qflags=torch.empty(cap, F, dtype=torch.int32, device=dev))
         return bufs
 
     def _grow(self):
@@ -212,6 +238,8 @@ class FaceTracker(object):
         with torch.cuda.device(det.dev):
             self._bufs = self._alloc(self.capacity)
             self._state = torch.zeros(F, state_size(det.K), dtype=torch.float64, device=det.dev)
+            if self.gate is not None:                      # what imm_track_step reads in place of the detector's landmarks
+                self._mu_gated = torch.empty(F, det.K, 2, device=det.dev)
             det._fork()
             with torch.cuda.stream(det.stream):
                 det._ensure_capacity(self.bucket)
@@ -234,7 +262,15 @@ class FaceTracker(object):
         det._stage(F, bucket, packed=(src, offs_d, hw_d, rows))
         det._run(bucket, M)
         mc, be, dc, c, te, off = self.consts
-        ops.track_step(det._mu[:F], rows, hw_d, self._state, det.S, next_image, 1 if t == 0 else 0, self.box_smooth, mc, be, dc, c, te, off,
+        mu = det._mu[:F]
+        if self.gate is not None:
+            # the first frame is scored only: z0 is not written yet, and the caller vouches for the first boxes
+            first = t == 0
+            ops.landmark_scores(det._py[:F], det._px[:F], mu, rows, None if first else self._state.view(-1)[STATE_HEAD:],
+                                state_size(det.K), det.S, self.gate.max_spread, self.gate.max_residual, 0 if first else 1,
+                                b['spread'][t], b['score'][t], b['qflags'][t], self._mu_gated)
+            mu = self._mu_gated
+        ops.track_step(mu, rows, hw_d, self._state, det.S, next_image, 1 if t == 0 else 0, self.box_smooth, mc, be, dc, c, te, off,
                        b['points'][t], b['smooth'][t], b['boxes'][t + 1], det._geom[:F], b['flags'][t])
         b['mu'][t].copy_(det._mu[:F])
         if M is not None:
@@ -265,6 +301,13 @@ class FaceTracker(object):
             self._advance(src, offs_d, hw_d, 0)
         return self
 
+    def track(self, frames, boxes, chunk_frames=32):
+        """A whole clip at once with this tracker's settings (its gate among them): what LandmarkDetector.track does, which takes no
+        gate.  frames, boxes, chunk_frames: as LandmarkDetector.track takes them.  Returns the Track; the tracker starts afresh."""
+        frames, rows, _b, _c, chunk = plan_track(frames, boxes, self.det.max_batch, chunk_frames=chunk_frames)
+        self.capacity = max(self.capacity, len(frames))
+        return self.run(frames, rows, chunk)
+
     def run(self, frames, rows, chunk_frames):
         """track(): every frame of a checked clip, uploaded chunk_frames at a time; the caller's stream waits once, at the end."""
         self._begin(rows)
@@ -280,5 +323,6 @@ class FaceTracker(object):
         if self.F == 0:
             raise RuntimeError('start(frame, boxes) comes first')
         b, t = self._bufs, self.t
+        extra = {} if self.gate is None else dict(spread=b['spread'][:t], score=b['score'][:t], qflags=b['qflags'][:t])
         return Track(b['mu'][:t], b['points'][:t], b['smooth'][:t], b['boxes'][:t, :, 1:], b['flags'][:t],
-                     b['kp'][:t] if self.reg is not None else None)
+                     b['kp'][:t] if self.reg is not None else None, **extra)

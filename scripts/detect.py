@@ -15,7 +15,13 @@ With --track the images of the folder, in sorted order, are the frames of one cl
 (LandmarkDetector.tracker, imm_amd/tracking.py), and the file holds per frame and face: `mu`, `landmarks` [T, F, K, 2], `points` and
 `points_smooth` [T, F, K, 2] ((y, x) source pixels, raw and after the One-Euro filter; --no-filter makes them equal), `boxes`
 [T, F, 4] (the box each frame was cut with), `flags` [T, F] (bit 0: lost, bit 1: the box left the photo) and, with --regressor,
-`keypoints` [T, F, M, 2].  --fps is the clip's frame rate, --box-smooth the weight of a frame in the box filter."""
+`keypoints` [T, F, M, 2].  --fps is the clip's frame rate, --box-smooth the weight of a frame in the box filter.
+With --quality the file also holds, per image, `spread` [N, K] (how widely each landmark's probability is spread), `score` [N, 2] (the
+mean spread, and the residual of the --template shape under the best similarity; 0 without --template) and `quality_flags` [N] (set by
+a NaN score, or by the thresholds of --gate).  With --track --gate FILE (a gate written by scripts/test.py --save-gate) a face that
+fails the gate on a frame is lost on that frame, and the same three arrays are written per frame and face ([T, F, ..]; the residual is
+against the face's own first-frame shape).  No thresholds are built in: how well these scores tell a face from a non-face is unmeasured
+(imm_amd/quality.py)."""
 from __future__ import print_function
 
 import argparse
@@ -68,7 +74,11 @@ def track(args, det, reg, files):
     owner, boxes = read_boxes(args.boxes, files)
     if len(owner) == 0 or (owner != 0).any():
         raise ValueError('%s: with --track every row names the first frame, %s' % (args.boxes, files[0]))
-    live = det.tracker(regressor=reg, box_smooth=args.box_smooth, one_euro=None if args.no_filter else OneEuro(), fps=args.fps)
+    gate = None
+    if args.gate:
+        from imm_amd.quality import QualityGate
+        gate = QualityGate.load(args.gate, detector=det)
+    live = det.tracker(regressor=reg, box_smooth=args.box_smooth, one_euro=None if args.no_filter else OneEuro(), fps=args.fps, gate=gate)
     sizes = []
     for i, f in enumerate(files):                       # one decoded frame on the host at a time
         im = decode_image(osp.join(args.images_dir, f))
@@ -83,9 +93,11 @@ def track(args, det, reg, files):
                points=tr.points.numpy(), points_smooth=tr.points_smooth.numpy(), boxes=tr.boxes.numpy(), flags=tr.flags.numpy())
     if reg is not None:
         out['keypoints'] = tr.keypoints.numpy()
+    if gate is not None:
+        out.update(spread=tr.spread.numpy(), score=tr.score.numpy(), quality_flags=tr.qflags.numpy())
     np.savez(args.out, **out)
-    print('%d frames, %d faces tracked, %d landmarks each -> %s (%d lost)' % (mu.shape[0], mu.shape[1], mu.shape[2], args.out,
-                                                                               int(tr.lost.sum())))
+    print('%d frames, %d faces tracked, %d landmarks each -> %s (%d lost%s)' % (
+        mu.shape[0], mu.shape[1], mu.shape[2], args.out, int(tr.lost.sum()), '' if gate is None else ', %d unsure' % int(tr.unsure.sum())))
 
 
 def main(args):
@@ -100,6 +112,16 @@ def main(args):
     reg = LandmarkRegressor.load(args.regressor, detector=det) if args.regressor else None
     if args.track:
         return track(args, det, reg, files)
+    if args.gate or args.template:
+        if not args.quality:
+            raise ValueError('--gate and --template go with --quality or --track')
+    gate = template = None
+    if args.quality:
+        from imm_amd.alignment import LandmarkTemplate
+        from imm_amd.quality import QualityGate
+        gate = QualityGate.load(args.gate, detector=det) if args.gate else None
+        template = LandmarkTemplate.load(args.template, detector=det) if args.template else None
+    quality = []
     if args.boxes and reg is None:
         raise ValueError('--boxes needs --regressor')
     owner, boxes = read_boxes(args.boxes, files) if args.boxes else (None, None)
@@ -110,6 +132,8 @@ def main(args):
         ims = [decode_image(osp.join(args.images_dir, f)) for f in files[i:i + chunk]]
         sizes += [im.shape[:2] for im in ims]
         mus.append(det.detect(ims).cpu().numpy())
+        if args.quality:
+            quality.append(det.quality(ims, template=template, gate=gate).cpu())
         if reg is not None and boxes is None:
             kps[i:i + len(ims)] = det.keypoints(ims, reg).cpu().numpy()
         elif reg is not None:
@@ -120,6 +144,9 @@ def main(args):
     mu = np.concatenate(mus)
     landmarks = ((mu + 1) / 2.0) * args.im_size
     out = dict(files=np.array(files), mu=mu, landmarks=landmarks, sizes=np.array(sizes, dtype=np.int32))
+    if args.quality:
+        out.update(spread=np.concatenate([q.spread.numpy() for q in quality]), score=np.concatenate([q.score.numpy() for q in quality]),
+                   quality_flags=np.concatenate([q.flags.numpy() for q in quality]))
     if reg is not None:
         if boxes is None:
             owner = np.arange(len(files), dtype=np.int64)
@@ -127,6 +154,10 @@ def main(args):
         out.update(keypoints=kps, boxes=boxes.astype(np.int32), owner=owner.astype(np.int32))
     np.savez(args.out, **out)
     print('%d images, %d landmarks each -> %s' % (mu.shape[0], mu.shape[1], args.out))
+    if args.quality:
+        print('quality: mean spread %.4f .. %.4f, residual %.4f .. %.4f, %d flagged' % (
+            out['score'][:, 0].min(), out['score'][:, 0].max(), out['score'][:, 1].min(), out['score'][:, 1].max(),
+            int((out['quality_flags'] != 0).sum())))
     if reg is not None:
         print('%d faces, %d keypoints each (%s)' % (kps.shape[0], reg.M, ', '.join(reg.labels)))
     if args.plot and reg is not None:
@@ -183,4 +214,9 @@ if __name__ == '__main__':
     parser.add_argument('--fps', type=float, default=25.0, help='--track: the frame rate of the clip')
     parser.add_argument('--box-smooth', type=float, default=0.5, help='--track: the weight of a frame in the box filter, in (0, 1]')
     parser.add_argument('--no-filter', action='store_true', help='--track: no One-Euro filter (points_smooth equals points)')
+    parser.add_argument('--quality', action='store_true', help='also write the quality scores of every image: spread, score, quality_flags')
+    parser.add_argument('--template', type=str, default=None,
+                        help='--quality: a landmark template .npz (scripts/test.py --save-template), the reference shape of the residual')
+    parser.add_argument('--gate', type=str, default=None,
+                        help='--track / --quality: a quality gate .npz (scripts/test.py --save-gate); there are no built-in thresholds')
     main(parser.parse_args())

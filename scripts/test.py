@@ -6,7 +6,11 @@ or, without dataset files, from .npz files with `image`, `future_image` (NHWC fl
     python scripts/test.py --configs a.yaml b.yaml --train-npz mafl_train.npz --test-npz mafl_test.npz --checkpoint x.pt
 --save-regressor PATH also writes the regressor behind the printed error (coef, intercept, K, S, ...; imm_amd/keypoints.py), which
 scripts/detect.py --regressor applies to photos.  --save-template PATH writes the mean landmark shape of the regressor's training
-split (imm_amd/alignment.py: LandmarkTemplate, Procrustes-refined), which scripts/align.py --template aligns photos to."""
+split (imm_amd/alignment.py: LandmarkTemplate, Procrustes-refined), which scripts/align.py --template aligns photos to.
+--save-gate PATH --gate-quantile Q --gate-margin M (all three together) fits a quality gate (imm_amd/quality.py: QualityGate.fit) on the
+faces of the test split: thresholds of M times the Q-quantile of their mean landmark spread and, with --template FILE (a template
+written earlier by --save-template), of their shape residual against it; scripts/detect.py --track --gate applies it.  Q and M have no
+defaults: nobody has measured which values suit footage."""
 from __future__ import print_function
 
 import argparse
@@ -45,7 +49,29 @@ def landmark_dataset(name, datadir, subset, im_size, max_samples=None):
     raise ValueError('Dataset %s not supported.' % name)
 
 
+def fit_gate(args, net, detector, test_it):
+    """--save-gate: the quality scores of the test split's faces (the pose encoder's input, `future_image`) -> a fitted QualityGate."""
+    from imm_amd.alignment import LandmarkTemplate
+    from imm_amd.quality import QualityGate
+    det = detector if detector is not None else net.landmark_detector(args.im_size, max_batch=args.batch_size)
+    template = LandmarkTemplate.load(args.template, detector=det) if args.template else None
+    scores = []
+    for batch in test_it:
+        scores.append(det.quality(batch['future_image'], template=template).cpu().score.numpy())
+    score = np.concatenate(scores).astype(np.float64)
+    gate = QualityGate.fit((score[:, 0], score[:, 1]), args.gate_quantile, args.gate_margin)
+    gate.K, gate.S, gate.heatmap = det.K, det.S, det.He
+    gate.save(args.save_gate)
+    print('quality gate of %d faces (quantile %g, margin %g): max_spread %s, max_residual %s -> %s' % (
+        len(score), args.gate_quantile, args.gate_margin, gate.max_spread, gate.max_residual, args.save_gate))
+
+
 def main(args):
+    given = [args.save_gate is not None, args.gate_quantile is not None, args.gate_margin is not None]
+    if any(given) and not all(given):
+        raise ValueError('--save-gate, --gate-quantile and --gate-margin go together (the quantile and the margin have no defaults)')
+    if args.template and not args.save_gate:
+        raise ValueError('--template goes with --save-gate')
     config = load_configs([args.paths_config, osp.join('configs', 'experiments', args.experiment_name + '.yaml')]
                           if args.configs is None else args.configs)
     torch.cuda.set_device(0)
@@ -90,6 +116,12 @@ def main(args):
     if args.save_template:
         from imm_amd.alignment import LandmarkTemplate
         LandmarkTemplate.from_landmarks(landmarks['gauss_yx'], args.im_size, dataset=train_name, checkpoint=ckpt).save(args.save_template)
+    if args.save_gate:                                     # a fresh pass over the test split: the evaluation used its iterator up
+        if args.train_npz is not None:
+            again = npz_batches(args.test_npz, args.batch_size, dev)
+        else:
+            again = test_dset.get_dataset(args.batch_size, repeat=False, shuffle=False, device=dev)
+        fit_gate(args, net, detector, again)
     model_dataset = config.training.train_dset_params.dataset if hasattr(config.training, 'train_dset_params') and \
         'dataset' in config.training.train_dset_params else getattr(config.training, 'dset', '?')
     print('')
@@ -125,4 +157,11 @@ if __name__ == '__main__':
     parser.add_argument('--save-template', type=str, default=None,
                         help="also write the mean landmark shape of the regressor's training split to this .npz "
                              '(imm_amd/alignment.py; for scripts/align.py --template)')
+    parser.add_argument('--save-gate', type=str, default=None,
+                        help='also fit a quality gate on the faces of the test split and write it to this .npz (imm_amd/quality.py; for '
+                             'scripts/detect.py --track --gate); needs --gate-quantile and --gate-margin')
+    parser.add_argument('--gate-quantile', type=float, default=None, help='--save-gate: the quantile of the scores, in (0, 1]; no default')
+    parser.add_argument('--gate-margin', type=float, default=None, help='--save-gate: the factor on that quantile, >= 1; no default')
+    parser.add_argument('--template', type=str, default=None,
+                        help='--save-gate: a landmark template .npz, the reference shape of the residual (default: the spread alone)')
     main(parser.parse_args())

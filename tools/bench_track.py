@@ -6,7 +6,12 @@ the table to profiles/track_bench.txt.
 Both sides are wall-clock times of the whole clip (the loop synchronises every frame by construction, so stream events would not
 see its host share), from the call to a final synchronisation.  After untimed warm-up runs of both, the two sides alternate, one
 clip each per window; the table gives the median and the range over the windows.
-Usage: python tools/bench_track.py [--faces 1 4 16] [--frames 64] [--windows 7]"""
+Usage: python tools/bench_track.py [--faces 1 4 16] [--frames 64] [--windows 7]
+
+--gate measures what a quality gate costs instead: track() without a gate against tracker(gate=QualityGate()).track(), whose thresholds are both
+None, so every frame is scored (one more launch, imm_landmark_scores) and nothing is blanked: the two runs follow the same boxes.  Same
+clip, same alternation; the table (profiles/track_gate_bench.txt) gives both sides, the difference per frame, and the spread of the
+ungated side over its windows, which is what a comparison with another build of the ungated path has to exceed."""
 import argparse
 import json
 import os
@@ -22,6 +27,7 @@ from imm_amd.tracking import OneEuro                      # noqa: E402
 from bench_detect import model_config                     # noqa: E402
 
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'track_bench.txt')
+GATE_OUT = os.path.join(os.path.dirname(OUT), 'track_gate_bench.txt')
 
 
 class HostTracker(object):
@@ -84,7 +90,59 @@ def wall_ms(fn):
     return (time.perf_counter() - t0) * 1e3
 
 
+def gate_main(args):
+    from imm_amd.quality import QualityGate
+    torch.cuda.set_device(0)
+    dev = 'cuda:0'
+    S, K, T = 128, 10, args.frames
+    rng = np.random.RandomState(0)
+    frames = [rng.randint(0, 256, size=(512, 384, 3)).astype(np.uint8) for _ in range(T)]
+    props = torch.cuda.get_device_properties(0)
+    lines = ['device: %s (%s, %d CUs)' % (props.name, props.gcnArchName, props.multi_processor_count),
+             'S %d, K %d, bf16; %d u8 frames of 512 x 384, F faces of 160 x 128 px; box_smooth 0.5, OneEuro(), 25 fps' % (S, K, T),
+             'wall-clock ms per clip, the two sides alternating, median (min .. max) of %d windows after %d warm-up clips each' % (
+                 args.windows, args.warmup),
+             'plain = LandmarkDetector.track(frames, boxes, chunk_frames=32)',
+             'gated = LandmarkDetector.tracker(gate=QualityGate()).track(frames, boxes, chunk_frames=32): every frame scored by imm_landmark_scores, nothing blanked',
+             '%4s %30s %30s %14s %16s' % ('F', 'plain ms', 'gated ms', 'gate us/frame', 'plain spread %')]
+    rows = []
+    for F in args.faces:
+        boxes = [(20 + 19 * (i % 16), 10 + 13 * (i % 16), 180 + 19 * (i % 16), 138 + 13 * (i % 16)) for i in range(F)]
+        model = IMMModel(model_config(K), dtype=torch.bfloat16, device=dev)
+        x = torch.zeros(max(F, 2), S, S, 3, device=dev)
+        model.build({'image': x, 'future_image': x}, training_pl=False, build_loss=False)
+        det = model.landmark_detector(S, max_batch=max(F, 1))
+        oe, gate = OneEuro(), QualityGate()
+        plain = lambda: det.track(frames, boxes, box_smooth=0.5, one_euro=oe, fps=25.0, chunk_frames=32)
+        gated = lambda: det.tracker(box_smooth=0.5, one_euro=oe, fps=25.0, gate=gate).track(frames, boxes, chunk_frames=32)
+        for _ in range(args.warmup):
+            plain()
+            gated()
+        t_plain, t_gated = [], []
+        for _ in range(args.windows):
+            t_plain.append(wall_ms(plain))
+            t_gated.append(wall_ms(gated))
+        mp, mg = float(np.median(t_plain)), float(np.median(t_gated))
+        row = {'faces': F, 'frames': T, 'plain_ms': mp, 'gated_ms': mg, 'plain_ms_all': t_plain, 'gated_ms_all': t_gated,
+               'gate_us_per_frame': (mg - mp) / T * 1e3, 'plain_spread_percent': (max(t_plain) - min(t_plain)) / mp * 100.0}
+        rows.append(row)
+        fmt = lambda v: '%8.2f (%7.2f .. %7.2f)' % (float(np.median(v)), min(v), max(v))
+        lines.append('%4d %30s %30s %14.2f %16.2f' % (F, fmt(t_plain), fmt(t_gated), row['gate_us_per_frame'], row['plain_spread_percent']))
+        print(lines[-1], flush=True)
+        del det, model
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    if args.out:
+        with open(GATE_OUT if args.out == OUT else args.out, 'w') as f:
+            f.write(text)
+    print(json.dumps({'image_size': S, 'n_maps': K, 'dtype': 'bf16', 'rows': rows}))
+
+
 def main(args):
+    if args.gate:
+        return gate_main(args)
     torch.cuda.set_device(0)
     dev = 'cuda:0'
     S, K, T = 128, 10, args.frames
@@ -141,4 +199,5 @@ if __name__ == '__main__':
     p.add_argument('--windows', type=int, default=7)
     p.add_argument('--warmup', type=int, default=2)
     p.add_argument('--out', type=str, default=OUT)
+    p.add_argument('--gate', action='store_true', help='the cost of a quality gate: track() with and without gate=QualityGate()')
     main(p.parse_args())
