@@ -1036,6 +1036,91 @@ class LandmarkDetector(BucketRunner):
                             chunk_frames, self.max_batch, gate)
         return CL.run(self, plan)
 
+    def redact(self, photos, boxes=None, mode='pixelate', blocks=8, mask=None, grow=1.25, mask_feather=0.1, feather=0.0, landmarks=None,
+               return_transform=False):
+        """The photos with every box's face made unreadable: a list of u8 device tensors [h_i, w_i, 3], one per photo, views of one
+        packed buffer (what warp returns).  photos, boxes: as warp takes them.  The box is cut into square cells, at most `blocks` (an
+        int in [1, 64]) along its longer side, every cell takes the mean of the ORIGINAL pixels it covers, and the box is pasted over
+        with those means (mode='pixelate', a mosaic) or with their bilinear interpolation (mode='smooth', a blur), faded into the photo
+        over `feather` of the box side (include/imm_redact.h states the rule).  Rows are applied in row order.
+        mask: None (the default: the whole box) or 'hull': only the convex hull of the face's landmarks, grown by `grow` and softened
+        inwards over mask_feather * min(H, W) pixels, as morph takes them.  landmarks: f32 [n, K, 2] where the caller has them; the pose
+        program is then skipped.  Redaction FAILS CLOSED: a row whose hull is degenerate or whose landmarks are not finite (they are not
+        refused) is redacted over its WHOLE box, where morph would leave it alone.  feather=0 and mask=None are the defaults because the
+        hard, whole box is the conservative reading; nobody has measured how recognisable a face stays at any setting, and no anonymity
+        is claimed.
+        Per bucket, on the detector's stream, nothing returning to the host: with mask=None imm_redact_cells_u8 and imm_redact_u8 and
+        NO pose program; with mask='hull' imm_resize_crop_u8 and the captured pose program (unless landmarks is given), imm_hull_fit
+        reading the pose head's landmarks in place, then the same two.
+        return_transform=True: (photos, a redaction.PhotoRedaction: rows, cells, cell, grid, mode, blocks, mu, hull_edges, hull_flags,
+        inv_soft, weight)."""
+        from . import redaction as RD
+        from .generation import PasteSetup
+        K = self.K
+        plan = RD.plan_redact(photos, boxes, K, mode, blocks, mask, grow, mask_feather, feather, landmarks)
+        photos, rows, nb, hull = plan.photos, plan.rows, plan.blocks, plan.mask == 'hull'
+        n, code = len(rows), RD.MODES[plan.mode]
+        held = _Held(self.dev)
+        lm = None if plan.landmarks is None or not hull else held.keep(plan.landmarks.to(device=self.dev, dtype=torch.float32).contiguous())
+        buckets = plan_buckets(n, self.max_batch)
+        ps = PasteSetup(photos, rows, buckets, plan.feather, self.dev)              # all photos, once per call
+        held.keep(*ps.tensors())
+        extra = {}                                                                  # redact_u8's optional tensors, one row each
+        with torch.cuda.device(self.dev):
+            cells = held.empty(n, nb * nb * 3, dtype=torch.uint8)
+            mu_out = None
+            if hull:
+                grow_d = held.up(plan.grow)
+                extra = dict(edges=held.empty(n, K, 3), inv_soft=held.up(plan.inv_soft), hull_flags=held.empty(n, dtype=torch.int32))
+                mu_out = held.empty(n, K, 2) if return_transform and lm is None else None
+        with self._forked(*held):
+            for start, count, bucket in buckets:
+                part = slice(start, start + count)
+                opt = {k: t[part] for k, t in extra.items()}
+                if hull:
+                    if lm is None:
+                        self._stage(count, bucket, packed=ps.packed(part))
+                        self._run(bucket)
+                        own = self._mu[:count]
+                    else:
+                        own = lm[part]
+                    ops.hull_fit(own, ps.boxes_d[part], grow_d[part], opt['edges'], opt['hull_flags'])
+                    if mu_out is not None:
+                        mu_out[part].copy_(own)
+                ops.redact_cells_u8(ps.src, ps.offs_d, ps.hw_d, ps.boxes_d[part], nb, cells[part])
+                ops.redact_u8(ps.canvas, ps.offs_d, ps.hw_d, ps.boxes_d[part], ps.links_d[part], ps.ramp_d[part], cells[part], nb, code,
+                              ps.max_pixels(part), **opt)
+        out = unpack_u8(ps.canvas, photos)
+        if return_transform:
+            return out, RD.PhotoRedaction(rows, cells, plan.mode, nb, plan.feather, mu=(mu_out if lm is None else lm) if hull else None,
+                                          hull_edges=extra.get('edges'), hull_flags=extra.get('hull_flags'),
+                                          inv_soft=plan.inv_soft if hull else None)
+        return out
+
+    def redact_clip(self, frames, boxes, mode='pixelate', blocks=8, mask=None, grow=1.25, mask_feather=0.1, feather=0.0, smooth=True,
+                    box_smooth=0.5, one_euro=OneEuro(), fps=25.0, chunk_frames=32, gate=None):
+        """The faces of a clip followed from its first frame and redacted on every frame: track() and redact() joined on the device, a
+        redaction.ClipRedaction (frames, track, own, hull_flags).
+        frames, boxes, box_smooth, one_euro, fps, chunk_frames: exactly as track takes them; boxes are the F faces of frames[0], at most
+        max_batch of them.  mode, blocks, mask, grow, mask_feather, feather: as redact takes them.  smooth=True: with mask='hull' the hull
+        is fitted to the tracker's One-Euro points brought back into the frame of each frame's box; False: to the pose head's mu.
+        gate: a quality.QualityGate handed to the tracker, or None.
+        ONLY THE FACES BOXED ON THE FIRST FRAME ARE FOLLOWED.  A face that enters the clip later is not redacted: detection of new faces
+        is out of scope.
+        A face the tracker lost on a frame (Track.lost), or that the gate found unsure, keeps the box row the tracker's unchanged state
+        gives it; imm_clip_rows hands it NaN landmarks, imm_hull_fit flags it and the paste covers its whole box.  On the first frame
+        the tracker scores the faces without losing any, so the gate's verdict is OR-ed into the flags on the device (bit 2 of
+        hull_flags): a face the gate finds unsure is covered whole on every frame, the first included.  With mask=None the hull
+        launches are not issued and the box is covered anyway.  A lost or unsure face is never shown.
+        Per chunk the frames are uploaded and copied into a canvas on the device; per frame the tracker's launches, imm_clip_rows,
+        with the mask imm_hull_fit, imm_redact_cells_u8 from the frame's original pixels and imm_redact_u8 run on the detector's stream
+        with the box rows the frame before left in device memory.  Between the first and the last frame's launches nothing is copied to
+        the host and the stream is not synchronised."""
+        from . import redaction as RD
+        plan = RD.plan_redact_clip(frames, boxes, self.K, mode, blocks, mask, grow, mask_feather, feather, smooth, box_smooth, one_euro,
+                                   fps, chunk_frames, self.max_batch, gate)
+        return RD.run_clip(self, plan)
+
     def colour_stats(self, photos, boxes=None):
         """The statistics colour matching works from, per box row and channel: (count int64 [n], mean f64 [n, 3], standard deviation f64
         [n, 3]) on the host.  photos, boxes: as morph takes them (a list of u8 arrays; box rows, by default one whole-photo box per

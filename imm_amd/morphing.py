@@ -91,6 +91,18 @@ def check_max_gain(max_gain):
     return g
 
 
+def check_grow(grow, n):
+    """grow of mask='hull' (morph, redact): a number or one per row in (0, 16] -> f32 [n]."""
+    return _share(grow, n, 'grow', ('(0, %g]' % MAX_GROW, lambda v: (v > 0.0) & (v <= MAX_GROW),
+                                    'the factor by which the landmark hull is grown about its centroid'))
+
+
+def check_mask_feather(mask_feather, n):
+    """mask_feather of mask='hull' (morph, redact): a number or one per row in [0, 1] -> f32 [n]."""
+    return _share(mask_feather, n, 'mask_feather', ('[0, 1]', lambda v: (v >= 0.0) & (v <= 1.0),
+                                                    'the share of the box\'s shorter side over which the mask softens inwards'))
+
+
 def hull_inv_soft(rows, mask_feather):
     """inv_soft f32 [n] of morph(mask='hull'): (float)(1 / max(1, mask_feather * min(H, W))), formed in f64 from the f32 mask_feather
     widened: the hull's weight is 0 on the grown hull's edge and 1 that many pixels (at least one) inside it."""
@@ -203,10 +215,7 @@ def plan_morph(photos, donors, boxes, donor_boxes, shape, texture, feather, K, a
             if (area > COLOUR_MAX_AREA).any():
                 raise ValueError('%s: row %d has %d pixels; colour matching serves boxes of at most 2^30' % (
                     name, int(np.argmax(area > COLOUR_MAX_AREA)), int(area.max())))
-    grow = _share(grow, n, 'grow', ('(0, %g]' % MAX_GROW, lambda v: (v > 0.0) & (v <= MAX_GROW),
-                                    'the factor by which the landmark hull is grown about its centroid'))
-    mask_feather = _share(mask_feather, n, 'mask_feather', ('[0, 1]', lambda v: (v >= 0.0) & (v <= 1.0),
-                                                            'the share of the box\'s shorter side over which the mask softens inwards'))
+    grow, mask_feather = check_grow(grow, n), check_mask_feather(mask_feather, n)
     seamless = _share(seamless, n, 'seamless', ('[0, 1]', lambda v: (v >= 0.0) & (v <= 1.0),
                                                 'the share of the mean-value correction that is added to the donor\'s pixels'))
     ring = check_ring(ring)

@@ -1235,6 +1235,72 @@ def clip_ema(x, state, seen, skip, lost, alpha):
     call('imm_clip_ema', _p(x), _p(state), _p(seen), _p(skip), None if lost is None else _p(lost), n, width, alpha, _s())
 
 
+REDACT_MAX_BLOCKS = 64        # cells along the longer side of a redacted box (include/imm_redact.h)
+REDACT_MODES = {'pixelate': 0, 'smooth': 1}      # IMM_REDACT_*
+
+
+def _check_redact(name, buf, offsets, hw, boxes, blocks, cells):
+    """What the two redaction entries share: the packed buffer, the box rows, blocks and the cells buffer -> (n, blocks)."""
+    if boxes.dim() != 2:
+        raise ValueError('boxes must be int32 [n, 5], got %s' % (tuple(boxes.shape),))
+    n = int(boxes.shape[0])
+    if n < 1 or n > 65535:
+        raise ValueError('%s serves 1..65535 rows, got n = %d' % (name, n))
+    if isinstance(blocks, bool) or int(blocks) != blocks or not 1 <= int(blocks) <= REDACT_MAX_BLOCKS:
+        raise ValueError('blocks must be an int in [1, %d], got %r' % (REDACT_MAX_BLOCKS, blocks))
+    blocks = int(blocks)
+    _check_tensors([('photos', buf, torch.uint8, (None,)), ('hw', hw, torch.int32, (None, 2))])
+    if hw.shape[0] < 1:
+        raise ValueError('hw must hold at least one image, got %s' % (tuple(hw.shape),))
+    _check_tensors([('boxes', boxes, torch.int32, (n, 5)), ('offsets', offsets, torch.int64, (hw.shape[0],)),
+                    ('cells', cells, torch.uint8, (n, blocks * blocks * 3))])
+    if _overlap(cells, buf):
+        raise ValueError('cells overlaps the photos')
+    return n, blocks
+
+
+def redact_cells_u8(src, offsets, hw, boxes, blocks, cells):
+    """The cell means of every row's box (include/imm_redact.h: imm_redact_cells_u8): src u8 [bytes] with offsets i64 [images] and hw i32
+    [images, 2] (a packed buffer, as warp_u8 reads it) and boxes i32 [n, 5] -> cells u8 [n, blocks * blocks * 3]: per row the box cut
+    into gy x gx square cells of side ceil(max(H, W) / blocks), every cell the mean (half up, in integers) of the bytes it covers inside
+    the photo, dense as [gy, gx, 3] at the start of the row's slice; every other byte, and the slice of a row that is not active, 0."""
+    n, blocks = _check_redact('redact_cells_u8', src, offsets, hw, boxes, blocks, cells)
+    call('imm_redact_cells_u8', _p(src), _p(offsets), _p(hw), int(hw.shape[0]), _p(boxes), blocks, n, _p(cells), _s())
+
+
+def redact_u8(dst, offsets, hw, boxes, links, inv_ramp, cells, blocks, mode, max_box_pixels, edges=None, inv_soft=None, hull_flags=None):
+    """The packed u8 photos dst redacted in place (include/imm_redact.h: imm_redact_u8): every pixel of row b's box takes its cell's mean
+    (mode 0 or 'pixelate') or the bilinear sample of the grid of means (1 or 'smooth') from cells u8 [n, blocks * blocks * 3]
+    (redact_cells_u8's output for these rows, taken from the ORIGINAL pixels), blended with the edge ramp inv_ramp f32 [n, 2] and rounded
+    to u8, in row order.  boxes, links, max_box_pixels as warp_u8 takes them.  edges f32 [n, K, 3], inv_soft f32 [n] and hull_flags i32
+    [n] (hull_fit's output for these rows) come together or not at all: with them the ramp is multiplied by the hull's weight, a pixel
+    outside the hull is left alone, and a row whose flag is not 0 is redacted over its WHOLE box."""
+    n, blocks = _check_redact('redact_u8', dst, offsets, hw, boxes, blocks, cells)
+    mode = REDACT_MODES.get(mode, mode) if isinstance(mode, str) else mode
+    if isinstance(mode, bool) or mode not in (0, 1):
+        raise ValueError("mode must be 0 ('pixelate') or 1 ('smooth'), got %r" % (mode,))
+    _check_tensors([('links', links, torch.int32, (n, 2)), ('inv_ramp', inv_ramp, torch.float32, (n, 2))])
+    if int(max_box_pixels) < 1:
+        raise ValueError('max_box_pixels must be positive, got %r' % (max_box_pixels,))
+    trio = dict(edges=edges, inv_soft=inv_soft, hull_flags=hull_flags)
+    absent = [k for k, t in trio.items() if t is None]
+    if absent and len(absent) < 3:
+        raise ValueError('edges, inv_soft and hull_flags come together: %s is None' % absent[0])
+    K = 0
+    if edges is not None:
+        if edges.dim() != 3 or not 1 <= int(edges.shape[1]) <= WARP_MAX_POINTS:
+            raise ValueError('edges must be f32 [n, K, 3] with 1 <= K <= %d, got %s' % (WARP_MAX_POINTS, tuple(edges.shape)))
+        K = int(edges.shape[1])
+        _check_tensors([('edges', edges, torch.float32, (n, K, 3)), ('inv_soft', inv_soft, torch.float32, (n,)),
+                        ('hull_flags', hull_flags, torch.int32, (n,))])
+    for k, t in dict(trio, links=links, inv_ramp=inv_ramp, boxes=boxes, offsets=offsets, hw=hw).items():
+        if t is not None and _overlap(t, dst):
+            raise ValueError('%s overlaps dst' % k)
+    call('imm_redact_u8', _p(dst), _p(offsets), _p(hw), int(hw.shape[0]), _p(boxes), _p(links), _p(inv_ramp), _p(cells), blocks, int(mode),
+         None if edges is None else _p(edges), None if edges is None else _p(inv_soft), None if edges is None else _p(hull_flags), K, n,
+         int(max_box_pixels), _s())
+
+
 def masked_sse_pool(a, b, batch, s, c, mask, S, partial, pool_a, pool_b):
     call('imm_masked_sse_pool', _p(a), _p(b), dtype_enum(a.dtype), batch, s, c, _p(mask), S, _p(partial), _p(pool_a), _p(pool_b), _s())
 

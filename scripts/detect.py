@@ -21,7 +21,13 @@ mean spread, and the residual of the --template shape under the best similarity;
 a NaN score, or by the thresholds of --gate).  With --track --gate FILE (a gate written by scripts/test.py --save-gate) a face that
 fails the gate on a frame is lost on that frame, and the same three arrays are written per frame and face ([T, F, ..]; the residual is
 against the face's own first-frame shape).  No thresholds are built in: how well these scores tell a face from a non-face is unmeasured
-(imm_amd/quality.py)."""
+(imm_amd/quality.py).
+With --redact pixelate|smooth --out-dir DIR nothing is measured: every image is written to DIR as a PNG of its own size with the faces of
+--boxes (without --boxes: each whole image) made unreadable (LandmarkDetector.redact: a mosaic of --blocks cells along the longer side
+of a box, or the blur of that mosaic; --mask hull keeps the redaction to the landmark hull, grown by --grow and softened over
+--mask-feather; --feather fades the box into the photo).  With --track the faces of the first frame are followed and redacted on every
+frame (LandmarkDetector.redact_clip); a face that enters the clip later is NOT redacted.  A face whose landmarks cannot be trusted is
+redacted over its whole box.  Nobody has measured how recognisable a face stays at any setting: no anonymity is claimed."""
 from __future__ import print_function
 
 import argparse
@@ -39,6 +45,7 @@ from imm_amd.keypoints import LandmarkRegressor              # noqa: E402
 from imm_amd.utils.config import load_configs               # noqa: E402
 
 EXTENSIONS = ('.jpg', '.jpeg', '.png', '.bmp')
+REDACT_ONLY = ('out_dir', 'blocks', 'mask', 'grow', 'mask_feather', 'feather')      # arguments that go with --redact alone (default None)
 
 
 def read_boxes(path, files):
@@ -100,6 +107,41 @@ def track(args, det, reg, files):
         mu.shape[0], mu.shape[1], mu.shape[2], args.out, int(tr.lost.sum()), '' if gate is None else ', %d unsure' % int(tr.unsure.sum())))
 
 
+def redact(args, det, files):
+    """--redact: the images written back to --out-dir with their faces pixelated or smoothed."""
+    from PIL import Image
+    from imm_amd.tracking import OneEuro
+    if not args.out_dir:
+        raise ValueError('--redact goes with --out-dir (the images are written back with their faces redacted)')
+    kw = dict(mode=args.redact, mask=args.mask)                    # what is not given keeps the detector's default
+    kw.update({k: getattr(args, k) for k in REDACT_ONLY if k != 'out_dir' and getattr(args, k) is not None})
+    ims = [decode_image(osp.join(args.images_dir, f)) for f in files]
+    if args.track:
+        if not args.boxes:
+            raise ValueError('--track needs --boxes with the faces of the first frame')
+        owner, boxes = read_boxes(args.boxes, files)
+        if len(owner) == 0 or (owner != 0).any():
+            raise ValueError('%s: with --track every row names the first frame, %s' % (args.boxes, files[0]))
+        gate = None
+        if args.gate:
+            from imm_amd.quality import QualityGate
+            gate = QualityGate.load(args.gate, detector=det)
+        cr = det.redact_clip(ims, boxes.tolist(), box_smooth=args.box_smooth, one_euro=None if args.no_filter else OneEuro(), fps=args.fps,
+                             gate=gate, **kw)
+        out, said = cr.frames, '%d frames, %d faces redacted (%d lost, covered whole)' % (len(cr), len(boxes), int(cr.track.lost.sum()))
+    else:
+        rows = None
+        if args.boxes:
+            owner, boxes = read_boxes(args.boxes, files)
+            rows = np.concatenate([owner[:, None], boxes], axis=1).tolist()
+        out = det.redact(ims, rows, **kw)
+        said = '%d faces redacted in %d images' % (len(ims) if rows is None else len(rows), len(ims))
+    os.makedirs(args.out_dir, exist_ok=True)
+    for f, im in zip(files, out):
+        Image.fromarray(im.cpu().numpy()).save(osp.join(args.out_dir, osp.splitext(osp.basename(f))[0] + '.png'))
+    print('%s (%s, %d blocks) -> %s' % (said, args.redact, kw.get('blocks', 8), args.out_dir))
+
+
 def main(args):
     config = load_configs(args.configs)
     torch.cuda.set_device(0)
@@ -110,6 +152,10 @@ def main(args):
     det = LandmarkDetector.from_checkpoint(config.model, args.checkpoint, image_size=args.im_size, max_batch=args.batch_size,
                                            dtype=dtype, device='cuda:0')
     reg = LandmarkRegressor.load(args.regressor, detector=det) if args.regressor else None
+    if args.redact:
+        return redact(args, det, files)
+    if any(getattr(args, k) is not None for k in REDACT_ONLY):
+        raise ValueError('--out-dir, --blocks, --mask, --grow, --mask-feather and --feather go with --redact')
     if args.track:
         return track(args, det, reg, files)
     if args.gate or args.template:
@@ -219,4 +265,14 @@ if __name__ == '__main__':
                         help='--quality: a landmark template .npz (scripts/test.py --save-template), the reference shape of the residual')
     parser.add_argument('--gate', type=str, default=None,
                         help='--track / --quality: a quality gate .npz (scripts/test.py --save-gate); there are no built-in thresholds')
+    parser.add_argument('--redact', choices=('pixelate', 'smooth'), default=None,
+                        help='with --out-dir: write every image back with the faces of --boxes made unreadable (a mosaic, or its blur); '
+                             'with --track the faces of the first frame are followed through the clip')
+    parser.add_argument('--out-dir', type=str, default=None, help='--redact: the folder the redacted images are written to (PNG)')
+    parser.add_argument('--blocks', type=int, default=None, help='--redact: cells along the longer side of a box, in [1, 64] (default 8)')
+    parser.add_argument('--mask', choices=('hull',), default=None, help='--redact: only the landmark hull (default: the whole box)')
+    parser.add_argument('--grow', type=float, default=None, help='--redact --mask hull: the factor by which the hull is grown (default 1.25)')
+    parser.add_argument('--mask-feather', type=float, default=None,
+                        help='--redact --mask hull: the share of the box side the mask softens over (default 0.1)')
+    parser.add_argument('--feather', type=float, default=None, help='--redact: the share of the box side over which the paste fades (default 0)')
     main(parser.parse_args())
