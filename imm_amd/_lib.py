@@ -20,7 +20,7 @@ CONV_BIAS, CONV_RELU, CONV_STATS, CONV_MASK, CONV_OUT_F32 = 1, 2, 4, 8, 16
 SSE_BLOCKS = 512
 OPTIMIZERS = {'adam': 0, 'adadelta': 1, 'adagrad': 2}      # IMM_OPT_* (scripts/train.py:97-104)
 GAUSS_MODES = {'rot': 0, 'flat': 1, 'ankush': 2}     # IMM_GAUSS_* (config key gauss_mode, imm_model.py:48-72)
-ABI_VERSION = 37     # the history stands next to IMM_ABI_VERSION in include/imm_hip.h
+ABI_VERSION = 38     # the history stands next to IMM_ABI_VERSION in include/imm_hip.h
 
 
 class ImmHipError(RuntimeError):
@@ -226,6 +226,11 @@ _header('imm_score.h', {  # the landmark-quality entry point (ABI 36)
 _header('imm_redact.h', {  # the redaction entry points (ABI 37)
     'imm_redact_cells_u8': [_P, _P, _P, _I, _P, _I, _I, _P, _P],
     'imm_redact_u8': [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P],
+})
+
+_header('imm_annotate.h', {  # the annotation entry points (ABI 38)
+    'imm_annotate_points': [_P, _P, _I, _I, _P, _P],
+    'imm_annotate_u8': [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
 })
 
 _lib = None

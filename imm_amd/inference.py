@@ -1121,6 +1121,90 @@ class LandmarkDetector(BucketRunner):
                                    fps, chunk_frames, self.max_batch, gate)
         return RD.run_clip(self, plan)
 
+    def annotate(self, photos, boxes=None, landmarks=None, draw=('points', 'box'), size=2.5, thickness=1, labels=None, status=None, grow=1.25,
+                 alpha=1.0, return_transform=False, pad=None, label_scale=1):
+        """The photos with what the detector found drawn into them: a list of u8 device tensors [h_i, w_i, 3], one per photo, views of
+        one packed buffer (what redact returns).  photos, boxes: as redact takes them.  draw: a subset of ('points', 'box', 'hull',
+        'label'): the landmarks of every box as the markers of utils/plot_landmarks.py (8 colours x 7 shapes, radius `size` pixels, in
+        (0, 32]), the box frame `thickness` pixels wide (an int in [1, 16]) in the colour of the row's status (annotation.STATUS_PALETTE:
+        ok, lost, outside, unsure; status: None or int32 [n], imm_track.h's bits with bit 2 for unsure), the outline of the landmark hull
+        grown by `grow` (what mask='hull' of morph and redact covers) and labels (None: the row's number; ints in 0..9999) in a 5 x 7
+        font of label_scale pixels a dot.  alpha in (0, 1] is the opacity of the markers.  landmarks: f32 [n, K, 2] in the frame of the
+        boxes where the caller has them; the pose program is then skipped.  A row whose status has bit 0 set (lost) draws its frame and
+        label only.  Rows are applied in row order; a row draws inside its box grown by pad pixels (default ceil(size) + 2), so that a
+        marker on the box edge is drawn whole.  include/imm_annotate.h states the rule.
+        On the detector's stream, nothing returning to the host: per bucket imm_resize_crop_u8 and the captured pose program (unless
+        landmarks is given, or neither points nor hull are drawn), then imm_annotate_points, imm_hull_fit only when the hull is drawn,
+        and ONE imm_annotate_u8 launch per call.
+        return_transform=True: (photos, an annotation.PhotoAnnotation: rows, points, hull_edges, hull_flags, status)."""
+        from . import annotation as AN
+        from .generation import PasteSetup
+        K = self.K
+        plan = AN.plan_annotate(photos, boxes, K, landmarks, draw, size, thickness, labels, status, grow, alpha, 0, pad, label_scale)
+        photos, rows, bits = plan.photos, plan.rows, plan.bits
+        n, pts, hull = len(rows), bool(bits & AN.BITS['points']), bool(bits & AN.BITS['hull'])
+        held = _Held(self.dev)
+        lm = None if plan.landmarks is None or not (pts or hull) else held.keep(plan.landmarks.to(device=self.dev, dtype=torch.float32).contiguous())
+        buckets = plan_buckets(n, self.max_batch)
+        ps = PasteSetup(photos, rows, [(0, n, n)], 0.0, self.dev)                   # all photos, once per call; the links of ONE launch
+        held.keep(*ps.tensors())
+        extra = {}
+        with torch.cuda.device(self.dev):
+            palette_d = held.up(plan.palette)
+            mu = points = hflags = None
+            if pts or hull:
+                mu = lm if lm is not None else held.empty(n, K, 2)
+                points = held.empty(1, n, K, 2)
+            if pts:
+                extra.update(marks=points, group_style=held.up(plan.group_style), mark_style=held.up(plan.mark_style))
+            if hull:
+                grow_d, hflags = held.up(plan.grow), held.empty(n, dtype=torch.int32)
+                extra.update(edges=held.empty(n, K, 3))
+            if plan.labels is not None:
+                extra.update(labels=held.up(plan.labels))
+            if plan.status is not None:
+                extra.update(status=held.up(plan.status))
+        with self._forked(*held):
+            if mu is not None:
+                if lm is None:
+                    for start, count, bucket in buckets:
+                        part = slice(start, start + count)
+                        self._stage(count, bucket, packed=ps.packed(part))
+                        self._run(bucket)
+                        mu[part].copy_(self._mu[:count])
+                ops.annotate_points(mu, ps.boxes_d, points[0])
+            if hull:
+                ops.hull_fit(mu, ps.boxes_d, grow_d, extra['edges'], hflags)
+            ops.annotate_u8(ps.canvas, ps.offs_d, ps.hw_d, ps.boxes_d, ps.links_d, palette_d, bits, plan.thickness, plan.pad, plan.label_scale,
+                            plan.max_pixels, **extra)
+        out = unpack_u8(ps.canvas, photos)
+        if return_transform:
+            return out, AN.PhotoAnnotation(rows, None if points is None else points[0], extra.get('edges'), hflags, plan.status)
+        return out
+
+    def annotate_clip(self, frames, boxes=None, track=None, draw=('points', 'box'), trail=0, smooth=True, gate=None, size=2.5, thickness=1,
+                      labels=None, grow=1.25, alpha=1.0, pad=None, label_scale=1, box_smooth=0.5, one_euro=OneEuro(), fps=25.0,
+                      chunk_frames=32):
+        """The faces of a clip followed from its first frame and drawn on every frame: track() and annotate() joined on the device, an
+        annotation.ClipAnnotation (frames, track, status).  Exactly one of boxes and track is given.
+        boxes: the F faces of frames[0]; frames, box_smooth, one_euro, fps, chunk_frames, gate: exactly as track / redact_clip take them.
+        track: a tracking.Track of these frames the caller already has: the tracker is skipped and its points, boxes and flags (and
+        qflags) are drawn; the bytes are those of the tracked call that produced it.
+        draw, size, thickness, labels, grow, alpha, pad, label_scale: as annotate takes them (labels=None with 'label' numbers the faces).
+        trail: an int in [0, 15]: the landmarks of that many earlier frames as fading discs under the markers; the first frames of a clip
+        have fewer.  smooth=True draws the tracker's One-Euro points, False its raw points.  The hull is fitted to the frame's own
+        landmarks (Track.mu) in the frame's box.
+        The frame of a face is coloured by its status, formed on the device: the tracker's flags (bit 0 lost, bit 1 the next box left
+        the photo) with the gate's verdict OR-ed in as bit 2; a lost face keeps the box the tracker's unchanged state gives it and draws
+        its frame and label only.
+        Per chunk the frames are uploaded and copied into a canvas on the device; per frame the tracker's launches, imm_hull_fit when
+        the hull is drawn and ONE imm_annotate_u8 launch run on the detector's stream, the marks a view of the tracker's own point
+        slots.  Between the first and the last frame's launches nothing is copied to the host and the stream is not synchronised."""
+        from . import annotation as AN
+        plan = AN.plan_annotate_clip(frames, boxes, track, self.K, draw, trail, smooth, gate, size, thickness, labels, grow, alpha, pad,
+                                     label_scale, box_smooth, one_euro, fps, chunk_frames, self.max_batch)
+        return AN.run_clip(self, plan)
+
     def colour_stats(self, photos, boxes=None):
         """The statistics colour matching works from, per box row and channel: (count int64 [n], mean f64 [n, 3], standard deviation f64
         [n, 3]) on the host.  photos, boxes: as morph takes them (a list of u8 arrays; box rows, by default one whole-photo box per

@@ -1301,6 +1301,81 @@ def redact_u8(dst, offsets, hw, boxes, links, inv_ramp, cells, blocks, mode, max
          int(max_box_pixels), _s())
 
 
+ANNOTATE_BITS = {'points': 1, 'box': 2, 'hull': 4, 'label': 8}      # IMM_ANNOTATE_*
+ANNOTATE_MAX_GROUPS, ANNOTATE_MAX_PAD = 16, 64                      # include/imm_annotate.h
+
+
+def annotate_points(mu, boxes, points):
+    """Landmarks from the frame of their box to photo pixels (include/imm_annotate.h: imm_annotate_points): mu f32 [n, K, 2] in [-1, 1]
+    of boxes i32 [n, 5] -> points f32 [n, K, 2], py = y0 + (mu_y + 1) * (0.5 * H) in f64 rounded once; a value that is not finite is
+    stored as it is."""
+    if mu.dim() != 3 or mu.shape[2] != 2:
+        raise ValueError('mu must be f32 [n, K, 2], got %s' % (tuple(mu.shape),))
+    n, K = int(mu.shape[0]), int(mu.shape[1])
+    if n < 1 or n > 65535 or K < 1 or K > WARP_MAX_POINTS:
+        raise ValueError('annotate_points serves 1..65535 rows of 1..%d landmarks, got n = %d, K = %d' % (WARP_MAX_POINTS, n, K))
+    _check_tensors([('mu', mu, torch.float32, (n, K, 2)), ('boxes', boxes, torch.int32, (n, 5)), ('points', points, torch.float32, (n, K, 2))])
+    if _overlap(mu, points):
+        raise ValueError('mu overlaps points: the output is written while the input is read')
+    call('imm_annotate_points', _p(mu), _p(boxes), K, n, _p(points), _s())
+
+
+def annotate_u8(dst, offsets, hw, boxes, links, palette, draw_bits, thickness, pad, label_scale, max_box_pixels, marks=None, group_style=None,
+                mark_style=None, edges=None, status=None, labels=None):
+    """The packed u8 photos dst drawn into in place (include/imm_annotate.h: imm_annotate_u8).  boxes, links, max_box_pixels as warp_u8
+    takes them (max_box_pixels: the largest extent, a box grown by pad on every side); palette u8 [P, 3]; draw_bits a sum of
+    ANNOTATE_BITS.  With 'points': marks f32 [G, n, K, 2] in photo pixels (group G - 1 the markers, the groups before it the trail, oldest
+    first), group_style f32 [G, 4] = (R, 1 / (2 R), h, alpha) and mark_style u8 [K, 4] = (r, g, b, shape).  With 'hull': edges f32
+    [n, K, 3] (hull_fit's lines).  With 'label': labels i32 [n].  status i32 [n] or None picks every row's colour; a row with bit 0 set
+    draws its frame and label only."""
+    if boxes.dim() != 2:
+        raise ValueError('boxes must be int32 [n, 5], got %s' % (tuple(boxes.shape),))
+    n = int(boxes.shape[0])
+    if n < 1 or n > 65535:
+        raise ValueError('annotate_u8 serves 1..65535 rows, got n = %d' % n)
+    for name, v, lo, hi in (('draw_bits', draw_bits, 0, 15), ('thickness', thickness, 1, 16), ('pad', pad, 0, ANNOTATE_MAX_PAD),
+                            ('label_scale', label_scale, 1, 8), ('max_box_pixels', max_box_pixels, 1, 2 ** 31 - 1)):
+        if isinstance(v, bool) or int(v) != v or not lo <= int(v) <= hi:
+            raise ValueError('%s must be an int in [%d, %d], got %r' % (name, lo, hi, v))
+    bits = int(draw_bits)
+    _check_tensors([('photos', dst, torch.uint8, (None,)), ('hw', hw, torch.int32, (None, 2)), ('palette', palette, torch.uint8, (None, 3))])
+    if hw.shape[0] < 1 or not 1 <= int(palette.shape[0]) <= 32:
+        raise ValueError('hw must hold at least one image and palette 1..32 colours, got %s and %s' % (tuple(hw.shape), tuple(palette.shape)))
+    _check_tensors([('boxes', boxes, torch.int32, (n, 5)), ('offsets', offsets, torch.int64, (hw.shape[0],)), ('links', links, torch.int32, (n, 2))])
+    given = dict(boxes=boxes, offsets=offsets, hw=hw, links=links, palette=palette)
+    K = G = 1
+    if bits & 1:
+        _need('annotate_u8 with points', marks=marks, group_style=group_style, mark_style=mark_style)
+        if marks.dim() != 4 or not 1 <= int(marks.shape[0]) <= ANNOTATE_MAX_GROUPS or not 1 <= int(marks.shape[2]) <= WARP_MAX_POINTS:
+            raise ValueError('marks must be f32 [G, n, K, 2] with 1 <= G <= %d and 1 <= K <= %d, got %s'
+                             % (ANNOTATE_MAX_GROUPS, WARP_MAX_POINTS, tuple(marks.shape)))
+        G, K = int(marks.shape[0]), int(marks.shape[2])
+        _check_tensors([('marks', marks, torch.float32, (G, n, K, 2)), ('group_style', group_style, torch.float32, (G, 4)),
+                        ('mark_style', mark_style, torch.uint8, (K, 4))])
+        given.update(marks=marks, group_style=group_style, mark_style=mark_style)
+    if bits & 4:
+        _need('annotate_u8 with the hull', edges=edges)
+        if edges.dim() != 3 or not 1 <= int(edges.shape[1]) <= WARP_MAX_POINTS or (bits & 1 and int(edges.shape[1]) != K):
+            raise ValueError('edges must be f32 [n, K, 3] with 1 <= K <= %d (the K of marks), got %s' % (WARP_MAX_POINTS, tuple(edges.shape)))
+        K = int(edges.shape[1])
+        _check_tensors([('edges', edges, torch.float32, (n, K, 3))])
+        given.update(edges=edges)
+    if bits & 8:
+        _need('annotate_u8 with labels', labels=labels)
+        _check_tensors([('labels', labels, torch.int32, (n,))])
+        given.update(labels=labels)
+    if status is not None:
+        _check_tensors([('status', status, torch.int32, (n,))])
+        given.update(status=status)
+    for k, t in given.items():
+        if _overlap(t, dst):
+            raise ValueError('%s overlaps dst' % k)
+    opt = lambda t, bit: _p(t) if bits & bit else None
+    call('imm_annotate_u8', _p(dst), _p(offsets), _p(hw), int(hw.shape[0]), _p(boxes), _p(links), opt(marks, 1), opt(group_style, 1),
+         opt(mark_style, 1), opt(edges, 4), None if status is None else _p(status), _p(palette), int(palette.shape[0]), opt(labels, 8), bits,
+         int(thickness), int(pad), int(label_scale), K, G, n, int(max_box_pixels), _s())
+
+
 def masked_sse_pool(a, b, batch, s, c, mask, S, partial, pool_a, pool_b):
     call('imm_masked_sse_pool', _p(a), _p(b), dtype_enum(a.dtype), batch, s, c, _p(mask), S, _p(partial), _p(pool_a), _p(pool_b), _s())
 

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define IMM_ABI_VERSION 37   /* 37: redaction, imm_redact_cells_u8 and imm_redact_u8 in imm_redact.h (faces pixelated or smoothed inside their u8 photos: the box cut into square cells, every cell the integer mean of the original pixels it covers, pasted through the skeleton of the other paste kernels; with the landmark-hull mask a row whose hull is flagged is redacted over its whole box).  36: landmark quality, imm_landmark_scores in imm_score.h (the soft-argmax marginals and the landmarks of every face -> the spread of the landmarks' probability and the residual of a reference shape under the best similarity, with landmarks that are NaN for a face that fails the caller's thresholds, which imm_track_step then treats as lost).  35: clip morph, the rows and the filter of imm_clip.h (a donor's face follows a tracked face through a clip: the per-row values morph forms on the host are formed on the device from the tracker's box rows, and the colour gain and the membrane's differences pass a first-order filter).  34: the seamless morph, imm_seam_fit and imm_morph_seam_u8 in imm_seam.h (a mean-value membrane over the hull mask: the colour differences at B samples of the mask's outline, weighed per pixel in closed form, take the donor's pixels onto the photo's own values on the outline).  33: the landmark-hull mask of morph, imm_hull_fit and imm_morph_hull_u8 in imm_hull.h (the convex hull of a row's target landmarks, grown and softened, multiplies the box ramp, so that only the face is pasted; pixels outside it skip the spline).  32: colour matching for morph, imm_colour_stats_u8, imm_colour_gain and imm_morph_colour_u8 in imm_colour.h (the mean and spread of a face's and its donor's pixels give a gain and an offset per channel, applied to the donor's sample in front of the mix).  31: morph, imm_morph_poses and imm_morph_u8 in imm_morph.h (two faces blended in shape and texture from their own pixels: the pose blend and a two-source sampling kernel behind ONE imm_warp_fit launch).  30: warp, imm_warp_fit and imm_warp_u8 in imm_warp.h (faces re-posed from the photo's own pixels by a thin-plate spline fitted per face on the device).  29: re-enactment, imm_retarget in imm_retarget.h (a tracked driving face -> the poses of still source faces, on the device).  28: face tracking, imm_track_step in imm_track.h (landmarks -> the next frame's box row, on the device).  27: unalign, imm_unalign_maps and imm_unalign_u8 in imm_unalign.h (aligned faces pasted back through the inverse alignment map).  26: imm_compose_u8 in imm_compose.h (faces pasted back into u8 photos).  25: alignment, imm_align_coeffs and imm_align_warp_u8 in imm_align.h.  24: box-crop mode of imm_resize_crop_u8 (boxes), keypoint epilogue of imm_pose_head_fwd (imm_keypoint_desc).  23: render-only mode of the soft-argmax forward (heat == NULL: mu is the input).  22: s2f / conv_first accept IMM_CONV_RELU.  21: imm_masked_sse_all.  20: imm_vgg_head_fwd / imm_vgg_head_supported / imm_vgg_head_scratch_bytes (conv1_1 + conv1_2 in one launch).  19: imm_set_cu_limit / imm_get_cu_limit, imm_masked_sse_pool with pool_a == NULL.  18: imm_copy_f32.  17: imm_cost_ema, imm_rms16 (summaries).  16: imm_conv2d_variant.  15: imm_conv2d_dgrad_s2, imm_conv2d_nol, imm_conv_first, imm_wgrad_job.x_scale/x_shift/x_relu; entry points removed
+#define IMM_ABI_VERSION 38   /* 38: annotation, imm_annotate_points and imm_annotate_u8 in imm_annotate.h (what the detector, the tracker, the quality gate and the hull mask decided, drawn into the u8 photos on the device: markers, trails, the box frame in the colour of the row's status, the hull's outline and a number per face, one more policy over the skeleton of the paste kernels).  37: redaction, imm_redact_cells_u8 and imm_redact_u8 in imm_redact.h (faces pixelated or smoothed inside their u8 photos: the box cut into square cells, every cell the integer mean of the original pixels it covers, pasted through the skeleton of the other paste kernels; with the landmark-hull mask a row whose hull is flagged is redacted over its whole box).  36: landmark quality, imm_landmark_scores in imm_score.h (the soft-argmax marginals and the landmarks of every face -> the spread of the landmarks' probability and the residual of a reference shape under the best similarity, with landmarks that are NaN for a face that fails the caller's thresholds, which imm_track_step then treats as lost).  35: clip morph, the rows and the filter of imm_clip.h (a donor's face follows a tracked face through a clip: the per-row values morph forms on the host are formed on the device from the tracker's box rows, and the colour gain and the membrane's differences pass a first-order filter).  34: the seamless morph, imm_seam_fit and imm_morph_seam_u8 in imm_seam.h (a mean-value membrane over the hull mask: the colour differences at B samples of the mask's outline, weighed per pixel in closed form, take the donor's pixels onto the photo's own values on the outline).  33: the landmark-hull mask of morph, imm_hull_fit and imm_morph_hull_u8 in imm_hull.h (the convex hull of a row's target landmarks, grown and softened, multiplies the box ramp, so that only the face is pasted; pixels outside it skip the spline).  32: colour matching for morph, imm_colour_stats_u8, imm_colour_gain and imm_morph_colour_u8 in imm_colour.h (the mean and spread of a face's and its donor's pixels give a gain and an offset per channel, applied to the donor's sample in front of the mix).  31: morph, imm_morph_poses and imm_morph_u8 in imm_morph.h (two faces blended in shape and texture from their own pixels: the pose blend and a two-source sampling kernel behind ONE imm_warp_fit launch).  30: warp, imm_warp_fit and imm_warp_u8 in imm_warp.h (faces re-posed from the photo's own pixels by a thin-plate spline fitted per face on the device).  29: re-enactment, imm_retarget in imm_retarget.h (a tracked driving face -> the poses of still source faces, on the device).  28: face tracking, imm_track_step in imm_track.h (landmarks -> the next frame's box row, on the device).  27: unalign, imm_unalign_maps and imm_unalign_u8 in imm_unalign.h (aligned faces pasted back through the inverse alignment map).  26: imm_compose_u8 in imm_compose.h (faces pasted back into u8 photos).  25: alignment, imm_align_coeffs and imm_align_warp_u8 in imm_align.h.  24: box-crop mode of imm_resize_crop_u8 (boxes), keypoint epilogue of imm_pose_head_fwd (imm_keypoint_desc).  23: render-only mode of the soft-argmax forward (heat == NULL: mu is the input).  22: s2f / conv_first accept IMM_CONV_RELU.  21: imm_masked_sse_all.  20: imm_vgg_head_fwd / imm_vgg_head_supported / imm_vgg_head_scratch_bytes (conv1_1 + conv1_2 in one launch).  19: imm_set_cu_limit / imm_get_cu_limit, imm_masked_sse_pool with pool_a == NULL.  18: imm_copy_f32.  17: imm_cost_ema, imm_rms16 (summaries).  16: imm_conv2d_variant.  15: imm_conv2d_dgrad_s2, imm_conv2d_nol, imm_conv_first, imm_wgrad_job.x_scale/x_shift/x_relu; entry points removed
                                   since 14 (imm_bn_bwd_reduce_finalize, imm_conv2d_stats_workspace_bytes) finally counted */
 
 /* IMM_F32 (round 6): f32 activation storage — the exact-arithmetic WITNESS of the wiring, a test instrument (the reference computes
@@ -625,6 +625,11 @@ int imm_resize_crop_u8(const uint8_t* src, const int64_t* offsets, const int32_t
  * blur) over the box with the ramp, the row order and the links of the other paste kernels, and with the landmark-hull mask redacts the
  * whole box of a row whose hull is flagged, are declared in imm_redact.h, included at the end as well. ---- */
 
+/* ---- annotation (ABI 38): imm_annotate_points, which moves every row's landmarks from the frame of its box to photo pixels, and
+ * imm_annotate_u8, which draws the markers and their trail, the box frame in the colour of the row's status, the outline of the grown
+ * landmark hull and a decimal label into the photos with the rounding, the row order and the links of the other paste kernels, are
+ * declared in imm_annotate.h, included at the end as well. ---- */
+
 /* ---- host utility: CRC-32C of TensorFlow checkpoint bundles (cnn_train_multi.py:404-439 tf.train.Saver files) ---- */
 /* *crc_inout = crc32c(*crc_inout continued over data[0..n)); start with 0.  Host memory, no GPU work. */
 int imm_crc32c(const void* data, uint64_t n, uint32_t* crc_inout);
@@ -645,4 +650,5 @@ int imm_crc32c(const void* data, uint64_t n, uint32_t* crc_inout);
 #include "imm_clip.h"
 #include "imm_score.h"
 #include "imm_redact.h"
+#include "imm_annotate.h"
 #endif /* IMM_HIP_H */

@@ -27,7 +27,12 @@ With --redact pixelate|smooth --out-dir DIR nothing is measured: every image is 
 of a box, or the blur of that mosaic; --mask hull keeps the redaction to the landmark hull, grown by --grow and softened over
 --mask-feather; --feather fades the box into the photo).  With --track the faces of the first frame are followed and redacted on every
 frame (LandmarkDetector.redact_clip); a face that enters the clip later is NOT redacted.  A face whose landmarks cannot be trusted is
-redacted over its whole box.  Nobody has measured how recognisable a face stays at any setting: no anonymity is claimed."""
+redacted over its whole box.  Nobody has measured how recognisable a face stays at any setting: no anonymity is claimed.
+With --annotate --out-dir DIR nothing is measured either: every image is written to DIR as a PNG of its own size with what the detector
+decided drawn into it on the device (LandmarkDetector.annotate: --draw points,box,hull,label; --marker-size the markers' radius; --grow
+the hull's).  With --track the faces of the first frame are followed and every frame shows its landmarks, --trail earlier frames of them,
+and each face's box in the colour of its status: ok, lost, outside, unsure with --gate (LandmarkDetector.annotate_clip).  --annotate and
+--redact do not go together."""
 from __future__ import print_function
 
 import argparse
@@ -45,6 +50,7 @@ from imm_amd.keypoints import LandmarkRegressor              # noqa: E402
 from imm_amd.utils.config import load_configs               # noqa: E402
 
 EXTENSIONS = ('.jpg', '.jpeg', '.png', '.bmp')
+ANNOTATE_ONLY = ('draw', 'trail', 'marker_size')                                       # arguments that go with --annotate alone
 REDACT_ONLY = ('out_dir', 'blocks', 'mask', 'grow', 'mask_feather', 'feather')      # arguments that go with --redact alone (default None)
 
 
@@ -142,7 +148,60 @@ def redact(args, det, files):
     print('%s (%s, %d blocks) -> %s' % (said, args.redact, kw.get('blocks', 8), args.out_dir))
 
 
+def check_annotate(args):
+    """--annotate and what goes with it, checked before anything is loaded."""
+    if args.annotate and args.redact:
+        raise ValueError('--annotate and --redact do not go together: run the script once for each')
+    if args.annotate and not args.out_dir:
+        raise ValueError('--annotate goes with --out-dir (the images are written back with the annotation drawn into them)')
+    if not args.annotate and any(getattr(args, k) is not None for k in ANNOTATE_ONLY):
+        raise ValueError('--draw, --trail and --marker-size go with --annotate')
+    if args.annotate and any(getattr(args, k) is not None for k in ('blocks', 'mask', 'mask_feather', 'feather')):
+        raise ValueError('--blocks, --mask, --mask-feather and --feather go with --redact')
+
+
+def annotate(args, det, files):
+    """--annotate: the images written back to --out-dir with landmarks, boxes, hulls and numbers drawn into them."""
+    from PIL import Image
+    from imm_amd.tracking import OneEuro
+    kw = dict(draw=tuple(d for d in (args.draw or 'points,box').split(',') if d))
+    if args.marker_size is not None:
+        kw['size'] = args.marker_size
+    if args.grow is not None:
+        kw['grow'] = args.grow
+    ims = [decode_image(osp.join(args.images_dir, f)) for f in files]
+    if args.track:
+        if not args.boxes:
+            raise ValueError('--track needs --boxes with the faces of the first frame')
+        owner, boxes = read_boxes(args.boxes, files)
+        if len(owner) == 0 or (owner != 0).any():
+            raise ValueError('%s: with --track every row names the first frame, %s' % (args.boxes, files[0]))
+        gate = None
+        if args.gate:
+            from imm_amd.quality import QualityGate
+            gate = QualityGate.load(args.gate, detector=det)
+        ca = det.annotate_clip(ims, boxes.tolist(), trail=args.trail or 0, box_smooth=args.box_smooth, smooth=not args.no_filter,
+                               one_euro=None if args.no_filter else OneEuro(), fps=args.fps, gate=gate, **kw)
+        out = ca.frames
+        said = '%d frames, %d faces annotated (%d lost%s)' % (len(ca), len(boxes), int(ca.track.lost.sum()),
+                                                            '' if gate is None else ', %d unsure' % int(ca.track.unsure.sum()))
+    else:
+        if args.trail:
+            raise ValueError('--trail goes with --track')
+        rows = None
+        if args.boxes:
+            owner, boxes = read_boxes(args.boxes, files)
+            rows = np.concatenate([owner[:, None], boxes], axis=1).tolist()
+        out = det.annotate(ims, rows, **kw)
+        said = '%d faces annotated in %d images' % (len(ims) if rows is None else len(rows), len(ims))
+    os.makedirs(args.out_dir, exist_ok=True)
+    for f, im in zip(files, out):
+        Image.fromarray(im.cpu().numpy()).save(osp.join(args.out_dir, osp.splitext(osp.basename(f))[0] + '.png'))
+    print('%s (%s) -> %s' % (said, ','.join(kw['draw']), args.out_dir))
+
+
 def main(args):
+    check_annotate(args)
     config = load_configs(args.configs)
     torch.cuda.set_device(0)
     files = sorted(f for f in os.listdir(args.images_dir) if f.lower().endswith(EXTENSIONS))
@@ -154,6 +213,8 @@ def main(args):
     reg = LandmarkRegressor.load(args.regressor, detector=det) if args.regressor else None
     if args.redact:
         return redact(args, det, files)
+    if args.annotate:
+        return annotate(args, det, files)
     if any(getattr(args, k) is not None for k in REDACT_ONLY):
         raise ValueError('--out-dir, --blocks, --mask, --grow, --mask-feather and --feather go with --redact')
     if args.track:
@@ -275,4 +336,11 @@ if __name__ == '__main__':
     parser.add_argument('--mask-feather', type=float, default=None,
                         help='--redact --mask hull: the share of the box side the mask softens over (default 0.1)')
     parser.add_argument('--feather', type=float, default=None, help='--redact: the share of the box side over which the paste fades (default 0)')
+    parser.add_argument('--annotate', action='store_true',
+                        help='with --out-dir: write every image back with the landmarks and boxes of --boxes drawn into it; with '
+                             '--track the faces of the first frame are followed and every frame shows what the tracker and --gate decided')
+    parser.add_argument('--draw', type=str, default=None,
+                        help='--annotate: a comma list of points, box, hull, label (default points,box); --grow sets the hull')
+    parser.add_argument('--trail', type=int, default=None, help='--annotate --track: the landmarks of that many earlier frames, in [0, 15]')
+    parser.add_argument('--marker-size', type=float, default=None, help='--annotate: the radius of a marker in pixels, in (0, 32] (default 2.5)')
     main(parser.parse_args())
