@@ -11,7 +11,7 @@ gate and the hull mask decided, in the same u8 buffers and at the speed the fram
 PIL markers on the host, one enlarged image at a time, and stays as it is; the marker styles here are its table (8 colours x 7 shapes).
 
 The frame of a face takes the colour of its status: STATUS_PALETTE = (ok, lost, outside, unsure), the lowest set bit of the tracker's
-flags (bit 0 lost, bit 1 outside) with the gate's verdict OR-ed in as bit 2 (FLAG_UNSURE, redaction's bit).  A lost face draws its
+flags (bit 0 lost, bit 1 outside) with the gate's verdict OR-ed in as bit 2 (tracking.FLAG_UNSURE).  A lost face draws its
 frame and label only: its landmarks are not to be believed.
 
 This module holds the host side: the style tables, plan_annotate (every argument checked before anything reaches the device),
@@ -21,12 +21,13 @@ import math
 import numpy as np
 
 from . import morphing as MP
+from .inference import _Plan
+from .tracking import FLAG_LOST, FLAG_OUTSIDE, FLAG_UNSURE        # noqa: F401  the bits of a status
 from .utils.plot_landmarks import COLORS, MARKERS
 
 DRAW = ('points', 'box', 'hull', 'label')
 BITS = {'points': 1, 'box': 2, 'hull': 4, 'label': 8}            # IMM_ANNOTATE_*
 MAX_GROUPS, MAX_PAD, MAX_K = 16, 64, 80
-FLAG_LOST, FLAG_OUTSIDE, FLAG_UNSURE = 1, 2, 4                    # the bits of a status; bit 2 as redaction.FLAG_UNSURE
 # ok, lost, outside, unsure: the frame of a row takes palette[0] for status 0, else palette[1 + its lowest set bit]
 STATUS_PALETTE = np.array([(40, 220, 60), (235, 30, 30), (255, 150, 0), (250, 230, 20)], dtype=np.uint8)
 # seven rows of five columns per digit, as include/imm_annotate.h prints them in hex
@@ -115,16 +116,12 @@ def check_row_ints(name, v, shape):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
-class AnnotatePlan(object):
+class AnnotatePlan(_Plan):
     """What plan_annotate returns, by name: photos (decoded u8 arrays), rows int32 [n, 5], bits (draw as IMM_ANNOTATE_* bits), size,
     thickness, trail, alpha, pad, label_scale, labels int32 [n] or None, status int32 [n] or None, grow f32 [n], landmarks (None or an f32
     tensor [n, K, 2]), mark_style u8 [K, 4], group_style f32 [trail + 1, 4], palette u8 [4, 3], max_pixels (grid_pixels of the rows)."""
     FIELDS = ('photos', 'rows', 'bits', 'size', 'thickness', 'trail', 'alpha', 'pad', 'label_scale', 'labels', 'status', 'grow', 'landmarks',
               'mark_style', 'group_style', 'palette', 'max_pixels')
-
-    def __init__(self, **fields):
-        assert set(fields) == set(self.FIELDS)
-        self.__dict__.update(fields)
 
 
 def plan_annotate(photos, boxes, K, landmarks=None, draw=('points', 'box'), size=2.5, thickness=1, labels=None, status=None, grow=1.25,
@@ -135,27 +132,19 @@ def plan_annotate(photos, boxes, K, landmarks=None, draw=('points', 'box'), size
     [0, 15]; alpha in (0, 1]; pad an int in [0, 64], by default ceil(size) + 2; label_scale an int in [1, 8]; labels and status None or
     integers [n] (labels=None with 'label' numbers the rows); grow as morph takes it; landmarks None or [n, K, 2] in the frame of the
     boxes (redact's convention; values that are not finite are not refused: they draw nothing); at most 65535 rows."""
-    import torch
     from .generation import NEEDS_U8
-    from .inference import decode_u8
-    from .keypoints import check_boxes
+    from .inference import check_landmarks, photos_and_rows
     bits, size, thickness, trail, alpha, pad, label_scale = check_style(K, draw, size, thickness, trail, alpha, pad, label_scale)
-    if not isinstance(photos, (list, tuple)) or not len(photos):
-        raise ValueError('photos: %s' % NEEDS_U8)
-    photos = decode_u8(photos)
-    rows = check_boxes([(0, 0, a.shape[0], a.shape[1]) for a in photos] if boxes is None else boxes, len(photos))
+    needs = 'photos: %s' % NEEDS_U8
+    photos, rows = photos_and_rows(photos, boxes, needs, needs,
+                                   limit=(65535, 'an annotation serves at most 65535 rows a call (n <= 65535), got n = %d'))
     n = len(rows)
-    if n > 65535:
-        raise ValueError('an annotation serves at most 65535 rows a call (n <= 65535), got n = %d' % n)
     labels, status = check_row_ints('labels', labels, (n,)), check_row_ints('status', status, (n,))
     if labels is None and bits & BITS['label']:
         labels = np.arange(n, dtype=np.int32)
     grow = MP.check_grow(grow, n)
     if landmarks is not None:
-        landmarks = torch.as_tensor(landmarks)
-        if landmarks.dim() != 3 or tuple(landmarks.shape) != (n, int(K), 2):
-            raise ValueError('landmarks must be [%d, %d, 2], got %s' % (n, int(K), tuple(landmarks.shape)))
-        landmarks = landmarks.float()
+        landmarks = check_landmarks(landmarks, (n,), K)
     return AnnotatePlan(photos=photos, rows=rows, bits=bits, size=size, thickness=thickness, trail=trail, alpha=alpha, pad=pad,
                         label_scale=label_scale, labels=labels, status=status, grow=grow, landmarks=landmarks, mark_style=mark_styles(K),
                         group_style=group_styles(size, trail + 1, alpha), palette=STATUS_PALETTE.copy(), max_pixels=grid_pixels(rows, pad))
@@ -182,13 +171,11 @@ class ClipAnnotation(object):
         return len(self.frames)
 
 
-class ClipAnnotatePlan(object):
+class ClipAnnotatePlan(_Plan):
     """annotate_clip()'s checked arguments: frames (decoded u8 arrays), rows int32 [F, 5] (with boxes) or None, track (with track=) or
     None, style (the AnnotatePlan of the first frame's rows: every setting of the drawing), smooth, box_smooth, one_euro, fps,
     chunk_frames, gate."""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
+    FIELDS = ('frames', 'rows', 'track', 'style', 'smooth', 'box_smooth', 'one_euro', 'fps', 'chunk_frames', 'gate')
 
 
 def plan_annotate_clip(frames, boxes, track, K, draw=('points', 'box'), trail=0, smooth=True, gate=None, size=2.5, thickness=1, labels=None,
@@ -217,8 +204,8 @@ def plan_annotate_clip(frames, boxes, track, K, draw=('points', 'box'), trail=0,
 
 
 def run_clip(det, plan):
-    """The launches of annotate_clip() for a checked plan; called with the caller's stream current.  The frame loop of
-    redaction.run_clip: per chunk one upload and one canvas copy; per frame, on the detector's stream, FaceTracker._advance (skipped
+    """The launches of annotate_clip() for a checked plan; called with the caller's stream current.  The frame loop is
+    tracking.run_frames: per chunk one upload and one canvas copy; per frame, on the detector's stream, FaceTracker._advance (skipped
     with track=), imm_hull_fit on the frame's landmarks (Track.mu) when the hull is drawn and ONE imm_annotate_u8 launch whose marks
     are a view of the slots [t - trail', t] of the tracker's points (points_smooth with smooth=True), trail' = min(trail, t): the start
     of a clip uses fewer groups, never another clip's data.  The status is formed on the device: the tracker's flags with the gate's
@@ -228,82 +215,57 @@ def run_clip(det, plan):
     from . import tracking as TR
     from .clip import GRID_AREAS
     from .generation import compose_links
-    from .inference import pack_u8, unpack_u8
-    st, frames, rows = plan.style, plan.frames, plan.rows
+    from .inference import _Held
+    st, frames, rows, track = plan.style, plan.frames, plan.rows, plan.track
     K, dev = det.K, det.dev
     F, T, bits = len(rows), len(frames), st.bits
     hull, points = bool(bits & BITS['hull']), bool(bits & BITS['points'])
     max_pixels = int(min(GRID_AREAS * st.max_pixels, 2 ** 31 - 1))
-    up = lambda a: ops.to_device_pinned(a, dev)
+    held = _Held(dev)                                          # what the loop's _join records: every tensor made below
+    up = held.up
     with torch.cuda.device(dev):
         links_d, palette_d, mstyle_d = up(compose_links(rows)), up(st.palette), up(st.mark_style)
         # group_style of every G the clip uses: the first frames have fewer groups than trail + 1
         gstyles = [up(group_styles(st.size, G, st.alpha)) for G in range(1, min(st.trail, T - 1) + 2)]
         labels_d = None if st.labels is None else up(st.labels)
-        status = torch.empty(T, F, dtype=torch.int32, device=dev) if plan.track is None else None
-        shared = [links_d, palette_d, mstyle_d, labels_d, status] + gstyles
         grow_d = edges = hflags = None
         if hull:
             grow_d = up(st.grow)
-            edges, hflags = torch.empty(F, K, 3, device=dev), torch.empty(F, dtype=torch.int32, device=dev)
-            shared += [grow_d, edges, hflags]
-    track = plan.track
-    if track is None:
-        tracker = TR.FaceTracker(det, None, plan.box_smooth, plan.one_euro, plan.fps, capacity=T, gate=plan.gate)
-        tracker._begin(rows)
-        cur = tracker._cur = det._fork()
-    else:
-        # the Track's tensors on the device, as the tracker's buffers hold them; the rows of frame t name its place in its chunk
-        cur = det._fork()
-        with torch.cuda.device(dev):
+            edges, hflags = held.empty(F, K, 3), held.empty(F, dtype=torch.int32)
+        if track is None:
+            tracker = TR.FaceTracker(det, None, plan.box_smooth, plan.one_euro, plan.fps, capacity=T, gate=plan.gate)
+            status = held.empty(T, F, dtype=torch.int32)
+        else:
+            # the Track's tensors on the device, as the tracker's buffers hold them; the rows of frame t name its place in its chunk
+            tracker = None
             on = lambda t: torch.as_tensor(t).to(device=dev).contiguous()
-            t_mu, t_pts, t_flags = on(track.mu).float(), on(track.points_smooth if plan.smooth else track.points).float(), on(track.flags).int()
-            t_rows = torch.zeros(T, F, 5, dtype=torch.int32, device=dev)
+            t_mu, t_flags = held.keep(on(track.mu).float(), on(track.flags).int())
+            t_pts = held.keep(on(track.points_smooth if plan.smooth else track.points).float())
+            t_rows = held.zeros(T, F, 5, dtype=torch.int32)
             t_rows[:, :, 1:] = on(track.boxes).int()
             t_rows[:, :, 0] = (torch.arange(T, device=dev, dtype=torch.int32) % plan.chunk_frames)[:, None]
-            status = t_flags.clone()
+            status = held.keep(t_flags.clone())
             if track.qflags is not None:
-                status.bitwise_or_(on(track.qflags).ne(0).to(torch.int32).mul_(FLAG_UNSURE))
-            shared += [t_mu, t_pts, t_flags, t_rows, status]
-    out = []
-    for c0 in range(0, T, plan.chunk_frames):
-        chunk = frames[c0:c0 + plan.chunk_frames]
+                TR.or_unsure(status, on(track.qflags))
+
+    def frame(t, f):
         if track is None:
-            fsrc, foffs_d, fhw_d, count = tracker._upload(chunk)
+            b = f.bufs
+            rows_t, mu_t, pts = b['boxes'][t], b['mu'][t], b['smooth' if plan.smooth else 'points']
+            status[t].copy_(b['flags'][t])
+            if plan.gate is not None:
+                TR.or_unsure(status[t], b['qflags'][t])
         else:
-            with torch.cuda.device(dev):
-                fsrc, foffs_d, fhw_d, _ = pack_u8(chunk, dev)
-            count = len(chunk)
-            det.stream.wait_stream(cur)
-            shared += [fsrc, foffs_d, fhw_d]
-        with torch.cuda.device(dev):
-            canvas = torch.empty_like(fsrc)
-            shared.append(canvas)
-            with torch.cuda.stream(det.stream):
-                canvas.copy_(fsrc)
-        for i in range(count):
-            t = c0 + i
-            with torch.cuda.device(dev), torch.cuda.stream(det.stream):
-                if track is None:
-                    tracker._advance(fsrc, foffs_d, fhw_d, i + 1 if i + 1 < count else 0)
-                    b = tracker._bufs                          # per-frame slots: nothing a later frame overwrites is read below
-                    rows_t, mu_t, pts = b['boxes'][t], b['mu'][t], b['smooth' if plan.smooth else 'points']
-                    status[t].copy_(b['flags'][t])
-                    if plan.gate is not None:
-                        status[t].bitwise_or_(b['qflags'][t].ne(0).to(torch.int32).mul_(FLAG_UNSURE))
-                else:
-                    rows_t, mu_t, pts = t_rows[t], t_mu[t], t_pts
-                G = min(st.trail, t) + 1
-                extra = {}
-                if hull:
-                    ops.hull_fit(mu_t, rows_t, grow_d, edges, hflags)
-                    extra['edges'] = edges
-                if points:
-                    extra.update(marks=pts[t + 1 - G:t + 1], group_style=gstyles[G - 1], mark_style=mstyle_d)
-                ops.annotate_u8(canvas, foffs_d, fhw_d, rows_t, links_d, palette_d, bits, st.thickness, st.pad, st.label_scale, max_pixels,
-                                status=status[t], labels=labels_d, **extra)
-        out += unpack_u8(canvas, chunk)
-    det._join(cur, *shared)
-    if track is None:
-        track = tracker.result()
-    return ClipAnnotation(out, track, status)
+            rows_t, mu_t, pts = t_rows[t], t_mu[t], t_pts
+        G = min(st.trail, t) + 1
+        extra = {}
+        if hull:
+            ops.hull_fit(mu_t, rows_t, grow_d, edges, hflags)
+            extra['edges'] = edges
+        if points:
+            extra.update(marks=pts[t + 1 - G:t + 1], group_style=gstyles[G - 1], mark_style=mstyle_d)
+        ops.annotate_u8(f.canvas, f.offs, f.hw, rows_t, links_d, palette_d, bits, st.thickness, st.pad, st.label_scale, max_pixels,
+                        status=status[t], labels=labels_d, **extra)
+
+    out = TR.run_frames(det, frames, plan.chunk_frames, held, frame, tracker, rows)
+    return ClipAnnotation(out, tracker.result() if track is None else track, status)

@@ -9,8 +9,8 @@ detector.track follows the faces of a clip and detector.morph blends a donor's f
 reenact.py joins the tracker to the generator.  Once per call the donors are packed and uploaded, their landmarks detected (unless
 given), their colour sums taken (imm_colour_stats_u8), the links of the paste formed (all F rows of a frame lie in one photo, so
 generation.compose_links of the first rows serves every frame) and the per-face settings uploaded.  Per chunk the tracker uploads
-the frames and the canvas is a device copy of them.  Per frame, on the detector's stream, without anything returning to the host
-between the clip's first and last launch:
+the frames and the canvas is a device copy of them: the frame loop is tracking.run_frames.  Per frame, on the detector's stream,
+without anything returning to the host between the clip's first and last launch:
 
     FaceTracker._advance             crop, pose program, imm_track_step, copy: the next frame's box rows stay on the device
     imm_clip_rows                    this frame's rows -> own[t] (the landmarks that are blended), inv_ramp[t], inv_soft[t]
@@ -36,6 +36,7 @@ import torch
 
 from . import morphing as MP
 from . import tracking as TR
+from .inference import _Plan
 
 GRID_AREAS = 4                 # the paste and stats grids are sized for this many times the first frame's largest box
 
@@ -51,13 +52,11 @@ def check_smooth(value, name):
     return a
 
 
-class ClipPlan(object):
+class ClipPlan(_Plan):
     """morph_clip()'s checked arguments: frames (decoded u8 arrays), rows int32 [F, 5], morph (the morphing.MorphPlan of the first
     frame's rows and the donors: every setting of the morph), smooth, colour_smooth, seam_smooth, box_smooth, one_euro, fps,
     chunk_frames, gate (a quality.QualityGate handed to the tracker, or None)."""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
+    FIELDS = ('frames', 'rows', 'morph', 'smooth', 'colour_smooth', 'seam_smooth', 'box_smooth', 'one_euro', 'fps', 'chunk_frames', 'gate')
 
 
 def plan_clip(frames, boxes, donors, donor_boxes=None, shape=0.0, texture=1.0, feather=0.125, K=10, anchors=2, lam=0.0,
@@ -101,92 +100,75 @@ def grid_pixels(rows):
 
 
 def run(det, plan):
-    """The launches of morph_clip() for a checked plan (see the module docstring); called with the caller's stream current."""
+    """The launches of morph_clip() for a checked plan (see the module docstring); called with the caller's stream current.  The frame
+    loop is tracking.run_frames; `frame` is what a frame adds behind the tracker's launches."""
     from . import ops
     from . import warping as WP
     from .generation import box_areas, compose_links
-    from .inference import pack_u8, pose_landmarks, unpack_u8
+    from .inference import _Held, pack_u8, pose_landmarks
     mp, frames, rows = plan.morph, plan.frames, plan.rows
     S, K, dev, M, m = det.S, det.K, det.dev, mp.M, mp.anchors
     F, T, B = len(rows), len(frames), mp.ring
     matched, hull, seam = bool(mp.colour.any()), mp.mask == 'hull', bool(mp.seamless.any())
     filter_gain, filter_diff = matched and plan.colour_smooth < 1.0, seam and plan.seam_smooth < 1.0
     max_pixels = grid_pixels(rows)
-    up = lambda a: ops.to_device_pinned(a, dev)
+    held = _Held(dev)                                          # what the loop's _join records: every tensor made below
+    up, empty = held.up, held.empty
     with torch.cuda.device(dev):
         # once per call, on the caller's stream: the donors, their landmarks, the links and the per-face settings
-        lm_b = pose_landmarks(det, ('photos', mp.donors, mp.donor_rows_given) if mp.donor_landmarks is None else
-                              ('landmarks', mp.donor_landmarks), F).contiguous()
-        don, doffs_d, dhw_d, dboxes_d = pack_u8(mp.donors, dev, mp.donor_rows)
+        lm_b = held.keep(pose_landmarks(det, ('photos', mp.donors, mp.donor_rows_given) if mp.donor_landmarks is None else
+                                        ('landmarks', mp.donor_landmarks), F).contiguous())
+        don, doffs_d, dhw_d, dboxes_d = held.keep(*pack_u8(mp.donors, dev, mp.donor_rows))
         links_d, shape_d, texture_d = up(compose_links(rows)), up(mp.shape), up(mp.texture)
         anchors_d = up(WP.warp_anchors(m).astype(np.float32)) if m else None
-        empty = lambda *shape, **kw: torch.empty(*shape, device=dev, **kw)
         own, fit_flags, inv_ramp = empty(T, F, K, 2), empty(T, F, dtype=torch.int32), empty(T, F, 2)
         poses2, mu2 = empty(2, F, K, 2), empty(2, F, K, 2)
         coef2, ctrl2, flags2 = empty(2, F, M + 3, 2), empty(2, F, M, 2), empty(2, F, dtype=torch.int32)
-        shared = [lm_b, don, doffs_d, dhw_d, dboxes_d, links_d, shape_d, texture_d, anchors_d, own, fit_flags, inv_ramp, poses2, mu2, coef2,
-                  ctrl2, flags2]
         gain = cflags = hflags = diff = sflags = inv_soft = feather_d = None
         if matched:
             colour_d, sums_a, sums_b = up(mp.colour), empty(F, 7, dtype=torch.int64), empty(F, 7, dtype=torch.int64)
             gain, cflags = empty(T, F, 3, 2), empty(T, F, dtype=torch.int32)
-            gain_state, gain_seen = empty(F, 6), torch.zeros(F, dtype=torch.int32, device=dev)
-            shared += [colour_d, sums_a, sums_b, gain, cflags, gain_state, gain_seen]
+            gain_state, gain_seen = empty(F, 6), held.zeros(F, dtype=torch.int32)
         if hull:
             grow_d, feather_d = up(mp.grow), up(mp.mask_feather)
             inv_soft, edges, hflags = empty(T, F), empty(F, K, 3), empty(T, F, dtype=torch.int32)
-            shared += [grow_d, feather_d, inv_soft, edges, hflags]
         if seam:
             seamless_d, dirs_d = up(mp.seamless), up(MP.seam_dirs(B))
             ring, diff, sflags = empty(F, B, 2), empty(T, F, B, 3), empty(T, F, dtype=torch.int32)
-            diff_state, diff_seen = empty(F, 3 * B), torch.zeros(F, dtype=torch.int32, device=dev)
-            shared += [seamless_d, dirs_d, ring, diff, sflags, diff_state, diff_seen]
-        cur = det._fork()
-        if matched:                                            # once per call: the donors' sums
+            diff_state, diff_seen = empty(F, 3 * B), held.zeros(F, dtype=torch.int32)
+        if matched:                                            # once per call, behind a fork of its own: the donors' sums
+            det._fork()
             with torch.cuda.stream(det.stream):
                 ops.colour_stats_u8(don, doffs_d, dhw_d, dboxes_d, int(box_areas(mp.donor_rows).max()), sums_b)
+
+    def frame(t, f):
+        b, fsrc, foffs_d, fhw_d = f.bufs, f.src, f.offs, f.hw
+        rows_t, lost_t = b['boxes'][t], b['flags'][t]
+        ops.clip_rows(rows_t, lost_t, b['mu'][t], b['smooth'][t] if plan.smooth else None, S, mp.feather, feather_d, own[t], inv_ramp[t],
+                      inv_soft[t] if hull else None)
+        extra = {}
+        if matched:
+            ops.colour_stats_u8(fsrc, foffs_d, fhw_d, rows_t, max_pixels, sums_a)
+            ops.colour_gain(sums_a, sums_b, colour_d, mp.max_gain, gain[t], cflags[t])
+            if filter_gain:
+                ops.clip_ema(gain[t].view(F, 6), gain_state, gain_seen, cflags[t], lost_t, plan.colour_smooth)
+            extra['gain'] = gain[t]
+        ops.morph_poses(own[t], lm_b, shape_d, poses2, mu2)
+        if hull:                                               # the blended landmarks, read in place
+            ops.hull_fit(poses2[0], rows_t, grow_d, edges, hflags[t])
+            extra['edges'], extra['inv_soft'] = edges, inv_soft[t]
+        ops.warp_fit(poses2.view(2 * F, K, 2), mu2.view(2 * F, K, 2), anchors_d, 1.0, mp.lam, coef2.view(2 * F, M + 3, 2),
+                     ctrl2.view(2 * F, M, 2), flags2.view(2 * F))
+        torch.bitwise_or(flags2[0], flags2[1], out=fit_flags[t])
+        if seam:
+            ops.seam_fit(poses2[0], rows_t, grow_d, edges, hflags[t], dirs_d, fsrc, foffs_d, fhw_d, don, doffs_d, dhw_d, dboxes_d,
+                         texture_d, ctrl2[0], coef2[0], coef2[1], gain[t] if matched else None, ring, diff[t], sflags[t])
+            if filter_diff:
+                ops.clip_ema(diff[t].view(F, 3 * B), diff_state, diff_seen, sflags[t], lost_t, plan.seam_smooth)
+            extra['ring'], extra['diff'], extra['seamless'] = ring, diff[t], seamless_d
+        ops.morph_paste(fsrc, f.canvas, foffs_d, fhw_d, don, doffs_d, dhw_d, rows_t, dboxes_d, links_d, inv_ramp[t], texture_d,
+                        ctrl2[0], coef2[0], coef2[1], max_pixels, **extra)
+
     tracker = TR.FaceTracker(det, None, plan.box_smooth, plan.one_euro, plan.fps, capacity=T, gate=plan.gate)
-    tracker._begin(rows)
-    tracker._cur = det._fork()
-    out = []
-    for c0 in range(0, T, plan.chunk_frames):
-        chunk = frames[c0:c0 + plan.chunk_frames]
-        fsrc, foffs_d, fhw_d, count = tracker._upload(chunk)
-        with torch.cuda.device(dev):
-            canvas = torch.empty_like(fsrc)
-            shared.append(canvas)
-            with torch.cuda.stream(det.stream):
-                canvas.copy_(fsrc)
-        for i in range(count):
-            t = c0 + i
-            with torch.cuda.device(dev), torch.cuda.stream(det.stream):
-                tracker._advance(fsrc, foffs_d, fhw_d, i + 1 if i + 1 < count else 0)
-                b = tracker._bufs                              # per-frame slots: nothing a later frame overwrites is read below
-                rows_t, lost_t = b['boxes'][t], b['flags'][t]
-                ops.clip_rows(rows_t, lost_t, b['mu'][t], b['smooth'][t] if plan.smooth else None, S, mp.feather, feather_d, own[t],
-                              inv_ramp[t], inv_soft[t] if hull else None)
-                extra = {}
-                if matched:
-                    ops.colour_stats_u8(fsrc, foffs_d, fhw_d, rows_t, max_pixels, sums_a)
-                    ops.colour_gain(sums_a, sums_b, colour_d, mp.max_gain, gain[t], cflags[t])
-                    if filter_gain:
-                        ops.clip_ema(gain[t].view(F, 6), gain_state, gain_seen, cflags[t], lost_t, plan.colour_smooth)
-                    extra['gain'] = gain[t]
-                ops.morph_poses(own[t], lm_b, shape_d, poses2, mu2)
-                if hull:                                       # the blended landmarks, read in place
-                    ops.hull_fit(poses2[0], rows_t, grow_d, edges, hflags[t])
-                    extra['edges'], extra['inv_soft'] = edges, inv_soft[t]
-                ops.warp_fit(poses2.view(2 * F, K, 2), mu2.view(2 * F, K, 2), anchors_d, 1.0, mp.lam, coef2.view(2 * F, M + 3, 2),
-                             ctrl2.view(2 * F, M, 2), flags2.view(2 * F))
-                torch.bitwise_or(flags2[0], flags2[1], out=fit_flags[t])
-                if seam:
-                    ops.seam_fit(poses2[0], rows_t, grow_d, edges, hflags[t], dirs_d, fsrc, foffs_d, fhw_d, don, doffs_d, dhw_d, dboxes_d,
-                                 texture_d, ctrl2[0], coef2[0], coef2[1], gain[t] if matched else None, ring, diff[t], sflags[t])
-                    if filter_diff:
-                        ops.clip_ema(diff[t].view(F, 3 * B), diff_state, diff_seen, sflags[t], lost_t, plan.seam_smooth)
-                    extra['ring'], extra['diff'], extra['seamless'] = ring, diff[t], seamless_d
-                ops.morph_paste(fsrc, canvas, foffs_d, fhw_d, don, doffs_d, dhw_d, rows_t, dboxes_d, links_d, inv_ramp[t], texture_d,
-                                ctrl2[0], coef2[0], coef2[1], max_pixels, **extra)
-        out += unpack_u8(canvas, chunk)
-    det._join(cur, *shared)
+    out = TR.run_frames(det, frames, plan.chunk_frames, held, frame, tracker, rows)
     return ClipMorph(out, tracker.result(), own, fit_flags, gain, cflags, hflags, diff, sflags)

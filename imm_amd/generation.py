@@ -31,8 +31,8 @@ from . import _lib as L
 from . import ops
 from .engine import n_renderer_out, render_sizes, renderer_spec, trainable_spec
 from .inference import (NEEDS_U8, BucketRunner, LandmarkDetector, _Launch, alloc_encoder_weights, as_image_batch, check_limits,
-                        decode_u8, fold_batch_norm, folded_encoder_program, pack_folded_encoder, pack_u8, photo_boxes, plan_buckets,
-                        pose_landmarks, read_variables, unalign_grid_pixels, unpack_u8)
+                        decode_u8, fold_batch_norm, folded_encoder_program, pack_folded_encoder, pack_u8, photo_boxes, photos_and_rows,
+                        plan_buckets, pose_landmarks, read_variables, unalign_grid_pixels, unpack_u8)
 from .keypoints import check_boxes
 from .tracking import OneEuro
 
@@ -106,10 +106,7 @@ def plan_repose(photos, poses, boxes, pose_boxes, feather, K):
     """repose()'s arguments checked on the host, before anything reaches the device: (photos as decoded u8 arrays, box rows int32
     [n, 5], poses, feather).  poses comes back as ('landmarks', f32 tensor [n or 1, K, 2]) or ('photos', decoded u8 arrays, pose_boxes)."""
     feather = check_feather(feather)
-    if not isinstance(photos, (list, tuple)):
-        raise ValueError(NEEDS_U8)
-    photos = decode_u8(photos)
-    rows = check_boxes([(0, 0, a.shape[0], a.shape[1]) for a in photos] if boxes is None else boxes, len(photos))
+    photos, rows = photos_and_rows(photos, boxes)
     n = len(rows)
     if isinstance(poses, (list, tuple)) and len(poses) and not np.isscalar(poses[0]) and np.asarray(poses[0]).dtype == np.uint8:
         pose_photos = decode_u8(poses)

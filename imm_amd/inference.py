@@ -337,6 +337,33 @@ def photo_boxes(images, boxes, S):
     return images, True, check_boxes([(0, 0, a.shape[0], a.shape[1]) for a in images] if boxes is None else boxes, len(images))
 
 
+def photos_and_rows(photos, boxes, needs=NEEDS_U8, empty=None, not_u8=TypeError, limit=None):
+    """What every plan_* does with a list of u8 photos and optional boxes: (photos decoded (decode_u8), box rows int32 [n, 5]
+    (keypoints.check_boxes; one whole-photo box per photo without boxes)).  The refusals are worded by the caller: needs, the ValueError
+    for photos that are no list; empty, the ValueError for an empty list (None: the list goes on to check_boxes); not_u8, the type
+    decode_u8's TypeError is raised as; limit = (rows, text with one %d for the count): the ValueError for more rows than that."""
+    if not isinstance(photos, (list, tuple)):
+        raise ValueError(needs)
+    if empty is not None and not len(photos):
+        raise ValueError(empty)
+    try:
+        photos = decode_u8(photos)
+    except TypeError as e:
+        raise not_u8(str(e))
+    rows = check_boxes([(0, 0, a.shape[0], a.shape[1]) for a in photos] if boxes is None else boxes, len(photos))
+    if limit is not None and len(rows) > limit[0]:
+        raise ValueError(limit[1] % len(rows))
+    return photos, rows
+
+
+def check_landmarks(landmarks, counts, K, name='landmarks'):
+    """landmarks given by a caller: an f32 tensor [n, K, 2] with n one of counts, where it lies; values are not looked at."""
+    t = torch.as_tensor(landmarks)
+    if t.dim() != 3 or tuple(t.shape[1:]) != (int(K), 2) or t.shape[0] not in counts:
+        raise ValueError('%s must be [%s, %d, 2], got %s' % (name, ' or '.join(str(c) for c in counts), int(K), tuple(t.shape)))
+    return t.float()
+
+
 def photo_rows(images, boxes, S):
     """photo_boxes and the rows' geometry f32 [n, 4] (keypoints.box_geometry; (0, 0, 1, 1) per image of a tensor batch):
     (images, u8, rows, geom)."""
@@ -357,9 +384,9 @@ def pose_landmarks(detector, pose, n, from_photos=None):
 
 
 class _Held(list):
-    """The device tensors a call allocates on the caller's stream and uses on the object's: the record list of BucketRunner._forked,
-    complete because every such tensor is made through it.  keep(tensors...) takes tensors made elsewhere (pack_u8's, a PasteSetup's; None
-    is skipped), up(array) uploads one (ops.to_device_pinned), empty(*shape) allocates one; each returns what it holds."""
+    """The device tensors a call allocates on the caller's stream and uses on the object's: the record list of BucketRunner._forked
+    and of tracking.run_frames, complete because every such tensor is made through it.  keep(tensors...) takes tensors made elsewhere (pack_u8's, a PasteSetup's; None
+    is skipped), up(array) uploads one (ops.to_device_pinned), empty(*shape) and zeros(*shape) allocate one; each returns what it holds."""
 
     def __init__(self, device):
         super(_Held, self).__init__()
@@ -374,6 +401,19 @@ class _Held(list):
 
     def empty(self, *shape, **kw):
         return self.keep(torch.empty(*shape, device=self.device, **kw))
+
+    def zeros(self, *shape, **kw):
+        return self.keep(torch.zeros(*shape, device=self.device, **kw))
+
+
+class _Plan(object):
+    """The checked arguments of a call, by name: a plan_* function's result.  A subclass names its FIELDS; a field that is missing
+    or misspelt fails here, where the plan is made."""
+    FIELDS = ()
+
+    def __init__(self, **fields):
+        assert set(fields) == set(self.FIELDS), sorted(set(fields) ^ set(self.FIELDS))
+        self.__dict__.update(fields)
 
 
 class _Launch(object):
@@ -1213,14 +1253,9 @@ class LandmarkDetector(BucketRunner):
         imm_colour_stats_u8 launch on the caller's stream, the kernel morph(colour > 0) runs; the sums come back as integers and the
         moments are formed on the host in imm_colour_gain's order."""
         from . import morphing as MP
-        from .generation import NEEDS_U8, box_areas
-        from .keypoints import check_boxes
-        if not isinstance(photos, (list, tuple)) or not len(photos):
-            raise ValueError('photos: %s' % NEEDS_U8)
-        photos = decode_u8(photos)
-        rows = check_boxes([(0, 0, a.shape[0], a.shape[1]) for a in photos] if boxes is None else boxes, len(photos))
-        if len(rows) > 65535:
-            raise ValueError('colour_stats serves at most 65535 rows a call, got %d' % len(rows))
+        from .generation import box_areas
+        needs = 'photos: %s' % NEEDS_U8
+        photos, rows = photos_and_rows(photos, boxes, needs, needs, limit=(65535, 'colour_stats serves at most 65535 rows a call, got %d'))
         with torch.cuda.device(self.dev):
             src, offs_d, hw_d, boxes_d = pack_u8(photos, self.dev, rows)
             sums = torch.empty(len(rows), 7, dtype=torch.int64, device=self.dev)

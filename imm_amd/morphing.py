@@ -27,6 +27,7 @@ Here: the pose blend in the kernel's f32 order, the argument checks of morph() a
 Nothing here needs a GPU."""
 import numpy as np
 
+from .inference import _Plan
 from .warping import _host, check_spline, displacement
 
 MAX_ROWS = 32767               # rows of one morph() call: imm_warp_fit takes 2 n <= 65535 rows
@@ -71,10 +72,8 @@ def _given_landmarks(lm, counts, K, name):
     """landmarks= / donor_landmarks=: f32 [n, K, 2] (or one of the other counts allowed) as a tensor; a host tensor must be finite (a device
     tensor is not read back: its rows are judged by the fit)."""
     import torch
-    t = torch.as_tensor(lm)
-    if t.dim() != 3 or tuple(t.shape[1:]) != (K, 2) or t.shape[0] not in counts:
-        raise ValueError('%s must be [%s, %d, 2], got %s' % (name, ' or '.join(str(c) for c in counts), K, tuple(t.shape)))
-    t = t.float()
+    from .inference import check_landmarks
+    t = check_landmarks(lm, counts, K, name)
     if not t.is_cuda and not bool(torch.isfinite(t).all()):
         raise ValueError('%s must be finite' % name)
     return t
@@ -155,7 +154,7 @@ def seam_field(ring, diff, H, W):
     return out
 
 
-class MorphPlan(object):
+class MorphPlan(_Plan):
     """What plan_morph returns, by name: photos and donors (decoded u8 arrays), rows and donor_rows int32 [n, 5] (ONE donor row is repeated
     for every face), donor_rows_given (the donor rows as given: what detector.landmarks(donors, .) is asked for), shape and texture f32
     [n], feather, anchors (per side), lam, M (control points), landmarks and donor_landmarks (None or f32 tensors), colour f32 [n] and
@@ -163,10 +162,6 @@ class MorphPlan(object):
     the membrane's: seamless f32 [n] and ring (an int)."""
     FIELDS = ('photos', 'rows', 'donors', 'donor_rows', 'donor_rows_given', 'shape', 'texture', 'feather', 'anchors', 'lam', 'M', 'landmarks',
               'donor_landmarks', 'colour', 'max_gain', 'mask', 'grow', 'mask_feather', 'inv_soft', 'seamless', 'ring')
-
-    def __init__(self, **fields):
-        assert set(fields) == set(self.FIELDS)
-        self.__dict__.update(fields)
 
 
 def plan_morph(photos, donors, boxes, donor_boxes, shape, texture, feather, K, anchors=2, lam=0.0, landmarks=None, donor_landmarks=None,
@@ -186,19 +181,14 @@ def plan_morph(photos, donors, boxes, donor_boxes, shape, texture, feather, K, a
     from .generation import NEEDS_U8, check_feather
     if mask not in MASKS:
         raise ValueError("mask must be None or 'hull', got %r" % (mask,))
-    from .inference import decode_u8
-    from .keypoints import check_boxes
+    from .inference import photos_and_rows
     m, lam, _strength, M = check_spline(anchors, lam, 1.0, K)
     feather = check_feather(feather)
-    for name, ims in (('photos', photos), ('donors', donors)):
-        if not isinstance(ims, (list, tuple)) or not len(ims):
-            raise ValueError('%s: %s' % (name, NEEDS_U8))
-    photos, donors = decode_u8(photos), decode_u8(donors)
-    rows = check_boxes([(0, 0, a.shape[0], a.shape[1]) for a in photos] if boxes is None else boxes, len(photos))
-    drows = check_boxes([(0, 0, a.shape[0], a.shape[1]) for a in donors] if donor_boxes is None else donor_boxes, len(donors))
+    needs, needs_donors = 'photos: %s' % NEEDS_U8, 'donors: %s' % NEEDS_U8
+    photos, rows = photos_and_rows(photos, boxes, needs, needs, limit=(
+        MAX_ROWS, 'a morph serves at most %d rows a call (one fit over twice as many), got %%d' % MAX_ROWS))
+    donors, drows = photos_and_rows(donors, donor_boxes, needs_donors, needs_donors)
     n, n_d = len(rows), len(drows)
-    if n > MAX_ROWS:
-        raise ValueError('a morph serves at most %d rows a call (one fit over twice as many), got %d' % (MAX_ROWS, n))
     if n_d not in (n, 1):
         raise ValueError('%d donors for %d faces: give one per face, or one for all' % (n_d, n))
     shape = _share(shape, n, 'shape')

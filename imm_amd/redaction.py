@@ -26,11 +26,12 @@ PhotoRedaction and ClipRedaction (the results) and run_clip (the launches of red
 import numpy as np
 
 from . import morphing as MP
+from .inference import _Plan
+from .tracking import FLAG_UNSURE              # noqa: F401  ClipRedaction.hull_flags: bit 2, the gate found the face unsure on that frame
 from .warping import _host
 
 MODES = {'pixelate': 0, 'smooth': 1}      # IMM_REDACT_PIXELATE, IMM_REDACT_SMOOTH
 MAX_BLOCKS = 64                           # cells along the longer side of a box
-FLAG_UNSURE = 4                           # ClipRedaction.hull_flags: bit 2, the quality gate found the face unsure on that frame
 
 
 def cell_size(H, W, blocks):
@@ -61,15 +62,11 @@ def check_blocks(blocks):
     return int(blocks)
 
 
-class RedactPlan(object):
+class RedactPlan(_Plan):
     """What plan_redact returns, by name: photos (decoded u8 arrays), rows int32 [n, 5], mode ('pixelate' or 'smooth'), blocks, feather,
     mask (None or 'hull'), grow f32 [n], mask_feather f32 [n], inv_soft f32 [n] (morphing.hull_inv_soft of the rows) and landmarks (None
     or an f32 tensor [n, K, 2]; it may hold values that are not finite: such a row is redacted whole)."""
     FIELDS = ('photos', 'rows', 'mode', 'blocks', 'feather', 'mask', 'grow', 'mask_feather', 'inv_soft', 'landmarks')
-
-    def __init__(self, **fields):
-        assert set(fields) == set(self.FIELDS)
-        self.__dict__.update(fields)
 
 
 def plan_redact(photos, boxes, K, mode='pixelate', blocks=8, mask=None, grow=1.25, mask_feather=0.1, feather=0.0, landmarks=None):
@@ -78,27 +75,18 @@ def plan_redact(photos, boxes, K, mode='pixelate', blocks=8, mask=None, grow=1.2
     'smooth'; blocks: an int in [1, 64]; feather in [0, 0.5]; mask: None or 'hull'; grow and mask_feather as morph takes them (checked
     whatever mask is).  landmarks: None or [n, K, 2]; values that are not finite are NOT refused: redaction fails closed, and such a
     row is redacted over its whole box."""
-    import torch
     from .generation import NEEDS_U8, check_feather
-    from .inference import decode_u8
-    from .keypoints import check_boxes
+    from .inference import check_landmarks, photos_and_rows
     mode, blocks = check_mode(mode), check_blocks(blocks)
     if mask not in MP.MASKS:
         raise ValueError("mask must be None or 'hull', got %r" % (mask,))
     feather = check_feather(feather)
-    if not isinstance(photos, (list, tuple)) or not len(photos):
-        raise ValueError('photos: %s' % NEEDS_U8)
-    photos = decode_u8(photos)
-    rows = check_boxes([(0, 0, a.shape[0], a.shape[1]) for a in photos] if boxes is None else boxes, len(photos))
+    needs = 'photos: %s' % NEEDS_U8
+    photos, rows = photos_and_rows(photos, boxes, needs, needs, limit=(65535, 'a redaction serves at most 65535 rows a call, got %d'))
     n = len(rows)
-    if n > 65535:
-        raise ValueError('a redaction serves at most 65535 rows a call, got %d' % n)
     grow, mask_feather = MP.check_grow(grow, n), MP.check_mask_feather(mask_feather, n)
     if landmarks is not None:
-        landmarks = torch.as_tensor(landmarks)
-        if landmarks.dim() != 3 or tuple(landmarks.shape) != (n, int(K), 2):
-            raise ValueError('landmarks must be [%d, %d, 2], got %s' % (n, int(K), tuple(landmarks.shape)))
-        landmarks = landmarks.float()
+        landmarks = check_landmarks(landmarks, (n,), K)
     return RedactPlan(photos=photos, rows=rows, mode=mode, blocks=blocks, feather=feather, mask=mask, grow=grow, mask_feather=mask_feather,
                       inv_soft=MP.hull_inv_soft(rows, mask_feather), landmarks=landmarks)
 
@@ -165,12 +153,10 @@ class ClipRedaction(object):
         return int(self.own.shape[0])
 
 
-class ClipRedactPlan(object):
+class ClipRedactPlan(_Plan):
     """redact_clip()'s checked arguments: frames (decoded u8 arrays), rows int32 [F, 5], redact (the RedactPlan of the first frame's rows:
     every setting of the redaction), smooth, box_smooth, one_euro, fps, chunk_frames, gate."""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
+    FIELDS = ('frames', 'rows', 'redact', 'smooth', 'box_smooth', 'one_euro', 'fps', 'chunk_frames', 'gate')
 
 
 def plan_redact_clip(frames, boxes, K, mode='pixelate', blocks=8, mask=None, grow=1.25, mask_feather=0.1, feather=0.0, smooth=True,
@@ -186,64 +172,48 @@ def plan_redact_clip(frames, boxes, K, mode='pixelate', blocks=8, mask=None, gro
 
 
 def run_clip(det, plan):
-    """The launches of redact_clip() for a checked plan; called with the caller's stream current.  The frame loop of clip.run: per chunk
-    one upload and one canvas copy; per frame, on the detector's stream, FaceTracker._advance, imm_clip_rows, with the mask
-    imm_hull_fit on own[t], imm_redact_cells_u8 from the frame's ORIGINAL pixels and imm_redact_u8 into the canvas, with the frame's
-    rows as they lie in the tracker's buffer.  Nothing returns to the host between the first and the last frame's launches."""
+    """The launches of redact_clip() for a checked plan; called with the caller's stream current.  The frame loop is
+    tracking.run_frames: per chunk one upload and one canvas copy; per frame, on the detector's stream, FaceTracker._advance,
+    imm_clip_rows, with the mask imm_hull_fit on own[t], imm_redact_cells_u8 from the frame's ORIGINAL pixels and imm_redact_u8 into the
+    canvas, with the frame's rows as they lie in the tracker's buffer.  Nothing returns to the host between the first and the last
+    frame's launches."""
     import torch
     from . import ops
     from . import tracking as TR
     from .clip import grid_pixels
     from .generation import compose_links
-    from .inference import unpack_u8
+    from .inference import _Held
     rp, frames, rows = plan.redact, plan.frames, plan.rows
     S, K, dev = det.S, det.K, det.dev
     F, T, hull, mode = len(rows), len(frames), rp.mask == 'hull', MODES[rp.mode]
     max_pixels = grid_pixels(rows)
-    up = lambda a: ops.to_device_pinned(a, dev)
+    held = _Held(dev)                                          # what the loop's _join records: every tensor made below
+    up, empty = held.up, held.empty
     with torch.cuda.device(dev):
-        empty = lambda *shape, **kw: torch.empty(*shape, device=dev, **kw)
         links_d = up(compose_links(rows))          # all F rows of a frame lie in one photo: these links serve every frame
         own, inv_ramp = empty(T, F, K, 2), empty(T, F, 2)
         cells = empty(F, rp.blocks * rp.blocks * 3, dtype=torch.uint8)
-        shared = [links_d, own, inv_ramp, cells]
         grow_d = feather_d = inv_soft = edges = hflags = None
         if hull:
             grow_d, feather_d = up(rp.grow), up(rp.mask_feather)
             inv_soft, edges, hflags = empty(T, F), empty(F, K, 3), empty(T, F, dtype=torch.int32)
-            shared += [grow_d, feather_d, inv_soft, edges, hflags]
+
+    def frame(t, f):
+        b = f.bufs
+        rows_t = b['boxes'][t]
+        ops.clip_rows(rows_t, b['flags'][t], b['mu'][t], b['smooth'][t] if plan.smooth else None, S, rp.feather, feather_d, own[t],
+                      inv_ramp[t], inv_soft[t] if hull else None)
+        extra = {}
+        if hull:                                               # a lost face has NaN landmarks: flagged, and redacted whole
+            ops.hull_fit(own[t], rows_t, grow_d, edges, hflags[t])
+            if plan.gate is not None:
+                # the gate's verdict goes into the flag the paste reads: the tracker scores the first frame without losing
+                # its faces (the caller vouches for the first boxes), and a face that is unsure there has finite landmarks
+                TR.or_unsure(hflags[t], b['qflags'][t])
+            extra = dict(edges=edges, inv_soft=inv_soft[t], hull_flags=hflags[t])
+        ops.redact_cells_u8(f.src, f.offs, f.hw, rows_t, rp.blocks, cells)
+        ops.redact_u8(f.canvas, f.offs, f.hw, rows_t, links_d, inv_ramp[t], cells, rp.blocks, mode, max_pixels, **extra)
+
     tracker = TR.FaceTracker(det, None, plan.box_smooth, plan.one_euro, plan.fps, capacity=T, gate=plan.gate)
-    tracker._begin(rows)
-    # ONE fork, here, after the uploads above and after _begin (which forks and captures on its own): clip.run forks a second time in
-    # front of its donor work, which this loop does not have; the tracker records its grown buffers against the same stream
-    cur = tracker._cur = det._fork()
-    out = []
-    for c0 in range(0, T, plan.chunk_frames):
-        chunk = frames[c0:c0 + plan.chunk_frames]
-        fsrc, foffs_d, fhw_d, count = tracker._upload(chunk)
-        with torch.cuda.device(dev):
-            canvas = torch.empty_like(fsrc)
-            shared.append(canvas)
-            with torch.cuda.stream(det.stream):
-                canvas.copy_(fsrc)
-        for i in range(count):
-            t = c0 + i
-            with torch.cuda.device(dev), torch.cuda.stream(det.stream):
-                tracker._advance(fsrc, foffs_d, fhw_d, i + 1 if i + 1 < count else 0)
-                b = tracker._bufs                              # per-frame slots: nothing a later frame overwrites is read below
-                rows_t = b['boxes'][t]
-                ops.clip_rows(rows_t, b['flags'][t], b['mu'][t], b['smooth'][t] if plan.smooth else None, S, rp.feather, feather_d, own[t],
-                              inv_ramp[t], inv_soft[t] if hull else None)
-                extra = {}
-                if hull:                                       # a lost face has NaN landmarks: flagged, and redacted whole
-                    ops.hull_fit(own[t], rows_t, grow_d, edges, hflags[t])
-                    if plan.gate is not None:
-                        # the gate's verdict goes into the flag the paste reads: the tracker scores the first frame without losing
-                        # its faces (the caller vouches for the first boxes), and a face that is unsure there has finite landmarks
-                        hflags[t].bitwise_or_(b['qflags'][t].ne(0).to(torch.int32).mul_(FLAG_UNSURE))
-                    extra = dict(edges=edges, inv_soft=inv_soft[t], hull_flags=hflags[t])
-                ops.redact_cells_u8(fsrc, foffs_d, fhw_d, rows_t, rp.blocks, cells)
-                ops.redact_u8(canvas, foffs_d, fhw_d, rows_t, links_d, inv_ramp[t], cells, rp.blocks, mode, max_pixels, **extra)
-        out += unpack_u8(canvas, chunk)
-    det._join(cur, *shared)
+    out = TR.run_frames(det, frames, plan.chunk_frames, held, frame, tracker, rows)
     return ClipRedaction(out, tracker.result(), own, hflags)

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import tracking as TR
+from .inference import _Plan
 
 MOTIONS = ('relative', 'absolute')
 FLAG_HELD = 1
@@ -59,11 +60,10 @@ def check_driver_box(driver_box):
     return TR.check_first_boxes(box, 'frames[0]')
 
 
-class ReenactPlan(object):
+class ReenactPlan(_Plan):
     """reenact()'s checked arguments."""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
+    FIELDS = ('photos', 'rows', 'frames', 'driver_row', 'relative', 'rigid', 'gain', 'smooth', 'feather', 'paste', 'box_smooth', 'one_euro',
+              'fps', 'chunk_frames')
 
 
 def plan_reenact(photos, frames, driver_box, boxes=None, max_batch=128, motion='relative', rigid=True, gain=1.0, smooth=True,
@@ -71,8 +71,7 @@ def plan_reenact(photos, frames, driver_box, boxes=None, max_batch=128, motion='
     """reenact()'s arguments checked on the host, before anything reaches the device: a ReenactPlan of the photos as decoded u8 arrays,
     their box rows int32 [n, 5], the frames as decoded u8 arrays, the driver's row int32 [1, 5], and the checked settings."""
     from .generation import NEEDS_U8, check_feather
-    from .inference import decode_u8
-    from .keypoints import check_boxes
+    from .inference import photos_and_rows
     if template is not None:
         raise NotImplementedError('reenact with a template (re-enactment in the aligned frame) is not implemented: the faces are '
                                   'rendered in their raw box crops')
@@ -80,15 +79,7 @@ def plan_reenact(photos, frames, driver_box, boxes=None, max_batch=128, motion='
         raise NotImplementedError('reenact carries the driver\'s motion over with a similarity; model=%r (the tps and affine models) '
                                   'is not implemented' % (model,))
     motion, gain, feather = check_motion(motion), check_gain(gain), check_feather(feather)
-    if not isinstance(photos, (list, tuple)):
-        raise ValueError(NEEDS_U8)
-    if len(photos) == 0:
-        raise ValueError('no photos')
-    try:
-        photos = decode_u8(photos)
-    except TypeError as e:
-        raise ValueError(str(e))
-    rows = check_boxes([(0, 0, a.shape[0], a.shape[1]) for a in photos] if boxes is None else boxes, len(photos))
+    photos, rows = photos_and_rows(photos, boxes, NEEDS_U8, 'no photos', not_u8=ValueError)
     if len(rows) > int(max_batch):
         raise ValueError('%d faces, the generator\'s max_batch is %d' % (len(rows), int(max_batch)))
     drow = check_driver_box(driver_box)
@@ -126,30 +117,29 @@ def check_render_keeps_features(gen, bucket):
 
 
 def run(gen, plan, return_faces=False):
-    """The launches of reenact() for a checked plan (see the module docstring); called with the caller's stream current."""
+    """The launches of reenact() for a checked plan (see the module docstring); called with the caller's stream current.  The frame
+    loop is tracking.run_frames, without a canvas; `frame` is the retargeting behind the tracker's launches and the generator's half."""
     from . import ops
     from .generation import PasteSetup
-    from .inference import pack_u8, plan_buckets, unpack_u8
+    from .inference import _Held, pack_u8, plan_buckets, unpack_u8
     det, S, K, dev = gen.detector, gen.S, gen.K, gen.dev
     photos, rows, frames = plan.photos, plan.rows, plan.frames
     n, T = len(rows), len(frames)
     buckets = plan_buckets(n, gen.max_batch)                   # one: n <= max_batch
     bucket = buckets[0][2]
+    held = _Held(dev)                                          # what both _joins record: every tensor made below
     with torch.cuda.device(dev):
         if plan.paste:
             ps = PasteSetup(photos, rows, buckets, plan.feather, dev, clone=False)      # all photos, once per call
+            held.keep(*ps.tensors())
             packed, max_pixels = ps.packed(slice(None)), ps.max_pixels(slice(None))
-            canvas = torch.empty(T, ps.src.numel(), dtype=torch.uint8, device=dev)
-            shared = [ps.links_d, ps.ramp_d, canvas]
+            canvas = held.empty(T, ps.src.numel(), dtype=torch.uint8)
         else:
-            packed, shared = pack_u8(photos, dev, rows), []
+            packed = held.keep(*pack_u8(photos, dev, rows))
         src, offs_d, hw_d, boxes_d = packed
-        m = torch.empty(n, K, 2, device=dev)
-        lm = torch.empty(T, n, K, 2, device=dev)
-        flags = torch.empty(T, n, dtype=torch.int32, device=dev)
-        anchor = torch.zeros(K, 2, dtype=torch.float64, device=dev)
-        faces = torch.empty(T, n, S, S, 3, device=dev) if return_faces else None
-        shared += list(packed) + [m, lm, flags, anchor, faces]
+        m, lm, flags = held.empty(n, K, 2), held.empty(T, n, K, 2), held.empty(T, n, dtype=torch.int32)
+        anchor = held.zeros(K, 2, dtype=torch.float64)
+        faces = held.empty(T, n, S, S, 3) if return_faces else None
         # once per call, on the detector's stream: the faces' own landmarks (detector.landmarks(photos, boxes), from the packed photos)
         cur = det._fork()
         with torch.cuda.stream(det.stream):
@@ -165,30 +155,25 @@ def run(gen, plan, return_faces=False):
             gen._mu[:bucket].zero_()
             gen._capture('render', bucket)                     # capture (and its synchronisation) ahead of the first frame
             gen._run('appearance', bucket)
-    tracker = TR.FaceTracker(det, None, plan.box_smooth, plan.one_euro, plan.fps, capacity=T)
-    tracker._begin(plan.driver_row)
-    tracker._cur = det._fork()
     which = 'smooth' if plan.smooth else 'points'
-    for c0 in range(0, T, plan.chunk_frames):
-        fsrc, foffs_d, fhw_d, count = tracker._upload(frames[c0:c0 + plan.chunk_frames])
-        for i in range(count):
-            t = c0 + i
-            with torch.cuda.device(dev), torch.cuda.stream(det.stream):
-                tracker._advance(fsrc, foffs_d, fhw_d, i + 1 if i + 1 < count else 0)
-                b = tracker._bufs                              # per-frame slots: nothing a later frame overwrites is read below
-                ops.retarget(b[which][t, 0], anchor, b['flags'][t], m, lm[t - 1] if t else m, int(t == 0), plan.relative, plan.rigid,
-                             plan.gain, lm[t], flags[t])
-            gen.stream.wait_stream(det.stream)
-            with torch.cuda.device(dev), torch.cuda.stream(gen.stream):
-                gen._mu[:n].copy_(lm[t])
-                gen._run('render', bucket)
-                if plan.paste:
-                    canvas[t].copy_(src)
-                    ops.compose_u8(canvas[t], offs_d, hw_d, boxes_d, ps.links_d, ps.ramp_d, gen._pred[:n], max_pixels)
-                if return_faces:
-                    faces[t].copy_(gen._pred[:n, ..., :3])
-    det._join(cur, *shared)
-    gen._join(cur, *shared)
+
+    def frame(t, f):
+        b = f.bufs
+        ops.retarget(b[which][t, 0], anchor, b['flags'][t], m, lm[t - 1] if t else m, int(t == 0), plan.relative, plan.rigid,
+                     plan.gain, lm[t], flags[t])
+        gen.stream.wait_stream(det.stream)
+        with torch.cuda.stream(gen.stream):
+            gen._mu[:n].copy_(lm[t])
+            gen._run('render', bucket)
+            if plan.paste:
+                canvas[t].copy_(src)
+                ops.compose_u8(canvas[t], offs_d, hw_d, boxes_d, ps.links_d, ps.ramp_d, gen._pred[:n], max_pixels)
+            if return_faces:
+                faces[t].copy_(gen._pred[:n, ..., :3])
+
+    tracker = TR.FaceTracker(det, None, plan.box_smooth, plan.one_euro, plan.fps, capacity=T)
+    TR.run_frames(det, frames, plan.chunk_frames, held, frame, tracker, plan.driver_row, canvas=False)
+    gen._join(cur, *held)
     out = None
     if plan.paste:
         out = [unpack_u8(canvas[t], photos) for t in range(T)]

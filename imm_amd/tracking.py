@@ -19,7 +19,8 @@ NaN landmarks for a face that fails the gate's thresholds.  The lost rule of imm
 filter pairs, its points are NaN and FLAG_LOST is set.  Without a gate the launches, arguments and buffers are those of before.
 
 This module holds the host side: OneEuro (the filter's constants), plan_track (every argument checked before anything reaches the
-device), the state layout, Track (the result) and FaceTracker (the launches).  It imports without a GPU."""
+device), the state layout, Track (the result), FaceTracker (the launches of a frame) and run_frames, the one frame loop under track and
+under every clip operation built on the tracker (morph_clip, redact_clip, annotate_clip, reenact).  It imports without a GPU."""
 import math
 
 import numpy as np
@@ -29,6 +30,12 @@ from . import keypoints as KP
 
 STATE_HEAD = 5                # h0, w0, cy, cx, s in front of z0, xhat, dxhat (include/imm_track.h)
 FLAG_LOST, FLAG_OUTSIDE = 1, 2
+FLAG_UNSURE = 4               # not the tracker's: the bit under which a clip operation ORs the gate's verdict into its flags (or_unsure)
+
+
+def or_unsure(flags, qflags):
+    """flags |= FLAG_UNSURE where the gate's verdict qflags is not 0, in place on the device (int32, one value per face)."""
+    return flags.bitwise_or_(qflags.ne(0).to(torch.int32).mul_(FLAG_UNSURE))
 
 
 def state_size(K):
@@ -309,13 +316,9 @@ class FaceTracker(object):
         return self.run(frames, rows, chunk)
 
     def run(self, frames, rows, chunk_frames):
-        """track(): every frame of a checked clip, uploaded chunk_frames at a time; the caller's stream waits once, at the end."""
-        self._begin(rows)
-        with self.det._forked() as self._cur:
-            for c0 in range(0, len(frames), chunk_frames):
-                src, offs_d, hw_d, count = self._upload(frames[c0:c0 + chunk_frames])
-                for i in range(count):
-                    self._advance(src, offs_d, hw_d, i + 1 if i + 1 < count else 0)
+        """track(): every frame of a checked clip, uploaded chunk_frames at a time (run_frames, with no body and no canvas); the caller's
+        stream waits once, at the end."""
+        run_frames(self.det, frames, chunk_frames, (), None, self, rows, canvas=False)
         return self.result()
 
     def result(self):
@@ -326,3 +329,59 @@ class FaceTracker(object):
         extra = {} if self.gate is None else dict(spread=b['spread'][:t], score=b['score'][:t], qflags=b['qflags'][:t])
         return Track(b['mu'][:t], b['points'][:t], b['smooth'][:t], b['boxes'][:t, :, 1:], b['flags'][:t],
                      b['kp'][:t] if self.reg is not None else None, **extra)
+
+
+class Frame(object):
+    """What run_frames hands a body: the chunk's packed frames (src, offs, hw: pack_u8's), the chunk's canvas (None without one), the
+    frame's index i within its chunk and bufs, the tracker's buffers as this frame's _advance left them (None without a tracker)."""
+    __slots__ = ('src', 'offs', 'hw', 'canvas', 'i', 'bufs')
+
+
+def run_frames(det, frames, chunk_frames, held, body, tracker=None, rows=None, canvas=True):
+    """THE frame loop of track and of every clip operation (morph_clip, redact_clip, annotate_clip, reenact); called with the caller's
+    stream current, behind the operation's once-per-call work.  Per chunk of chunk_frames frames one upload and, with canvas=True, one
+    canvas: a device copy of the chunk, made on the detector's stream.  Per frame, with the detector's device and stream current,
+    tracker._advance and then body(t, f): t the frame's index in the clip, f a Frame.  next_image of _advance is the place of the NEXT
+    frame in the upload it will be read from (0 behind a chunk's last frame): the box row a frame leaves for its successor names it.
+    _grow may replace the tracker's buffers in _advance, so f.bufs is taken behind it and a body takes its per-frame slot views
+    (f.bufs['boxes'][t], ...) itself; nothing a later frame overwrites may be read through them.
+    tracker: a fresh FaceTracker, begun here with `rows`.  ONE fork stands here, behind _begin (which forks, and may capture, on its
+    own); the tracker records its grown buffers against the same stream.  An operation with once-per-call work on the detector's stream
+    (clip.run's donor sums, reenact.run's own landmarks) forks a second time, in front of that work.  Without a tracker
+    (annotate_clip(track=)) the chunks are packed on the caller's stream and the detector's stream waits for it once per chunk.
+    held: the inference._Held of every tensor the operation made on the caller's stream; the chunks' tensors join it and the final
+    _join records it.  Returns the frames of the canvases (unpack_u8: one view per frame), None with canvas=False."""
+    from .inference import pack_u8, unpack_u8
+    dev = det.dev
+    if tracker is not None:
+        tracker._begin(rows)
+    cur = det._fork()
+    if tracker is not None:
+        tracker._cur = cur
+    out, f = [] if canvas else None, Frame()
+    f.canvas = f.bufs = None
+    for c0 in range(0, len(frames), chunk_frames):
+        chunk = frames[c0:c0 + chunk_frames]
+        if tracker is not None:
+            f.src, f.offs, f.hw, _ = tracker._upload(chunk)
+        else:
+            with torch.cuda.device(dev):
+                f.src, f.offs, f.hw, _ = held.keep(*pack_u8(chunk, dev))
+            det.stream.wait_stream(cur)
+        if canvas:
+            with torch.cuda.device(dev):
+                f.canvas = held.keep(torch.empty_like(f.src))
+                with torch.cuda.stream(det.stream):
+                    f.canvas.copy_(f.src)
+        for i in range(len(chunk)):
+            with torch.cuda.device(dev), torch.cuda.stream(det.stream):
+                if tracker is not None:
+                    tracker._advance(f.src, f.offs, f.hw, i + 1 if i + 1 < len(chunk) else 0)
+                    f.bufs = tracker._bufs
+                if body is not None:
+                    f.i = i
+                    body(c0 + i, f)
+        if canvas:
+            out += unpack_u8(f.canvas, chunk)
+    det._join(cur, *held)
+    return out

@@ -56,8 +56,10 @@ class Recorder(object):
 
 
 def cases():
-    """name -> (fn(det, gen), [(object staged: 'det' | 'gen', count, bucket)]): the calls, and the padded buckets they leave."""
+    """name -> (fn(det, gen), [(object staged: 'det' | 'gen', count, bucket)]): the calls, and the padded buckets they leave.  A fourth
+    entry before(det, gen) runs ahead of the recorder; what it returns is fn's third argument."""
     from imm_amd import alignment as AL
+    from imm_amd.quality import QualityGate
     from imm_amd.keypoints import LandmarkRegressor
     from imm_amd.inference import plan_buckets
     assert plan_buckets(len(ROWS), MAX_BATCH) == [(0, 4, 4), (4, 3, 4)]
@@ -93,6 +95,19 @@ def cases():
         ('repose_template', lambda det, gen: gen.repose(ims, lm, ROWS, template=tpl), pad + gpad),
         ('track', lambda det, gen: det.track(frames, FACES, chunk_frames=2), pad),
         ('reenact', lambda det, gen: gen.reenact(ims, frames, DRIVER, ROWS[:3], return_faces=True), pad + gpad),
+        # no pose program: nothing is staged
+        ('redact', lambda det, gen: det.redact(ims, ROWS), []),
+        ('redact_hull', lambda det, gen: det.redact(ims, ROWS, mode='smooth', mask='hull'), pad),
+        ('annotate', lambda det, gen: det.annotate(ims, ROWS, draw=('points', 'box', 'hull', 'label')), pad),
+        # three frames in chunks of two: a full chunk and a chunk of one frame; three faces and three donor rows: one padded bucket each
+        ('morph_clip', lambda det, gen: det.morph_clip(frames, FACES, ims, ROWS[:3], chunk_frames=2), pad),
+        ('morph_clip_full', lambda det, gen: det.morph_clip(frames, FACES, ims, ROWS[:3], colour=0.5, mask='hull', seamless=0.5,
+                                                            colour_smooth=0.25, seam_smooth=0.5, chunk_frames=2), pad),
+        ('redact_clip', lambda det, gen: det.redact_clip(frames, FACES, mask='hull', gate=QualityGate(0.5, 0.5), chunk_frames=2), pad),
+        ('annotate_clip', lambda det, gen: det.annotate_clip(frames, FACES, draw=('points', 'box', 'hull'), trail=1, chunk_frames=2), pad),
+        ('annotate_clip_track', lambda det, gen, tr: det.annotate_clip(frames, track=tr, draw=('points', 'box', 'hull'), trail=1,
+                                                                       chunk_frames=2), [],
+         lambda det, gen: det.track(frames, FACES, chunk_frames=2)),
     ]
 
 
@@ -101,11 +116,12 @@ def record(model):
     from imm_amd.generation import ImageGenerator
     gens = {g: ImageGenerator(model, image_size=S, max_batch=MAX_BATCH, use_graph=g) for g in (False, True)}
     out = {}
-    for name, fn, padded in cases():
+    for name, fn, padded, *before in cases():
         out[name] = {}
         for mode in ('eager', 'capture', 'replay'):
             gen = gens[mode != 'eager']
             objs = {'det': gen.detector, 'gen': gen}
+            made = [b(gen.detector, gen) for b in before]
             torch.cuda.synchronize()
             for x in objs.values():
                 if mode == 'capture':
@@ -113,7 +129,7 @@ def record(model):
                 x._ensure_capacity(MAX_BATCH)
                 x._img.fill_(1.0)
             with Recorder() as rec:
-                fn(gen.detector, gen)
+                fn(gen.detector, gen, *made)
             torch.cuda.synchronize()
             for who, count, bucket in padded:
                 assert not objs[who]._img[count:bucket].any(), '%s (%s): the padded rows of %s._img are not zero' % (name, mode, who)
@@ -175,6 +191,33 @@ EXPECTED = {
                      [CROP] + captured(POSE) + [CROP] + captured(RENDER) + captured(ENC) + captured(POSE) + ([CROP, GO] + FRAME + [GO, COMPOSE]) * 3,
                      [CROP, GO, CROP, GO] + ([CROP, GO] + FRAME + [GO, COMPOSE]) * 3),
 }
+# redact, annotate and the clip calls, written from their docstrings' "per bucket" and "per frame" sentences and confirmed by this file's
+# recorder on the parent of the frame-loop refactor.  A clip's pose program is captured by the call's first use of the bucket: the
+# donors' landmarks in morph_clip, else the tracker ahead of the first frame.
+CELLS, HULL, ROWS_T, EMA, DRAW = ['imm_redact_cells_u8', 'imm_redact_u8'], 'imm_hull_fit', 'imm_clip_rows', 'imm_clip_ema', 'imm_annotate_u8'
+STATS = 'imm_colour_stats_u8'
+EXPECTED['redact'] = modes(CELLS * 2, CELLS * 2, CELLS * 2)
+EXPECTED['redact_hull'] = modes(([CROP] + POSE + [HULL] + CELLS) * 2, [CROP] + captured(POSE) + [HULL] + CELLS + [CROP, GO, HULL] + CELLS,
+                                ([CROP, GO, HULL] + CELLS) * 2)
+EXPECTED['annotate'] = {m: LANDMARKS[m] + ['imm_annotate_points', HULL, DRAW] for m in LANDMARKS}
+
+
+def clip(once, frame, scores=False):
+    """A clip call of three frames: `once` per call in front of the tracker, then per frame the tracker's launches and `frame`."""
+    step = (['imm_landmark_scores'] if scores else []) + [STEP]
+    return modes(once['eager'] + ([CROP] + POSE + step + frame) * 3, once['capture'] + ([CROP, GO] + step + frame) * 3,
+                 once['replay'] + ([CROP, GO] + step + frame) * 3)
+
+
+DONORS = modes([CROP] + POSE, [CROP] + captured(POSE), [CROP, GO])            # the donors' landmarks: one bucket
+AHEAD = modes([], captured(POSE), [])                                         # the tracker's capture ahead of the first frame
+EXPECTED['morph_clip'] = clip(DONORS, [ROWS_T] + MORPH)
+EXPECTED['morph_clip_full'] = clip({m: DONORS[m] + [STATS] for m in DONORS},
+                                   [ROWS_T, STATS, 'imm_colour_gain', EMA, 'imm_morph_poses', HULL, 'imm_warp_fit', 'imm_seam_fit', EMA,
+                                    'imm_morph_seam_u8'])
+EXPECTED['redact_clip'] = clip(AHEAD, [ROWS_T, HULL] + CELLS, scores=True)
+EXPECTED['annotate_clip'] = clip(AHEAD, [HULL, DRAW])
+EXPECTED['annotate_clip_track'] = modes(*[[HULL, DRAW] * 3] * 3)
 # the pose photo's one row (a detector bucket of 1) in front of repose's own launches
 EXPECTED['repose_pose_photos'] = modes([CROP] + POSE + EXPECTED['repose']['eager'], [CROP] + captured(POSE) + EXPECTED['repose']['capture'],
                                        [CROP, GO] + EXPECTED['repose']['replay'])
