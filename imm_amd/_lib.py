@@ -20,7 +20,7 @@ CONV_BIAS, CONV_RELU, CONV_STATS, CONV_MASK, CONV_OUT_F32 = 1, 2, 4, 8, 16
 SSE_BLOCKS = 512
 OPTIMIZERS = {'adam': 0, 'adadelta': 1, 'adagrad': 2}      # IMM_OPT_* (scripts/train.py:97-104)
 GAUSS_MODES = {'rot': 0, 'flat': 1, 'ankush': 2}     # IMM_GAUSS_* (config key gauss_mode, imm_model.py:48-72)
-ABI_VERSION = 38     # the history stands next to IMM_ABI_VERSION in include/imm_hip.h
+ABI_VERSION = 39     # the history stands next to IMM_ABI_VERSION in include/imm_hip.h
 
 
 class ImmHipError(RuntimeError):
@@ -68,8 +68,6 @@ _header('imm_hip.h', {
     'imm_last_error': (C.c_char_p, []),
     'imm_source_digest': (C.c_char_p, []),
     'imm_device_info': [_P],
-    'imm_set_cu_limit': [_I],
-    'imm_get_cu_limit': [],
     'imm_graph_begin': [_P],
     'imm_graph_end': [_P, C.POINTER(C.c_void_p)],
     'imm_graph_launch': [_P, _P],
@@ -128,9 +126,6 @@ _header('imm_hip.h', {
     'imm_conv_first_supported': [_I, _I, _I, _I],
     'imm_conv_first_stats_blocks': [_I, _I],
     'imm_conv_first': [_P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P],
-    'imm_conv2d_nol_supported': [C.POINTER(ConvDesc)],
-    'imm_conv2d_nol_stats_blocks': [C.POINTER(ConvDesc)],
-    'imm_conv2d_nol': [C.POINTER(ConvDesc), _I, _P, _P, _P, _I, _P, _P, _P, _P, _P],
     'imm_conv2d_dgrad_s2_supported': [_I, _I, _I, _I, _I, _I],
     'imm_conv2d_dgrad_s2': [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
     'imm_conv2d_group_stats_blocks': [_P, _I],

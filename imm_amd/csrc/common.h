@@ -176,22 +176,17 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
 
 static inline int imm_div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
-// The three environment variables the library reads, each on the first call that needs it and all in runtime.hip:
+// The two environment variables the library reads, each on the first call that needs it and both in runtime.hip:
 //   IMM_CONV_DISABLE=<comma list>: take a specialised convolution kernel out of the dispatch so that the layer falls back to
 //     the next more general one (A/B timing and the fallback paths' tests): halo, halo2, hdeep, deepk, group, group32, wgrad_tr,
 //     wgrad_halo, s2d / s2d_halo (one-launch stride-2 data gradient, deep-K / whole-filter form -> the four class launches),
-//     nol (imm_conv2d_nol_supported -> 0), hdeep6 (six-k-steps-per-barrier 16x16x128 tile -> conv_hdeep's tap-at-a-time form),
+//     hdeep6 (six-k-steps-per-barrier 16x16x128 tile -> conv_hdeep's tap-at-a-time form),
 //     s2f (stride-2 forward LDS-halo kernel -> im2col), first, vgg_head.  Every tuning constant is compiled in.
-//   IMM_HALO2X=1: conv_halo2's 32x32x16 form (imm_halo2_x32);  IMM_HDEEP_PROF: conv_hdeep's clock stamps (diagnosis builds).
+//   IMM_HDEEP_PROF: conv_hdeep's clock stamps (diagnosis builds).
 bool imm_conv_disabled(const char* name);
-enum ImmEnvFlag { IMM_ENV_HALO2X, IMM_ENV_HDEEP_PROF };
-bool imm_env_flag(ImmEnvFlag which);    // latched at first use
-// The CU count a persistent / chip-sized launch of THIS THREAD sizes its grid for: the device's, or the caller's smaller
-// imm_set_cu_limit() value (runtime.hip) — a launch confined to a share of the chip leaves the other CUs to the kernels of a
-// concurrent stream (the frozen VGG's ground-truth half beside the encoder chains, imm_amd/engine.py).
-int imm_limit_cus(int device_cus);
-int imm_device_cus();                   // the current device's CU count: one cached query, 256 without a device
-static inline int imm_launch_cus() { return imm_limit_cus(imm_device_cus()); }
+bool imm_hdeep_prof();                  // latched at first use
+int imm_device_cus();                   // the current device's CU count: one cached query, 256 without a device.  Persistent and
+                                        // chip-sized launches size their grids for it
 
 // ---------------------------------------------------------------------------------------------
 // launches with dynamic LDS.  More than 64 KB needs an opt-in per kernel, made once per instantiation.  The flag is per

@@ -15,9 +15,6 @@ bool imm_halo_applicable(const imm_conv_desc* d);                               
 int imm_halo_variant(const imm_conv_desc* d);
 int imm_halo_grid(const imm_conv_desc* d);
 void imm_conv_halo_launch(int dtype, const imm_conv_desc* d, const ConvArgs& a, hipStream_t s);
-bool imm_halo_nol_applicable(const imm_conv_desc* d);                              //   normalise on load
-void imm_conv_halo_nol_launch(int dtype, const imm_conv_desc* d, const ConvArgs& a, const float* scale, const float* shift, int relu,
-                              hipStream_t s);
 bool imm_halo_s2d_applicable(const imm_conv_desc* d);                              //   one-launch stride-2 data gradient
 void imm_conv_halo_s2d_launch(int dtype, const imm_conv_desc* d, const ConvArgs& a, hipStream_t s);
 bool imm_hdeep_applicable(const imm_conv_desc* d);                                 // conv_hdeep.hip: LDS halo, deep K

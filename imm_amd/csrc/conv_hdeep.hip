@@ -617,7 +617,7 @@ __global__ __launch_bounds__(NW * 64) void conv_hdeep_kernel(const HdArgs ha) {
 struct HdPlan { int ph, bn, n_patches, n_wg, cus; bool map8, persist, row3; };   // cus: the CU count the plan was made for
 
 static HdPlan hd_plan(const imm_conv_desc* d) {
-  const int cus = imm_launch_cus();
+  const int cus = imm_device_cus();
   constexpr int small_below = 2;   // x CUs (round 3: 4 -> 2.  128 -> 64 channels at 64x64 maps, batch 32 — renderer conv_5, VGG conv2_1's data
                                    // gradient — as 512 tiles of 16x16x64 (8 waves) instead of 1024 of 8x16x64: -12 us per step, same box)
   HdPlan p;
@@ -701,7 +701,7 @@ template <typename ET, int BN, int NW, int PH, bool MAP8 = false, int NSB_ = 0, 
 static void hd_launch_cfg(const HdArgs& ha, hipStream_t s) {
   constexpr int hstage = MAP8 ? 25 * 64 : HD_HSTAGE(PH), nsb = NSB_ ? NSB_ : MAP8 ? 3 : 4;
   constexpr int lds = (2 * hstage + 64 + nsb * BN * 8) * 16 + (PERSIST ? NW * BN * 4 : 0);   // + [NW/2][2][BN] f32 stats scratch
-  const int cus = imm_launch_cus();
+  const int cus = imm_device_cus();
   const int grid = PERSIST ? (ha.n_wg < cus ? ha.n_wg : cus) : ha.n_wg;
   imm_launch<conv_hdeep_kernel<ET, BN, NW, PH, MAP8, NSB_, PERSIST, ROW3, S2D>>(dim3(grid), dim3(NW * 64), lds, s, ha);
 }
@@ -731,7 +731,7 @@ static void hd_prof_dump() {
 void imm_conv_hdeep_launch(int dtype, const imm_conv_desc* d, const ConvArgs& a, hipStream_t s) {
   HdArgs ha;
   ha.c = a;
-  const bool prof = imm_env_flag(IMM_ENV_HDEEP_PROF);
+  const bool prof = imm_hdeep_prof();
   if (prof && !hd_prof_buf && hipMalloc((void**)&hd_prof_buf, 4000 * sizeof(unsigned long long)) == hipSuccess) {
     (void)hipMemset(hd_prof_buf, 0, 4000 * sizeof(unsigned long long));
     atexit(hd_prof_dump);
@@ -783,7 +783,7 @@ void imm_conv_hdeep_s2d_launch(int dtype, const imm_conv_desc* d, const ConvArgs
   ha.c.wt_bytes = (uint32_t)((int64_t)d->co * d->kpad * 2);
   // one round of workgroups or less: the row-at-a-time schedule (119 KB of LDS, one workgroup per CU anyway); larger grids keep
   // the 78 KB tap-at-a-time form
-  const bool row3 = ha.n_wg <= imm_launch_cus();
+  const bool row3 = ha.n_wg <= imm_device_cus();
   if (dtype == IMM_BF16) {
     if (row3) hd_launch_cfg<BF16, 64, 4, 8, false, 9, false, true, true>(ha, s);
     else hd_launch_cfg<BF16, 64, 4, 8, false, 0, false, false, true>(ha, s);

@@ -29,11 +29,7 @@ bool imm_conv_disabled(const char* name) {
   }
   return false;
 }
-bool imm_env_flag(ImmEnvFlag which) {
-  if (which == IMM_ENV_HALO2X) {
-    static const bool on = getenv("IMM_HALO2X") && getenv("IMM_HALO2X")[0] == '1';
-    return on;
-  }
+bool imm_hdeep_prof() {
   static const bool prof = getenv("IMM_HDEEP_PROF") != nullptr;
   return prof;
 }
@@ -55,14 +51,6 @@ bool imm_dyn_lds_opt_in(const void* kernel, size_t bytes) {
   return e == hipSuccess;
 }
 
-static thread_local int imm_cu_limit_tl = 0;
-int imm_limit_cus(int device_cus) { return (imm_cu_limit_tl > 0 && imm_cu_limit_tl < device_cus) ? imm_cu_limit_tl : device_cus; }
-extern "C" int imm_set_cu_limit(int cus) {
-  IMM_REQUIRE(cus >= 0 && cus % 8 == 0, "set_cu_limit: %d is not 0 or a multiple of 8 (one share per XCD)", cus);
-  imm_cu_limit_tl = cus;
-  return 0;
-}
-extern "C" int imm_get_cu_limit(void) { return imm_cu_limit_tl; }
 #ifndef IMM_SOURCE_DIGEST
 #define IMM_SOURCE_DIGEST "unknown"
 #endif

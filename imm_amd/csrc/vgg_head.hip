@@ -412,7 +412,7 @@ extern "C" int imm_vgg_head_fwd(const float* gt, const float* pred, int ldp, int
   ha.gray_bytes = (uint32_t)(npix * 4);
   ha.act_bytes = (uint32_t)(npix * 128);
   const size_t lds = (size_t)(2 * VH_HSTAGE_U4 + VH_NG * VH_GSTAGE_U4) * 16;
-  const int cus = imm_launch_cus();
+  const int cus = imm_device_cus();
   const int grid = ha.n_patches < cus ? ha.n_patches : cus;
   IMM_DISPATCH_DTYPE(dtype, imm_launch<conv_halo2_vgg_head_kernel<ET>>(dim3(grid), dim3(256), lds, st, ha));
   IMM_CHECK_LAUNCH("imm_vgg_head_fwd");

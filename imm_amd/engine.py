@@ -29,9 +29,6 @@ from . import ops
 
 BN_EPS = 1e-3          # tf.layers.batch_normalization default (nn_utils.py:201)
 BN_MOMENTUM = 0.99
-# Partial rows of batch-norm sums that the fused finalize + apply passes reduce themselves; layers with more rows get a parallel
-# pre-reduction launch (imm_rows_reduce) in front.  IMM_BN_DIRECT_ROWS: A/B only (profiles/r06_bn_direct_rows_ab.txt).
-BN_DIRECT_ROWS = int(os.environ.get('IMM_BN_DIRECT_ROWS', '512'))
 WEIGHT_DECAY = 1e-5    # base_model.py:62-69
 INIT_STD = 0.01
 PERCEPTUAL_WS = [100.0, 1.6, 2.3, 1.8, 2.8, 100.0]   # imm_model.py:131
@@ -152,13 +149,10 @@ def synthetic_vgg_weights(seed=2):
 
 
 class _Launch:
-    __slots__ = ('fn', 'tag', 'flops', 'bytes', 'name', 'lane', 'variant', 'cus', 'group')
+    __slots__ = ('fn', 'tag', 'flops', 'bytes', 'name', 'lane', 'variant')
 
-    def __init__(self, fn, tag, flops=0.0, nbytes=0.0, name='', lane=0, variant='', cus=0, group=''):
+    def __init__(self, fn, tag, flops=0.0, nbytes=0.0, name='', lane=0, variant=''):
         self.fn, self.tag, self.flops, self.bytes, self.name, self.lane, self.variant = fn, tag, flops, nbytes, name, lane, variant
-        # cus: the launch is issued under imm_set_cu_limit(cus) (0 = whole device); group: 'gt' = the frozen VGG's ground-truth
-        # lane (launches AND its fork / join / event marks): needed by the loss only (forward_model_only drops it)
-        self.cus, self.group = cus, group
 
 
 class _ConvLayer:
@@ -169,6 +163,26 @@ class _ConvLayer:
 class IMMEngine:
     def __init__(self, cfg, batch, image_size, device='cuda:0', act_dtype=torch.bfloat16, seed=1, vgg_weights=None,
                  hparams=None, world_size=1, dp_buckets=None):
+        # ---- environment switches: read here, once; nothing below __init__ looks at the environment ------------
+        # IMM_TWO_STREAMS=0: everything on one stream (A/B of the two-lane schedule; the results are identical)
+        self.two_streams = os.environ.get('IMM_TWO_STREAMS', '1') != '0'
+        # IMM_VGG_HEAD=0: VGG conv1_1 and conv1_2 as two launches instead of the fused head (imm_vgg_head_fwd)
+        self.vgg_head = os.environ.get('IMM_VGG_HEAD', '1') != '0'
+        # IMM_SSE_ALL=0: the image pair's error sum as a launch of its own instead of inside imm_masked_sse_all
+        self.sse_all = os.environ.get('IMM_SSE_ALL', '1') != '0'
+        # IMM_BN_DIRECT_ROWS=n: most partial rows of batch-norm sums that the fused finalize + apply passes reduce themselves;
+        # layers with more get a parallel pre-reduction launch (imm_rows_reduce) in front (profiles/r06_bn_direct_rows_ab.txt)
+        self.bn_direct_rows = int(os.environ.get('IMM_BN_DIRECT_ROWS', '512'))
+        # IMM_DP_BUCKETS=n: default of the `dp_buckets` argument (gradient-exchange buckets the backward program is laid out for)
+        env_dp_buckets = int(os.environ.get('IMM_DP_BUCKETS', '1'))
+        # IMM_DEBUG_SKIP_TAGS=tag,tag: timing experiment only (results become wrong): drop every launch whose tag is listed, to
+        # measure how much of the step's critical path a kernel class occupies under graph replay / stream concurrency
+        self._skip_tags = set(t for t in os.environ.get('IMM_DEBUG_SKIP_TAGS', '').split(',') if t)
+        # IMM_DEBUG_STAMPS=marks|all: device wall-clock probes between the launches (lane boundaries / every launch) -> a
+        # profiler-free timeline of a graph replay, read with stamp_report()
+        self._stamp_mode = os.environ.get('IMM_DEBUG_STAMPS', '')
+        # (IMM_CONV_DISABLE, the kernel-family ablation list, is read by the library: csrc/runtime.hip)
+
         if cfg.gauss_mode not in L.GAUSS_MODES:
             raise ValueError('Unknown mode: ' + str(cfg.gauss_mode))       # imm_model.py:75
         if cfg.reconstruction_loss not in ('perceptual', 'l2'):
@@ -198,7 +212,7 @@ class IMMEngine:
         # gradient-exchange buckets the backward program is laid out for (1 = one all-reduce after the backward pass; 2 = the
         # renderer's filter gradients are issued and reduced early so that their bucket can travel while the encoders' backward
         # runs).  Decided HERE, once, and read back by TrainStep (IMM_DP_BUCKETS is only the default of this argument).
-        self.dp_buckets = int(dp_buckets if dp_buckets is not None else os.environ.get('IMM_DP_BUCKETS', '1'))
+        self.dp_buckets = int(dp_buckets if dp_buckets is not None else env_dp_buckets)
         self.use_mask = bool(cfg.loss_mask)
         self.n_cu, self.arch = ops.device_info()
         self._alloc_bytes = 0
@@ -258,20 +272,7 @@ class IMMEngine:
             ops.upload(self.vgg_w[k], v, k)               # (pinned staging + read-back: see ops.upload)
 
         self.prog_pack, self.prog_fwd, self.prog_bwd, self.prog_opt = [], [], [], []
-        # IMM_TWO_STREAMS=0: everything on one stream (A/B of the two-lane schedule; the results are identical)
-        self.two_streams = os.environ.get('IMM_TWO_STREAMS', '1') != '0'
-        # IMM_NOL=1: normalise on load (round 4) — the batch-norm apply pass of a block folded into the LDS halo tiles of its two
-        # readers (next convolution forward, its filter gradient) where both are LDS-halo kernels: encoder conv_1..3, renderer
-        # conv_5 / conv_7.  Built, parity-tested, and MEASURED SLOWER on the step (3.137 -> 3.216 ms, same box, DESIGN.md item 47:
-        # the affine + ReLU costs ~3.5 VALU instructions per element at one wave per SIMD with nothing to hide them behind —
-        # forward convolutions +5..8 us for 11..15 us of apply pass saved, filter gradients +100 us), so it is off by default.
-        self.nol = os.environ.get('IMM_NOL', '0') != '0' and not self.f32
-        # IMM_DEBUG_SKIP_TAGS=tag,tag: timing experiment only (results become wrong): drop every launch whose tag is listed, to
-        # measure how much of the step's critical path a kernel class occupies under graph replay / stream concurrency
-        self._skip_tags = set(t for t in os.environ.get('IMM_DEBUG_SKIP_TAGS', '').split(',') if t)
-        # IMM_DEBUG_STAMPS=marks|all: device wall-clock probes between the launches (lane boundaries / every launch) -> a
-        # profiler-free timeline of a graph replay, read with stamp_report()
-        self._stamp_mode = os.environ.get('IMM_DEBUG_STAMPS', '')
+        self._cur_lane, self._cur_scope = 0, ''       # lane and scope that _add stamps on the launches it registers
         self._stamp_buf = torch.zeros(8192, dtype=torch.int64, device=self.dev) if self._stamp_mode else None
         self._stamp_names = []
         self._side = None
@@ -363,21 +364,13 @@ class IMMEngine:
     def _add(self, prog, fn, tag, flops=0.0, nbytes=0.0, name='', desc=None, variant=''):
         """desc: the imm_conv_desc of a convolution launch — its kernel variant (imm_conv2d_variant) is recorded with the launch
         (tools/layer_table.py: layer -> kernel -> time -> floor)."""
-        cus = int(getattr(self, '_cur_cus', 0))
         if desc is not None:
-            if cus:
-                ops.set_cu_limit(cus)            # the variant the launch will take under its CU limit
-            try:
-                variant = '%s:%d' % ops.conv2d_variant(desc, self.dt)
-            finally:
-                if cus:
-                    ops.set_cu_limit(0)
-        prog.append(_Launch(fn, tag, flops, nbytes, name or getattr(self, '_cur_scope', ''), getattr(self, '_cur_lane', 0), variant,
-                            cus, getattr(self, '_cur_group', '')))
+            variant = '%s:%d' % ops.conv2d_variant(desc, self.dt)
+        prog.append(_Launch(fn, tag, flops, nbytes, name or self._cur_scope, self._cur_lane, variant))
 
     def _signal(self, prog, key, lane=None):
         """Record an event on `lane` (default: the current lane) that other lanes can wait for."""
-        prog.append(_Launch(None, 'record:' + key, lane=self._cur_lane if lane is None else lane, group=getattr(self, '_cur_group', '')))
+        prog.append(_Launch(None, 'record:' + key, lane=self._cur_lane if lane is None else lane))
 
     def _wait(self, prog, key, lane):
         prog.append(_Launch(None, 'wait:' + key, lane=lane))
@@ -386,41 +379,19 @@ class IMMEngine:
         """'fork': side stream `lane` may start once everything issued so far on the main stream has finished; 'join': the main
         stream waits for side stream `lane`.  Launches registered with that lane in between run on the side stream: the two
         encoders (and their backward passes) are independent chains of small kernels that do not fill 256 CUs on their own
-        (lane 1); lane 2 carries chip-filling work CONFINED to a share of the CUs (_Launch.cus) beside those chains: the
-        ground-truth half of the frozen VGG16 forward, the renderer's filter gradients."""
-        prog.append(_Launch(None, what, lane=lane, group=getattr(self, '_cur_group', '')))
-
-    def _nol_consumer_ok(self, H, W, ci, ldx, co, k, stride, bn, out_f32):
-        """Can a convolution of this geometry take the RAW output of the conv + BN + ReLU block in front of it (normalise on
-        load)?  Both readers of the normalised tensor must rebuild it in LDS: the forward convolution (imm_conv2d_nol) and
-        its filter gradient (an LDS-halo variant of imm_conv2d_wgrad_multi).  IMM_CONV_DISABLE=nol turns the path off."""
-        if not self.nol or k != 3 or ci != ldx:
-            return False
-        ldy = ops.round_up(co, 4) if out_f32 else ops.round_up(co, 8)
-        flags = L.CONV_BIAS | (L.CONV_OUT_F32 if out_f32 else 0) | (L.CONV_STATS if bn else 0)
-        fd = ops.fwd_desc(self.B, H, W, ci, ldx, co, ldy, k, stride, flags)
-        if not ops.conv2d_nol_supported(fd):
-            return False
-        lddy = ldy if not out_f32 else ops.round_up(co, 32)
-        key, _wps, _units, _pcu = ops.conv2d_wgrad_variant(fd, lddy, self.dt)
-        return key // 100000 == 2
+        (lane 1).  Chip-filling work confined to a share of the CUs on a further lane beside them was zero-sum: DESIGN.md item 59."""
+        prog.append(_Launch(None, what, lane=lane))
 
     def _conv_block(self, scope, x, H, W, ci_real, ci_pad, ldx, co, k, stride, bn, relu, needs_dgrad,
-                    out=None, ldo=None, out_f32=False, kw=None, up2x=False, fwd_launch=True, nol_src=None, defer_apply=False,
-                    first_src=None):
+                    out=None, ldo=None, out_f32=False, kw=None, up2x=False, fwd_launch=True):
         """Registers forward launches now and returns a layer record whose .backward(d_out, dx) registers the
         backward launches later (in reverse order).
-        nol_src: the conv + BN + ReLU block in front of this convolution whose normalised output is NOT stored: x is its raw
-        conv output y, and this convolution (and its filter gradient) apply relu(scale * y + shift) on load.
-        defer_apply: this block is such a producer — statistics and a finalize launch, no apply pass, no `out`.
-        first_src: the f32 image behind the tap-unrolled input x of the first encoder convolution: the forward launch reads IT
-        (imm_conv_first builds the unrolled tile in LDS); x is then only the filter gradient's operand."""
+        (Normalise on load — this block's apply pass folded into the LDS halo tiles of the next convolution — made the step
+        slower: DESIGN.md item 47.)"""
         B, dt, dev = self.B, self.dt, self.dev
         self._cur_scope = scope
         lay = _ConvLayer()
         lay.scope, lay.bn, lay.relu, lay.x, lay.ldx = scope, bn, relu, x, ldx
-        lay.nol_src = nol_src
-        assert nol_src is None or (nol_src.bn and x is nol_src.y and ldx == nol_src.ldy)
         kw = k if kw is None else kw      # kw != k only for the tap-unrolled first encoder conv (7x1 over 21 channels)
         lay.ci_real, lay.ci_pad, lay.co, lay.k, lay.stride, lay.H, lay.W, lay.kw = ci_real, ci_pad, co, k, stride, H, W, kw
         flags = L.CONV_BIAS | (L.CONV_OUT_F32 if out_f32 else 0)
@@ -438,15 +409,7 @@ class IMMEngine:
         lay.y = self._zeros(B, fd.ho, fd.wo, ldy, dtype=torch.float32 if out_f32 else dt)
         flops = 2.0 * npix * k * kw * ci_real * co
         if bn:
-            cus_q = int(getattr(self, '_cur_cus', 0))
-            if cus_q:
-                ops.set_cu_limit(cus_q)         # the partial rows of the tile plan the launch will take under its CU limit
-            try:
-                nblk = (ops.conv_first_stats_blocks(B, H) if first_src is not None else
-                        ops.conv_stats_blocks(fd) if nol_src is None else ops.conv2d_nol_stats_blocks(fd))
-            finally:
-                if cus_q:
-                    ops.set_cu_limit(0)
+            nblk = ops.conv_stats_blocks(fd)
             lay.stats = self._zeros(nblk, 2, co)
             lay.scale, lay.shift, lay.mean, lay.rstd = (self._zeros(co) for _ in range(4))
             mm, mv = self._zeros(co), self._zeros(co)
@@ -454,39 +417,22 @@ class IMMEngine:
             self.state[scope + '/moving_mean'], self.state[scope + '/moving_variance'] = mm, mv
             gamma, beta = self.pview[scope + '/gamma'], self.pview[scope + '/beta']
             # an up-sampled block taken by the fused finalize + apply + up-sample pass never stores its own normalised tensor (nobody
-            # reads it): it is not allocated either (a zero-filled `out` that looks valid).  lay.nol marks "normalise on
-            # load" (the consumers read y); lay.out is None alone no longer means that.
-            fused_up = bool(up2x) and not defer_apply and nblk <= BN_DIRECT_ROWS and co % 32 == 0
-            if out is None and not defer_apply and not fused_up:
+            # reads it): it is not allocated either (a zero-filled `out` that looks valid).
+            fused_up = bool(up2x) and nblk <= self.bn_direct_rows and co % 32 == 0
+            if out is None and not fused_up:
                 out, ldo = self._act(B, fd.ho, fd.wo, co), co
             lay.out, lay.ldo = out, (ldo if out is not None else None)
-            lay.nol = bool(defer_apply)
 
             def f_conv():
-                if first_src is not None:
-                    ops.conv_first(first_src, lay.wt, b, lay.y, ldy, lay.stats if self._training else None, B, H, co,
-                                   L.CONV_BIAS | (L.CONV_STATS if self._training else 0))
-                elif nol_src is not None:
-                    ops.conv2d_nol(fd if self._training else fd_eval, x, nol_src.scale, nol_src.shift, nol_src.relu, lay.wt, b, lay.y,
-                                   lay.stats if self._training else None)
-                else:
-                    ops.conv2d(fd if self._training else fd_eval, x, lay.wt, b, lay.y, lay.stats if self._training else None)
+                ops.conv2d(fd if self._training else fd_eval, x, lay.wt, b, lay.y, lay.stats if self._training else None)
 
             def f_fin():
                 ops.bn_finalize(lay.stats, nblk, co, npix, gamma, beta, BN_EPS, BN_MOMENTUM, self._training, mm, mv,
                                 lay.scale, lay.shift, lay.mean, lay.rstd)
             cbytes = 2.0 * (B * H * W * ci_pad + npix * co + fd.kpad * co)
-            self._add(self.prog_fwd, f_conv, 'conv_fwd', flops, cbytes, desc=(fd if (first_src is None and nol_src is None) else None),
-                      variant=('first' if first_src is not None else 'halo:nol' if nol_src is not None else ''))
+            self._add(self.prog_fwd, f_conv, 'conv_fwd', flops, cbytes, desc=fd)
             lay.up = None
-            if defer_apply:
-                # normalise on load: the consumers rebuild relu(scale * y + shift) in LDS, so the apply pass (read y, write out:
-                # 4 B per element of HBM traffic) is gone; what is left of the batch norm's forward is this finalize of the
-                # partial rows (one workgroup per 32 channels; <= 768 rows: the producers are persistent kernels)
-                assert up2x is False and out is None
-                lay.out, lay.ldo = None, None
-                self._add(self.prog_fwd, f_fin, 'bn_finalize')
-            elif nblk <= BN_DIRECT_ROWS and co % 32 == 0:
+            if nblk <= self.bn_direct_rows and co % 32 == 0:
                 # few partial rows: the finalize is redone by every workgroup of the apply pass (one launch, one kernel
                 # boundary and a 6-9 us latency chain less per layer); the renderer's x2 up-sampling rides along
                 if up2x:
@@ -521,10 +467,7 @@ class IMMEngine:
         else:
             lay.out, lay.ldo = lay.y, ldy
             lay.fwd_flops = flops
-            if fwd_launch and nol_src is not None:
-                self._add(self.prog_fwd, lambda: ops.conv2d_nol(fd_eval, x, nol_src.scale, nol_src.shift, nol_src.relu, lay.wt, b, lay.y),
-                          'conv_fwd', flops, 2.0 * (B * H * W * ci_pad + fd.kpad * co) + npix * co * (4.0 if out_f32 else 2.0))
-            elif fwd_launch:      # (the pose head's convolution is part of the fused imm_pose_head_fwd launch instead)
+            if fwd_launch:      # (the pose head's convolution is part of the fused imm_pose_head_fwd launch instead)
                 self._add(self.prog_fwd, lambda: ops.conv2d(fd_eval, x, lay.wt, b, lay.y), 'conv_fwd', flops,
                           2.0 * (B * H * W * ci_pad + fd.kpad * co) + npix * co * (4.0 if out_f32 else 2.0), desc=fd_eval)
 
@@ -598,7 +541,7 @@ class IMMEngine:
                           'bn_bwd_reduce', 0.0, npix * co * 4.0)
             if co % 32 == 0:
                 rows, nrows = lay.bwd_partial, nblk
-                if nblk > BN_DIRECT_ROWS:
+                if nblk > self.bn_direct_rows:
                     g = max(32, -(-nblk // 32))
                     nrows = -(-nblk // g)
                     lay.bwd_red = rows_red = self._zeros(nrows, 2, co)
@@ -652,9 +595,8 @@ class IMMEngine:
             self._add(self.prog_bwd, lambda: ops.conv2d(dd, dy, lay.wt_d, None, dx), 'conv_dgrad', flops,
                       2.0 * (npix * lddy + B * lay.H * lay.W * lay.ci_real + dd.kpad * lay.ci_real), desc=dd)
 
-    def _flush_wgrads(self, name, cus=0):
-        """cus: size the members' splits for that many compute units instead of the whole chip (a confined lane).
-        Issue the collected filter-gradient jobs as ONE multi-problem launch per kernel variant (imm_conv2d_wgrad_multi) and
+    def _flush_wgrads(self, name):
+        """Issue the collected filter-gradient jobs as ONE multi-problem launch per kernel variant (imm_conv2d_wgrad_multi) and
         register their slab reductions.  Jobs that share a launch share the chip, so a layer no longer needs enough pixel
         splits to fill 256 CUs on its own: the splits of a group are sized to a common length per workgroup with about
         one round of resident workgroups in total (the library reports how many of a variant's workgroups fit a CU) — slab
@@ -668,31 +610,14 @@ class IMMEngine:
             groups.setdefault((key, pcu), []).append((lay, dy, lddy, wps, units, flops))
         chunks = plan_wgrad_chunks(groups, WGRAD_MULTI_MAX_JOBS, WGRAD_MULTI_MAX_VARIANTS)
         for ci_, chunk in enumerate(chunks):
-            self._issue_wgrad_chunk(chunk, name if len(chunks) == 1 else '%s [%d/%d]' % (name, ci_ + 1, len(chunks)), cus)
+            self._issue_wgrad_chunk(chunk, name if len(chunks) == 1 else '%s [%d/%d]' % (name, ci_ + 1, len(chunks)))
 
-    def _issue_wgrad_chunk(self, chunk, name, cus=0):
-        # IMM_WG_LANES=n (round 6 experiment; default 1): the kernel variants of a chunk as separate launches
-        # spread over n lanes (largest group on the main lane) instead of one after the other on one stream; IMM_WG_LANE_SHARE =
-        # the share of the chip the groups on the side lanes are planned for
-        n_lanes = int(os.environ.get('IMM_WG_LANES', '1'))
-        if n_lanes > 1 and len(chunk) > 1 and not cus and self._cur_lane == 0:
-            share = float(os.environ.get('IMM_WG_LANE_SHARE', '1.0'))
-            groups = sorted(chunk, key=lambda g: -sum(m[5] for m in g[1]))
-            lanes = sorted(set(1 + (i - 1) % (n_lanes - 1) for i in range(1, len(groups))))
-            for ln in lanes:
-                self._mark(self.prog_bwd, 'fork', lane=ln)
-            for i, g in enumerate(groups):
-                self._cur_lane = 0 if i == 0 else 1 + (i - 1) % (n_lanes - 1)
-                self._issue_wgrad_chunk([g], '%s [variant %d]' % (name, g[0][0]),
-                                        cus=0 if i == 0 else max(8, int(self.n_cu * share) // 8 * 8) if share < 1.0 else 0)
-            self._cur_lane = 0
-            for ln in lanes:
-                self._mark(self.prog_bwd, 'join', lane=ln)
-            return
+    def _issue_wgrad_chunk(self, chunk, name):
+        # (The kernel variants of a chunk as separate launches side by side on several lanes bought nothing: DESIGN.md item 66.)
         multi_jobs, flops_total = [], 0.0
         for (key, pcu), members in chunk:
             kind = key // 100000                    # 0 generic kernel (one launch per job), 1 transpose-read, 2 LDS-halo
-            target = pcu * (cus or self.n_cu)
+            target = pcu * self.n_cu
             # shortest useful workgroup: 16 steps of 32 pixels / 2 (sliced) or 4 (whole-filter) patches of 128 pixels
             floor_units = [16 if kind != 2 else (2 if wps > 1 else 4) for _l, _d, _ld, wps, _u, _f in members]
 
@@ -716,9 +641,7 @@ class IMMEngine:
                 lay.nsplit = nsplit
                 flops_total += flops
                 lay.slab = self._zeros(nsplit, lay.fd.kpad, lay.co)
-                ns_ = getattr(lay, 'nol_src', None)
-                multi_jobs.append((lay.fd, lay.x, dy, lddy, lay.slab, nsplit,
-                                   None if ns_ is None else (ns_.scale, ns_.shift, ns_.relu)))
+                multi_jobs.append((lay.fd, lay.x, dy, lddy, lay.slab, nsplit))
                 gw = self.gview[lay.scope + '/w']
                 job = (lay.slab.data_ptr(), gw.data_ptr(), nsplit, lay.k * lay.kw, lay.ci_pad, lay.ci_real, lay.co, lay.fd.kpad)
                 self._reduce_jobs.append((job, lay.k * lay.kw * lay.ci_real * lay.co))
@@ -751,49 +674,23 @@ class IMMEngine:
             k1 = encoder_spec(nf)[0][0]
             ld1 = ops.round_up(3 * k1, 32)
             xin = self._act(B, S, S, ld1)
-            f_pack = (lambda: ops.pack_image_taps(src, xin, B, S, S, k1, (k1 - 1) // 2, ld1), 'pack_image',
-                      0.0, B * S * S * (12.0 + 2.0 * ld1), scope + '/pack')
-            # imm_conv_first reads the f32 image itself: the tap-unrolled copy is then only the operand of conv_1's filter gradient
-            # (the end of the backward pass) and its packing leaves the head of the forward chain for the tail of the shorter lane
-            co1 = encoder_spec(nf)[0][2]
-            # (IMM_CONV_FIRST=1: built, bit-compatible, measured NEUTRAL on the step — 26.7 us against 12 + 20 us for the two launches it
-            # takes off the chain, whose packing pass still runs at the lane's tail; DESIGN.md item 49 — so the default stays the 7x1 form)
-            direct = (os.environ.get('IMM_CONV_FIRST', '0') != '0' and not self.f32 and k1 == 7 and ld1 == 32 and
-                      ops.conv_first_supported(B, S, co1, ops.round_up(co1, 8)))
-            if direct:
-                self._deferred_packs.append(f_pack)
-            else:
-                self._add(self.prog_fwd, f_pack[0], f_pack[1], f_pack[2], f_pack[3], name=f_pack[4])
+            # (imm_conv_first — conv_1 straight from the f32 image, the packing pass moved to the lane's tail — was neutral on the step:
+            # DESIGN.md item 49; the detector uses that kernel)
+            self._add(self.prog_fwd, lambda: ops.pack_image_taps(src, xin, B, S, S, k1, (k1 - 1) // 2, ld1), 'pack_image',
+                      0.0, B * S * S * (12.0 + 2.0 * ld1), name=scope + '/pack')
             layers, x, H, ci_real, ci_pad, ldx = [], xin, S, 3 * k1, ld1, ld1
             spec = encoder_spec(nf)
-            # normalise on load: block i keeps only its raw conv output when the next convolution (its ONLY reader, forward
-            # and filter gradient) can rebuild the normalised tensor in LDS — the high-resolution layers, where the apply
-            # pass is pure HBM traffic (conv_2, conv_3, conv_4 of each encoder at 128x128 / 64x64)
-            hs, h_ = [], S
-            for (_k, _ci, _co, st) in spec:
-                hs.append(h_); h_ = -(-h_ // st)
-            defer = [i + 1 < len(spec) and self._nol_consumer_ok(hs[i + 1], hs[i + 1], spec[i][2], ops.round_up(spec[i][2], 8),
-                                                               spec[i + 1][2], spec[i + 1][0], spec[i + 1][3], True, False)
-                     for i in range(len(spec))]
-            prev = None
             for i, (k, ci, co, stride) in enumerate(spec):
                 last = i == len(spec) - 1
                 out, ldo = (None, None)
                 if last and scope == 'model/image_encoder' and He == 16:
                     out, ldo = self.joint, Cj       # conv_8 writes straight into the concat buffer
-                nol_src = prev if (prev is not None and getattr(prev, 'nol', False)) else None
                 lay = self._conv_block('%s/encoder/conv_%d' % (scope, i + 1), x, H, H, ci_real, ci_pad, ldx, co, k,
-                                       stride, True, True, needs_dgrad=(i > 0), out=out, ldo=ldo, kw=(1 if i == 0 else None),
-                                       nol_src=nol_src, defer_apply=defer[i], first_src=(src if (i == 0 and direct) else None))
+                                       stride, True, True, needs_dgrad=(i > 0), out=out, ldo=ldo, kw=(1 if i == 0 else None))
                 layers.append(lay)
-                prev = lay
-                if lay.nol:
-                    x, H, ci_real, ci_pad, ldx = lay.y, lay.Ho, co, co, lay.ldy
-                else:
-                    x, H, ci_real, ci_pad, ldx = lay.out, lay.Ho, co, co, lay.ldo
+                x, H, ci_real, ci_pad, ldx = lay.out, lay.Ho, co, co, lay.ldo
             return layers
 
-        self._deferred_packs = []
         self._mark(self.prog_fwd, 'fork')
         self._cur_lane = 1                      # image encoder: side stream, concurrent with the pose encoder
         # the weight-decay term of the loss depends on the parameters only: computed here, beside the (longer) pose branch,
@@ -833,36 +730,18 @@ class IMMEngine:
             self._add(self.prog_fwd, lambda: ops.softargmax_gauss_fwd(self.heat, self.ldh, B, He, He, K, self.inv_std, 16,
                                                                       self.mu, self.py, self.px, gview, Cj, dt, cfg.gauss_mode), 'bottleneck')
 
-        if self._deferred_packs:
-            # the tap-unrolled image copies (filter-gradient operands of the two first convolutions): at the tail of the image-encoder
-            # lane, which is shorter than the pose lane by the pose head
-            self._cur_lane = 1
-            for fn, tag, fl, nb, nm in self._deferred_packs:
-                self._cur_scope = nm
-                self._add(self.prog_fwd, fn, tag, fl, nb, name=nm)
-            self._cur_lane = 0
         self._mark(self.prog_fwd, 'join')
         # ---- renderer ---------------------------------------------------------------------------------
         self.ren, self.ren_up = [], []
         x, H, ci_real, ci_pad, ldx = self.joint, 16, 8 * nf + K, Cj, Cj
         rspec = renderer_spec(cfg, S, n_renderer_out(cfg))
-        prev = None
         for i, (k, ci, co, bn, up) in enumerate(rspec):
             assert ci == ci_real, (ci, ci_real)
-            # normalise on load (see build_encoder): a block that is not up-sampled and whose next convolution takes the raw tensor
-            defer = False
-            if bn and not up and i + 1 < len(rspec) and co % 8 == 0:
-                k2, _ci2, co2, bn2, _up2 = rspec[i + 1]
-                defer = self._nol_consumer_ok(H, H, co, co, co2, k2, 1, bn2, not bn2)
-            nol_src = prev if (prev is not None and prev.bn and getattr(prev, 'nol', False)) else None
             lay = self._conv_block('model/renderer/conv_%d' % (i + 1), x, H, H, ci_real, ci_pad, ldx, co, k, 1, bn, bn,
-                                   needs_dgrad=True, out_f32=not bn, up2x=bool(up and bn), nol_src=nol_src, defer_apply=defer)
+                                   needs_dgrad=True, out_f32=not bn, up2x=bool(up and bn))
             self.ren.append(lay)
-            prev = lay
-            if lay.bn and lay.nol:
-                x, ci_real, ci_pad, ldx = lay.y, co, co, lay.ldy
-            else:       # (an up-sampled block without a stored `out`: x becomes the up-sampled tensor below, pixel stride co)
-                x, ci_real, ci_pad, ldx = lay.out, co, co, (lay.ldo if lay.out is not None else co)
+            # (an up-sampled block without a stored `out`: x becomes the up-sampled tensor below, pixel stride co)
+            x, ci_real, ci_pad, ldx = lay.out, co, co, (lay.ldo if lay.out is not None else co)
             if up:
                 ub = getattr(lay, 'up', None)
                 if ub is None:       # not taken by the fused finalize + apply + up-sample pass
@@ -895,120 +774,59 @@ class IMMEngine:
         self.sse_partial = self._zeros(nfeat, L.SSE_BLOCKS)
         fuse_ok = not self.l1                    # the fused SSE+pool / unpool+tap passes exist for the squared error only
         fused_sse = set()
-        # the image-space term ('input' feature: prediction against the future image) needs the renderer's output only: with
-        # IMM_SSE_INPUT_LANE=1 its error sum runs on lane 1 beside the VGG launches instead of in the one-lane tail in front of the
-        # loss.  Round 6, measured NEUTRAL (same box, two alternations: 3.2027 / 3.2077, 3.1943 / 3.1950 ms — the 11 us launch
-        # leaves the tail, the extra fork / join nodes cost as much): off by default.
-        self._sse_input_early = ('input' in self.tap_idx and bool(self.vgg_layers) and
-                                 os.environ.get('IMM_SSE_INPUT_LANE', '0') != '0')
-        if self._sse_input_early:
-            idx0 = self.tap_idx['input']
-            self._cur_scope = 'loss'
-            self._mark(self.prog_fwd, 'fork', lane=1)
-            self._cur_lane = 1
-            self._add(self.prog_fwd, lambda: ops.masked_sse_f32(self.in_future, 3, self.pred, self.ldp, B, S, 3, self.in_mask,
-                                                                self.sse_partial[idx0], self.l1), 'sse')
-            self._cur_lane = 0
-        # Round 6, built and MEASURED WITHOUT GAIN, off by default (IMM_VGG_SPLIT=1 turns it on): the
-        # ground-truth half of concat([gt, pred]) (imm_model.py:126) depends on the input batch only.  With the split it runs on a
-        # lane of its own (lane 2) that forks at the START of the forward program, every persistent convolution CONFINED to
-        # `gt_cus` compute units (imm_set_cu_limit; IMM_GT_CUS, 0 = no limit); the prediction half follows the renderer on the
-        # main lane with the whole chip and waits for the ground-truth activation of a tapped layer right in front of that
-        # layer's error sum.  Same box, ms/step: one launch per layer 3.193 / 3.206 | split with 128 / 96 / 64 / all CUs 3.199 /
-        # 3.238 / 3.256 / 3.261 (profiles/r06_lanes_ab.txt).  The per-lane stamps (profiles/r06_lanes_timeline_split.txt) say why:
-        # the lane's 0.29 ms of chip time take 0.80 ms beside the chains, the encoder lanes finish at 0.58 ms instead of 0.40, and
-        # the half-batch launches of the deep layers (conv4_x / conv5_x: 128 tiles) under-fill the chip the prediction half then
-        # has to itself (0.37 ms for what the 2B-image launches do in 0.25).  The chains' "latency-bound" launches are not idle
-        # CUs: every one of them puts a 119 KB-LDS workgroup on each of the 256 CUs and runs it at a third of the CU's matrix
-        # rate, and neither LDS nor registers leave room for a second kernel's workgroup on the same CU — so a CU given to the
-        # lane is a CU taken from the chains.
-        split = bool(self.vgg_layers) and os.environ.get('IMM_VGG_SPLIT', '0') != '0'
-        self.vgg_split = split
-        self.gt_cus = int(os.environ.get('IMM_GT_CUS', '128')) if split else 0
-        halves = ([('gt', slice(0, B), 2, self.gt_cus), ('pred', slice(B, 2 * B), 0, 0)] if split else
-                  [('', slice(0, 2 * B), 0, 0)])
-        gt_prog = []
-        for hname, hs, lane, cus in halves:
-            if not self.vgg_layers:
-                break
-            prog = gt_prog if hname == 'gt' else self.prog_fwd
-            self._cur_lane, self._cur_cus, self._cur_group = lane, cus, ('gt' if hname == 'gt' else '')
-            sfx = ' [%s]' % hname if hname else ''
-            nb = hs.stop - hs.start
-            if hname != 'pred':
-                self.w11 = self._zeros(9, 64); self.b11 = self._zeros(64)
-                a = self._act(2 * B, S, S, 64)
-                self.vgg_act['conv1_1'] = (a, S)
-            a = self.vgg_act['conv1_1'][0]
-            hv = {'': 3, 'gt': 1, 'pred': 2}[hname]
+        # (The image pair's error sum on lane 1 beside the VGG launches was neutral: DESIGN.md item 63; the ground-truth half of
+        # every layer on a confined lane of its own gave no gain: item 59.)
+        if self.vgg_layers:
+            nb = 2 * B
+            self.w11 = self._zeros(9, 64); self.b11 = self._zeros(64)
+            a = self._act(nb, S, S, 64)
+            self.vgg_act['conv1_1'] = (a, S)
             # The head in ONE launch (round 6, imm_vgg_head_fwd: vgg_head.hip): conv1_2's persistent workgroups produce the conv1_1
             # halo of their patches on the matrix cores, so conv1_1's 2B-image activation (the largest tensor of the step) is neither
             # written nor read back; only its prediction half is stored (the ReLU mask of conv1_2's data gradient).  IMM_VGG_HEAD=0 /
-            # IMM_CONV_DISABLE=vgg_head / the split program / the f32 witness keep the two launches.
-            head_fused = (not split and len(self.vgg_layers) > 1 and not self.f32 and os.environ.get('IMM_VGG_HEAD', '1') != '0'
-                          and ops.vgg_head_supported(B, S, dt))
+            # IMM_CONV_DISABLE=vgg_head / the f32 witness keep the two launches.
+            head_fused = len(self.vgg_layers) > 1 and not self.f32 and self.vgg_head and ops.vgg_head_supported(B, S, dt)
             self.vgg_head_fused = head_fused
             if head_fused:
                 self.vgg_gray = torch.empty(ops.vgg_head_scratch_bytes(B, S), dtype=torch.uint8, device=self.dev)
             else:
-                self._add(prog, (lambda a=a, hv=hv: ops.vgg_conv1_1_fwd(self.in_future, self.pred, self.ldp, B, S, self.w11, self.b11, a, hv)),
-                          'vgg_conv1_1', 2.0 * nb * S * S * 9 * 64, nb * S * S * 128.0, name='vgg16/conv1_1' + sfx)
+                self._add(self.prog_fwd, (lambda a=a: ops.vgg_conv1_1_fwd(self.in_future, self.pred, self.ldp, B, S, self.w11, self.b11, a, 3)),
+                          'vgg_conv1_1', 2.0 * nb * S * S * 9 * 64, nb * S * S * 128.0, name='vgg16/conv1_1')
             x, H = a, S
             for li, (name, cin, cout) in enumerate(self.vgg_layers[1:], start=1):
                 fd = ops.fwd_desc(nb, H, H, cin, cin, cout, cout, 3, 1, L.CONV_BIAS | L.CONV_RELU)
-                if hname != 'pred':
-                    wt = self._zeros(ops.round_up(cout, 128), fd.kpad, dtype=dt)
-                    wtd = self._zeros(ops.round_up(cin, 128), ops.round_up(9 * cout, 32), dtype=dt)
-                    y = self._act(2 * B, H, H, cout)
-                    self.vgg_wt[name], self.vgg_wtd[name], self.vgg_desc[name] = wt, wtd, fd
-                    self.vgg_act[name] = (y, H)
-                wt, y = self.vgg_wt[name], self.vgg_act[name][0]
+                wt = self._zeros(ops.round_up(cout, 128), fd.kpad, dtype=dt)
+                wtd = self._zeros(ops.round_up(cin, 128), ops.round_up(9 * cout, 32), dtype=dt)
+                y = self._act(nb, H, H, cout)
+                self.vgg_wt[name], self.vgg_wtd[name], self.vgg_desc[name] = wt, wtd, fd
+                self.vgg_act[name] = (y, H)
                 bias = self.vgg_w['vgg16/%s/biases' % name]
                 if li == 1 and head_fused:
                     # algorithmic bytes: the two images in, conv1_1's prediction half and conv1_2's activation out
-                    self._add(prog, (lambda a=a, wt=wt, bias=bias, y=y: ops.vgg_head_fwd(
+                    self._add(self.prog_fwd, (lambda a=a, wt=wt, bias=bias, y=y: ops.vgg_head_fwd(
                         self.in_future, self.pred, self.ldp, B, S, self.w11, self.b11, wt, bias, a, B, y, self.vgg_gray)),
                               'vgg_fwd', 2.0 * nb * S * S * 9 * (64 + cin * cout),
                               nb * S * S * 12.0 + 2.0 * (B * S * S * 64 + nb * S * S * cout + 9 * cin * cout),
                               name='vgg16/conv1_1+' + name, variant='vgg_head')
                 else:
-                    self._add(prog, (lambda fd=fd, x=x, wt=wt, bias=bias, y=y, hs=hs: ops.conv2d(fd, x[hs], wt, bias, y[hs])),
+                    self._add(self.prog_fwd, (lambda fd=fd, x=x, wt=wt, bias=bias, y=y: ops.conv2d(fd, x, wt, bias, y)),
                               'vgg_fwd', 2.0 * nb * H * H * 9 * cin * cout, 2.0 * (nb * H * H * (cin + cout) + 9 * cin * cout),
-                              name='vgg16/' + name + sfx, desc=fd)
-                if hname == 'gt' and name in taps:
-                    self._signal(prog, 'gt:' + name)
+                              name='vgg16/' + name, desc=fd)
                 x = y
                 if name in VGG_POOL_AFTER and li < len(self.vgg_layers) - 1:      # the deepest layer is not pooled: nobody reads it
-                    if hname != 'pred':
-                        self.vgg_pool[name] = self._act(2 * B, H // 2, H // 2, cout)
-                    p = self.vgg_pool[name]
-                    if name in taps and fuse_ok and hname != 'gt':
+                    p = self.vgg_pool[name] = self._act(nb, H // 2, H // 2, cout)
+                    if name in taps and fuse_ok:
                         # the loss taps this layer AND it is pooled next: one pass computes the masked SSE of the two halves
-                        # and both pooled halves (the feature map is read once instead of twice); with the ground-truth lane the
-                        # pooled ground-truth half is that lane's (imm_maxpool2_fwd below) and this pass writes the prediction's
+                        # and both pooled halves (the feature map is read once instead of twice)
                         idx = self.tap_idx[name]
                         fused_sse.add(name)
-                        if hname == 'pred':
-                            self._wait(prog, 'gt:' + name, lane=0)
-                        pa = None if hname == 'pred' else p[:B]
-                        self._add(prog, (lambda x=x, p=p, pa=pa, H=H, cout=cout, idx=idx: ops.masked_sse_pool(
-                            x[:B], x[B:], B, H, cout, self.in_mask, S, self.sse_partial[idx], pa, p[B:])), 'sse',
+                        self._add(self.prog_fwd, (lambda x=x, p=p, H=H, cout=cout, idx=idx: ops.masked_sse_pool(
+                            x[:B], x[B:], B, H, cout, self.in_mask, S, self.sse_partial[idx], p[:B], p[B:])), 'sse',
                                   0.0, 2 * B * H * H * cout * 2.5, name='vgg16/%s+pool' % name)
                     else:
-                        self._add(prog, (lambda x=x, p=p, H=H, cout=cout, hs=hs, nb=nb: ops.maxpool2_fwd(x[hs], p[hs], nb, H, H, cout)),
-                                  'maxpool', 0.0, nb * H * H * cout * 2.5, name='vgg16/pool_' + name + sfx)
+                        self._add(self.prog_fwd, (lambda x=x, p=p, H=H, cout=cout: ops.maxpool2_fwd(x, p, nb, H, H, cout)),
+                                  'maxpool', 0.0, nb * H * H * cout * 2.5, name='vgg16/pool_' + name)
                     x, H = p, H // 2
-        self._cur_lane, self._cur_cus, self._cur_group = 0, 0, ''
-        if gt_prog:
-            # the ground-truth lane forks in front of everything else (list order = host issue order; the lane's stream is
-            # released by an event at the head of the main stream); it is joined in front of the loss below
-            self._cur_group = 'gt'
-            head = []
-            self._mark(head, 'fork', lane=2)
-            self._cur_group = ''
-            self.prog_fwd[0:0] = head + gt_prog
-            self.n_fwd_model += len(head) + len(gt_prog)
-        if self.vgg_layers:
             self._pack_vgg()
 
         # ---- loss -------------------------------------------------------------------------------------------
@@ -1029,23 +847,14 @@ class IMMEngine:
         mask = self.in_mask
         l1 = self.l1
         self._cur_scope = 'loss'
-        if self._sse_input_early:
-            self._mark(self.prog_fwd, 'join', lane=1)
         tail = [name for name in taps if name not in fused_sse]
         # the image pair's error sum rides in the launch of the deep layers' sums (imm_masked_sse_all, round 6: one launch less on the
         # one-lane path in front of the loss; IMM_SSE_ALL=0 keeps the two launches — same partial sums bit for bit)
-        sse_all = ('input' in self.tap_idx and not self._sse_input_early and len(tail) > 1 and
-                   os.environ.get('IMM_SSE_ALL', '1') != '0')
-        if 'input' in self.tap_idx and not self._sse_input_early and not sse_all:
+        sse_all = 'input' in self.tap_idx and len(tail) > 1 and self.sse_all
+        if 'input' in self.tap_idx and not sse_all:
             idx0 = self.tap_idx['input']
             self._add(self.prog_fwd, lambda: ops.masked_sse_f32(self.in_future, 3, self.pred, self.ldp, B, S, 3, mask,
                                                                 self.sse_partial[idx0], l1), 'sse')
-        if self.vgg_split:
-            # the last launch of the ground-truth lane produced the deepest tapped activation: the lane is joined here (every tap
-            # that is not pooled next — conv3_2, conv4_2, conv5_2 — is read by the error sums below)
-            self._cur_group = 'gt'
-            self._mark(self.prog_fwd, 'join', lane=2)
-            self._cur_group = ''
         if len(tail) > 1:
             # the deep tapped layers' error sums in one launch (they sit back to back in front of the loss)
             feats = []
@@ -1242,20 +1051,8 @@ class IMMEngine:
             self._add(self.prog_bwd, lambda: ops.wgrad_reduce_multi(self.reduce_tab_ren), 'wgrad_reduce', name='renderer')
             self._reduce_jobs = []
             self.n_bwd_bucket0 = len(self.prog_bwd)
-        # Round 6, built and measured, off by default (IMM_WG_CUS=<CUs> turns it on): the renderer's filter
-        # gradients (46 % of the trainable filter-gradient FLOPs, ready here) as a CONFINED launch group on lane 2 — splits sized
-        # for `wg_cus` compute units — beside the encoders' backward chains.  Same box: off 3.193 / 3.206 ms | 96 CUs 3.172 | 128
-        # CUs 3.257 | 64 CUs 3.373.  At 96 CUs the final filter-gradient phase shrinks by 113 us and the encoders' backward grows
-        # by 110 (profiles/r06_lanes_timeline_split.txt): zero-sum for the reason given at IMM_VGG_SPLIT above.
-        self.wg_cus = int(os.environ.get('IMM_WG_CUS', '0')) if self.dp_buckets < 2 else 0
-        if self.wg_cus:
-            self._mark(self.prog_bwd, 'fork', lane=2)
-            self._cur_lane = 2
-            self._flush_wgrads('renderer', cus=self.wg_cus)
-            self.reduce_tab_ren = ops.reduce_table([j for j, _n in self._reduce_jobs], [n for _j, n in self._reduce_jobs], self.dev)
-            self._add(self.prog_bwd, lambda: ops.wgrad_reduce_multi(self.reduce_tab_ren), 'wgrad_reduce', name='renderer')
-            self._reduce_jobs = []
-            self._cur_lane = 0
+        # (The renderer's filter gradients as a launch group confined to a share of the CUs on a lane of its own were
+        # zero-sum: what the final filter-gradient phase lost, the encoders' backward chains gained)
         self.bucket0_offset = self.tab.offsets[[n for n, _s, _w in self.spec].index('model/renderer/conv_1/w')]
         # ---- bottleneck + pose encoder backward (main stream) || image encoder backward (side stream) --------------
         self._mark(self.prog_bwd, 'fork')       # d_joint is complete here
@@ -1305,14 +1102,12 @@ class IMMEngine:
         self._colsum_pending = []
         self._cur_lane = 0
         self._mark(self.prog_bwd, 'join')
-        if self.wg_cus:
-            self._mark(self.prog_bwd, 'join', lane=2)
-        self._flush_wgrads('encoders' if (self.n_bwd_bucket0 is not None or self.wg_cus) else 'all layers')
+        self._flush_wgrads('encoders' if self.n_bwd_bucket0 is not None else 'all layers')
         # one table-driven launch sums every layer's split-K slabs into the flat gradient buffer
         if self._reduce_jobs:
             self.reduce_tab = ops.reduce_table([j for j, _n in self._reduce_jobs], [n for _j, n in self._reduce_jobs], self.dev)
             self._add(self.prog_bwd, lambda: ops.wgrad_reduce_multi(self.reduce_tab), 'wgrad_reduce',
-                      name='encoders' if (self.n_bwd_bucket0 is not None or self.wg_cus) else 'all layers')
+                      name='encoders' if self.n_bwd_bucket0 is not None else 'all layers')
 
     def _encoder_backward(self, layers, d_out, ldd):
         B = self.B
@@ -1330,13 +1125,13 @@ class IMMEngine:
     # execution
     # ------------------------------------------------------------------------------------------
     def run(self, prog):
-        """Issue a launch program.  Lane 0 = the caller's current stream; lanes 1, 2 = side streams (encoder branch,
-        filter gradients) tied to it with events, so the same code serves eager execution and HIP-graph capture
+        """Issue a launch program.  Lane 0 = the caller's current stream; lane 1 = a side stream (the image-encoder
+        branch) tied to it with events, so the same code serves eager execution and HIP-graph capture
         (a side stream joins the capture when it waits on an event recorded in the capturing stream)."""
         if not self.two_streams:
             for l in prog:
                 if l.fn is not None:
-                    self._issue(l)
+                    l.fn()
             return
         main = torch.cuda.current_stream(self.dev)
         streams = {0: main}
@@ -1366,21 +1161,21 @@ class IMMEngine:
                 continue
             if l.fn is not None:
                 if l.lane == 0:
-                    self._issue(l)
+                    l.fn()
                 else:
                     with torch.cuda.stream(lane_stream(l.lane)):
-                        self._issue(l)
+                        l.fn()
                 if self._stamp_mode == 'all':
                     stamp(l.lane, '%s %s' % (l.tag, l.name))
             elif l.tag == 'fork':
-                stamp(0, 'fork' if l.lane == 1 else 'fork%d' % l.lane)
+                stamp(0, 'fork')
                 ev = torch.cuda.Event(); ev.record(main); lane_stream(l.lane).wait_event(ev)
                 stamp(l.lane, 'fork: lane %d released' % l.lane)
             elif l.tag == 'join':
                 stamp(l.lane, 'join: lane %d done' % l.lane)
-                stamp(0, 'join: lane 0 arrives' if l.lane == 1 else 'join%d: lane 0 arrives' % l.lane)
+                stamp(0, 'join: lane 0 arrives')
                 ev = torch.cuda.Event(); ev.record(lane_stream(l.lane)); main.wait_event(ev)
-                stamp(0, 'join: lane 0 resumes' if l.lane == 1 else 'join%d: lane 0 resumes' % l.lane)
+                stamp(0, 'join: lane 0 resumes')
             elif l.tag.startswith('record:'):
                 stamp(l.lane, l.tag)
                 ev = torch.cuda.Event(); ev.record(lane_stream(l.lane)); events[l.tag[7:]] = ev
@@ -1389,19 +1184,6 @@ class IMMEngine:
                 lane_stream(l.lane).wait_event(events[l.tag[5:]])
                 stamp(l.lane, l.tag + ' resumes')
         stamp(0, 'end')
-
-    @staticmethod
-    def _issue(l):
-        """One launch, under its CU limit (imm_set_cu_limit is thread-local host state read by the launch code: the confined
-        grid is baked into the launch, also when it is captured into a graph)."""
-        if l.cus:
-            ops.set_cu_limit(l.cus)
-            try:
-                l.fn()
-            finally:
-                ops.set_cu_limit(0)
-        else:
-            l.fn()
 
     def stamp_report(self):
         """[(microseconds since the first probe of the step, lane, label)] of the last step issued with IMM_DEBUG_STAMPS set."""
@@ -1425,7 +1207,7 @@ class IMMEngine:
                 continue
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            self._issue(l)
+            l.fn()
             e1.record()
             evs.append((l, e0, e1))
         torch.cuda.synchronize()
@@ -1452,7 +1234,7 @@ class IMMEngine:
     def forward_model_only(self, training=False):
         """IMMModel.build(build_loss=False): encoders, bottleneck, renderer (no VGG, no loss)."""
         self._training = bool(training)
-        self.run([l for l in self.prog_fwd[:self.n_fwd_model] if l.group != 'gt'])   # the VGG ground-truth lane: loss only
+        self.run(self.prog_fwd[:self.n_fwd_model])
 
     def backward(self):
         self.run(self.prog_bwd)

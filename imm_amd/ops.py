@@ -85,12 +85,6 @@ def device_info():
     return int(out[0]), int(out[1])
 
 
-def set_cu_limit(cus):
-    """Size the persistent convolution launches this thread issues from now on for `cus` compute units (0 = the whole device):
-    include/imm_hip.h imm_set_cu_limit."""
-    call('imm_set_cu_limit', int(cus))
-
-
 # ---- graph capture ---------------------------------------------------------------------------
 class Graph:
     """A captured launch sequence (HIP graph) on torch's current stream."""
@@ -1416,24 +1410,6 @@ def conv_first(image, wt, bias, y, ldy, stats, batch, s, co, flags):
     """First encoder convolution (7x7 over RGB) straight from the f32 image (imm_conv_first); wt = the 7x1 packed filter image."""
     call('imm_conv_first', _p(image), _p(wt), int(wt.shape[1]), _p(bias), _p(y), ldy, _p(stats), dtype_enum(y.dtype), batch, s, co,
          flags, _s())
-
-
-def conv2d_nol_supported(desc):
-    """imm_conv2d_nol (normalise on load) serves this forward convolution?"""
-    return bool(L.load().imm_conv2d_nol_supported(C.byref(desc)))
-
-
-def conv2d_nol_stats_blocks(desc):
-    n = L.load().imm_conv2d_nol_stats_blocks(C.byref(desc))
-    if n <= 0:
-        raise L.ImmHipError('imm_conv2d_nol_stats_blocks: ' + L.load().imm_last_error().decode())
-    return n
-
-
-def conv2d_nol(desc, x_raw, x_scale, x_shift, x_relu, wt, bias, y, stats=None):
-    """Convolution of relu(x_scale * x_raw + x_shift) without that tensor being stored (imm_conv2d_nol)."""
-    call('imm_conv2d_nol', C.byref(desc), dtype_enum(x_raw.dtype), _p(x_raw), _p(x_scale), _p(x_shift), int(bool(x_relu)), _p(wt),
-         _p(bias), _p(y), _p(stats), _s())
 
 
 def conv2d_dgrad_s2_supported(batch, h, w, lddy, c_dx, lddx):

@@ -17,7 +17,7 @@
  *     writers with disjoint columns).  Every entry point reads channels [0, c) of an input pixel and nothing of [c, ld), and
  *     writes channels [0, c) of an output pixel and nothing of [c, ld): those columns belong to the caller, whatever they
  *     hold (NaN included).  For convolutions c is `ci` (the K-loop channels, zero padded by the caller up to ci) on the input
- *     and `co` on the output and the mask.  This holds for imm_conv2d (all families, forward and data gradient), imm_conv2d_nol,
+ *     and `co` on the output and the mask.  This holds for imm_conv2d (all families, forward and data gradient),
  *     imm_conv2d_group, imm_conv2d_dgrad_s2, imm_conv_first, imm_conv2d_wgrad / _multi (x and dy), imm_colsum, imm_bn_apply_relu,
  *     imm_bn_apply_fused (x_out and up2x_out), imm_bn_bwd_reduce / _reduce_up / _apply / _apply_fused, imm_upsample2x_fwd / _bwd /
  *     _bwd_bn, imm_resize_ac_fwd / _bwd, imm_pose_head_fwd (feat, heat, gauss_out) and imm_pose_head_bwd (dgauss, dfeat).
@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define IMM_ABI_VERSION 38   /* 38: annotation, imm_annotate_points and imm_annotate_u8 in imm_annotate.h (what the detector, the tracker, the quality gate and the hull mask decided, drawn into the u8 photos on the device: markers, trails, the box frame in the colour of the row's status, the hull's outline and a number per face, one more policy over the skeleton of the paste kernels).  37: redaction, imm_redact_cells_u8 and imm_redact_u8 in imm_redact.h (faces pixelated or smoothed inside their u8 photos: the box cut into square cells, every cell the integer mean of the original pixels it covers, pasted through the skeleton of the other paste kernels; with the landmark-hull mask a row whose hull is flagged is redacted over its whole box).  36: landmark quality, imm_landmark_scores in imm_score.h (the soft-argmax marginals and the landmarks of every face -> the spread of the landmarks' probability and the residual of a reference shape under the best similarity, with landmarks that are NaN for a face that fails the caller's thresholds, which imm_track_step then treats as lost).  35: clip morph, the rows and the filter of imm_clip.h (a donor's face follows a tracked face through a clip: the per-row values morph forms on the host are formed on the device from the tracker's box rows, and the colour gain and the membrane's differences pass a first-order filter).  34: the seamless morph, imm_seam_fit and imm_morph_seam_u8 in imm_seam.h (a mean-value membrane over the hull mask: the colour differences at B samples of the mask's outline, weighed per pixel in closed form, take the donor's pixels onto the photo's own values on the outline).  33: the landmark-hull mask of morph, imm_hull_fit and imm_morph_hull_u8 in imm_hull.h (the convex hull of a row's target landmarks, grown and softened, multiplies the box ramp, so that only the face is pasted; pixels outside it skip the spline).  32: colour matching for morph, imm_colour_stats_u8, imm_colour_gain and imm_morph_colour_u8 in imm_colour.h (the mean and spread of a face's and its donor's pixels give a gain and an offset per channel, applied to the donor's sample in front of the mix).  31: morph, imm_morph_poses and imm_morph_u8 in imm_morph.h (two faces blended in shape and texture from their own pixels: the pose blend and a two-source sampling kernel behind ONE imm_warp_fit launch).  30: warp, imm_warp_fit and imm_warp_u8 in imm_warp.h (faces re-posed from the photo's own pixels by a thin-plate spline fitted per face on the device).  29: re-enactment, imm_retarget in imm_retarget.h (a tracked driving face -> the poses of still source faces, on the device).  28: face tracking, imm_track_step in imm_track.h (landmarks -> the next frame's box row, on the device).  27: unalign, imm_unalign_maps and imm_unalign_u8 in imm_unalign.h (aligned faces pasted back through the inverse alignment map).  26: imm_compose_u8 in imm_compose.h (faces pasted back into u8 photos).  25: alignment, imm_align_coeffs and imm_align_warp_u8 in imm_align.h.  24: box-crop mode of imm_resize_crop_u8 (boxes), keypoint epilogue of imm_pose_head_fwd (imm_keypoint_desc).  23: render-only mode of the soft-argmax forward (heat == NULL: mu is the input).  22: s2f / conv_first accept IMM_CONV_RELU.  21: imm_masked_sse_all.  20: imm_vgg_head_fwd / imm_vgg_head_supported / imm_vgg_head_scratch_bytes (conv1_1 + conv1_2 in one launch).  19: imm_set_cu_limit / imm_get_cu_limit, imm_masked_sse_pool with pool_a == NULL.  18: imm_copy_f32.  17: imm_cost_ema, imm_rms16 (summaries).  16: imm_conv2d_variant.  15: imm_conv2d_dgrad_s2, imm_conv2d_nol, imm_conv_first, imm_wgrad_job.x_scale/x_shift/x_relu; entry points removed
+#define IMM_ABI_VERSION 39   /* 39: the entry points of the retired experiments removed: the normalise-on-load forward convolution with its two queries, and the thread-local CU limit with its getter.  38: annotation, imm_annotate_points and imm_annotate_u8 in imm_annotate.h (what the detector, the tracker, the quality gate and the hull mask decided, drawn into the u8 photos on the device: markers, trails, the box frame in the colour of the row's status, the hull's outline and a number per face, one more policy over the skeleton of the paste kernels).  37: redaction, imm_redact_cells_u8 and imm_redact_u8 in imm_redact.h (faces pixelated or smoothed inside their u8 photos: the box cut into square cells, every cell the integer mean of the original pixels it covers, pasted through the skeleton of the other paste kernels; with the landmark-hull mask a row whose hull is flagged is redacted over its whole box).  36: landmark quality, imm_landmark_scores in imm_score.h (the soft-argmax marginals and the landmarks of every face -> the spread of the landmarks' probability and the residual of a reference shape under the best similarity, with landmarks that are NaN for a face that fails the caller's thresholds, which imm_track_step then treats as lost).  35: clip morph, the rows and the filter of imm_clip.h (a donor's face follows a tracked face through a clip: the per-row values morph forms on the host are formed on the device from the tracker's box rows, and the colour gain and the membrane's differences pass a first-order filter).  34: the seamless morph, imm_seam_fit and imm_morph_seam_u8 in imm_seam.h (a mean-value membrane over the hull mask: the colour differences at B samples of the mask's outline, weighed per pixel in closed form, take the donor's pixels onto the photo's own values on the outline).  33: the landmark-hull mask of morph, imm_hull_fit and imm_morph_hull_u8 in imm_hull.h (the convex hull of a row's target landmarks, grown and softened, multiplies the box ramp, so that only the face is pasted; pixels outside it skip the spline).  32: colour matching for morph, imm_colour_stats_u8, imm_colour_gain and imm_morph_colour_u8 in imm_colour.h (the mean and spread of a face's and its donor's pixels give a gain and an offset per channel, applied to the donor's sample in front of the mix).  31: morph, imm_morph_poses and imm_morph_u8 in imm_morph.h (two faces blended in shape and texture from their own pixels: the pose blend and a two-source sampling kernel behind ONE imm_warp_fit launch).  30: warp, imm_warp_fit and imm_warp_u8 in imm_warp.h (faces re-posed from the photo's own pixels by a thin-plate spline fitted per face on the device).  29: re-enactment, imm_retarget in imm_retarget.h (a tracked driving face -> the poses of still source faces, on the device).  28: face tracking, imm_track_step in imm_track.h (landmarks -> the next frame's box row, on the device).  27: unalign, imm_unalign_maps and imm_unalign_u8 in imm_unalign.h (aligned faces pasted back through the inverse alignment map).  26: imm_compose_u8 in imm_compose.h (faces pasted back into u8 photos).  25: alignment, imm_align_coeffs and imm_align_warp_u8 in imm_align.h.  24: box-crop mode of imm_resize_crop_u8 (boxes), keypoint epilogue of imm_pose_head_fwd (imm_keypoint_desc).  23: render-only mode of the soft-argmax forward (heat == NULL: mu is the input).  22: s2f / conv_first accept IMM_CONV_RELU.  21: imm_masked_sse_all.  20: imm_vgg_head_fwd / imm_vgg_head_supported / imm_vgg_head_scratch_bytes (conv1_1 + conv1_2 in one launch).  19: a thread-local CU limit (removed in 39), imm_masked_sse_pool with pool_a == NULL.  18: imm_copy_f32.  17: imm_cost_ema, imm_rms16 (summaries).  16: imm_conv2d_variant.  15: imm_conv2d_dgrad_s2, a normalise-on-load forward convolution (removed in 39), imm_conv_first, imm_wgrad_job.x_scale/x_shift/x_relu; entry points removed
                                   since 14 (imm_bn_bwd_reduce_finalize, imm_conv2d_stats_workspace_bytes) finally counted */
 
 /* IMM_F32 (round 6): f32 activation storage — the exact-arithmetic WITNESS of the wiring, a test instrument (the reference computes
@@ -85,16 +85,6 @@ const char* imm_last_error(void);
 const char* imm_source_digest(void);
 /* device properties the host needs to size launches: [0]=CU count, [1]=gfx arch number (950) */
 int imm_device_info(int32_t* out2_host);
-/* Confine the launches THIS THREAD issues from now on to a share of the chip: the persistent / chip-sized convolution kernels
- * (conv_halo, conv_halo2, conv_hdeep, conv_hdeep6) size their grids — and choose their tiles — as if the device had `cus` compute
- * units (a multiple of 8: one share per XCD; 0 = the whole device, the default).  The other CUs stay free for the kernels of a
- * concurrent stream: the weight-independent ground-truth half of the frozen VGG16 forward (concat([gt, pred]),
- * imm/models/imm_model.py:126) runs beside the latency-bound encoder chains this way (imm_amd/engine.py).  Results do not depend
- * on the limit except through the tile choice (accumulation order).  Row-count queries (imm_conv_stats_blocks ...) follow the
- * limit in force when they are called: query and launch under the same one (launches with IMM_CONV_STATS are never confined by
- * the engine).  Thread-local, like imm_last_error. */
-int imm_set_cu_limit(int cus);
-int imm_get_cu_limit(void);
 /* timeline probe: slots[index] = the device's constant-rate wall clock (100 MHz ticks) when this one-thread kernel runs on
  * `stream`.  Placed between the launches of a captured program it gives a profiler-free timeline of a HIP-graph replay
  * (IMM_DEBUG_STAMPS=1 in imm_amd/engine.py). */
@@ -143,18 +133,6 @@ int imm_wgrad_reduce_multi(const int64_t* jobs, const int32_t* blk_first, int n_
 int imm_conv2d_group(const imm_conv_desc* descs, int n, int dtype, const void* x, const void* const* wts, void* y,
                      float* stats_partial, const void* mask_ref, void* stream);
 int imm_conv2d_group_stats_blocks(const imm_conv_desc* descs, int n);
-/* Normalise on load: the convolution of a conv + batch-norm + ReLU block's output WITHOUT that output ever being stored
- * (tf.layers.batch_normalization + tf.nn.relu feeding the next tf.nn.conv2d, nn_utils.py:201-209 -> :100).  x_raw is the 16-bit
- * output y of the PRECEDING convolution; this convolution reads relu(x_scale[c] * y + x_shift[c]) (x_relu != 0; zero padding is of
- * the normalised tensor), the affine + ReLU being applied once per halo pixel in LDS after the tile's DMA.  x_scale / x_shift:
- * f32 [ci] as written by imm_bn_finalize.  Everything else as imm_conv2d (bias, IMM_CONV_STATS partial rows — their count is
- * imm_conv2d_nol_stats_blocks(desc), not imm_conv_stats_blocks).  Served by the LDS-halo kernel of conv_halo.hip: 3x3, ci in
- * {32, 64}, co <= 64, stride 1 at >= 64x64 maps, or the 32 -> 64-channel stride-2 form; imm_conv2d_nol_supported(desc) = 1 / 0.
- * Results equal imm_bn_apply_relu + imm_conv2d up to the convolution's accumulation order. */
-int imm_conv2d_nol_supported(const imm_conv_desc* desc_host);
-int imm_conv2d_nol_stats_blocks(const imm_conv_desc* desc_host);
-int imm_conv2d_nol(const imm_conv_desc* desc_host, int dtype, const void* x_raw, const float* x_scale, const float* x_shift,
-                   int x_relu, const void* wt, const float* bias, void* y, float* stats_partial, void* stream);
 /* The data gradient of a 3x3 STRIDE-2 SAME convolution (encoder conv_3 / conv_5 / conv_7, imm_model.py:197,204,211:
  * tf.nn.conv2d_backprop_input at those nn_utils.py:100 call sites) as ONE launch over ONE halo of dy: input pixel (2i+py, 2j+px)
  * receives only the taps of its parity class (4 / 2 / 2 / 1 of the nine); a workgroup keeps four accumulator sets for an 8x16
@@ -181,7 +159,7 @@ int imm_conv2d_dgrad_s2(const void* dy, int lddy, const void* wt, int kpad, void
  * Ownership of y: channels [0, co) of every output pixel of the launch are written, exactly once; the padding channels [co, ldy) belong to the
  * caller and are never written, in any kernel family and for 16-bit and f32 outputs alike (a caller that feeds y to another
  * convolution zeroes them once, see the conventions above).  Nothing before y[0] or past the last pixel's channel co - 1 is
- * written.  The same holds for imm_conv2d_nol and imm_conv_first; tests/test_kernels_gpu.py asserts
+ * written.  The same holds for imm_conv_first; tests/test_kernels_gpu.py asserts
  * it on buffers whose padding and surroundings are pre-filled (tests/guarded.py). */
 int imm_conv2d(const imm_conv_desc* desc_host, int dtype, const void* x, const void* wt, const float* bias,
                void* y, float* stats_partial, const void* mask_ref, void* stream);
@@ -227,7 +205,7 @@ typedef struct imm_wgrad_job {
   imm_conv_desc desc;          /* the FORWARD convolution */
   const void* x; const void* dy; float* slab;
   int32_t lddy, nsplit;
-  /* normalise on load (imm_conv2d_nol below): x is the RAW output of the conv + batch-norm + ReLU block in front of this
+  /* normalise on load: x is the RAW output of the conv + batch-norm + ReLU block in front of this
    * convolution and the filter gradient is taken against relu(x_scale[c] * x + x_shift[c]) (x_relu != 0), rebuilt in LDS.
    * NULL / NULL / 0 = x is the stored activation.  Only for jobs whose variant is an LDS-halo kernel
    * (imm_conv2d_wgrad_variant(...) / 100000 == 2); imm_conv2d_wgrad_multi_plan refuses others. */

@@ -120,9 +120,8 @@ def test_conv_first_relu_epilogue_bit_exact(ops, B, S, dt):
 
 
 def test_unchanged_refusals(ops):
-    """imm_conv2d_nol still refuses RELU (the new flag reaches s2f and conv_first only); conv_first still refuses MASK."""
+    """conv_first still refuses MASK (the new flag reaches s2f and conv_first only)."""
     from imm_amd import _lib as L
-    assert not ops.conv2d_nol_supported(ops.fwd_desc(2, 128, 128, 32, 32, 32, 32, 3, 1, L.CONV_BIAS | L.CONV_RELU))
     img = guarded.out((2, 64, 64, 3), torch.float32, DEV, fill=0)
     wt = guarded.out((128, 224), torch.bfloat16, DEV, fill=0)
     y = guarded.out((2, 64, 64, 32), torch.bfloat16, DEV, fill=0)

@@ -170,7 +170,7 @@ def test_every_entry_point_named_in_the_documents_exists():
                 continue
             bad.append((doc, name))
     assert not bad, bad
-    assert len(exported) == 98 and ('%d entry points' % len(exported)) in open(os.path.join(ROOT, 'INTEGRATION.md')).read()
+    assert len(exported) == 93 and ('%d entry points' % len(exported)) in open(os.path.join(ROOT, 'INTEGRATION.md')).read()
 
 
 def test_reference_import_paths_resolve_to_the_product_modules():
@@ -304,3 +304,28 @@ def test_convolution_host_side_has_one_definition_of_each_fact():
     assert not missing, missing
     defined = {name for fn in hips for name, kinds in functions(text[fn]).items() if 'def' in kinds}
     assert not set(shared) - defined, sorted(set(shared) - defined)
+
+
+def test_environment_switches_are_the_ones_the_readme_lists():
+    """Every IMM_* variable read through os.environ in imm_amd/**/*.py or through getenv in csrc/runtime.hip (the library's only
+    file that reads the environment) stands in the switch table of README.md and the table names no other; the engine reads its
+    switches in IMMEngine.__init__ and nowhere below it."""
+    import ast
+    import glob
+    read = set()
+    for path in glob.glob(os.path.join(ROOT, 'imm_amd', '**', '*.py'), recursive=True):
+        read |= set(re.findall(r"""os\.environ(?:\.get\(|\[|\.pop\()\s*['"](IMM_\w+)['"]""", open(path).read()))
+        read |= set(re.findall(r"""['"](IMM_\w+)['"]\s+(?:not\s+)?in\s+os\.environ""", open(path).read()))
+    read |= set(re.findall(r'getenv\("(IMM_\w+)"\)', open(os.path.join(ROOT, 'imm_amd', 'csrc', 'runtime.hip')).read()))
+    readme = open(os.path.join(ROOT, 'README.md')).read()
+    table = re.search(r'^\| Switch \|.*?\n((?:\|.*\n)+)', readme, flags=re.M).group(1)
+    listed = set(re.findall(r'^\| `(IMM_\w+)`', table, flags=re.M))
+    assert len(listed) > 10 and read == listed, (sorted(read - listed), sorted(listed - read))
+    src = open(os.path.join(ROOT, 'imm_amd', 'engine.py')).read()
+    tree = ast.parse(src)
+    init = next(f for c in tree.body if isinstance(c, ast.ClassDef) and c.name == 'IMMEngine'
+                for f in c.body if isinstance(f, ast.FunctionDef) and f.name == '__init__')
+    lines = src.split('\n')
+    outside = [i + 1 for i, l in enumerate(lines) if re.search(r'\benviron\b|\bgetenv\b', l) and not init.lineno <= i + 1 <= init.end_lineno]
+    assert not outside, outside
+    assert any('environ' in l for l in lines[init.lineno - 1:init.end_lineno])

@@ -330,18 +330,6 @@ def test_conv_dgrad_stride2_parity_classes(ops, H, ci, co, dt):
     close(dx, gx, 1e-2, 2e-3, 'dgrad_s2_classes')       # every pixel written exactly once (no NaN left)
 
 
-NOL_CASES = [
-    # B, H, ci, co, stride, out_f32, tag           (the shapes whose input is a batch-norm output: encoder conv_2/3/4, renderer conv_6/8)
-    (2, 128, 32, 32, 1, False, 'enc_conv2_32_32'),
-    (2, 128, 32, 64, 2, False, 'enc_conv3_stride2'),
-    (2, 64, 64, 64, 1, False, 'enc_conv4_64_64'),
-    (3, 64, 64, 32, 1, False, 'halo_64_32'),
-    (1, 128, 32, 9, 1, True, 'ren_conv8_f32_head'),
-    (70, 64, 32, 64, 1, False, 'many_patches_32_64'),
-    (33, 64, 32, 64, 2, False, 'stride2_many_patches'),
-]
-
-
 def _nol_inputs(B, H, ci, dt, seed):
     """raw conv output y (16-bit), per-channel scale (both signs) / shift, and the normalised tensor the stand-alone apply pass
     stores: relu(scale * y + shift) rounded to 16 bits."""
@@ -356,60 +344,9 @@ def _nol_inputs(B, H, ci, dt, seed):
     return y, scale, shift, out
 
 
-@pytest.mark.parametrize('case', NOL_CASES, ids=[c[-1] for c in NOL_CASES])
-@pytest.mark.parametrize('dt', [torch.bfloat16, torch.float16], ids=['bf16', 'f16'])
-def test_conv_norm_on_load(ops, case, dt):
-    """imm_conv2d_nol: the convolution reads the RAW output of the conv + BN + ReLU block in front of it and applies the affine +
-    ReLU in its LDS halo tile — against the two-launch path (imm_bn_apply_relu, then imm_conv2d on the stored tensor: same
-    16-bit operands, accumulation order may differ) and against the oracle convolution of that tensor; the batch-norm partial
-    sums of ITS output too."""
-    from imm_amd import _lib as L
-    B, H, ci, co, stride, out_f32, _tag = case
-    y, scale, shift, out = _nol_inputs(B, H, ci, dt, 900)
-    w = rnd((3, 3, ci, co), 902, 0.05, dt)
-    bias = rnd((co,), 903, 0.1, torch.float32).float()
-    flags = L.CONV_BIAS | L.CONV_STATS | (L.CONV_OUT_F32 if out_f32 else 0)
-    ldy = ops.round_up(co, 4 if out_f32 else 8)
-    desc = ops.fwd_desc(B, H, H, ci, ci, co, ldy, 3, stride, flags)
-    assert ops.conv2d_nol_supported(desc)
-    rows = ops.round_up(co, 128)
-    wt = guarded.out((rows, desc.kpad), dt, DEV, fill=0)
-    ops.pack_weights(w.float().to(DEV).contiguous(), wt, 0, 3, 3, ci, co, ci, rows, desc.kpad)
-    bd = bias.to(DEV)
-    odt = torch.float32 if out_f32 else dt
-    z_nol = guarded.out((B, desc.ho, desc.wo, ldy), odt, DEV)
-    st_nol = guarded.out((ops.conv2d_nol_stats_blocks(desc), 2, co), torch.float32, DEV)
-    ops.conv2d_nol(desc, y, scale, shift, True, wt, bd, z_nol, st_nol)
-    z_ref = guarded.out((B, desc.ho, desc.wo, ldy), odt, DEV)
-    st_ref = guarded.out((ops.conv_stats_blocks(desc), 2, co), torch.float32, DEV)
-    ops.conv2d(desc, out, wt, bd, z_ref, st_ref)
-    torch.cuda.synchronize()
-    zo = O.conv2d_same(out.float().cpu(), w.float(), bias, stride)
-    close(z_nol[..., :co], zo, 1e-2 if not out_f32 else 2e-3, 2e-3, 'conv_nol vs oracle')
-    close(z_nol[..., :co], z_ref[..., :co], (2.0 ** -7 if dt == torch.bfloat16 else 2.0 ** -10) if not out_f32 else 1e-4, 1e-4,
-          'conv_nol vs apply + conv')
-    close(st_nol.sum(0), st_ref.sum(0), 2e-4, 2e-4, 'conv_nol batch-norm partial sums')
-    assert untouched(z_nol[..., co:]) and untouched(z_ref[..., co:]), 'padding channels [co, ldy) belong to the caller'
-    # without the ReLU (a block built with relu = False)
-    ops.conv2d_nol(desc, y, scale, shift, False, wt, bd, z_nol, st_nol)
-    out2 = guarded.out(y.shape, y.dtype, DEV)
-    ops.bn_apply_relu(y, B * H * H, ci, ci, scale, shift, False, out2, ci)
-    ops.conv2d(desc, out2, wt, bd, z_ref, st_ref)
-    torch.cuda.synchronize()
-    close(z_nol[..., :co], z_ref[..., :co], (2.0 ** -7 if dt == torch.bfloat16 else 2.0 ** -10) if not out_f32 else 1e-4, 1e-4,
-          'conv_nol (no relu) vs apply + conv')
-
-
 def test_conv_norm_on_load_rejects_unserved_shapes(ops):
     from imm_amd import _lib as L
-    assert not ops.conv2d_nol_supported(ops.fwd_desc(2, 32, 32, 128, 128, 128, 128, 3, 1, L.CONV_BIAS))     # deep layer: hdeep
-    assert not ops.conv2d_nol_supported(ops.fwd_desc(2, 64, 64, 64, 64, 128, 128, 3, 2, L.CONV_BIAS))       # stride 2 from 64 channels
-    assert not ops.conv2d_nol_supported(ops.fwd_desc(2, 128, 128, 32, 32, 32, 32, 3, 1, L.CONV_BIAS | L.CONV_RELU))
-    d = ops.fwd_desc(2, 32, 32, 128, 128, 128, 128, 3, 1, L.CONV_BIAS)
-    x = guarded.out((2, 32, 32, 128), torch.bfloat16, DEV, fill=0)
     v = guarded.out((128,), torch.float32, DEV, fill=0)
-    with pytest.raises(L.ImmHipError):
-        ops.conv2d_nol(d, x, v, v, True, guarded.out((128, d.kpad), torch.bfloat16, DEV, fill=0), v, guarded.out(x.shape, x.dtype, DEV))
     # a filter-gradient job with normalise-on-load must be an LDS-halo variant
     d8 = ops.fwd_desc(2, 8, 8, 128, 128, 128, 128, 3, 1, 0)            # 8x8 maps: the transpose-read kernel's job
     assert ops.conv2d_wgrad_variant(d8, 128, torch.bfloat16)[0] // 100000 != 2
@@ -2282,42 +2219,6 @@ def test_conv_wgrad_halo_stride2_non_square(ops, B, H, W, co, dt):
         ops.conv2d_wgrad_reduce(slab, ns, 3, 3, ci, ci, co, d.kpad, dw)
         torch.cuda.synchronize()
         close(dw, gw, 2e-3, 5e-4, 'wgrad_halo_s2/%d%s/ldx%d' % (ns, 'm' if multi else '', ldx))
-
-
-@pytest.mark.parametrize('dt', [torch.bfloat16, torch.float16], ids=['bf16', 'f16'])
-@pytest.mark.parametrize('B,H,W,ci,co,stride,out_f32', [(2, 32, 128, 32, 32, 1, False), (2, 128, 32, 64, 64, 1, False),
-                                                       (2, 64, 256, 32, 64, 2, False), (1, 128, 32, 32, 9, 1, True)],
-                         ids=['s1_wide', 's1_tall_64_64', 's2_wide', 'f32_head_tall'])
-def test_conv_norm_on_load_non_square_and_wide_strides(ops, B, H, W, ci, co, stride, out_f32, dt):
-    """imm_conv2d_nol (test_conv_norm_on_load) with the raw tensor in rows of ci + 8 (NaN beyond ci), ldy above the minimum, h != w:
-    against the oracle convolution of the normalised tensor that imm_bn_apply_relu stores."""
-    from imm_amd import _lib as L
-    raw = rnd((B, H, W, ci), 900, 1.0, dt)
-    g = torch.Generator().manual_seed(901)
-    scale = dev((torch.randn(ci, generator=g) * 0.8 + 0.3))
-    shift = dev((torch.randn(ci, generator=g) * 0.7 + 0.4))
-    ldx, ldy = ci + 8, ops.round_up(co, 8) + 8
-    yw = wide(raw, ldx)
-    out = guarded.out((B, H, W, ci), dt, DEV)
-    ops.bn_apply_relu(yw, B * H * W, ci, ldx, scale, shift, True, out, ci)
-    w = rnd((3, 3, ci, co), 902, 0.05, dt)
-    bias = rnd((co,), 903, 0.1, torch.float32).float()
-    flags = L.CONV_BIAS | L.CONV_STATS | (L.CONV_OUT_F32 if out_f32 else 0)
-    desc = ops.fwd_desc(B, H, W, ci, ldx, co, ldy, 3, stride, flags)
-    assert ops.conv2d_nol_supported(desc)
-    rows = ops.round_up(co, 128)
-    wt = guarded.out((rows, desc.kpad), dt, DEV, fill=0)
-    ops.pack_weights(w.float().to(DEV).contiguous(), wt, 0, 3, 3, ci, co, ci, rows, desc.kpad)
-    z = guarded.out((B, desc.ho, desc.wo, ldy), torch.float32 if out_f32 else dt, DEV)
-    st = guarded.out((ops.conv2d_nol_stats_blocks(desc), 2, co), torch.float32, DEV)
-    ops.conv2d_nol(desc, yw, scale, shift, True, wt, dev(bias), z, st)
-    torch.cuda.synchronize()
-    zo = O.conv2d_same(out.float().cpu(), w.float(), bias, stride)
-    close(z[..., :co], zo, 1e-2 if not out_f32 else 2e-3, 2e-3, 'conv_nol vs oracle')
-    assert untouched(z[..., co:]), 'padding channels [co, ldy) belong to the caller'
-    s = st.sum(0).cpu()
-    close(s[0], zo.sum(dim=(0, 1, 2)), 1e-3, 1e-3, 'conv_nol/sum')
-    close(s[1], (zo ** 2).sum(dim=(0, 1, 2)), 1e-3, 1e-3, 'conv_nol/sumsq')
 
 
 @pytest.mark.parametrize('B,H,W,ci,co', [(2, 16, 64, 64, 128), (2, 64, 16, 64, 128), (3, 8, 32, 32, 64), (3, 32, 8, 128, 256)],

@@ -1,6 +1,7 @@
 """Every IMM_* environment switch the product path still reads, exercised in both positions: the
 kernel-dispatch ablation list IMM_CONV_DISABLE (each specialised kernel family off -> the layer falls back to the next more
-general kernel, same numbers to accumulation order), IMM_NOL, IMM_CONV_FIRST, IMM_VGG_HEAD, IMM_SSE_ALL, IMM_BN_DIRECT_ROWS, IMM_HALO2X, IMM_TWO_STREAMS, IMM_VGG_SPLIT / IMM_GT_CUS / IMM_WG_CUS / IMM_WG_LANES / IMM_SSE_INPUT_LANE (lane experiments of round 6), IMM_DEBUG_STAMPS, IMM_DEBUG_SKIP_TAGS.  The switches are
+general kernel, same numbers to accumulation order), IMM_VGG_HEAD, IMM_SSE_ALL, IMM_BN_DIRECT_ROWS, IMM_TWO_STREAMS,
+IMM_DEBUG_STAMPS, IMM_DEBUG_SKIP_TAGS.  The switches are
 read once per process (static dispatch tables / engine construction), hence the child processes (tests/_switch_probe.py).
 IMM_DP_BUCKETS, IMM_RCCL_NATIVE and IMM_RCCL_GRAPH have their tests in test_dp_gpu.py / test_step_gpu.py; IMM_HIP_LIB and
 IMM_HIPCC_FLAGS (A/B builds) in test_host_cpu.py."""
@@ -74,16 +75,6 @@ def test_bn_direct_rows_threshold_is_the_same_step():
 
 
 @pytest.mark.timeout(300)
-def test_halo2_on_32x32_tiles_is_the_same_step(base):
-    """IMM_HALO2X=1: the 64 -> 64 channel launches of conv_halo2 without batch-norm sums (VGG conv1_2's data gradient; its forward
-    when the head is two launches) on v_mfma_f32_32x32x16 tiles (conv_halo2x_kernel: built and measured in round 6, slower, off by
-    default) — the same step to the accumulation order of the nine taps (selfsup/vgg16.py:346)."""
-    for env in ({'IMM_HALO2X': 1}, {'IMM_HALO2X': 1, 'IMM_VGG_HEAD': 0}):
-        got = probe(**env)
-        assert same(base, got, 2e-4), (env, base, got)
-
-
-@pytest.mark.timeout(300)
 def test_error_sums_in_one_launch_are_the_same_step(base):
     """IMM_SSE_ALL=0: the image pair's error sum and the deep layers' error sums as the two launches imm_masked_sse_all replaces
     (imm_model.py:126-147): one launch more, every partial sum — and so the step — bit for bit the same."""
@@ -93,46 +84,12 @@ def test_error_sums_in_one_launch_are_the_same_step(base):
 
 
 @pytest.mark.timeout(300)
-def test_normalise_on_load_is_the_same_step(base):
-    """IMM_NOL=1: the apply passes of encoder conv_1..3 / renderer conv_5, conv_7 folded into their readers' LDS tiles
-    (imm_conv2d_nol, imm_wgrad_job.x_scale): fewer launches, the same step to accumulation order."""
-    got = probe(IMM_NOL=1)
-    assert got['n_launches'] <= base['n_launches'], (got['n_launches'], base['n_launches'])
-    assert same(base, got, 2e-4), (base, got)
-
-
-@pytest.mark.timeout(300)
-def test_first_convolution_from_the_image_is_the_same_step(base):
-    """IMM_CONV_FIRST=1: conv_1 of both encoders straight from the f32 image (imm_conv_first), the tap-unrolled copies packed at the
-    tail of the image-encoder lane for the filter gradients: the same step to accumulation order."""
-    got = probe(IMM_CONV_FIRST=1)
-    assert got['n_launches'] == base['n_launches']
-    assert same(base, got, 2e-4), (base, got)
-
-
-@pytest.mark.timeout(300)
 def test_single_stream_and_eager_equal_the_two_lane_graph(base):
     """IMM_TWO_STREAMS=0 (one stream, no fork/join) and eager execution: the same launches in another schedule — bitwise."""
     one = probe(IMM_TWO_STREAMS=0)
     eager = probe(PROBE_GRAPH=0)
     for got in (one, eager):
         assert all(got[k] == base[k] for k in ('loss0', 'loss1', 'mu_abs_sum', 'params_abs_sum')), (base, got)
-
-
-@pytest.mark.timeout(400)
-def test_confined_lanes_are_the_same_step(base):
-    """Round 6, opt-in (measured without gain: DESIGN.md item 59).  IMM_VGG_SPLIT=1: the ground-truth half of the VGG forward on
-    lane 2, persistent launches confined to IMM_GT_CUS compute units (imm_set_cu_limit), the prediction half behind the renderer,
-    error sums waiting for the lane's events; IMM_WG_CUS: the renderer's filter gradients planned for a share of the chip on lane 2
-    beside the encoders' backward; IMM_WG_LANES: the filter-gradient kernel variants on several lanes; IMM_SSE_INPUT_LANE: the image-space
-    error sum beside the VGG launches.  Same step up to the tile choice / split counts (accumulation order); and each of them on ONE
-    stream (list order alone) is bitwise the three-lane graph."""
-    for env in (dict(IMM_VGG_SPLIT=1, IMM_GT_CUS=64), dict(IMM_WG_CUS=96), dict(IMM_VGG_SPLIT=1, IMM_GT_CUS=0, IMM_WG_CUS=64),
-                dict(IMM_WG_LANES=3, IMM_SSE_INPUT_LANE=1)):
-        got = probe(**env)
-        assert same(base, got, 2e-4), (env, base, got)
-        one = probe(IMM_TWO_STREAMS=0, **env)
-        assert all(one[k] == got[k] for k in ('loss0', 'loss1', 'mu_abs_sum', 'params_abs_sum')), (env, got, one)
 
 
 @pytest.mark.timeout(300)

@@ -1,10 +1,10 @@
 """Dump what the library answers about kernel dispatch for a grid of convolution descriptors, one line per descriptor: run it
 against two builds (IMM_HIP_LIB=<other .so>) and diff the outputs — a refactor of the host-side dispatch leaves 0 lines.
 
-    python tools/diag/conv_dispatch_dump.py [--cu-limit N] [--programs] > dump.txt
+    python tools/diag/conv_dispatch_dump.py [--programs] > dump.txt
 
-Queries only (no launch): it runs without a GPU (the library then plans for 256 CUs).  IMM_CONV_DISABLE / IMM_HALO2X in the
-environment select the fallback dispatch.  --programs (needs a GPU) adds the (name, tag, variant) list of the benchmark engine's
+Queries only (no launch): it runs without a GPU (the library then plans for 256 CUs).  IMM_CONV_DISABLE in the
+environment selects the fallback dispatch.  --programs (needs a GPU) adds the (name, tag, variant) list of the benchmark engine's
 forward and backward programs.  The last lines count the descriptors per kernel family and the positive answers per
 "supported" query; the script fails when one of them is 0 (the sweep would prove nothing about that family)."""
 import argparse
@@ -50,12 +50,10 @@ def quiet(fn, *a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--cu-limit', type=int, default=0)
     ap.add_argument('--programs', action='store_true')
     args = ap.parse_args()
-    ops.set_cu_limit(args.cu_limit)
     lib = L.load()
-    families, positives = {f: 0 for f in range(1, 9)}, {'tap': 0, 'nol': 0, 'dgrad_s2': 0}
+    families, positives = {f: 0 for f in range(1, 9)}, {'tap': 0, 'dgrad_s2': 0}
     out = []
     for label, d in descs():
         lddy = ops.round_up(d.co, 8)
@@ -66,12 +64,11 @@ def main():
                 fam, key = fam
                 families[key // 100000] += 1
             cols.append('%s:%s/%s' % (dname, key, ','.join(str(v) for v in ops.conv2d_wgrad_variant(d, lddy, dt))))
-        tap, nol = int(ops.conv2d_tap_supported(d)), int(ops.conv2d_nol_supported(d))
+        tap = int(ops.conv2d_tap_supported(d))
         positives['tap'] += tap
-        positives['nol'] += nol
-        out.append('%s | %s | rows %s ws %d splits %s tap %d nol %d' % (
+        out.append('%s | %s | rows %s ws %d splits %s tap %d' % (
             label, ' '.join(cols), quiet(ops.conv_stats_blocks, d), lib.imm_conv2d_workspace_bytes(C.byref(d)),
-            quiet(ops.conv2d_wgrad_splits, d, lddy), tap, nol))
+            quiet(ops.conv2d_wgrad_splits, d, lddy), tap))
     # the one-launch stride-2 data gradient and the four-class group it replaces
     for batch, side, ci, co, (fname, flags) in itertools.product((1, 2, 8, 32), SIDES, CHANNELS, CHANNELS + (20,), (FLAG_SETS[0], FLAG_SETS[4])):
         ld = ops.round_up(co, 8)
