@@ -230,19 +230,19 @@ def tap_grad(d_in, ap, ag, mask, S, ck, relu, l1):
 
 
 def window_argmax(ap):
-    """[B, s/2, s/2, c]: the index 0..3 of the FIRST maximum of each 2x2 window in the order (0,0), (0,1), (1,0), (1,1)."""
-    B, s, _, c = ap.shape
-    w = ap.reshape(B, s // 2, 2, s // 2, 2, c).transpose(0, 1, 3, 2, 4, 5).reshape(B, s // 2, s // 2, 4, c)
+    """[B, h/2, w/2, c]: the index 0..3 of the FIRST maximum of each 2x2 window in the order (0,0), (0,1), (1,0), (1,1)."""
+    B, h, wd, c = ap.shape
+    w = ap.reshape(B, h // 2, 2, wd // 2, 2, c).transpose(0, 1, 3, 2, 4, 5).reshape(B, h // 2, wd // 2, 4, c)
     return w.argmax(3), w                                                    # numpy: the first occurrence
 
 
 def unpool(dpool, ap):
     """max_pool2d's backward: dpool routed to the first maximum of each window."""
-    B, s, _, c = ap.shape
+    B, h, wd, c = ap.shape
     am, _w = window_argmax(ap)
     hot = np.arange(4)[None, None, None, :, None] == am[:, :, :, None, :]
     up = np.where(hot, dpool[:, :, :, None, :], 0.0)
-    return up.reshape(B, s // 2, s // 2, 2, 2, c).transpose(0, 1, 3, 2, 4, 5).reshape(B, s, s, c)
+    return up.reshape(B, h // 2, wd // 2, 2, 2, c).transpose(0, 1, 3, 2, 4, 5).reshape(B, h, wd, c)
 
 
 def unpool_tap_grad(dpool, ap, ag, mask, S, ck):
